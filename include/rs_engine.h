@@ -170,6 +170,11 @@ int rs_engine_stage_count(rs_engine* e);
  * flops = algorithmic FLOPs of one call at the last batch size (0 for non-GEMM stages),
  * bytes = algorithmic HBM bytes of one call (inputs read once + outputs written once). */
 int rs_engine_stage_info(rs_engine* e, int i, char* name_out, double* ms_total, int* calls, double* flops, double* bytes);
+/* Saturation counts: elements that a stage clamped to the fp16 range (NaN or |value| > 65504 where it rounds an fp32 value to fp16;
+ * DESIGN.md 3.6) in the most recent forward whose results have been fetched (rs_engine_infer, rs_engine_fetch, or rs_engine_fetch_wait /
+ * rs_engine_fetch_crops_wait after the matching *_async).  counts[i] for stage i (names: rs_engine_stage_info), i < min(cap, stage count);
+ * returns the stage count (< 0 on error).  Stages that store fp32 (every stage of precision 1) always report 0. */
+int rs_engine_saturation(rs_engine* e, int64_t* counts, int cap);
 /* Kernel symbol (tile variant) the stage's last call launched, "" for non-GEMM stages. name_out: >= 96 bytes. */
 int rs_engine_stage_kernel(rs_engine* e, int i, char* name_out);
 /* Tile-variant number of the stage's last call (-2 = not a GEMM stage, -1 = fp32 kernel; numbering: rs_op_conv_variant). */
@@ -242,6 +247,11 @@ int rs_op_conv_variant(int m, int cin, int k, int cout, int cin2, int deconv2x, 
  * workgroup that rs_op_conv2d's 256x256 deep-prefetch kernel fills with {shader clocks, 100 MHz ticks} spent in its K loop.
  * No effect in the production build. */
 int rs_debug_set_conv_probe(void* buffer);
+
+/* Saturation counter of the calling thread's stand-alone operators (rs_op_conv2d, rs_op_conv2d_split, rs_op_conv2d_dual, rs_op_bneck_tail,
+ * rs_op_bneck_tail_split): while non-null, each such call adds the number of elements it clamped to the fp16 range into *(uint64_t*)dev_u64 (device
+ * memory).  Null (the default) = not counted. */
+int rs_op_set_saturation_counter(void* dev_u64);
 
 /* rs_op_conv2d in the split-operand precision mode (rs_spec.precision == 2): `in`, `w`, `out`, `residual`, `upsample_add` point to
  * the hi plane of an fp16 tensor whose lo plane lies `*_lo` ELEMENTS behind it (value = hi + lo); w holds the weight rows scaled

@@ -162,6 +162,10 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_kernel(const BneckParams p) 
   // ---- pixel geometry of this lane's 4 pixels (pixel block j, column fi)
   long long opix[NJ];
   bool valid[NJ];
+  // Elements clamped to the fp16 range, valid pixels only (common.h rs_sat_flush).  The conv2 and block outputs are clamped in code without a divergent
+  // branch: their counts are wave-uniform sums of ballots (SGPRs; a per-lane counter, or any other value carried through the passes, spills).  The next
+  // conv1's output is counted per pixel block and flushed there.
+  unsigned satc = 0;
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int m = m0 + wave * PXW + j * 16 + fi;
@@ -248,7 +252,11 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_kernel(const BneckParams p) 
 #pragma unroll
       for (int i = 0; i < MIB; ++i)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { const float v = acc[i][j][r] + b2v[i][r]; acc[i][j][r] = clamp_h(v > 0.f ? v : 0.f); }
+        for (int r = 0; r < 4; ++r) {
+          const float v = acc[i][j][r] + b2v[i][r];
+          satc += __builtin_popcountll(__builtin_amdgcn_ballot_w64(valid[j] && v > 65504.f));      // after ReLU a NaN is 0: only v > 65504 counts
+          acc[i][j][r] = clamp_h(v > 0.f ? v : 0.f);
+        }
 #pragma unroll
       for (int s2 = 0; s2 < 2 * CB; ++s2) tf[s2][j] = pack8(acc[2 * s2][j], acc[2 * s2 + 1][j]);
     }
@@ -310,6 +318,7 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_kernel(const BneckParams p) 
         for (int r = 0; r < 4; ++r) {
           const float res = SC ? 0.f : (float)rb[pass & 1][j][i >> 1][(i & 1) * 4 + r];     // loaded one pass ago (gload16_untracked), covered by the wait above
           const float v = a2[i][r] + b3q[i][r] + res;
+          satc += __builtin_popcountll(__builtin_amdgcn_ballot_w64(valid[j] && v > 65504.f));
           a2[i][r] = clamp_h(v > 0.f ? v : 0.f);
         }
       const half8 o0 = pack8(a2[0], a2[1]), o1 = pack8(a2[2], a2[3]);
@@ -339,15 +348,22 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_kernel(const BneckParams p) 
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       if (!valid[j]) continue;
+      unsigned satn = 0;
 #pragma unroll
       for (int i = 0; i < MIB; ++i)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { const float v = acc3[i][j][r] + b1v[i][r]; acc3[i][j][r] = clamp_h(v > 0.f ? v : 0.f); }
+        for (int r = 0; r < 4; ++r) {
+          const float v = acc3[i][j][r] + b1v[i][r];
+          satn += v > 65504.f ? 1u : 0u;
+          acc3[i][j][r] = clamp_h(v > 0.f ? v : 0.f);
+        }
+      rs_sat_flush(p.sat, satn);
       half_t* op = p.t1n + opix[j] * CBW + fq * 4 * MIB;
 #pragma unroll
       for (int k = 0; k < MIB / 2; ++k) *(half8*)(op + 8 * k) = pack8(acc3[2 * k][j], acc3[2 * k + 1][j]);
     }
   }
+  if (lane == 0) rs_sat_flush(p.sat, satc);
 }
 
 template <int CB>

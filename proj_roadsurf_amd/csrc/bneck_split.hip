@@ -60,7 +60,11 @@ __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, half8& h,
     h[4 + r] = (half_t)b[r]; l[4 + r] = (half_t)(b[r] - (float)h[4 + r]);
   }
 }
-__device__ __forceinline__ float relu_clamp(float v) { v = v > 0.f ? v : 0.f; return v > 65504.f ? 65504.f : v; }
+__device__ __forceinline__ float relu_clamp(float v, unsigned& satc, bool count) {    // count: add a saturated value to satc (common.h rs_sat_flush)
+  v = v > 0.f ? v : 0.f;
+  satc += count ? rs_sat_bad(v) : 0u;
+  return v > 65504.f ? 65504.f : v;
+}
 
 #define RS_MFMA3(acc, wh, wl, xh, xl)                                      \
   acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl, acc, 0, 0, 0);      \
@@ -148,6 +152,7 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_split_kernel(const BneckSpli
 
   long long opix[NJ];
   bool valid[NJ];
+  unsigned satc = 0;        // elements clamped to the fp16 range at the three clamp points, valid pixels only
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int m = m0 + wave * PXW + j * 16 + fi;
@@ -200,7 +205,7 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_split_kernel(const BneckSpli
 #pragma unroll
       for (int j = 0; j < NJ; ++j)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) acc[i][j][r] = relu_clamp(acc[i][j][r] * sc[r] + bv[r]);
+        for (int r = 0; r < 4; ++r) acc[i][j][r] = relu_clamp(acc[i][j][r] * sc[r] + bv[r], satc, valid[j]);
     }
 #pragma unroll
     for (int s = 0; s < 2 * CB; ++s)
@@ -271,7 +276,7 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_split_kernel(const BneckSpli
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float res = PROJ ? 0.f : (float)rh[j][i >> 1][(i & 1) * 4 + r] + (float)rl[j][i >> 1][(i & 1) * 4 + r];
-          a2[i][r] = relu_clamp(a2[i][r] * s3v[r] + b3v[r] + res);
+          a2[i][r] = relu_clamp(a2[i][r] * s3v[r] + b3v[r] + res, satc, valid[j]);
         }
       }
       half8 o0h, o0l, o1h, o1l;
@@ -305,7 +310,7 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_split_kernel(const BneckSpli
         const f32x4 ba = *(const f32x4*)(p.b1 + fq * 4 * MIB + 8 * k), bb = *(const f32x4*)(p.b1 + fq * 4 * MIB + 8 * k + 4);
         f32x4 va, vb;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { va[r] = relu_clamp(acc3[2 * k][j][r] * sa[r] + ba[r]); vb[r] = relu_clamp(acc3[2 * k + 1][j][r] * sb2[r] + bb[r]); }
+        for (int r = 0; r < 4; ++r) { va[r] = relu_clamp(acc3[2 * k][j][r] * sa[r] + ba[r], satc, true); vb[r] = relu_clamp(acc3[2 * k + 1][j][r] * sb2[r] + bb[r], satc, true); }
         half8 h, l;
         split8(va, vb, h, l);
         *(half8*)(op + 8 * k) = h;
@@ -313,6 +318,7 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_split_kernel(const BneckSpli
       }
     }
   }
+  rs_sat_flush(p.sat, satc);
 }
 
 template <int CB, bool PROJ>

@@ -57,6 +57,18 @@ __device__ __forceinline__ float rs_fdiv(float a, float b) {
   const bool special = !(__builtin_fabsf(b) > 0.f && __builtin_fabsf(b) < __builtin_inff() && __builtin_fabsf(a) > 0.f && __builtin_fabsf(a) < __builtin_inff());
   return special ? a * y0 : q;
 }
+
+// Saturation counting.  Every epilogue that rounds an fp32 value to fp16 clamps it to +-65504 first; an element
+// "saturates" when that value is NaN or |f| > 65504 (rs_sat_bad).  Counts go to a u64 in device memory through rs_sat_flush: nothing when the
+// pointer is null or the count is 0, else one vector atomic add per calling wave (the compiler's atomic optimiser sums the lanes first).
+// Two forms: a per-lane counter of rs_sat_bad over every value, flushed once at the end (conv_deep, the split bottleneck tail and stem,
+// pre-processing); or, where the epilogue is on the critical path (conv_igemm, conv_wreg, the fp16 stem), a screen per pixel block -- the
+// largest or the summed |clamped value| -- with the exact count and its flush only in the rare block that can hold a saturated value.
+// Stored values do not change.
+__device__ __forceinline__ unsigned rs_sat_bad(float f) { return !(__builtin_fabsf(f) <= 65504.f); }
+__device__ __forceinline__ void rs_sat_flush(unsigned long long* sat, unsigned cnt) {
+  if (sat != nullptr && cnt != 0u) atomicAdd(sat, (unsigned long long)cnt);
+}
 #endif
 
 // Debug / experiment switches.  Every RS_* environment variable the library understands is read in ONE place
@@ -186,6 +198,7 @@ struct ConvParams {
   long long head_w_lo;        // fused head (head_w) in the split-operand mode: offset of its lo plane, and
   const float* head_scale;    // its inverse row scales [16]
   ConvSeg seg[RS_MAX_SEGS];
+  unsigned long long* sat;    // saturation counter (rs_sat_flush): += elements clamped to the fp16 range; nullptr = not counted
 };
 
 int launch_conv(const ConvParams& p, hipStream_t stream, int force_variant /* -1 auto */, int use_glds);
@@ -202,6 +215,7 @@ struct StemPoolParams {
   int N, in_Hp, in_Wp;
   int Hc, Wc;           // conv output size
   int Hq, Wq;           // pooled size
+  unsigned long long* sat;   // saturation counter (ConvParams::sat)
 };
 int launch_stem_pool(const StemPoolParams& p, hipStream_t stream);
 // The same launch in the split-operand precision mode: input and pooled output as hi + lo planes, the weight fragments as [2 planes][7][4][64][8]
@@ -215,6 +229,7 @@ struct StemPoolSplitParams {
   int N, in_Hp, in_Wp;
   int Hc, Wc;
   int Hq, Wq;
+  unsigned long long* sat;   // saturation counter (ConvParams::sat)
 };
 int launch_stem_pool_split(const StemPoolSplitParams& p, hipStream_t stream);
 
@@ -236,6 +251,7 @@ struct BneckParams {
   half_t* t1n;          // next block's conv1 output [N][H+2][W+2][64]
   int M, H, W, Hp, Wp;  // M = N*H*W pixels
   int CB;               // bottleneck width / 64: 1 (64 -> 256, res2) or 2 (128 -> 512, res3); every "64" / "256" above scales with it
+  unsigned long long* sat;   // saturation counter (ConvParams::sat): conv2 output, block output and next conv1 output all count
 };
 int launch_bneck_tail(const BneckParams& p, hipStream_t stream);
 
@@ -258,6 +274,7 @@ struct BneckSplitParams {
   const half_t* x0; long long x0_lo;
   int M, H, W, Hp, Wp;
   int CB;
+  unsigned long long* sat;   // saturation counter (ConvParams::sat): conv2 output, block output and next conv1 output all count
 };
 int launch_bneck_tail_split(const BneckSplitParams& p, hipStream_t stream);
 
@@ -302,6 +319,7 @@ struct PreprocParams {
   int out_f32;            // fp32 validation mode: out is float; 2 = split-operand mode: out is the hi plane, the lo plane out_lo elements behind it
   long long out_lo;
   float mean[4], stdv[4];
+  unsigned long long* sat;   // saturation counter (ConvParams::sat): normalised values with |f| > 65504 in the fp16 and split modes
 };
 int launch_preprocess(const PreprocParams& p, hipStream_t s);
 int launch_maxpool(const half_t* in, half_t* out, int N, int Hi, int Wi, int Ho, int Wo, int C, hipStream_t s);

@@ -392,6 +392,7 @@ __device__ __forceinline__ void conv_deep_tile(const ConvParams& p, char* smem, 
       wsc[i * 4 + 0] = s4[0]; wsc[i * 4 + 1] = s4[1]; wsc[i * 4 + 2] = s4[2]; wsc[i * 4 + 3] = s4[3];
     }
   }
+  unsigned satc = 0;                               // elements clamped to the fp16 range (common.h rs_sat_flush)
   if (!TRAIN && SPLIT && p.head_w) {
     // The fused 16-row head in the split-operand mode: relu(acc * scale + bias) is split into hi + lo exactly as the store would split it, and
     // the head is three MFMA products per 32-deep step (H_hi.B_hi, H_hi.B_lo, H_lo.B_hi) on the head's own hi / lo planes (row-scaled; the
@@ -403,17 +404,22 @@ __device__ __forceinline__ void conv_deep_tile(const ConvParams& p, char* smem, 
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       half8 b0, b1, l0, l1;
+      // the head's input counts too, flushed per 16-pixel block: a counter carried across the blocks beside hacc[] costs the split head scratch
+      const bool mv = m0 + wpx * WPX + j * 16 + fi < M;
+      unsigned sath = 0;
 #pragma unroll
       for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float f = acc[i][j][r] * wsc[i * 4 + r] + bias[i * 4 + r];
           if (p.relu) f = f > 0.f ? f : 0.f;
+          sath += mv ? rs_sat_bad(f) : 0u;
           f = f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f);
           const half_t h = (half_t)f;
           const half_t l = (half_t)(f - (float)h);
           if (i < 2) { b0[i * 4 + r] = h; l0[i * 4 + r] = l; } else { b1[(i - 2) * 4 + r] = h; l1[(i - 2) * 4 + r] = l; }
         }
+      rs_sat_flush(p.sat, sath);
       f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
       a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ha0, b0, a, 0, 0, 0);
       a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ha1, b1, a, 0, 0, 0);
@@ -458,15 +464,20 @@ __device__ __forceinline__ void conv_deep_tile(const ConvParams& p, char* smem, 
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       half8 b0, b1;
+      // the head's input counts too, flushed per 16-pixel block: a counter carried across the blocks beside hacc[] costs the split head scratch
+      const bool mv = m0 + wpx * WPX + j * 16 + fi < M;
+      unsigned sath = 0;
 #pragma unroll
       for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float f = acc[i][j][r] + bias[i * 4 + r];
           if (p.relu) f = f > 0.f ? f : 0.f;
+          sath += mv ? rs_sat_bad(f) : 0u;
           f = f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f);
           if (i < 2) b0[i * 4 + r] = (half_t)f; else b1[(i - 2) * 4 + r] = (half_t)f;
         }
+      rs_sat_flush(p.sat, sath);
       f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
       a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ha0, b0, a, 0, 0, 0);
       a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ha1, b1, a, 0, 0, 0);
@@ -588,6 +599,7 @@ __device__ __forceinline__ void conv_deep_tile(const ConvParams& p, char* smem, 
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
           float f = v[i * 4 + r];
+          satc += rs_sat_bad(f);
           f = f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f);
           h[r] = (half_t)f;
           if constexpr (SPLIT) l[r] = (half_t)(f - (float)h[r]);
@@ -597,6 +609,7 @@ __device__ __forceinline__ void conv_deep_tile(const ConvParams& p, char* smem, 
       }
     }
   }
+  rs_sat_flush(p.sat, satc);
 #ifdef RS_SPLIT_PHASES
   if constexpr (SPLIT) {
     const unsigned long long ph_issued = __builtin_amdgcn_s_memtime();

@@ -452,6 +452,8 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
         for (int i = 0; i < MI; ++i) *(f32x4*)(op + i * 4) = f32x4{v[i * 4], v[i * 4 + 1], v[i * 4 + 2], v[i * 4 + 3]};
       } else {
         half_t* op = (half_t*)p.out + opix * p.out_Cs + cb;
+        // saturation screen (common.h rs_sat_bad): the sum of |clamped value| is NaN or >= 65504 whenever an element is NaN or out of range
+        float scr = 0.f;
         if constexpr (MI % 2 == 0) {
 #pragma unroll
           for (int i = 0; i < MI; i += 2) {          // one 16-byte store per 8 channels (STORES_F16 per pixel)
@@ -460,6 +462,7 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
             for (int r = 0; r < 8; ++r) {
               float f = v[i * 4 + r];
               f = f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f);
+              scr += __builtin_fabsf(f);
               h[r] = (half_t)f;
               if constexpr (SPLIT) l[r] = (half_t)(f - (float)h[r]);
             }
@@ -474,12 +477,19 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
             for (int r = 0; r < 4; ++r) {
               float f = v[i * 4 + r];
               f = f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f);
+              scr += __builtin_fabsf(f);
               h[r] = (half_t)f;
               if constexpr (SPLIT) l[r] = (half_t)(f - (float)h[r]);
             }
             *(half4*)(op + i * 4) = h;
             if constexpr (SPLIT) *(half4*)(op + p.out_lo + i * 4) = l;
           }
+        }
+        if (!(scr < 65504.f)) {     // rare: count exactly
+          unsigned c = 0;
+#pragma unroll
+          for (int e = 0; e < 4 * MI; ++e) c += rs_sat_bad(v[e]);
+          rs_sat_flush(p.sat, c);
         }
       }
     }

@@ -325,6 +325,7 @@ __global__ __launch_bounds__(256 * NWPX, BM == 32 ? 2 : 1) void conv1x1_wreg_ker
         }
       }
       half_t* op = (half_t*)p.out + opix * p.out_Cs + crow;
+      float mx = 0.f;        // saturation screen (common.h rs_sat_bad): the largest |clamped value|, 65504 for a NaN or out-of-range element
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         half8 h;
@@ -334,9 +335,20 @@ __global__ __launch_bounds__(256 * NWPX, BM == 32 ? 2 : 1) void conv1x1_wreg_ker
           if (p.relu) f = f > 0.f ? f : 0.f;
           // conv_igemm's clamp (f > 65504 ? 65504 : f < -65504 ? -65504 : f) as one median: the same value for every f but NaN
           f = __builtin_amdgcn_fmed3f(f, lo, 65504.f);
+          mx = __builtin_fmaxf(mx, __builtin_fabsf(f));
           h[r] = (half_t)f;
         }
         *(half8*)(op + i * 8) = h;
+      }
+      if (mx >= 65504.f) {   // rare: count exactly, NaN included (it is stored as -65504)
+        unsigned c = 0;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          float f = v[e >> 1][e & 1];
+          if (p.relu) f = f > 0.f ? f : 0.f;
+          c += rs_sat_bad(f);
+        }
+        rs_sat_flush(p.sat, c);
       }
     }
     { const Pix nx = pix_add(ex, ey, en, dx, dy, dn, Wo, Ho); ex = nx.x; ey = nx.y; en = nx.n; }

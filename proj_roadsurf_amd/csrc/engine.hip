@@ -265,6 +265,27 @@ struct rs_engine {
   bool frozen_fusions_only = false;   // a trainer's forward engine: layer fusions only where nothing is differentiated (stem + res2 at FREEZE_AT 2)
   int merge_levels = 1;   // FPN output convs / RPN 3x3 of all levels as one multi-map launch each (inference engines, fp16 path)
   long long forward_index = 0;
+  // Saturation counts: one u64 per stage, indexed like `stages`; inference engines only (a trainer's forward engine: null).
+  // Every forward zeroes the live array at its start and copies it to the snapshot at the end of its last phase; the fetches copy the
+  // snapshot only, so a next forward that is already counting never races a result copy.
+  static constexpr int kSatCap = 512;
+  unsigned long long* sat_dev = nullptr;     // live counters of the forward in flight
+  unsigned long long* sat_snap = nullptr;    // the last finished forward's
+  unsigned long long* h_sat_copy = nullptr;  // pinned target of the fetch copies
+  bool sat_copy_pending = false;
+  std::vector<int64_t> h_sat;                // the most recent fetched forward's
+  unsigned long long* sat_slot() const { return sat_dev ? sat_dev + stages.size() : nullptr; }   // counter of the stage pushed next
+  int sat_copy(hipStream_t s) {
+    if (!sat_dev) return RS_OK;
+    RS_HIP(hipMemcpyAsync(h_sat_copy, sat_snap, stages.size() * 8, hipMemcpyDeviceToHost, s));
+    sat_copy_pending = true;
+    return RS_OK;
+  }
+  void sat_publish() {
+    if (!sat_copy_pending) return;
+    h_sat.assign(h_sat_copy, h_sat_copy + stages.size());
+    sat_copy_pending = false;
+  }
   std::set<int> warmed;
   std::map<int, hipGraphExec_t> graphs;
 };
@@ -373,6 +394,7 @@ int rs_engine::add_conv(const std::string& name, const std::string& wname, const
     defer->p = p; defer->m_per_image = m_per_image; defer->flops = st.flops_per_image; defer->bytes = st.bytes_per_image;
     return RS_OK;
   }
+  p.sat = sat_slot();
   st.fn = [p, m_per_image, glds](int n, hipStream_t s) mutable {
     p.M = n * m_per_image;
     return launch_conv(p, s, -1, glds);
@@ -404,6 +426,7 @@ int rs_engine::add_merged_convs(const std::string& name, const std::vector<Defer
     st.flops_per_image += d[i].flops;
     st.bytes_per_image += d[i].bytes;
   }
+  common.sat = sat_slot();
   st.fn = [common, segs, mpi](int n, hipStream_t s) {
     g_last_conv_variant = 12;
     return launch_conv_deep_multi(common, segs.data(), mpi.data(), (int)segs.size(), n, s);
@@ -468,6 +491,11 @@ int rs_engine::build() {
   RS_CHECK(S.in_channels >= 1 && S.in_channels <= 4 && S.in_channels == tile_c, RS_ERR_ARG, "tile channels %d vs PIXEL_MEAN %d", tile_c, S.in_channels);
   RS_CHECK(!S.mask_on || S.mask_pooler_resolution * 2 == RS_MASK_SIDE, RS_ERR_UNSUPPORTED, "mask side must be 28");
   int rc;
+  if (!frozen_fusions_only) {
+    if ((rc = alloc((void**)&sat_dev, kSatCap * 8))) return rc;
+    if ((rc = alloc((void**)&sat_snap, kSatCap * 8))) return rc;
+    RS_HIP(hipHostMalloc((void**)&h_sat_copy, kSatCap * 8, hipHostMallocDefault));
+  }
 
   // ---- resize tables + input staging
   RS_CHECK(alloc((void**)&tiles_dev, (size_t)NB * tile_h * tile_w * tile_c) == RS_OK, RS_ERR_HIP, "alloc tiles");
@@ -505,6 +533,7 @@ int rs_engine::build() {
     st.name = "preprocess";
     st.bytes_per_image = (double)tile_h * tile_w * tile_c + (double)net_h * net_w * 8;
     pp.tiles = tiles_dev;
+    pp.sat = sat_slot();
     const size_t x0_bytes = (size_t)NB * x0.Hp() * x0.Wp() * 4 * (f32 ? 4 : 2);       // one plane
     const int planes = split ? 2 : 1;
     st.fn = [this, pp, x0_bytes, planes](int n, hipStream_t s) mutable {
@@ -556,6 +585,7 @@ int rs_engine::build() {
     st.name = "stem.conv1+maxpool";
     st.flops_per_image = 2.0 * h2 * w2 * 49.0 * S.in_channels * 64;
     st.bytes_per_image = 2.0 * ((double)pad_h * pad_w * 4 + (double)h4 * w4 * 64);
+    sp.sat = sat_slot();
     st.fn = [sp](int n, hipStream_t s) mutable { sp.N = n; g_last_conv_variant = 21; return launch_stem_pool(sp, s); };
     stages.push_back(st);
   } else if (fuse_stem && split && use_glds > 0 && S.stem_out_channels == 64 && x0.C == 4 && x0.pad == 3 && stem_w && stem_b && find(bu + "stem.conv1.wsi") &&
@@ -571,6 +601,7 @@ int rs_engine::build() {
     st.name = "stem.conv1+maxpool";
     st.flops_per_image = 2.0 * h2 * w2 * 49.0 * S.in_channels * 64;
     st.bytes_per_image = 4.0 * ((double)pad_h * pad_w * 4 + (double)h4 * w4 * 64);
+    sp.sat = sat_slot();
     st.fn = [sp](int n, hipStream_t s) mutable { sp.N = n; g_last_conv_variant = 21; return launch_stem_pool_split(sp, s); };
     stages.push_back(st);
   } else {
@@ -665,6 +696,7 @@ int rs_engine::build() {
         st.name = nm + (tail_next ? ".conv2+conv3+next.conv1" : ".conv2+conv3");
         st.flops_per_image = 2.0 * mpi * (9.0 * bott * bott + (double)bott * cout + (tail0 ? 64.0 * cout : 0.0) + (tail_next ? (double)cout * bott : 0.0));
         st.bytes_per_image = 2.0 * mpi * ((double)bott + (tail0 ? 64.0 : (double)cout) + cout + (tail_next ? (double)bott : 0.0));       // t1 + x (or x0) in, out (+ t1n) out
+        bp.sat = sat_slot();
         st.fn = [bp, mpi](int n, hipStream_t s) mutable { bp.M = n * mpi; g_last_conv_variant = 13; return launch_bneck_tail(bp, s); };
         stages.push_back(st);
         have_t1 = tail_next;
@@ -698,6 +730,7 @@ int rs_engine::build() {
         st.name = nm + (tail_next ? ".conv2+conv3+next.conv1" : ".conv2+conv3");
         st.flops_per_image = 2.0 * mpi * (9.0 * bott * bott + (double)k3 * cout + (tail_next ? (double)cout * bott : 0.0));
         st.bytes_per_image = 4.0 * mpi * ((double)bott + (tail0_s ? 64.0 : (double)cout) + cout + (tail_next ? (double)bott : 0.0));       // two planes of t1 + x (or x0) in, out (+ t1n) out
+        bp.sat = sat_slot();
         st.fn = [bp, mpi](int n, hipStream_t s) mutable { bp.M = n * mpi; g_last_conv_variant = 23; return launch_bneck_tail_split(bp, s); };
         stages.push_back(st);
         have_t1 = tail_next;
@@ -937,6 +970,7 @@ int rs_engine::build() {
     st.name = name;
     st.flops_per_image = 2.0 * PC * (double)in.C * p.Cout;
     st.bytes_per_image = (double)PC * (in.C * 2 * (split ? 2 : 1) + p.Cout * (out32 ? 4 : (split ? 4 : 2)));
+    p.sat = out32 ? nullptr : sat_slot();
     st.fn = [p, glds, variant](int n, hipStream_t s) mutable { p.M = n * PC; return launch_conv(p, s, variant, glds); };
     stages.push_back(st);
     return RS_OK;
@@ -1108,6 +1142,7 @@ int rs_engine::build() {
         st.name = "mask.deconv";
         st.flops_per_image = 2.0 * D * per_roi * 256 * 1024;
         st.bytes_per_image = (double)D * per_roi * 256 * 2 * 5;
+        dp.sat = sat_slot();
         st.fn = [dp, per_roi, Dc, glds](int n, hipStream_t s) mutable { dp.M = n * Dc * per_roi; return launch_conv(dp, s, -1, glds); };
         stages.push_back(st);
       }
@@ -1140,6 +1175,8 @@ int rs_engine::build() {
       stages.push_back(st);
     }
   }
+  RS_CHECK(stages.size() <= (size_t)kSatCap, RS_ERR_UNSUPPORTED, "%d stages: more than the %d saturation counters", (int)stages.size(), kSatCap);
+  h_sat.assign(stages.size(), 0);
   RS_HIP(hipStreamSynchronize(stream));
   return RS_OK;
 }
@@ -1176,6 +1213,7 @@ int rs_engine::assign_phases() {
 }
 
 int rs_engine::run_stages(int n, bool record, int phase, bool all_wide) {
+  if (sat_dev && phase <= 0) RS_HIP(hipMemsetAsync(sat_dev, 0, stages.size() * 8, stream));   // a forward starts: its counters from zero
   for (size_t si = 0; si < stages.size(); ++si) {
     Stage& st = stages[si];
     if (phase >= 0 && st.phase != phase) continue;
@@ -1222,6 +1260,8 @@ int rs_engine::run_stages(int n, bool record, int phase, bool all_wide) {
     RS_HIP(hipStreamWaitEvent(stream, ev_join, 0));
     on_narrow = false;
   }
+  if (sat_dev && (phase < 0 || phase == RS_NUM_PHASES - 1))      // the forward is complete: what the fetches copy
+    RS_HIP(hipMemcpyAsync(sat_snap, sat_dev, stages.size() * 8, hipMemcpyDeviceToDevice, stream));
   return RS_OK;
 }
 
@@ -1374,6 +1414,7 @@ void rs_engine_destroy(rs_engine* e) {
   if (e->copy_stream) { (void)hipStreamSynchronize(e->copy_stream); (void)hipStreamDestroy(e->copy_stream); }
   if (e->ev_crop_hdr) (void)hipEventDestroy(e->ev_crop_hdr);
   if (e->h_crop_total) (void)hipHostFree(e->h_crop_total);
+  if (e->h_sat_copy) (void)hipHostFree(e->h_sat_copy);
   if (e->ev_results) (void)hipEventDestroy(e->ev_results);
   if (e->ev_copied) (void)hipEventDestroy(e->ev_copied);
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
@@ -1438,7 +1479,9 @@ int rs_engine_fetch(rs_engine* e, int n, rs_dets* o) {
     RS_CHECK(e->mask_probs, RS_ERR_ARG, "mask_probs requested but MASK_ON is false");
     RS_HIP(hipMemcpyAsync(o->mask_probs, e->mask_probs, (size_t)n * D * RS_MASK_SIDE * RS_MASK_SIDE * 4, hipMemcpyDeviceToHost, s));
   }
+  { int rc = e->sat_copy(s); if (rc) return rc; }
   RS_HIP(hipStreamSynchronize(s));
+  e->sat_publish();
   return RS_OK;
 }
 
@@ -1485,6 +1528,7 @@ int rs_engine_fetch_async(rs_engine* e, int n, rs_dets* o) {
   if (o->scores) RS_HIP(hipMemcpyAsync(o->scores, e->det_scores, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
   if (o->classes) RS_HIP(hipMemcpyAsync(o->classes, e->det_classes, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
   if (o->masks && e->masks) RS_HIP(hipMemcpyAsync(o->masks, e->masks, (size_t)n * D * e->tile_h * ((e->tile_w + 7) / 8), hipMemcpyDeviceToHost, s));
+  { int rc = e->sat_copy(s); if (rc) return rc; }
   RS_HIP(hipEventRecord(e->ev_copied, s));
   e->copy_pending = true;
   return RS_OK;
@@ -1518,6 +1562,7 @@ int rs_engine_fetch_crops_async(rs_engine* e, int n, rs_dets* o, rs_mask_crops* 
   RS_HIP(hipMemcpyAsync(c->rects, e->crop_rects, (size_t)n * D * 16, hipMemcpyDeviceToHost, s));
   RS_HIP(hipMemcpyAsync(c->offsets, e->crop_offsets, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
   RS_HIP(hipMemcpyAsync(e->h_crop_total, e->crop_total, 8, hipMemcpyDeviceToHost, s));
+  { int rc = e->sat_copy(s); if (rc) return rc; }
   RS_HIP(hipEventRecord(e->ev_copied, s));       // detections and canvases are free for the next forward: the crops live in their own buffer
   RS_HIP(hipEventRecord(e->ev_crop_hdr, s));
   e->copy_pending = true;
@@ -1532,12 +1577,14 @@ int rs_engine_fetch_crops_wait(rs_engine* e, rs_mask_crops* c) {
   c->used = used;
   if (used) RS_HIP(hipMemcpyAsync(c->data, e->crop_data, (size_t)used, hipMemcpyDeviceToHost, e->copy_stream));
   RS_HIP(hipStreamSynchronize(e->copy_stream));
+  e->sat_publish();
   return RS_OK;
 }
 
 int rs_engine_fetch_wait(rs_engine* e) {
   RS_CHECK(e, RS_ERR_ARG, "null engine");
   if (e->copy_stream) RS_HIP(hipStreamSynchronize(e->copy_stream));
+  e->sat_publish();
   return RS_OK;
 }
 
@@ -1574,6 +1621,12 @@ int rs_engine_set_profiling(rs_engine* e, int enabled) {
   return RS_OK;
 }
 int rs_engine_stage_count(rs_engine* e) { return e ? (int)e->stages.size() : 0; }
+int rs_engine_saturation(rs_engine* e, int64_t* counts, int cap) {
+  RS_CHECK(e && (counts || cap <= 0), RS_ERR_ARG, "null argument");
+  const int n = (int)e->stages.size();
+  for (int i = 0; i < n && i < cap; ++i) counts[i] = i < (int)e->h_sat.size() ? e->h_sat[i] : 0;
+  return n;
+}
 int rs_engine_stage_info(rs_engine* e, int i, char* name_out, double* ms_total, int* calls, double* flops, double* bytes) {
   RS_CHECK(e && i >= 0 && i < (int)e->stages.size(), RS_ERR_ARG, "stage index");
   if (e->ev_used) { int rc = e->resolve_profile(); if (rc) return rc; }
@@ -1665,6 +1718,7 @@ int rs_engine_net_shape(rs_engine* e, int* rh, int* rw, int* ph, int* pw) {
 
 // ------------------------------------------------------------------------- stand-alone operators
 static long long* g_conv_probe = nullptr;   // -DRS_CLOCK_PROBE diagnostic builds: see rs_debug_set_conv_probe
+static thread_local unsigned long long* g_op_sat = nullptr;   // rs_op_set_saturation_counter
 struct SplitArgs { long long in_lo, w_lo, out_lo, res_lo, up_lo; const float* wscale; };
 static int op_conv2d(const void* in, const void* w, const float* bias, void* out, const void* residual, const void* upsample_add,
                      int n, int hi, int wi, int cin, int in_halo, int kh, int kw, int stride, int pad, int cout, int kpad,
@@ -1685,6 +1739,7 @@ static int op_conv2d(const void* in, const void* w, const float* bias, void* out
   if (upsample_add) { p.up_Hp = ho / 2 + 2 * out_halo; p.up_Wp = wo / 2 + 2 * out_halo; p.up_Cs = cout; p.up_pad = out_halo; }
   p.relu = relu; p.mode = deconv2x ? 1 : 0; p.out_f32 = out_f32;
   p.probe = g_conv_probe;
+  p.sat = g_op_sat;
   if (sa) {
     RS_CHECK(sa->wscale && !in2, RS_ERR_ARG, "split-operand conv: row scales missing (or a second K source, which the operator does not take)");
     p.split = 1; p.in_lo = sa->in_lo; p.w_lo = sa->w_lo; p.out_lo = sa->out_lo; p.res_lo = sa->res_lo; p.up_lo = sa->up_lo; p.wscale = sa->wscale;
@@ -1712,6 +1767,7 @@ static int op_conv2d(const void* in, const void* w, const float* bias, void* out
 }
 
 int rs_debug_set_conv_probe(void* buffer) { g_conv_probe = (long long*)buffer; return RS_OK; }
+int rs_op_set_saturation_counter(void* dev_u64) { g_op_sat = (unsigned long long*)dev_u64; return RS_OK; }
 
 int rs_op_conv2d(const void* in, const void* w, const float* bias, void* out, const void* residual, const void* upsample_add,
                  int n, int hi, int wi, int cin, int in_halo, int kh, int kw, int stride, int pad, int cout, int kpad,
@@ -1749,6 +1805,7 @@ int rs_op_bneck_tail(const void* t1, const void* w2, const float* b2, const void
   p.t1 = (const half_t*)t1; p.w2 = (const half_t*)w2; p.b2 = b2; p.w3p = (const half_t*)w3p; p.b3 = b3; p.x = (const half_t*)x; p.out = (half_t*)out;
   p.w1p = (const half_t*)w1p; p.b1 = b1; p.t1n = (half_t*)t1n; p.x0 = (const half_t*)x0; p.wsc = (const half_t*)wsc;
   p.M = n * h * w; p.H = h; p.W = w; p.Hp = h + 2; p.Wp = w + 2; p.CB = width / 64;
+  p.sat = g_op_sat;
   return launch_bneck_tail(p, (hipStream_t)stream);
 }
 
@@ -1765,6 +1822,7 @@ int rs_op_bneck_tail_split(const void* t1, int64_t t1_lo, const void* w2, const 
   p.x = (const half_t*)x; p.x_lo = x_lo; p.x0 = (const half_t*)x0; p.x0_lo = x0_lo; p.out = (half_t*)out; p.out_lo = out_lo;
   p.w1p = (const half_t*)w1p; p.w1_lo = 4ll * width * width; p.s1 = s1; p.b1 = b1; p.t1n = (half_t*)t1n; p.t1n_lo = t1n_lo;
   p.M = n * h * w; p.H = h; p.W = w; p.Hp = h + 2; p.Wp = w + 2; p.CB = width / 64;
+  p.sat = g_op_sat;
   return launch_bneck_tail_split(p, (hipStream_t)stream);
 }
 

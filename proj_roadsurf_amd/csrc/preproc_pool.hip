@@ -58,6 +58,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const PreprocParams p) 
   }
   half4 o;
   float of[4];
+  unsigned satc = 0;       // normalised values outside the fp16 range (common.h rs_sat_flush; the fp32 mode does not count)
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     o[c] = (half_t)0.f;
@@ -69,6 +70,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const PreprocParams p) 
       for (int q = 0; q < 4; ++q) if (q == cs) v = p.need_v ? (vacc[q] >> 22) : val[q];
       if (p.need_v) v = v < 0 ? 0 : (v > 255 ? 255 : v);
       const float f = rs_fdiv((float)v - p.mean[c], p.stdv[c]);
+      satc += rs_sat_bad(f);
       o[c] = (half_t)f;
       of[c] = f;
     }
@@ -85,6 +87,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const PreprocParams p) 
       *(half4*)(p.out + p.out_lo + oidx) = lo;
     }
   }
+  rs_sat_flush(p.out_f32 == 1 ? nullptr : p.sat, satc);
 }
 
 // Tile form of the same arithmetic: a block = 64 output columns x 16 output rows of one tile.  Pillow's tap ranges are monotone in the
@@ -130,6 +133,7 @@ __global__ __launch_bounds__(256) void preprocess_tile_kernel(const PreprocParam
   }
   const uint8_t* sb = (const uint8_t*)src;
   const int xoff = (xmin - cx0) * C;
+  unsigned satc = 0;       // normalised values outside the fp16 range (common.h rs_sat_flush; the fp32 mode does not count)
 #pragma unroll 1
   for (int it = 0; it < PP_ROWS / 4; ++it) {
     const int Y = Y0 + it * 4 + ly;                           // wave-uniform
@@ -184,6 +188,7 @@ __global__ __launch_bounds__(256) void preprocess_tile_kernel(const PreprocParam
         for (int q = 0; q < 4; ++q) if (q == cs) v = NV ? (vacc[q] >> 22) : val[q];
         if (NV) v = v < 0 ? 0 : (v > 255 ? 255 : v);
         const float f = rs_fdiv((float)v - p.mean[c], p.stdv[c]);
+        satc += rs_sat_bad(f);
         o[c] = (half_t)f;
         of[c] = f;
       }
@@ -200,6 +205,7 @@ __global__ __launch_bounds__(256) void preprocess_tile_kernel(const PreprocParam
       }
     }
   }
+  rs_sat_flush(p.out_f32 == 1 ? nullptr : p.sat, satc);
 }
 
 int launch_preprocess(const PreprocParams& p, hipStream_t s) {

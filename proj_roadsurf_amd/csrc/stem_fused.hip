@@ -113,6 +113,8 @@ __global__ __launch_bounds__(NT) void stem_pool_kernel(const StemPoolParams p) {
     const int i = px / CC, j = px - i * CC;
     const int cy = 2 * a0 - 1 + i, cx = 2 * b0 - 1 + j;
     const bool inside = cy >= 0 && cy < p.Hc && cx >= 0 && cx < p.Wc;
+    const bool own = inside && i > 0 && j > 0;
+    float mx = 0.f;          // saturation screen: the largest conv value of the pixel (ReLU leaves no NaN)
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
       half4 h;
@@ -120,10 +122,20 @@ __global__ __launch_bounds__(NT) void stem_pool_kernel(const StemPoolParams p) {
       for (int r = 0; r < 4; ++r) {
         float f = acc[b][mi][r] + bv[mi][r];
         f = f > 0.f ? f : 0.f;
+        mx = __builtin_fmaxf(mx, f);
         f = f > 65504.f ? 65504.f : f;
         h[r] = inside ? (half_t)f : (half_t)0.f;
       }
       if (!(DBG & 8)) *(half4*)(ol + px * OP + (mi * 16 + fq * 4) * 2) = h;
+    }
+    // saturation count (common.h rs_sat_flush), rare: every conv pixel once -- patch row / column 0 is the previous patch's last (or the padding)
+    if (own && mx > 65504.f) {
+      unsigned c = 0;
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) c += acc[b][mi][r] + bv[mi][r] > 65504.f ? 1u : 0u;
+      rs_sat_flush(p.sat, c);
     }
   }
   __syncthreads();
@@ -187,6 +199,7 @@ __global__ __launch_bounds__(NT, 3) void stem_pool_split_kernel(const StemPoolSp
   const int a0 = blockIdx.y * PR, b0 = blockIdx.x * PC, n = blockIdx.z;
   char* il = smem_s;
   char* ol = smem_s + S_IN;
+  unsigned satc = 0;                              // saturation count (common.h rs_sat_flush)
 
   // ---- input patch -> LDS, plane after plane (see stem_pool_kernel)
   {
@@ -251,11 +264,13 @@ __global__ __launch_bounds__(NT, 3) void stem_pool_split_kernel(const StemPoolSp
         const int i = px / CC, j = px - i * CC;
         const int cy = 2 * a0 - 1 + i, cx = 2 * b0 - 1 + j;
         const bool inside = cy >= 0 && cy < p.Hc && cx >= 0 && cx < p.Wc;
+        const bool own = inside && i > 0 && j > 0;          // saturation count: every conv pixel once (stem_pool_kernel)
         u32x4 key;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float f = acc[b][mb][r] * sv[r] + bv[r];
           f = f > 0.f ? f : 0.f;
+          satc += own ? rs_sat_bad(f) : 0u;
           f = f > 65504.f ? 65504.f : f;
           const half_t h = (half_t)f, l = (half_t)(f - (float)h);
           key[r] = inside ? pair_key(h, l) : pair_key((half_t)0.f, (half_t)0.f);
@@ -287,6 +302,7 @@ __global__ __launch_bounds__(NT, 3) void stem_pool_split_kernel(const StemPoolSp
       }
     }
   }
+  rs_sat_flush(p.sat, satc);
 }
 
 }  // namespace

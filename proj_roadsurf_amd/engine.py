@@ -31,6 +31,26 @@ class RsError(RuntimeError):
     pass
 
 
+class RsSaturationError(RsError):
+    """``Predictor(on_saturation="raise")``: a batch had activations clamped to the fp16 range.
+    ``saturation`` holds the batch's non-zero counts by stage."""
+
+    def __init__(self, message: str, saturation: Dict[str, int]):
+        super().__init__(message)
+        self.saturation = saturation
+
+
+class SaturationWarning(RuntimeWarning):
+    """``Predictor(on_saturation="warn")``, the default: a batch had activations clamped to the fp16 range."""
+
+
+def saturation_message(what: str, sat: Dict[str, int], top: int = 3) -> str:
+    """One line: the elements clamped to the fp16 range in ``what`` and the ``top`` stages with the largest counts."""
+    worst = sorted(sat.items(), key=lambda kv: -kv[1])[:top]
+    return (f"{what}: {sum(sat.values())} activations clamped to the fp16 range (+-65504) in {len(sat)} stage(s), largest: "
+            + ", ".join(f"{k} {v}" for k, v in worst) + " -- results may be wrong; precision='fp32' stores fp32 and never clamps")
+
+
 class RsSpec(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32), ("in_channels", C.c_int32), ("flip_channels", C.c_int32),
@@ -104,6 +124,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.rs_engine_set_profiling.argtypes = [vp, i32]
     lib.rs_debug_run_stages_matching.argtypes = [vp, C.c_char_p, i32]
     lib.rs_engine_stage_count.argtypes = [vp]
+    lib.rs_engine_saturation.argtypes = [vp, C.POINTER(C.c_int64), i32]
+    lib.rs_op_set_saturation_counter.argtypes = [vp]
     lib.rs_engine_stage_info.argtypes = [vp, i32, C.c_char_p, C.POINTER(C.c_double), i32p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.rs_engine_stage_kernel.argtypes = [vp, i32, C.c_char_p]
     lib.rs_engine_stage_variant.argtypes = [vp, i32]
@@ -572,6 +594,27 @@ class Engine:
                         "kernel": kn.value.decode()})
         return out
 
+    def saturation(self) -> Dict[str, int]:
+        """Elements clamped to the fp16 range, by stage, in the most recent forward whose results were fetched (``infer``, ``fetch``,
+        ``wait_results`` / ``fetch_wait``); stages with a zero count are left out."""
+        n = self.lib.rs_engine_stage_count(self._h)
+        counts = np.zeros(max(n, 1), np.int64)
+        rc = self.lib.rs_engine_saturation(self._h, counts.ctypes.data_as(C.POINTER(C.c_int64)), n)
+        if rc < 0:
+            _check(self.lib, rc, "rs_engine_saturation")
+        names = getattr(self, "_stage_names", None)
+        if names is None or len(names) != n:
+            buf = C.create_string_buffer(96)
+            names = []
+            for i in range(n):
+                self.lib.rs_engine_stage_info(self._h, i, buf, None, None, None, None)
+                names.append(buf.value.decode())
+            self._stage_names = names
+        out: Dict[str, int] = {}
+        for i in np.flatnonzero(counts[:n]):
+            out[names[i]] = out.get(names[i], 0) + int(counts[i])
+        return out
+
     def stage_variants(self) -> Dict[str, int]:
         """Conv tile variant each GEMM stage launched in its last call (numbering: include/rs_engine.h rs_op_conv_variant)."""
         name = C.create_string_buffer(96)
@@ -633,6 +676,8 @@ class LanePipeline:
                                   for _ in range(lanes - 1)]
         self.k = 0
         self._pending: Optional[Tuple[int, int, int]] = None     # shared form: (lane, tiles ptr, n) whose phase 2 is still to be enqueued
+        # saturation counts (Engine.saturation) of the batch ``run`` yielded last: set before the batch is yielded
+        self.last_saturation: Dict[str, int] = {}
 
     def lane_of_next(self) -> Engine:
         return self.engines[self.k % len(self.engines)]
@@ -669,6 +714,11 @@ class LanePipeline:
         shared stream:
             submit(k): upload(k), phase0(k), phase2(k-1) + fetch_async(k-1), phase1(k);   then collect + yield batch k-2."""
         L = len(self.engines)
+
+        def counted(eng: Engine, res: List[Instances]) -> List[Instances]:
+            # the lane's counts were published by its wait_results and stay until its next one: read them with the batch's results
+            self.last_saturation = eng.saturation()
+            return res
         inflight = []                               # (lane, n) of submitted batches not yet yielded
         T = self.timing = {"pull": 0.0, "wait_results": 0.0, "upload": 0.0, "enqueue": 0.0, "collect": 0.0, "batches": 0}
         clock = time.perf_counter
@@ -687,7 +737,7 @@ class LanePipeline:
             if L == 1:                              # one lane has one set of host buffers: no look-ahead
                 e.infer_device(e.upload_async(np.ascontiguousarray(tiles)), n)
                 e.fetch_async(n)
-                yield e.fetch_wait(n)
+                yield counted(e, e.fetch_wait(n))
                 continue
             done = None
             if len(inflight) == L:
@@ -708,7 +758,7 @@ class LanePipeline:
                 res = None
                 if done is not None:                # the lane's previous results leave its pinned buffers BEFORE the next copy into them is enqueued
                     t0 = clock()
-                    res = self.engines[done[0]].collect_results(done[1])
+                    res = counted(self.engines[done[0]], self.engines[done[0]].collect_results(done[1]))
                     T["collect"] += clock() - t0
                 t1 = clock()
                 e.fetch_async(n)
@@ -729,7 +779,7 @@ class LanePipeline:
             inflight.append((lane, n))
             if done is not None:                    # host-side collection overlaps the batches just enqueued; this lane's next
                 t0 = clock()
-                res = self.engines[done[0]].collect_results(done[1])      # fetch_async comes one submit later
+                res = counted(self.engines[done[0]], self.engines[done[0]].collect_results(done[1]))      # fetch_async comes one submit later
                 T["collect"] += clock() - t0
                 yield res
         if self._pending is not None:
@@ -738,7 +788,7 @@ class LanePipeline:
             self.engines[pl].fetch_async(pn)
             self._pending = None
         for ol, on in inflight:
-            yield self.engines[ol].fetch_wait(on)
+            yield counted(self.engines[ol], self.engines[ol].fetch_wait(on))
 
     def sync(self) -> None:
         self.flush()
@@ -753,11 +803,31 @@ class LanePipeline:
 class Predictor:
     """Drop-in for ``detectron2.engine.DefaultPredictor``: ``predictor(im_bgr) -> {"instances": Instances}``.
     One two-lane pipeline is built per tile shape on first use (tilesets are single-shape: 256^2/512^2 z18 tiles,
-    R:config/config_obj_detec.yaml:45).  ``predict_batch`` is the batched, streaming form the CLI shim uses."""
+    R:config/config_obj_detec.yaml:45).  ``predict_batch`` is the batched, streaming form the CLI shim uses.
 
-    def __init__(self, spec: EngineSpec, weights: Dict[str, np.ndarray], max_batch: int = 16, device: int = 0, lanes: int = 2):
+    ``on_saturation``: what a batch whose activations were clamped to the fp16 range (precision fp16 / split) does --
+    "warn" (default) issues one ``SaturationWarning`` per affected batch, "raise" raises ``RsSaturationError`` once the batch's results
+    are collected, "ignore" does neither.  ``last_saturation`` holds, in every case, the non-zero counts by stage of the last result handed out:
+    the image of ``__call__``, the whole ``predict_batch`` call (summed over its batches), the batch ``predict_stream`` yielded."""
+
+    def __init__(self, spec: EngineSpec, weights: Dict[str, np.ndarray], max_batch: int = 16, device: int = 0, lanes: int = 2,
+                 on_saturation: str = "warn"):
+        if on_saturation not in ("warn", "raise", "ignore"):
+            raise ValueError(f"on_saturation must be 'warn', 'raise' or 'ignore', got {on_saturation!r}")
         self.spec, self.weights, self.max_batch, self.device, self.lanes = spec, weights, max_batch, device, lanes
+        self.on_saturation = on_saturation
+        self.last_saturation: Dict[str, int] = {}
         self._pipes: Dict[Tuple[int, int, int], LanePipeline] = {}
+
+    def _saturated(self, sat: Dict[str, int], what: str) -> None:
+        self.last_saturation = sat
+        if not sat or self.on_saturation == "ignore":
+            return
+        msg = saturation_message(what, sat)
+        if self.on_saturation == "raise":
+            raise RsSaturationError(msg, sat)
+        import warnings
+        warnings.warn(msg, SaturationWarning, stacklevel=3)
 
     def _pipe(self, shape: Tuple[int, int, int]) -> LanePipeline:
         if shape not in self._pipes:
@@ -778,12 +848,15 @@ class Predictor:
         if original_image.ndim != 3:
             raise ValueError("expected an HWC image")
         eng = self._pipe(tuple(original_image.shape)).engines[0]
-        return {"instances": eng.infer(original_image[None])[0]}
+        out = {"instances": eng.infer(original_image[None])[0]}
+        self._saturated(eng.saturation(), "image")
+        return out
 
     def predict_batch(self, images: Sequence[np.ndarray]) -> List[Dict[str, Instances]]:
         """Any number of images; runs of equal shape are cut into batches of ``max_batch`` and streamed through the lanes
         (``LanePipeline.run``: uploads, forwards and result copies of consecutive batches overlap)."""
         out: List[Dict[str, Instances]] = []
+        total: Dict[str, int] = {}                 # saturation counts of the whole call
         i = 0
         while i < len(images):
             shape = tuple(images[i].shape)
@@ -791,9 +864,15 @@ class Predictor:
             while j < len(images) and tuple(images[j].shape) == shape:
                 j += 1
             chunks = (np.stack(images[k:min(k + self.max_batch, j)]) for k in range(i, j, self.max_batch))
-            for res in self._pipe(shape).run(chunks):
+            pipe = self._pipe(shape)
+            for res in pipe.run(chunks):
+                first = len(out)
                 out.extend({"instances": r} for r in res)
+                for k, v in pipe.last_saturation.items():
+                    total[k] = total.get(k, 0) + v
+                self._saturated(pipe.last_saturation, f"batch of images {first}..{len(out) - 1}")
             i = j
+        self.last_saturation = total
         return out
 
     def predict_stream(self, batches) -> "Iterator[List[Dict[str, Instances]]]":
@@ -804,6 +883,7 @@ class Predictor:
         batches ahead of what is yielded."""
         it = iter(batches)
         carry: List[Any] = []            # a batch read ahead that does not fit the running pipeline
+        k = 0                            # batches yielded
 
         def next_batch():
             return carry.pop() if carry else next(it, None)
@@ -815,6 +895,7 @@ class Predictor:
             shapes = {tuple(im.shape) for im in first}
             if len(shapes) != 1 or len(first) > self.max_batch:
                 yield self.predict_batch(first)          # mixed shapes inside one batch: no streaming for it
+                k += 1
                 continue
             shape = shapes.pop()
 
@@ -825,7 +906,10 @@ class Predictor:
                         return
                     yield b if isinstance(b, np.ndarray) else np.stack(b)      # a decoded batch in shared memory is used in place
                     b = next_batch()
-            for res in self._pipe(shape).run(run_of_shape()):
+            pipe = self._pipe(shape)
+            for res in pipe.run(run_of_shape()):
+                self._saturated(pipe.last_saturation, f"batch {k} of the stream")
+                k += 1
                 yield [{"instances": r} for r in res]
 
     def close(self) -> None:

@@ -169,7 +169,18 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         log.info("inference in %s", {"fp32": "reference precision (fp32 on the matrix cores)", "split": "reference-equivalent precision (hi + lo fp16 operand planes, three products)",
                                      "fp16": "fp16 operands / fp32 accumulate"}[args.precision])
     from .engine import Predictor      # fails loudly without librs_engine.so / a HIP device
-    predictor = Predictor(spec, W, max_batch=args.batch, device=local_rank, lanes=args.lanes)
+    # saturation (activations clamped to the fp16 range) is reported once per dataset below, not per batch
+    predictor = Predictor(spec, W, max_batch=args.batch, device=local_rank, lanes=args.lanes, on_saturation="ignore")
+
+    class _Batch(list):       # one batch's results with the saturation counts of its forward, for finish()
+        saturation: Dict[str, int] = {}
+
+    def with_saturation(out: List[Any]) -> "_Batch":
+        b = _Batch(out)
+        b.saturation = dict(predictor.last_saturation)
+        return b
+
+    saturated: List[Tuple[str, Dict[str, int]]] = []      # (first tile of the batch, counts) of every batch that saturated
 
     # decode (PIL), GPU forward and vectorisation (C++, rs_vectorize_masks) overlap across batches (shard.run_sharded)
     busy = {"decode": 0.0, "predict": 0.0, "vectorise": 0.0}      # seconds summed over the threads that ran each stage
@@ -184,7 +195,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         t = time.perf_counter()
         out = predictor.predict_batch(ims)
         busy["predict"] += time.perf_counter() - t
-        return out
+        return with_saturation(out)
 
     def predict_stream(batches):
         # the whole dataset through one lane pipeline: batch k+1 uploads and runs while batch k's results come back
@@ -195,11 +206,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             busy["predict"] += time.perf_counter() - t
             if out is None:
                 return
-            yield out
+            yield with_saturation(out)
 
     def finish(entries: Sequence[dict], outs: List[Any]) -> List[Any]:
         # per tile: (GeoPackage rows, bbox[, GeoJSON features]) -- masks -> polygons -> RDP -> georeferenced blobs in C++
         t_fin = time.perf_counter()
+        if getattr(outs, "saturation", None) and entries:
+            saturated.append((entries[0]["file_name"], outs.saturation))
         res = []
         for e, o in zip(entries, outs):
             ext, epsg_t = tile_extent(meta, e["file_name"])
@@ -265,12 +278,25 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 # the COCO sizes (or the band count of the first tile) did not hold for every file: this dataset again on the thread path
                 log.warning("%s: %s -- running the dataset again with thread decoding", dataset, ex)
                 predictor.close()
-                predictor = Predictor(spec, W, max_batch=args.batch, device=local_rank, lanes=args.lanes)
+                saturated.clear()
+                predictor = Predictor(spec, W, max_batch=args.batch, device=local_rank, lanes=args.lanes, on_saturation="ignore")
                 per_tile = run_sharded(images, predict_batch, args.batch, rank, world, gather=False, prepare=prepare, finish=finish,
                                        workers=args.host_workers, predict_stream=predict_stream, prepared_source=None)
         except BaseException:
             _close_pools(pools)
             raise
+        if saturated:
+            order = {e["file_name"]: i for i, e in enumerate(images)}
+            total: Dict[str, int] = {}
+            for _, sat in saturated:
+                for k, v in sat.items():
+                    total[k] = total.get(k, 0) + v
+            first = min((f for f, _ in saturated), key=lambda f: order.get(f, len(order)))
+            top = ", ".join(f"{k} {v}" for k, v in sorted(total.items(), key=lambda kv: -kv[1])[:3])
+            log.warning("%s: %d batch(es) had activations clamped to the fp16 range (first affected batch starts at tile %s); largest counts: %s "
+                        "-- detections of those batches may be wrong, --precision fp32 never clamps", dataset, len(saturated),
+                        os.path.basename(first), top)
+            saturated.clear()
         # Every rank writes the rows of ITS block of tiles into its own GeoPackage shard (rank 0: the output file itself); rank 0 then appends the
         # other ranks' shards in rank order = tile order with SQLite ATTACH -- no row travels between processes ("each rank ...
         # its own output shard; host merges shards into one GeoPackage per dataset").  The ranks of one node share the working directory.
