@@ -296,8 +296,14 @@ int rs_op_conv2d_wgrad_f32(const void* dy, const void* in, float* grad, const fl
                        int in_halo, int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits,
                        void* stream);
 
-/* Greedy NMS over `segments` independent lists of up to 1024 boxes in priority order
- * (torchvision.ops.nms semantics: IoU > thresh suppresses). keep: [segments][cap] 0/1. */
+/* Greedy NMS over `segments` independent lists of up to `cap` (<= 2048) boxes in priority order
+ * (torchvision.ops.nms: suppress when the fp32 IoU > thresh). keep: [segments][cap] 0/1.
+ * The kernels compare the fp32 IoU with `thresh` in fp32.  torchvision compares it with a double threshold t; a
+ * caller who wants that gets it by passing the largest float <= t (for a float IoU x, x > t exactly when x exceeds
+ * that float).  RsSpec.rpn_nms_thresh and nms_thresh_test are read the same way; the Python binding
+ * (make_rs_spec) writes them so.
+ * Dispatch follows the engine's: the suppression mask lives in global memory at cap > 1024, and at cap <= 1024
+ * with <= 32 segments (rows shared by several workgroups, the scan in a second launch); in LDS otherwise. */
 int rs_op_nms(const float* boxes, const int32_t* counts, const uint8_t* valid, uint8_t* keep,
               int segments, int cap, float thresh, void* stream);
 

@@ -283,7 +283,9 @@ def stable_sort_desc(scores: Tensor) -> Tensor:
 
 def nms_sorted_np(boxes: np.ndarray, thresh: float) -> np.ndarray:
     """Greedy NMS over boxes already in priority order [EXT tv: csrc/ops/cpu/nms_kernel.cpp and
-    cuda/nms_kernel.cu ``devIoU``]: suppress j>i when inter/(areaA+areaB-inter) > thresh, all fp32.
+    cuda/nms_kernel.cu ``devIoU``]: suppress j>i when inter/(areaA+areaB-inter) > thresh.  The IoU is fp32;
+    the threshold is torchvision's ``float iou_threshold`` (a TorchScript float, i.e. a C++ double), so the
+    comparison is the fp32 IoU against the double threshold, not against float32(thresh).
     Returns bool keep mask in the given order."""
     n = boxes.shape[0]
     keep = np.ones(n, dtype=bool)
@@ -293,7 +295,7 @@ def nms_sorted_np(boxes: np.ndarray, thresh: float) -> np.ndarray:
     x1, y1, x2, y2 = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
     areas = (x2 - x1) * (y2 - y1)
     zero = np.float32(0)
-    t = np.float32(thresh)
+    t = float(thresh)
     for i in range(n):
         if not keep[i]:
             continue
@@ -306,7 +308,7 @@ def nms_sorted_np(boxes: np.ndarray, thresh: float) -> np.ndarray:
         inter = w * h
         with np.errstate(divide="ignore", invalid="ignore"):
             ovr = inter / (areas[i] + areas[i + 1:] - inter)
-        keep[i + 1:] &= ~(ovr > t)
+        keep[i + 1:] &= ~(ovr.astype(np.float64) > t)
     return keep
 
 

@@ -61,6 +61,19 @@ __device__ __forceinline__ int sort_size(unsigned c, int lo, int hi) {
   return n;
 }
 
+// assign_boxes_to_levels [EXT d2: modeling/poolers.py]: floor(4 + log2(v)) clamped to [2,5], minus 2, where
+// v = sqrt(area) / 224 + 1e-8 (fp32) and the log2 and the add are fp32 too.  The level is monotone in v, so it is decided by
+// three fp32 cut points: the smallest v of levels 1, 2, 3.  They are NOT 0.5, 1, 2: for v a few ulps below each power of two,
+// log2(v) rounds to within half an ulp of the integer, and 4 + log2(v) rounds up onto it.  The cut points below are those of a
+// correctly rounded log2 (tests/test_oracle_kat.py re-derives them); a device log2f is not used, since at 0.49999994 and
+// 0.49999997 the fp32 sum lies on or next to a rounding tie and a 1-ulp log2 error changes the level.
+__device__ __forceinline__ int fpn_level(float v) {
+  const float c1 = __uint_as_float(0x3efffffeu);   // 0.49999994
+  const float c2 = __uint_as_float(0x3f7fffffu);   // 0.99999994
+  const float c3 = __uint_as_float(0x3ffffffdu);   // 1.9999996
+  return v >= c3 ? 3 : (v >= c2 ? 2 : (v >= c1 ? 1 : 0));
+}
+
 // Box2BoxTransform.apply_deltas for one box, one delta quadruple (fp32, detectron2 op order).
 __device__ __forceinline__ void apply_deltas(const float b[4], const float d[4], float wx, float wy, float ww, float wh,
                                              float scale_clamp, float out[4]) {
@@ -452,7 +465,7 @@ __global__ __launch_bounds__(1024) void rpn_merge_kernel(const RpnMergeParams p)
       const float* b = p.prop_boxes + ((long long)n * p.cap + i) * 4;
       const float area = (b[2] - b[0]) * (b[3] - b[1]);
       const float v = rs_fdiv(sqrtf(area), 224.0f) + 1e-8f;
-      const unsigned lvl = v >= 2.0f ? 3u : (v >= 1.0f ? 2u : (v >= 0.5f ? 1u : 0u));
+      const unsigned lvl = (unsigned)fpn_level(v);
       unsigned yq = (unsigned)fmaxf(b[1], 0.f), xq = (unsigned)fmaxf(b[0], 0.f);
       yq = yq > 8191u ? 8191u : yq; xq = xq > 8191u ? 8191u : xq;
       const unsigned k32 = (lvl << 26) | (yq << 13) | xq;                 // ascending in (level, y, x) ...
@@ -507,11 +520,10 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const RoiAlignParams p) 
   }
   const float* r = p.rois + (long long)slot * 4;
   const float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3];
-  // assign_boxes_to_levels: floor(4 + log2(sqrt(area)/224 + 1e-8)) clamped to [2,5]; evaluated with
-  // exact power-of-two thresholds instead of log2 (identical wherever log2 is exact at 2^k).
+  // assign_boxes_to_levels: floor(4 + log2(sqrt(area)/224 + 1e-8)) clamped to [2,5], by its fp32 cut points (fpn_level)
   const float area = (x2 - x1) * (y2 - y1);
   const float v = rs_fdiv(sqrtf(area), 224.0f) + 1e-8f;
-  int lvl = v >= 2.0f ? 3 : (v >= 1.0f ? 2 : (v >= 0.5f ? 1 : 0));
+  int lvl = fpn_level(v);
   if (lvl > p.nlevels - 1) lvl = p.nlevels - 1;
   if (p.out_level) { if (tid == 0) p.out_level[entry] = lvl; }
   const int H = p.H[lvl], W = p.W[lvl];
@@ -683,7 +695,7 @@ __global__ __launch_bounds__(256, SPLIT ? 4 : 6) void roi_align_win_kernel(const
   const float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3];
   const float area = (x2 - x1) * (y2 - y1);
   const float v = rs_fdiv(sqrtf(area), 224.0f) + 1e-8f;
-  int lvl = v >= 2.0f ? 3 : (v >= 1.0f ? 2 : (v >= 0.5f ? 1 : 0));
+  int lvl = fpn_level(v);
   if (lvl > p.nlevels - 1) lvl = p.nlevels - 1;
   if (p.out_level) { if (tid == 0) p.out_level[entry] = lvl; }
   const int H = p.H[lvl], W = p.W[lvl];
@@ -849,7 +861,7 @@ __global__ __launch_bounds__(256) void roi_align_bwd_kernel(const RoiAlignParams
   const float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3];
   const float area = (x2 - x1) * (y2 - y1);
   const float v = rs_fdiv(sqrtf(area), 224.0f) + 1e-8f;
-  int lvl = v >= 2.0f ? 3 : (v >= 1.0f ? 2 : (v >= 0.5f ? 1 : 0));
+  int lvl = fpn_level(v);
   if (lvl > p.nlevels - 1) lvl = p.nlevels - 1;
   const int H = p.H[lvl], W = p.W[lvl];
   const float sc = p.scale[lvl];
@@ -1059,7 +1071,7 @@ __global__ __launch_bounds__(64) void roi_bwd_prep_kernel(const RoiAlignParams p
   const float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3];
   const float area = (x2 - x1) * (y2 - y1);
   const float v = rs_fdiv(sqrtf(area), 224.0f) + 1e-8f;
-  int lvl = v >= 2.0f ? 3 : (v >= 1.0f ? 2 : (v >= 0.5f ? 1 : 0));
+  int lvl = fpn_level(v);
   if (lvl > p.nlevels - 1) lvl = p.nlevels - 1;
   const int H = p.H[lvl], W = p.W[lvl];
   const float sc = p.scale[lvl];

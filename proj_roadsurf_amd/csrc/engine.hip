@@ -1915,8 +1915,13 @@ int rs_op_nms(const float* boxes, const int32_t* counts, const uint8_t* valid, u
   NmsParams p = {};
   p.boxes = boxes; p.count = counts; p.valid = valid; p.keep = keep; p.cap = cap; p.thresh = thresh;
   void* scratch = nullptr;
-  if (cap > 1024) {            // training capacity: the suppression mask lives in global memory
+  // the engine's dispatch: training capacity always keeps the suppression mask in global memory; at cap <= 1024 the engine passes
+  // scratch too, and launch_nms takes the global-memory form for <= 32 segments, the LDS form above that
+  if (cap > 1024) {
     RS_HIP(hipMalloc(&scratch, (size_t)segments * 2048 * 32 * 8));
+    p.scratch = (unsigned long long*)scratch;
+  } else if (segments <= 32) {
+    RS_HIP(hipMalloc(&scratch, (size_t)segments * 1024 * 16 * 8));
     p.scratch = (unsigned long long*)scratch;
   }
   int rc = launch_nms(p, segments, (hipStream_t)stream);
@@ -1933,6 +1938,7 @@ int rs_op_roi_align(const void* const feats[4], const int32_t heights[4], const 
   for (int l = 0; l < nlevels; ++l) { p.feat[l] = (const half_t*)feats[l]; p.H[l] = heights[l]; p.W[l] = widths[l]; p.scale[l] = scales[l]; }
   p.nlevels = nlevels; p.C = 256; p.rois = rois; p.S = n_rois; p.slots_per_image = rois_per_image;
   p.out = (half_t*)out; p.P = P; p.out_pad = out_halo; p.out_level = levels_out;
+  rs_debug_reload();                                         // RS_ROI_WINDOW: the operator tests switch between the two forward forms
   return launch_roi_align(p, (hipStream_t)stream);
 }
 

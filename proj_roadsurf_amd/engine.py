@@ -194,6 +194,17 @@ def cell_anchor_table(spec: EngineSpec) -> np.ndarray:
     return out
 
 
+def nms_thresh_f32(t: float) -> float:
+    """The largest float32 <= t.  torchvision's nms compares the fp32 IoU with its threshold as a C++ double
+    (``ovr > iou_threshold``); the kernels compare in fp32 (include/rs_engine.h, rs_op_nms), and for a float IoU x,
+    x > t exactly when x > nms_thresh_f32(t).  Rounding t to nearest instead would keep a pair whose IoU is
+    float32(t) whenever float32(t) > t (0.3, 0.4, 0.6, ...)."""
+    f = np.float32(t)
+    if float(f) > t:
+        f = np.nextafter(f, np.float32(-np.inf))
+    return float(f)
+
+
 def make_rs_spec(spec: EngineSpec) -> RsSpec:
     spec.check_supported()
     s = RsSpec()
@@ -222,9 +233,9 @@ def make_rs_spec(spec: EngineSpec) -> RsSpec:
         s.rpn_bbox_reg_weights[i] = spec.rpn_bbox_reg_weights[i]
         s.box_reg_weights[i] = spec.box_reg_weights[i]
     s.rpn_pre_nms_topk, s.rpn_post_nms_topk = spec.rpn_pre_nms_topk_test, spec.rpn_post_nms_topk_test
-    s.rpn_nms_thresh, s.rpn_min_size = spec.rpn_nms_thresh, spec.rpn_min_size
+    s.rpn_nms_thresh, s.rpn_min_size = nms_thresh_f32(spec.rpn_nms_thresh), spec.rpn_min_size
     s.num_classes = spec.num_classes
-    s.score_thresh_test, s.nms_thresh_test = spec.score_thresh_test, spec.nms_thresh_test
+    s.score_thresh_test, s.nms_thresh_test = spec.score_thresh_test, nms_thresh_f32(spec.nms_thresh_test)
     s.detections_per_image = spec.detections_per_image
     s.box_fc_dim, s.box_pooler_resolution = spec.box_fc_dim, spec.box_pooler_resolution
     s.mask_on, s.mask_pooler_resolution = int(spec.mask_on), spec.mask_pooler_resolution

@@ -86,57 +86,257 @@ def test_backbone_features(small):
         assert rel <= 1.5e-2, f"{name}: rel L2 err {rel}"
 
 
-def test_rpn_stage_exact(small):
-    spec, W, tiles, eng, _ = small
-    O = _oracle()
+# ---------------------------------------------------------------- stage checks on an engine after a forward of n tiles
+FEAT_SCALES = [1 / 4, 1 / 8, 1 / 16, 1 / 32]
+
+
+def _rpn_inputs(spec, eng, n):
     A = spec.num_anchors
     logits, deltas = [], []
-    for l in range(5):
-        h = torch.from_numpy(eng.tensor(f"rpn_head{l + 2}", n=3))          # (3,H,W,16) fp32
+    for l in range(len(spec.rpn_in_features)):
+        h = torch.from_numpy(eng.tensor(f"rpn_head{l + 2}", n=n))          # (n,H,W,16) fp32
         logits.append(h[..., :A].permute(0, 3, 1, 2).contiguous())
         deltas.append(h[..., A:5 * A].permute(0, 3, 1, 2).contiguous())
+    return logits, deltas
+
+
+def check_rpn_stage(spec, eng, n):
+    """RPN top-k sets and order per (image, level), proposal count, logits (exact) and boxes (1e-3 px), against the oracle on the
+    engine's own head outputs.  Returns the oracle's per-image result."""
+    O = _oracle()
+    logits, deltas = _rpn_inputs(spec, eng, n)
     nh, nw, _, _ = eng.net_shape()
-    ref = O.rpn_proposals(spec, logits, deltas, [(nh, nw)] * 3, nms_trick=False)
-    pb = eng.tensor("proposal_boxes", n=3)
-    pl = eng.tensor("proposal_logits", n=3)
-    pc = eng.tensor("proposal_count", n=3)
-    cidx = eng.tensor("rpn_cand_index", n=3)
-    ccount = eng.tensor("rpn_cand_count", n=3)
-    for i in range(3):
+    ref = O.rpn_proposals(spec, logits, deltas, [(nh, nw)] * n, nms_trick=False)
+    pb = eng.tensor("proposal_boxes", n=n)
+    pl = eng.tensor("proposal_logits", n=n)
+    pc = eng.tensor("proposal_count", n=n)
+    cidx = eng.tensor("rpn_cand_index", n=n)
+    ccount = eng.tensor("rpn_cand_count", n=n)
+    for i in range(n):
         # top-k selection (index work): exact
         off = 0
-        for l in range(5):
+        for l in range(len(logits)):
             k = int(ccount[i, l])
             want = ref[i]["pre_nms"]["anchor_idx"][off:off + k].numpy()
             assert np.array_equal(cidx[i, l, :k], want), f"image {i} level {l}: top-k anchor set/order differs"
             off += k
-        n = int(pc[i])
-        assert n == ref[i]["boxes"].shape[0], f"image {i}: {n} proposals vs {ref[i]['boxes'].shape[0]}"
+        m = int(pc[i])
+        assert m == ref[i]["boxes"].shape[0], f"image {i}: {m} proposals vs {ref[i]['boxes'].shape[0]}"
         # logits are copied, not computed: exact.  Boxes go through expf: 1e-3 px.
-        assert np.array_equal(pl[i, :n], ref[i]["logits"].numpy())
-        assert np.abs(pb[i, :n] - ref[i]["boxes"].numpy()).max() <= 1e-3
+        assert np.array_equal(pl[i, :m], ref[i]["logits"].numpy())
+        assert np.abs(pb[i, :m] - ref[i]["boxes"].numpy()).max() <= 1e-3
+    return ref
+
+
+def rpn_topk_ties(spec, eng, n):
+    """Per (image, level): (logits equal to the k-th largest, of them taken) where the level has more anchors than k."""
+    logits, _ = _rpn_inputs(spec, eng, n)
+    ccount = eng.tensor("rpn_cand_count", n=n)
+    cidx = eng.tensor("rpn_cand_index", n=n)
+    out = {}
+    for i in range(n):
+        for l, lg in enumerate(logits):
+            v = lg[i].permute(1, 2, 0).flatten().numpy()
+            k = int(ccount[i, l])
+            if k == 0 or k >= v.size:
+                continue
+            kth = v[cidx[i, l, k - 1]]
+            out[(i, l)] = (int((v == kth).sum()), int((v[cidx[i, l, :k]] == kth).sum()))
+    return out
+
+
+def nms_form(segments):
+    """The NMS kernel's form for a launch of `segments` segments at cap 1024 (launch_nms; the engine always passes scratch)."""
+    return "global" if segments <= 32 else "lds"
+
+
+def check_rpn_nms(spec, eng, n):
+    """rpn_cand_keep == the oracle's NMS over rpn_cand_boxes / rpn_cand_valid of each (image, level): exact."""
+    O = _oracle()
+    cb, cv = eng.tensor("rpn_cand_boxes", n=n), eng.tensor("rpn_cand_valid", n=n)
+    ck, cc = eng.tensor("rpn_cand_keep", n=n), eng.tensor("rpn_cand_count", n=n)
+    for i in range(n):
+        for l in range(cc.shape[1]):
+            c = int(cc[i, l])
+            v = cv[i, l, :c].astype(bool)
+            want = np.zeros(c, bool)
+            want[np.nonzero(v)[0][O.nms_sorted_np(cb[i, l, :c][v], spec.rpn_nms_thresh)]] = True
+            assert np.array_equal(ck[i, l, :c].astype(bool), want), f"image {i} level {l}: RPN NMS keep flags differ"
+    return nms_form(n * cc.shape[1])
+
+
+def check_box_nms(spec, eng, n):
+    """box_seg_keep == the oracle's NMS over box_seg_boxes of each (image, class): exact."""
+    O = _oracle()
+    sb, sk, sc = eng.tensor("box_seg_boxes", n=n), eng.tensor("box_seg_keep", n=n), eng.tensor("box_seg_count", n=n)
+    for i in range(n):
+        for k in range(sc.shape[1]):
+            c = int(sc[i, k])
+            want = O.nms_sorted_np(sb[i, k, :c], spec.nms_thresh_test)
+            assert np.array_equal(sk[i, k, :c].astype(bool), want), f"image {i} class {k}: box NMS keep flags differ"
+    return nms_form(n * sc.shape[1])
+
+
+def check_levels(eng, n):
+    """box_roi_level == oracle.assign_levels of the proposals: exact."""
+    O = _oracle()
+    pb, pc, lv = eng.tensor("proposal_boxes", n=n), eng.tensor("proposal_count", n=n), eng.tensor("box_roi_level", n=n)
+    for i in range(n):
+        m = int(pc[i])
+        assert np.array_equal(lv[i, :m], O.assign_levels(torch.from_numpy(pb[i, :m]), 2, 5).numpy()), f"image {i}: FPN level assignment must be exact"
+
+
+def _roi_grid(box, P, sc, H, W):
+    """(gh, gw) of torchvision's adaptive sampling and the feature-cell window [y0, y1) x [x0, x1) the RoI's samples can touch."""
+    f32 = np.float32
+    x1, y1, x2, y2 = (f32(v) for v in box)
+    sw, sh = f32(x1 * f32(sc) - f32(0.5)), f32(y1 * f32(sc) - f32(0.5))
+    ew, eh = f32(x2 * f32(sc) - f32(0.5)), f32(y2 * f32(sc) - f32(0.5))
+    gh = max(int(np.ceil(float(f32(f32(eh - sh) / f32(P))))), 0)
+    gw = max(int(np.ceil(float(f32(f32(ew - sw) / f32(P))))), 0)
+    y0, x0 = int(np.clip(np.floor(sh), 0, H - 1)), int(np.clip(np.floor(sw), 0, W - 1))
+    yb, xb = int(np.clip(np.floor(eh) + 2, 1, H)), int(np.clip(np.floor(ew) + 2, 1, W))
+    return gh, gw, (y0, max(yb, y0 + 1)), (x0, max(xb, x0 + 1))
+
+
+def _check_pooled(O, feats_i, box, lvl, P, got, precision, ratios):
+    """One RoI: fp16 -- the existing bound, 2e-3 * max(1, max|ref|) on the fp32 oracle; split / fp32 -- the oracle in float64 on
+    the engine's own maps and the bound of the kernels' operation order:
+    ((gh+2)(gw+2) + gh + gw + 4) * 2^-24 * max|F in the window| + s * |ref|, s = 2^-22 (two fp16 planes) or 2^-24 (fp32)."""
+    F_ = feats_i[lvl]
+    H, W = F_.shape[1:]
+    if precision == "fp16":
+        ref = O.roi_align_one(torch.from_numpy(F_), torch.from_numpy(box), P, FEAT_SCALES[lvl])
+        assert float((got - ref).abs().max()) <= 2e-3 * max(1.0, float(ref.abs().max()))
+        return
+    ref = O.roi_align_one(torch.from_numpy(F_).double(), torch.from_numpy(box), P, FEAT_SCALES[lvl]).double()
+    gh, gw, (y0, y1), (x0, x1) = _roi_grid(box, P, FEAT_SCALES[lvl], H, W)
+    fmax = float(np.abs(F_[:, y0:y1, x0:x1]).max()) if gh and gw else 0.0
+    s = 2.0 ** -22 if precision == "split" else 2.0 ** -24
+    bound = ((gh + 2) * (gw + 2) + gh + gw + 4) * 2.0 ** -24 * fmax + s * ref.abs()
+    err = (got.double() - ref).abs()
+    assert bool((err <= bound).all()), (box.tolist(), lvl, gh, gw, float(err.max()), float((err / bound.clamp_min(1e-30)).max()))
+    ratios.append(float((err / bound.clamp_min(1e-30)).max()))
+
+
+def _feats_of_image(eng, n, i, cache):
+    if "maps" not in cache:
+        cache["maps"] = [eng.tensor(f"p{l}", n=n) for l in (2, 3, 4, 5)]
+    return [np.ascontiguousarray(m[i].transpose(2, 0, 1)).astype(np.float32) for m in cache["maps"]]
+
+
+def _sample(rng, m, boxes, lv, P, eng_maps_hw, per_image):
+    """per_image RoIs with a fixed seed, plus every RoI whose sampling window exceeds the weight table (g > 21: the per-sample
+    fallback of roi_align_win_kernel)."""
+    pick = set(rng.choice(m, size=min(m, per_image), replace=False).tolist()) if m else set()
+    for r in range(m):
+        H, W = eng_maps_hw[lv[r]]
+        gh, gw, _, _ = _roi_grid(boxes[r], P, FEAT_SCALES[lv[r]], H, W)
+        if max(gh, gw) > 21:
+            pick.add(r)
+    return sorted(pick)
+
+
+def check_roi_align_box(spec, eng, n, precision, per_image=40, ratios=None):
+    """box RoIAlign of sampled proposals (at their oracle level) against the oracle on the engine's own FPN maps."""
+    O = _oracle()
+    ratios = [] if ratios is None else ratios
+    pb, pc = eng.tensor("proposal_boxes", n=n), eng.tensor("proposal_count", n=n)
+    PC = pb.shape[1]
+    P = spec.box_pooler_resolution
+    pooled = eng.tensor("box_pooled", strip_halo=False)        # (NB*PC, P, P, 256)
+    rng = np.random.default_rng(0)
+    cache = {}
+    for i in range(n):
+        m = int(pc[i])
+        feats_i = _feats_of_image(eng, n, i, cache)
+        lv = O.assign_levels(torch.from_numpy(pb[i, :m]), 2, 5).numpy()
+        for r in _sample(rng, m, pb[i], lv, P, [f.shape[1:] for f in feats_i], per_image):
+            got = torch.from_numpy(pooled[i * PC + r].astype(np.float32)).permute(2, 0, 1)
+            _check_pooled(O, feats_i, pb[i, r], lv[r], P, got, precision, ratios)
+    return ratios
+
+
+def check_roi_align_mask(spec, eng, dets, n, precision, per_image=40, ratios=None):
+    """mask RoIAlign of the detections (compact entries, image by image) against the oracle on the engine's own FPN maps."""
+    O = _oracle()
+    ratios = [] if ratios is None else ratios
+    dn = eng.tensor("det_boxes_net", n=n)
+    mp = eng.tensor("mask_pooled", strip_halo=True)
+    P = spec.mask_pooler_resolution
+    rng = np.random.default_rng(1)
+    cache = {}
+    e = 0
+    for i, d in enumerate(dets[:n]):
+        m = len(d)
+        if m == 0:
+            continue
+        feats_i = _feats_of_image(eng, n, i, cache)
+        lv = O.assign_levels(torch.from_numpy(dn[i, :m]), 2, 5).numpy()
+        if precision == "fp16":
+            pick = [r for r in range(m) if r % 7 == 0]
+        else:
+            pick = _sample(rng, m, dn[i], lv, P, [f.shape[1:] for f in feats_i], per_image)
+        for r in pick:
+            got = torch.from_numpy(mp[e + r].astype(np.float32)).permute(2, 0, 1)
+            _check_pooled(O, feats_i, dn[i, r], lv[r], P, got, precision, ratios)
+        e += m
+    return ratios
+
+
+def check_box_postprocess(spec, eng, dets, n, tile_hw):
+    """fast_rcnn_inference_single_image + detector_postprocess on the engine's own box-head output: detection count and
+    classes exact, scores 2e-6, boxes 1e-3 px (tile) / 2e-3 px (network input)."""
+    O = _oracle()
+    K = spec.num_classes
+    nh, nw, _, _ = eng.net_shape()
+    pred = torch.from_numpy(eng.tensor("box_pred", n=n))
+    pb = torch.from_numpy(eng.tensor("proposal_boxes", n=n))
+    pc = eng.tensor("proposal_count", n=n)
+    dn = eng.tensor("det_boxes_net", n=n)
+    for i in range(n):
+        m = int(pc[i])
+        probs = F.softmax(pred[i, :m, :K + 1], dim=-1)
+        dec = O.apply_deltas(pred[i, :m, K + 1:5 * K + 1], pb[i, :m], spec.box_reg_weights, spec.scale_clamp)
+        ref = O.fast_rcnn_inference_single_image(spec, dec, probs, (nh, nw), nms_trick=False)
+        fin = O.detector_postprocess(ref, (nh, nw), tile_hw[0], tile_hw[1])
+        d = dets[i]
+        assert len(d) == fin["boxes"].shape[0], f"image {i}: {len(d)} detections vs {fin['boxes'].shape[0]}"
+        assert np.array_equal(d.pred_classes, fin["classes"].numpy())
+        if len(d):
+            assert np.abs(d.scores - fin["scores"].numpy()).max() <= 2e-6
+            assert np.abs(d.pred_boxes - fin["boxes"].numpy()).max() <= 1e-3
+            assert np.abs(dn[i, :len(d)] - ref["boxes"].numpy()[: len(d)]).max() <= 2e-3
+
+
+def check_mask_paste(spec, dets, tile_hw, images=None):
+    """paste: oracle grid_sample on the engine's own probabilities and boxes; <= 1e-4 of the pixels + 2 differ."""
+    O = _oracle()
+    for i, d in enumerate(dets):
+        if len(d) == 0 or (images is not None and i not in images):
+            continue
+        ref = O.paste_masks(torch.from_numpy(d.mask_probs)[:, None], torch.from_numpy(d.pred_boxes), tile_hw[0], tile_hw[1],
+                            spec.mask_threshold).numpy()
+        gm = d.pred_masks
+        assert gm.shape == ref.shape
+        mism = np.logical_xor(gm, ref).sum()
+        assert mism <= 1e-4 * ref.size + 2, f"{mism} pasted-mask pixels differ"
+
+
+def test_rpn_stage_exact(small):
+    spec, W, tiles, eng, _ = small
+    check_rpn_stage(spec, eng, 3)
+
+
+def test_rpn_nms_stage_exact(small):
+    spec, W, tiles, eng, _ = small
+    assert check_rpn_nms(spec, eng, 3) == "global"
 
 
 def test_roi_align_box_stage(small):
     spec, W, tiles, eng, _ = small
-    O = _oracle()
-    feats = [torch.from_numpy(eng.tensor(f"p{l}", n=3).astype(np.float32)).permute(0, 3, 1, 2) for l in (2, 3, 4, 5)]
-    pb = eng.tensor("proposal_boxes", n=3)
-    pc = eng.tensor("proposal_count", n=3)
-    lv = eng.tensor("box_roi_level", n=3)
-    pooled = eng.tensor("box_pooled", strip_halo=False)        # (4*1024, 7, 7, 256)
-    scales = [1 / 4, 1 / 8, 1 / 16, 1 / 32]
-    rng = np.random.default_rng(0)
-    for i in range(3):
-        n = int(pc[i])
-        boxes = torch.from_numpy(pb[i, :n])
-        ref_lv = O.assign_levels(boxes, 2, 5).numpy()
-        assert np.array_equal(lv[i, :n], ref_lv), "FPN level assignment must be exact"
-        for r in rng.choice(n, size=min(n, 40), replace=False):
-            ref = O.roi_align_one(feats[ref_lv[r]][i], boxes[r], 7, scales[ref_lv[r]])
-            got = torch.from_numpy(pooled[i * 1024 + r].astype(np.float32)).permute(2, 0, 1)
-            # fp32 math on identical fp16 features, one fp16 rounding of the result
-            assert float((got - ref).abs().max()) <= 2e-3 * max(1.0, float(ref.abs().max()))
+    check_levels(eng, 3)
+    check_roi_align_box(spec, eng, 3, "fp16")
 
 
 def test_box_head_stage(small):
@@ -159,25 +359,12 @@ def test_box_head_stage(small):
 
 def test_box_postprocess_stage_exact(small):
     spec, W, tiles, eng, dets = small
-    O = _oracle()
-    K = spec.num_classes
-    nh, nw, _, _ = eng.net_shape()
-    pred = torch.from_numpy(eng.tensor("box_pred", n=3))
-    pb = torch.from_numpy(eng.tensor("proposal_boxes", n=3))
-    pc = eng.tensor("proposal_count", n=3)
-    dn = eng.tensor("det_boxes_net", n=3)
-    for i in range(3):
-        n = int(pc[i])
-        probs = F.softmax(pred[i, :n, :K + 1], dim=-1)
-        dec = O.apply_deltas(pred[i, :n, K + 1:5 * K + 1], pb[i, :n], spec.box_reg_weights, spec.scale_clamp)
-        ref = O.fast_rcnn_inference_single_image(spec, dec, probs, (nh, nw), nms_trick=False)
-        fin = O.detector_postprocess(ref, (nh, nw), 256, 256)
-        d = dets[i]
-        assert len(d) == fin["boxes"].shape[0], f"image {i}: {len(d)} detections vs {fin['boxes'].shape[0]}"
-        assert np.array_equal(d.pred_classes, fin["classes"].numpy())
-        assert np.abs(d.scores - fin["scores"].numpy()).max() <= 2e-6
-        assert np.abs(d.pred_boxes - fin["boxes"].numpy()).max() <= 1e-3
-        assert np.abs(dn[i, :len(d)] - ref["boxes"].numpy()[: len(d)]).max() <= 2e-3
+    check_box_postprocess(spec, eng, dets, 3, (256, 256))
+
+
+def test_box_nms_stage_exact(small):
+    spec, W, tiles, eng, _ = small
+    assert check_box_nms(spec, eng, 3) == "global"
 
 
 def test_mask_stage(small):
@@ -193,34 +380,81 @@ def test_mask_stage(small):
     got = np.concatenate([d.mask_probs for d in dets])
     # 6 fp16-rounded layers before the sigmoid: 2e-2 absolute on probabilities
     assert np.abs(got - probs[:, 0].numpy()).max() <= 2e-2
-    # paste: oracle grid_sample on the engine's own probabilities and boxes
-    for d in dets:
-        if len(d) == 0:
-            continue
-        ref = O.paste_masks(torch.from_numpy(d.mask_probs)[:, None], torch.from_numpy(d.pred_boxes), 256, 256, spec.mask_threshold).numpy()
-        gm = d.pred_masks
-        assert gm.shape == ref.shape
-        mism = np.logical_xor(gm, ref).sum()
-        assert mism <= 1e-4 * ref.size + 2, f"{mism} pasted-mask pixels differ"
+    check_mask_paste(spec, dets, (256, 256))
 
 
 def test_mask_roi_align_stage(small):
     spec, W, tiles, eng, dets = small
-    O = _oracle()
-    feats = [torch.from_numpy(eng.tensor(f"p{l}", n=3).astype(np.float32)).permute(0, 3, 1, 2) for l in (2, 3, 4, 5)]
-    dn = eng.tensor("det_boxes_net", n=3)
-    mp = eng.tensor("mask_pooled", strip_halo=True)
-    scales = [1 / 4, 1 / 8, 1 / 16, 1 / 32]
-    e = 0
-    for i, d in enumerate(dets):
-        boxes = torch.from_numpy(dn[i, :len(d)])
-        lv = O.assign_levels(boxes, 2, 5).numpy() if len(d) else []
-        for r in range(len(d)):
-            if r % 7 == 0:
-                ref = O.roi_align_one(feats[lv[r]][i], boxes[r], 14, scales[lv[r]])
-                got = torch.from_numpy(mp[e].astype(np.float32)).permute(2, 0, 1)
-                assert float((got - ref).abs().max()) <= 2e-3 * max(1.0, float(ref.abs().max()))
-            e += 1
+    check_roi_align_mask(spec, eng, dets, 3, "fp16")
+
+
+SMALL_SPEC = dict(num_classes=2, min_size_test=320, max_size_test=533, rpn_pre_nms_topk_test=300, rpn_post_nms_topk_test=300)
+
+
+def _tie_tiles(h, w):
+    """An all-zero tile, a tile with a constant no-data band over 40 % of it, and a synthetic scene."""
+    t = synthetic_tiles(3, h, w, 3, seed=91)
+    t[0] = 0
+    t[1, : int(0.4 * h)] = 0
+    return t
+
+
+# cell -> (precision, spec overrides, batch, tile side, tiles)
+STAGE_CELLS = {
+    "b_split_default_b16": ("split", {}, 16, 512, "synthetic"),
+    "c_split_default_b1_graph": ("split", {}, 1, 512, "synthetic"),
+    "d_fp32_small_b7": ("fp32", SMALL_SPEC, 7, 256, "synthetic"),
+    "e_fp16_small_k8_b5": ("fp16", dict(SMALL_SPEC, num_classes=8), 5, 256, "synthetic"),
+    "f_split_small_k1_ties": ("split", dict(SMALL_SPEC, num_classes=1), 3, 256, "ties"),
+}
+
+
+@pytest.mark.parametrize("cell", list(STAGE_CELLS))
+def test_stage_exact_across_configurations(gpu_required, cell):
+    """The stage checks of the fp16 `small` tests on the configurations the product runs: the split mode at
+    the bench configuration (batch 16: RPN NMS with the mask in LDS over 80 segments, top-k over 120 000 p2 anchors, the
+    detection cap) and at batch 1 through the hipGraph replay, the fp32 mode (per-sample roi_align_kernel; 35 RPN segments, LDS),
+    fp16 with 8 classes (40 box-NMS segments, LDS; det_merge at its class limit) and the split mode with one class on an
+    all-zero tile, a tile with a constant band and a scene, with the objectness weights zeroed so that logits tie exactly: at
+    least one (image, level) holds more logits equal to the k-th largest than the top-k takes, and the engine must take the
+    lower anchor indices first, as the oracle's stable sort does, through the top-k, the RPN NMS and the merge.  Index work is
+    exact; RoIAlign in split / fp32 is held to the bound of its operation order against a float64 oracle."""
+    precision, over, n, side, kind = STAGE_CELLS[cell]
+    spec = EngineSpec(**over).replace(precision=precision)
+    W = synthetic_weights(spec, seed=0)
+    if kind == "ties":
+        # objectness = its bias alone: every anchor of a type has the same logit in every image and level, so the top-k cut, the
+        # RPN NMS and the level merge all decide between equal scores (the random FPN maps alone never tie exactly: every
+        # position sees the zero padding of the deep layers)
+        W = dict(W)
+        k = "proposal_generator.rpn_head.objectness_logits.weight"
+        W[k] = W[k] * 0
+    tiles = _tie_tiles(side, side) if kind == "ties" else synthetic_tiles(max(n, 3), side, side, 3, seed=101)
+    eng = Engine(spec, W, (side, side, 3), max_batch=n)
+    try:
+        if n == 1:                                     # batch 1: warm-up and graph capture on other tiles, then the replay
+            for t in (2, 1):
+                eng.infer(tiles[t:t + 1], want_probs=True)
+        dets = eng.infer(tiles[:n], want_probs=True)
+        if kind == "ties":
+            ties = rpn_topk_ties(spec, eng, n)
+            assert any(eq > taken for eq, taken in ties.values()), ties
+        check_rpn_stage(spec, eng, n)
+        rpn_form = check_rpn_nms(spec, eng, n)
+        box_form = check_box_nms(spec, eng, n)
+        check_levels(eng, n)
+        rb = check_roi_align_box(spec, eng, n, precision)
+        rm = check_roi_align_mask(spec, eng, dets, n, precision)
+        check_box_postprocess(spec, eng, dets, n, (side, side))
+        check_mask_paste(spec, dets, (side, side), images=None if n <= 7 else set(range(0, n, 4)))
+        print(f"STAGE_CELL {cell}: rpn_nms={rpn_form} ({n * len(spec.rpn_in_features)} segments) box_nms={box_form} "
+              f"({n * spec.num_classes} segments) detections={[len(d) for d in dets]} "
+              f"roi_box_max_err_over_bound={max(rb) if rb else None} roi_mask_max_err_over_bound={max(rm) if rm else None} "
+              f"(box RoIs {len(rb)}, mask RoIs {len(rm)})")
+        if spec.num_classes == 8:
+            assert box_form == "lds"
+    finally:
+        eng.close()
 
 
 def test_end_to_end_small(small):
@@ -879,3 +1113,46 @@ def test_config3_4band_1024_tiles_batch8(gpu_required):
         assert fw["frac_matched"] >= 0.8 and bw["frac_matched"] >= 0.8, (fw, bw)
     finally:
         eng.close()
+
+
+_GRAPH_CHILD = r"""
+import sys, numpy as np
+sys.path.insert(0, sys.argv[1])
+from proj_roadsurf_amd.engine import Engine
+from proj_roadsurf_amd.spec import EngineSpec
+from proj_roadsurf_amd.weights import synthetic_weights
+from tests.util import synthetic_tiles
+spec = EngineSpec(precision=sys.argv[2])
+tiles = synthetic_tiles(4, 512, 512, 3, seed=4242)
+eng = Engine(spec, synthetic_weights(spec, seed=0), (512, 512, 3), max_batch=1)
+out = {}
+for k in range(4):                        # warm-up, capture, replay, replay -- each on a different tile
+    d = eng.infer(tiles[k:k + 1], want_probs=True)[0]
+    out.update({f"boxes{k}": d.pred_boxes, f"scores{k}": d.scores, f"classes{k}": d.pred_classes, f"packed{k}": d._packed,
+                f"probs{k}": d.mask_probs})
+eng.close()
+np.savez(sys.argv[3], **out)
+"""
+
+
+@pytest.mark.parametrize("precision", ["fp16", "split"])
+def test_graph_replay_equals_eager_masks_included(gpu_required, tmp_path, precision):
+    """Single-tile forwards at the default 512 x 512 spec through the captured hipGraph (RS_GRAPH_SMALL=1) and eagerly (=0), in
+    separate processes: boxes, scores, classes, mask probabilities and the packed masks of every forward -- warm-up, capture and
+    two replays, each on another tile -- are bit-identical."""
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = {}
+    for g in ("1", "0"):
+        path = str(tmp_path / f"graph{g}.npz")
+        p = subprocess.run([sys.executable, "-c", _GRAPH_CHILD, root, precision, path], env=dict(os.environ, RS_GRAPH_SMALL=g),
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        res[g] = dict(np.load(path))
+    assert res["1"].keys() == res["0"].keys()
+    assert sum(len(res["1"][f"boxes{k}"]) for k in range(4)) > 0
+    for key in res["1"]:
+        assert res["1"][key].dtype == res["0"][key].dtype and np.array_equal(res["1"][key], res["0"][key]), key

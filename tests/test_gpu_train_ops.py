@@ -225,7 +225,10 @@ def test_conv_dgrad_fpn_topdown_backward(gpu_required):
 def test_roi_align_backward_is_the_adjoint_of_forward(gpu_required, P):
     """RoIAlign is linear in the feature maps, so its backward is pinned by <roi_align(F), G> == <F, roi_align_bwd(G)>
     for random F, G (forward kernel: parity-tested against the oracle in test_gpu_engine.py).  Boxes cover all four
-    FPN levels, image borders (clamped / skipped samples) and an elongated one (per-sample fallback path)."""
+    FPN levels, image borders (clamped / skipped samples), an elongated one (per-sample fallback path) and, per image, boxes
+    just below the FPN level cut points (v = 0.49999994 .. 1.9999999, where floor(4 + log2(v)) is already the upper level):
+    a backward that assigned them another level than the forward would break the identity."""
+    from tests.util import fpn_level_boundary_boxes
     lib = load_library()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(P)
@@ -240,7 +243,10 @@ def test_roi_align_backward_is_the_adjoint_of_forward(gpu_required, P):
     side = torch.tensor([20.0, 60.0, 130.0, 250.0, 500.0, 33.0] * (n_img * rpi // 6))
     bw, bh = side.clone(), side.clone()
     bw[3], bh[3] = 900.0, 6.0                 # elongated: window larger than the LDS table
-    rois = torch.stack([cx - bw / 2, cy - bh / 2, cx + bw / 2, cy + bh / 2], 1).clamp(-20, 260).float().contiguous()
+    rois = torch.stack([cx - bw / 2, cy - bh / 2, cx + bw / 2, cy + bh / 2], 1).clamp(-20, 260).float()
+    edge = torch.from_numpy(fpn_level_boundary_boxes())
+    rois = torch.cat([rois.view(n_img, rpi, 4), edge.expand(n_img, -1, -1)], 1).reshape(-1, 4).contiguous()
+    rpi += edge.shape[0]
     rd = rois.to(dev)
     out = torch.zeros(n_img * rpi, P, P, 256, dtype=torch.float16, device=dev)
     G = (torch.randn(n_img * rpi, P, P, 256, generator=g) * 0.5).half()
@@ -273,7 +279,9 @@ def test_roi_align_backward_owner_computes_equals_atomics_and_is_reproducible(gp
     stores) against the float-atomic kernel of rounds 1-2 (RS_ROI_BWD_ATOMIC=1) on 2 x 512 clustered, overlapping RoIs over all four
     levels, image borders and one elongated box (left to the atomic kernel in both): the same gradient maps up to the fp32 summation
     order (a RoI's contribution to a cell is computed the same way in both), nothing in the halo, the maps ACCUMULATE (a second call
-    doubles them), and two runs of the new form agree BIT for bit -- the atomics did not."""
+    doubles them), and two runs of the new form agree BIT for bit -- the atomics did not.  Each image also holds boxes just below
+    the FPN level cut points (v = 0.49999994 .. 1.9999999, the upper level): the two forms assign levels in different kernels."""
+    from tests.util import fpn_level_boundary_boxes
     lib = load_library()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(77)
@@ -288,6 +296,9 @@ def test_roi_align_backward_owner_computes_equals_atomics_and_is_reproducible(gp
     bh = side * (0.6 + 0.8 * torch.rand(n_img * rpi, generator=g))
     bw[5], bh[5] = 900.0, 5.0                   # elongated: window larger than the tables
     rois = torch.stack([c[:, 0] - bw / 2, c[:, 1] - bh / 2, c[:, 0] + bw / 2, c[:, 1] + bh / 2], 1).clamp(-30, 630).float().contiguous()
+    edge = torch.from_numpy(fpn_level_boundary_boxes())
+    for n in range(n_img):
+        rois[n * rpi + 20:n * rpi + 20 + edge.shape[0]] = edge
     rd = rois.to(dev)
     Gd = (torch.randn(n_img * rpi, P, P, 256, generator=g) * 0.5).half().to(dev)
     vp4 = C.c_void_p * 4
@@ -609,30 +620,32 @@ def test_subsample_is_a_valid_uniform_sample(gpu_required):
 
 @pytest.mark.parametrize("cap", [1024, 2048])
 def test_nms_operator_both_capacities(gpu_required, cap):
-    """rs_op_nms == the oracle's greedy NMS (torchvision semantics, IoU > thr suppresses), exactly: capacity 1024 (inference, mask in
-    LDS) and 2048 (training, PRE_NMS_TOPK_TRAIN 2000, mask in global scratch); full, ragged, tiny and empty segments, a validity
+    """rs_op_nms == the oracle's greedy NMS (torchvision semantics, IoU > thr suppresses), exactly: capacity 1024 (inference) with
+    6 segments (mask in global memory, rows shared by several workgroups, as the engine runs <= 32 segments) and with 40 (mask in
+    LDS), and 2048 (training, PRE_NMS_TOPK_TRAIN 2000, mask in global scratch); full, ragged, tiny and empty segments, a validity
     mask, heavily overlapping boxes."""
     from oracle import maskrcnn_oracle as O
     lib = load_library()
     g = torch.Generator().manual_seed(cap)
-    counts = [cap, cap - 37, 700, 65, 1, 0]
-    S = len(counts)
-    boxes = torch.zeros(S, cap, 4)
-    valid = torch.ones(S, cap, dtype=torch.uint8)
-    for s_, c in enumerate(counts):
-        ctr = torch.rand(c, 2, generator=g) * 300                 # dense: many overlaps around the threshold
-        wh = torch.rand(c, 2, generator=g) * 80 + 20
-        boxes[s_, :c] = torch.cat([ctr - wh / 2, ctr + wh / 2], 1)
-    valid[1, ::7] = 0
-    bd, cd, vd = _dev(boxes), _dev(torch.tensor(counts, dtype=torch.int32)), _dev(valid)
-    keep = torch.full((S, cap), 7, dtype=torch.uint8, device=bd.device)
-    _check(lib, lib.rs_op_nms(_ptr(bd), _ptr(cd), _ptr(vd), _ptr(keep), S, cap, 0.7, None), "rs_op_nms")
-    torch.cuda.synchronize()
-    k = keep.cpu().numpy()
-    for s_, c in enumerate(counts):
-        b = boxes[s_, :c].numpy()
-        v = valid[s_, :c].numpy().astype(bool)
-        want = np.zeros(c, bool)
-        want[np.nonzero(v)[0][O.nms_sorted_np(b[v], 0.7)]] = True
-        assert np.array_equal(k[s_, :c].astype(bool), want), (cap, s_, c)
-        assert (k[s_, c:] == 0).all()
+    base = [cap, cap - 37, 700, 65, 1, 0]
+    for S in ((6, 40) if cap == 1024 else (6,)):
+        counts = [base[s_ % 6] for s_ in range(S)]
+        boxes = torch.zeros(S, cap, 4)
+        valid = torch.ones(S, cap, dtype=torch.uint8)
+        for s_, c in enumerate(counts):
+            ctr = torch.rand(c, 2, generator=g) * 300                 # dense: many overlaps around the threshold
+            wh = torch.rand(c, 2, generator=g) * 80 + 20
+            boxes[s_, :c] = torch.cat([ctr - wh / 2, ctr + wh / 2], 1)
+        valid[1, ::7] = 0
+        bd, cd, vd = _dev(boxes), _dev(torch.tensor(counts, dtype=torch.int32)), _dev(valid)
+        keep = torch.full((S, cap), 7, dtype=torch.uint8, device=bd.device)
+        _check(lib, lib.rs_op_nms(_ptr(bd), _ptr(cd), _ptr(vd), _ptr(keep), S, cap, 0.7, None), "rs_op_nms")
+        torch.cuda.synchronize()
+        k = keep.cpu().numpy()
+        for s_, c in enumerate(counts):
+            b = boxes[s_, :c].numpy()
+            v = valid[s_, :c].numpy().astype(bool)
+            want = np.zeros(c, bool)
+            want[np.nonzero(v)[0][O.nms_sorted_np(b[v], 0.7)]] = True
+            assert np.array_equal(k[s_, :c].astype(bool), want), (cap, S, s_, c)
+            assert (k[s_, c:] == 0).all()
