@@ -76,7 +76,16 @@ typedef struct rs_spec {
                                      "<layer>.ws" (fp16 [2][rows][Kpad]: hi rows then lo rows of the weight scaled by a power
                                      of two per row) and "<layer>.wsi" (fp32 [rows]: the inverse scales) blob entries.  The
                                      reference computes in fp32 (no SOLVER.AMP key, R:config/detectron2_config_3bands.yaml:268-305) */
+  int32_t batched_nms;            /* appended (RS_SPEC_SIZE_V1 = the struct without it, still accepted and read as 0).
+                                     0 = one NMS per category on the boxes as they are (RPN: per level; box head: per class);
+                                     1 = torchvision 0.11's batched_nms size rule, per image and NMS stage: when at most 1000 boxes enter the call
+                                     (boxes.numel() <= 4000) every box is shifted by category * (largest coordinate + 1) in fp32 before the IoUs
+                                     are computed, as `_batched_nms_coordinate_trick` does ([EXT tv: ops/boxes.py]); above 1000 as mode 0 */
 } rs_spec;
+#define RS_SPEC_SIZE_V1 ((int32_t)offsetof(rs_spec, batched_nms))
+/* The batched_nms mode a spec block selects: 0 for a caller compiled against the struct without the field (struct_size ==
+ * RS_SPEC_SIZE_V1), the field's value for the current struct; RS_ERR_ARG (negative) for any other struct_size or value.  Host only. */
+int rs_spec_batched_nms(const rs_spec* spec);
 
 /* Caller-allocated result block for n tiles, D = detections_per_image slots per tile.
  * Entries [0, count[i]) of tile i are valid and sorted by score (descending). Any pointer except
@@ -306,6 +315,16 @@ int rs_op_conv2d_wgrad_f32(const void* dy, const void* in, float* grad, const fl
  * with <= 32 segments (rows shared by several workgroups, the scan in a second launch); in LDS otherwise. */
 int rs_op_nms(const float* boxes, const int32_t* counts, const uint8_t* valid, uint8_t* keep,
               int segments, int cap, float thresh, void* stream);
+/* torchvision.ops.batched_nms over `images` independent calls of `segments_per_image` categories each: boxes / valid / keep
+ * [images][segments_per_image][cap]..., counts [images][segments_per_image].  rule = 0: rs_op_nms over all segments.  rule = 1: the
+ * size rule of rs_spec.batched_nms = 1, decided per image on the device from the number of valid boxes; launches and dispatch as in
+ * the engine's rpn.nms / box.nms stages; cap must exceed 1000 (the engine's are 1024 and 2048).  rs_op_batched_nms_decision is the
+ * same call and also hands out what the kernel decided (optional device buffers, rule = 1 only): rule_out [images][2] = {taken, boxes
+ * that enter the call}, unit_out [images] = fl(largest coordinate + 1) where taken, else 0 -- the engine's *_nms_rule / *_nms_unit. */
+int rs_op_batched_nms(const float* boxes, const int32_t* counts, const uint8_t* valid, uint8_t* keep, int images,
+                      int segments_per_image, int cap, float thresh, int rule, void* stream);
+int rs_op_batched_nms_decision(const float* boxes, const int32_t* counts, const uint8_t* valid, uint8_t* keep, int images,
+                               int segments_per_image, int cap, float thresh, int rule, int32_t* rule_out, float* unit_out, void* stream);
 
 /* ROIPooler + ROIAlign(aligned=True, sampling_ratio=0) over up to 4 NHWC fp16 levels (halo 1,
  * 256 channels). rois: [n_rois][4] image coordinates, batch_index = roi / rois_per_image.

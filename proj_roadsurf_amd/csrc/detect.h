@@ -36,6 +36,12 @@ struct NmsParams {
   unsigned long long* scratch;   // cap > 1024: [segments][2048][32] suppression-mask words in global memory
   int mode;                 // cap > 1024 only: 0 = mask build + scan in one workgroup, 1 = mask build only (gridDim.y workgroups share
                             // a segment's rows), 2 = scan only (after a mode-1 launch)
+  // torchvision's batched_nms size rule (rs_spec.batched_nms = 1; rule == null: off, NMS on the boxes as stored): segment s belongs to image
+  // s / group as its category s % group.  Every workgroup decides its image's rule in its prologue (nms_rule_decide) and, where taken,
+  // computes on boxes shifted by fl(category * unit); the image's first workgroup also writes the decision out for inspection.
+  int* rule;                // [images][2]: {rule taken, boxes that enter batched_nms}
+  float* unit;              // [images]: fl(max_coordinate + 1) where the rule is taken, else 0
+  int group;                // segments per image
 };
 
 struct RpnMergeParams {

@@ -287,6 +287,61 @@ __global__ __launch_bounds__(1024) void rpn_select_kernel(const RpnParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// torchvision.ops.batched_nms, the decision per image ([EXT tv: ops/boxes.py], 0.11): with boxes.numel() > 4000 one NMS per category,
+// else ONE NMS over boxes + category * (boxes.max() + 1).  A workgroup counts the boxes of its image that enter the call (valid entries of
+// all its segments) and, only where the rule is taken, reduces their largest coordinate.  Part of nms_kernel's prologue (NmsParams::rule):
+// every workgroup of an image repeats the image's reduction (at most 1000 boxes where it goes beyond the counts), which measured cheaper than
+// a launch of its own in front of the NMS.
+// Where this is not torch: fmaxf drops a NaN coordinate that boxes.max() would propagate (the RPN's valid flags already exclude non-finite
+// boxes; the box head's decoded, clipped boxes are finite unless the network's output is not); and entries beyond the capacity (count > cap)
+// are counted but carry no box, so callers keep cap >= 1001 in this mode (launch_nms checks it): the rule then cannot be taken with any such entry.
+// ---------------------------------------------------------------------------------------------
+// By all 1024 threads of a workgroup (uniform control flow, two barriers): returns rule taken, *total and *unit to every thread.
+__device__ __forceinline__ bool nms_rule_decide(const float* boxes, const int* count, const uint8_t* valid, int cap, int group, int img,
+                                                int* total_out, float* unit_out) {
+  __shared__ int s_cnt[16];
+  __shared__ float s_max[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long s0 = (long long)img * group;
+  int cnt = 0;
+  for (int g = 0; g < group; ++g) {
+    int raw = count[s0 + g];
+    if (raw < 0) raw = 0;
+    const int n = raw < cap ? raw : cap;
+    if (!valid) { if (tid == 0) cnt += raw; continue; }
+    if (tid == 0) cnt += raw - n;               // the uncapped count decides: entries beyond the capacity carry no flag
+    const uint8_t* v = valid + (s0 + g) * cap;
+    for (int i = tid; i < n; i += 1024) cnt += v[i] ? 1 : 0;
+  }
+  for (int o = 32; o; o >>= 1) cnt += __shfl_xor(cnt, o);
+  if (lane == 0) s_cnt[wave] = cnt;
+  __syncthreads();
+  int total = 0;
+  for (int w = 0; w < 16; ++w) total += s_cnt[w];
+  *total_out = total;
+  *unit_out = 0.f;
+  if (!(total >= 1 && total <= 1000)) return false;    // uniform.  !(boxes.numel() > 4000), and an empty call returns before the rule
+  float m = -INFINITY;
+  for (int g = 0; g < group; ++g) {
+    int n = count[s0 + g];
+    if (n > cap) n = cap;
+    const float* b4 = boxes + (s0 + g) * cap * 4;
+    const uint8_t* v = valid ? valid + (s0 + g) * cap : nullptr;
+    for (int i = tid; i < n; i += 1024) {
+      if (v && !v[i]) continue;
+      const float4 b = *(const float4*)(b4 + (long long)i * 4);
+      m = fmaxf(fmaxf(m, fmaxf(b.x, b.y)), fmaxf(b.z, b.w));
+    }
+  }
+  for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if (lane == 0) s_max[wave] = m;
+  __syncthreads();
+  for (int w = 0; w < 16; ++w) m = fmaxf(m, s_max[w]);
+  *unit_out = m + 1.0f;
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------
 // NMS over a segment of <= CAP boxes already in priority order.  CAP 1024: the suppression mask (128 KB) lives in LDS;
 // CAP 2048 (training, PRE_NMS_TOPK_TRAIN 2000): 512 KB per segment in a global scratch buffer (L2-resident).
 // ---------------------------------------------------------------------------------------------
@@ -310,8 +365,21 @@ __global__ __launch_bounds__(1024) void nms_kernel(const NmsParams p) {
   if (!(GM && p.mode == 1)) for (int i = tid; i < p.cap; i += 1024) keep[i] = 0;
   if (tid < WPR) sremoved[tid] = 0ull;
   __syncthreads();
+  // batched_nms's coordinate offsets (NmsParams::rule): `idxs.to(boxes) * (max_coordinate + 1)` is one rounded product, `boxes + offsets[:, None]`
+  // four rounded adds; areas and IoUs then come from the shifted values.  The boxes in memory stay as they are.
+  bool shift = false;
+  float off = 0.f;
+  if (p.rule && !(GM && p.mode == 2)) {         // (the scan launch reads no box)
+    const int img = s / p.group, g = s - img * p.group;
+    int total;
+    float unit;
+    shift = nms_rule_decide(p.boxes, p.count, p.valid, p.cap, p.group, img, &total, &unit);
+    if (shift) off = (float)g * unit;
+    if (g == 0 && blockIdx.y == 0 && tid == 0) { p.rule[2 * img] = shift ? 1 : 0; p.rule[2 * img + 1] = total; p.unit[img] = unit; }
+  }
   for (int ti = tid; ti < n; ti += 1024) {
-    const float4 b = *(const float4*)(boxes + ti * 4);
+    float4 b = *(const float4*)(boxes + ti * 4);
+    if (shift) { b.x = b.x + off; b.y = b.y + off; b.z = b.z + off; b.w = b.w + off; }
     sbox[ti] = b;
     sarea[ti] = (b.z - b.x) * (b.w - b.y);
     if (valid && !valid[ti]) atomicOr(&sremoved[ti >> 6], 1ull << (ti & 63));
@@ -1631,6 +1699,8 @@ int launch_nms(const NmsParams& p, int segments, hipStream_t s) {
     done = true;
   }
   RS_CHECK(p.cap > 0 && p.cap <= 2048 && (p.cap <= 1024 || p.scratch), RS_ERR_ARG, "nms: capacity %d (more than 1024 boxes need NmsParams::scratch)", p.cap);
+  RS_CHECK(!p.rule || (p.unit && p.group >= 1 && segments % p.group == 0), RS_ERR_ARG, "nms: %d segments in groups of %d", segments, p.group);
+  RS_CHECK(!p.rule || p.cap > 1000, RS_ERR_ARG, "nms: the batched_nms size rule needs a capacity above 1000 boxes per segment, got %d", p.cap);
   NmsParams q = p;
   q.debug = rs_debug().nms_debug;
   // few segments (images x levels / classes) and a quadratic mask build: with one workgroup per segment most of the chip idles, so the rows of a

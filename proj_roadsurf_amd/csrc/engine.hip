@@ -860,6 +860,17 @@ int rs_engine::build() {
   rp.img_h = (float)net_h; rp.img_w = (float)net_w;
   rp.wx = S.rpn_bbox_reg_weights[0]; rp.wy = S.rpn_bbox_reg_weights[1]; rp.ww = S.rpn_bbox_reg_weights[2]; rp.wh = S.rpn_bbox_reg_weights[3];
   rp.scale_clamp = S.scale_clamp; rp.min_size = S.rpn_min_size;
+  // rs_spec.batched_nms = 1: the NMS stage decides torchvision's size rule per image in its own prologue (NmsParams::rule) and leaves the decision
+  // in two tensors.  Decided on the device: launches, grids and a captured graph are the same for both outcomes and for both modes.
+  auto add_nms_rule = [&](const char* head, NmsParams* np, int group) -> int {
+    int rc2;
+    if ((rc2 = alloc((void**)&np->rule, (size_t)NB * 2 * 4))) return rc2;
+    if ((rc2 = alloc((void**)&np->unit, (size_t)NB * 4))) return rc2;
+    reg(std::string(head) + "_nms_rule", np->rule, DT_I32, {NB, 2}, 0);
+    reg(std::string(head) + "_nms_unit", np->unit, DT_F32, {NB}, 0);
+    np->group = group;
+    return RS_OK;
+  };
   uint8_t* cand_keep = nullptr;
   if ((rc = alloc((void**)&rp.cand_boxes, (size_t)NB * L * 1024 * 16))) return rc;
   if ((rc = alloc((void**)&rp.cand_scores, (size_t)NB * L * 1024 * 4))) return rc;
@@ -885,6 +896,7 @@ int rs_engine::build() {
     np.thresh = S.rpn_nms_thresh;
     // suppression masks in global memory for launches of few segments (batch 1-3: launch_nms shares a segment's mask build between workgroups)
     if ((rc = alloc((void**)&np.scratch, (size_t)(NB * L < 32 ? NB * L : 32) * 1024 * 16 * 8))) return rc;
+    if (S.batched_nms) { if ((rc = add_nms_rule("rpn", &np, L))) return rc; }
     Stage st;
     st.name = "rpn.nms";
     st.fn = [np, L](int n, hipStream_t s) { return launch_nms(np, n * L, s); };
@@ -1013,6 +1025,7 @@ int rs_engine::build() {
     NmsParams np = {};
     np.boxes = bc.seg_boxes; np.count = bc.seg_count; np.valid = nullptr; np.keep = seg_keep; np.cap = 1024; np.thresh = S.nms_thresh_test;
     if ((rc = alloc((void**)&np.scratch, (size_t)(NB * K < 32 ? NB * K : 32) * 1024 * 16 * 8))) return rc;
+    if (S.batched_nms) { if ((rc = add_nms_rule("box", &np, K))) return rc; }
     Stage st;
     st.name = "box.nms";
     st.fn = [np, K](int n, hipStream_t s) { return launch_nms(np, n * K, s); };
@@ -1356,10 +1369,20 @@ int rs_memcpy_h2d(void* dst, const void* src, size_t n) {
   return RS_OK;
 }
 
+int rs_spec_batched_nms(const rs_spec* spec) {
+  RS_CHECK(spec, RS_ERR_ARG, "null argument");
+  if (spec->struct_size == RS_SPEC_SIZE_V1) return 0;
+  RS_CHECK(spec->struct_size == (int32_t)sizeof(rs_spec), RS_ERR_ARG, "rs_spec size mismatch: caller %d, library %d (or %d without batched_nms)",
+           spec->struct_size, (int)sizeof(rs_spec), (int)RS_SPEC_SIZE_V1);
+  RS_CHECK(spec->batched_nms == 0 || spec->batched_nms == 1, RS_ERR_ARG, "rs_spec.batched_nms %d (0 = per category, 1 = torchvision's size rule)", spec->batched_nms);
+  return spec->batched_nms;
+}
+
 int rs_engine_create(const rs_spec* spec, const void* weights, size_t nbytes, int device_ordinal, int max_batch,
                      int tile_h, int tile_w, int tile_c, void* stream, rs_engine** out) {
   RS_CHECK(spec && weights && out, RS_ERR_ARG, "null argument");
-  RS_CHECK(spec->struct_size == (int32_t)sizeof(rs_spec), RS_ERR_ARG, "rs_spec size mismatch: caller %d, library %d", spec->struct_size, (int)sizeof(rs_spec));
+  const int nms_mode = rs_spec_batched_nms(spec);     // checks struct_size: the current struct, or the one that ends before batched_nms (mode 0)
+  if (nms_mode < 0) return nms_mode;
   RS_CHECK(max_batch >= 1 && tile_h >= 32 && tile_w >= 32, RS_ERR_ARG, "bad batch/tile shape");
   int ndev = 0;
   RS_HIP(hipGetDeviceCount(&ndev));
@@ -1367,7 +1390,9 @@ int rs_engine_create(const rs_spec* spec, const void* weights, size_t nbytes, in
   RS_CHECK(device_ordinal >= 0 && device_ordinal < ndev, RS_ERR_ARG, "device %d of %d", device_ordinal, ndev);
   RS_HIP(hipSetDevice(device_ordinal));
   rs_engine* e = new rs_engine();
-  e->spec = *spec;
+  memcpy(&e->spec, spec, (size_t)spec->struct_size);     // a caller's block may end before batched_nms
+  e->spec.struct_size = (int32_t)sizeof(rs_spec);
+  e->spec.batched_nms = nms_mode;
   e->device = device_ordinal;
   e->max_batch = max_batch; e->tile_h = tile_h; e->tile_w = tile_w; e->tile_c = tile_c;
   rs_debug_reload();
@@ -1926,6 +1951,40 @@ int rs_op_nms(const float* boxes, const int32_t* counts, const uint8_t* valid, u
   }
   int rc = launch_nms(p, segments, (hipStream_t)stream);
   if (scratch) { (void)hipStreamSynchronize((hipStream_t)stream); (void)hipFree(scratch); }
+  return rc;
+}
+
+int rs_op_batched_nms(const float* boxes, const int32_t* counts, const uint8_t* valid, uint8_t* keep, int images, int segments_per_image,
+                      int cap, float thresh, int rule, void* stream) {
+  return rs_op_batched_nms_decision(boxes, counts, valid, keep, images, segments_per_image, cap, thresh, rule, nullptr, nullptr, stream);
+}
+
+int rs_op_batched_nms_decision(const float* boxes, const int32_t* counts, const uint8_t* valid, uint8_t* keep, int images, int segments_per_image,
+                               int cap, float thresh, int rule, int32_t* rule_out, float* unit_out, void* stream) {
+  RS_CHECK(boxes && counts && keep && images > 0 && segments_per_image > 0, RS_ERR_ARG, "bad argument");
+  RS_CHECK(cap >= 1 && cap <= 2048, RS_ERR_ARG, "cap %d outside [1,2048]", cap);
+  RS_CHECK(rule == 0 || rule == 1, RS_ERR_ARG, "rule %d (0 = per category, 1 = torchvision's size rule)", rule);
+  const int segments = images * segments_per_image;
+  RS_CHECK(rule || (!rule_out && !unit_out), RS_ERR_ARG, "rule 0 takes no decision");
+  if (!rule) return rs_op_nms(boxes, counts, valid, keep, segments, cap, thresh, stream);
+  RS_CHECK(cap > 1000, RS_ERR_ARG, "cap %d: the size rule needs a capacity above 1000 boxes per segment", cap);
+  hipStream_t s = (hipStream_t)stream;
+  NmsParams p = {};
+  p.boxes = boxes; p.count = counts; p.valid = valid; p.keep = keep; p.cap = cap; p.thresh = thresh;
+  void *scratch = nullptr, *dec = nullptr;
+  RS_HIP(hipMalloc(&dec, (size_t)images * 12));
+  // the suppression mask as in rs_op_nms (= the engine's dispatch)
+  const size_t sbytes = cap > 1024 ? (size_t)segments * 2048 * 32 * 8 : (segments <= 32 ? (size_t)segments * 1024 * 16 * 8 : 0);
+  if (sbytes && hipMalloc(&scratch, sbytes) != hipSuccess) { (void)hipFree(dec); rs_set_error("hipMalloc(%zu)", sbytes); return RS_ERR_HIP; }
+  p.scratch = (unsigned long long*)scratch;
+  p.rule = (int*)dec; p.unit = (float*)((char*)dec + (size_t)images * 8); p.group = segments_per_image;
+  int rc = launch_nms(p, segments, s);
+  // the decision as nms_kernel's prologue left it (the engine's rpn_nms_rule / rpn_nms_unit tensors)
+  if (!rc && rule_out && hipMemcpyAsync(rule_out, p.rule, (size_t)images * 8, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = RS_ERR_HIP;
+  if (!rc && unit_out && hipMemcpyAsync(unit_out, p.unit, (size_t)images * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = RS_ERR_HIP;
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(dec);
+  if (scratch) (void)hipFree(scratch);
   return rc;
 }
 

@@ -766,6 +766,15 @@ int rs_trainer::build_box_training() {
     t_nms.boxes = t_rp.cand_boxes; t_nms.count = t_rp.cand_count; t_nms.valid = t_rp.cand_valid; t_nms.keep = keepb; t_nms.cap = CAPT;
     t_nms.thresh = S.rpn_nms_thresh;
     if ((rc = alloc((void**)&t_nms.scratch, (size_t)N * L * CAPT * (CAPT / 64) * 8))) return rc;
+    if (S.batched_nms) {
+      // find_top_rpn_proposals calls the same batched_nms in training: at most 1000 valid candidates per image take the shifted form
+      // (out of reach at PRE_NMS_TOPK_TRAIN 2000 x 5 levels on real maps; rs_trainer_set_rpn_topk and small inputs get there)
+      if ((rc = alloc((void**)&t_nms.rule, (size_t)N * 2 * 4))) return rc;
+      if ((rc = alloc((void**)&t_nms.unit, (size_t)N * 4))) return rc;
+      reg("train_rpn_nms_rule", t_nms.rule, DT_I32, {N, 2}, 0);
+      reg("train_rpn_nms_unit", t_nms.unit, DT_F32, {N}, 0);
+      t_nms.group = L;
+    }
     t_merge = RpnMergeParams{};
     t_merge.cand_boxes = t_rp.cand_boxes; t_merge.cand_scores = t_rp.cand_scores; t_merge.keep = keepb; t_merge.cand_count = t_rp.cand_count;
     t_merge.L = L; t_merge.cap = PC; t_merge.cand_cap = CAPT;

@@ -16,7 +16,7 @@ from typing import Any, Dict, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .spec import EngineSpec
+from .spec import BATCHED_NMS_MODES, EngineSpec
 from .weights import pack_weights
 
 _LIB: Optional[C.CDLL] = None
@@ -67,8 +67,12 @@ class RsSpec(C.Structure):
         ("box_fc_dim", C.c_int32), ("box_pooler_resolution", C.c_int32),
         ("mask_on", C.c_int32), ("mask_pooler_resolution", C.c_int32), ("mask_num_conv", C.c_int32),
         ("mask_conv_dim", C.c_int32), ("mask_threshold", C.c_float), ("scale_clamp", C.c_float),
-        ("precision", C.c_int32),
+        ("precision", C.c_int32), ("batched_nms", C.c_int32),
     ]
+
+
+# sizeof(rs_spec) before batched_nms was appended (RS_SPEC_SIZE_V1): the library still accepts it and reads the mode as 0
+RS_SPEC_SIZE_V1 = RsSpec.batched_nms.offset
 
 
 class RsDets(C.Structure):
@@ -143,6 +147,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.rs_op_conv2d_dgrad.argtypes = [vp] * 7 + [i32] * 14 + [vp]
     lib.rs_op_conv2d_wgrad.argtypes = [vp, vp, vp, vp] + [i32] * 13 + [vp]
     lib.rs_op_nms.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, vp]
+    lib.rs_op_batched_nms.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_float, i32, vp]
+    lib.rs_op_batched_nms_decision.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_float, i32, vp, vp, vp]
+    lib.rs_spec_batched_nms.argtypes = [C.POINTER(RsSpec)]
     lib.rs_op_roi_align.argtypes = [C.POINTER(vp), i32p, i32p, f32p, i32, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.rs_op_roi_align_bwd.argtypes = [C.POINTER(vp), i32p, i32p, f32p, i32, vp, i32, i32, i32, i32, vp, vp]
     f32 = C.c_float
@@ -242,6 +249,7 @@ def make_rs_spec(spec: EngineSpec) -> RsSpec:
     s.mask_num_conv, s.mask_conv_dim = spec.mask_num_conv, spec.mask_conv_dim
     s.mask_threshold, s.scale_clamp = spec.mask_threshold, spec.scale_clamp
     s.precision = {"fp16": 0, "fp32": 1, "split": 2}[spec.precision]
+    s.batched_nms = BATCHED_NMS_MODES.index(spec.batched_nms)
     return s
 
 

@@ -29,7 +29,7 @@ import yaml
 from .decode_pool import DecodePool, TileShapeError, read_tile, tile_header_shape
 from .gpkg import GpkgWriter
 from .shard import run_sharded
-from .spec import load_d2_yaml
+from .spec import BATCHED_NMS_HELP, load_d2_yaml
 from .vectorize import instances_to_features, instances_to_gpkg_rows
 from .weights import infer_num_classes, load_checkpoint, synthetic_weights
 
@@ -101,7 +101,7 @@ def host_pool_sizes(host_workers: Optional[int], decode_procs: Optional[int], ve
     return hw, (auto if decode_procs is None else decode_procs), (auto if vector_threads is None else vector_threads), share
 
 
-def main(argv: Optional[Sequence[str]] = None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("config_file", help="YAML with a 'make_detections.py' section (R:config/config_obj_detec.yaml)")
     ap.add_argument("--batch", type=int, default=16, help="tiles per engine call")
@@ -121,7 +121,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--tagged-samples", type=int, default=10,
                     help="tagged preview PNGs per dataset in sample_tagged_img_subfolder (0 = none)")
     ap.add_argument("--max-tiles", type=int, default=0, help="debug: only the first N tiles of every dataset")
-    args = ap.parse_args(argv)
+    ap.add_argument("--batched-nms", choices=("per-category", "torchvision"), default="per-category", help=BATCHED_NMS_HELP)
+    return ap
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    args = build_parser().parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s", stream=sys.stderr)
     args.host_workers, args.decode_procs, args.vector_threads, share = host_pool_sizes(args.host_workers, args.decode_procs, args.vector_threads)
     logging.getLogger("make_detections").info("host pools of this rank: %d decode processes, %d host threads, %d vectoriser threads (%d cores for the rank)",
@@ -168,6 +173,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         spec = spec.replace(precision=args.precision)
         log.info("inference in %s", {"fp32": "reference precision (fp32 on the matrix cores)", "split": "reference-equivalent precision (hi + lo fp16 operand planes, three products)",
                                      "fp16": "fp16 operands / fp32 accumulate"}[args.precision])
+    spec = spec.replace(batched_nms=args.batched_nms.replace("-", "_"))
+    log.info("batched_nms: %s", {"per_category": "per-category (one NMS per FPN level / class)",
+                                 "torchvision": "torchvision (size rule: shifted coordinates at <= 1000 boxes per image)"}[spec.batched_nms])
     from .engine import Predictor      # fails loudly without librs_engine.so / a HIP device
     # saturation (activations clamped to the fp16 range) is reported once per dataset below, not per batch
     predictor = Predictor(spec, W, max_batch=args.batch, device=local_rank, lanes=args.lanes, on_saturation="ignore")

@@ -42,6 +42,14 @@ def _get(d: Dict[str, Any], path: str, default: Any) -> Any:
     return _lit(cur)
 
 
+BATCHED_NMS_MODES = ("per_category", "torchvision")     # EngineSpec.batched_nms; rs_spec.batched_nms = the index
+# --batched-nms of make_detections.py and train_model.py
+BATCHED_NMS_HELP = ("how both NMS stages read torchvision.ops.batched_nms.  per-category (default): one NMS per FPN level / class on the boxes as they "
+                    "are; torchvision: torchvision 0.11's size rule as the reference runs it -- an image with at most 1000 boxes in the call gets ONE "
+                    "NMS over boxes shifted by category * (largest coordinate + 1) in fp32, which can decide a pair at the IoU threshold the other way "
+                    "(DESIGN.md section 4)")
+
+
 @dataclass(frozen=True)
 class EngineSpec:
     # ---- INPUT (R:26-30)
@@ -105,8 +113,17 @@ class EngineSpec:
     # ---- engine option (not a detectron2 key): "fp16" = production MFMA path, "fp32" = the reference's arithmetic on the fp32 matrix cores,
     # "split" = reference-equivalent arithmetic on the fp16 matrix cores (hi + lo operand planes, three products; inference engines)
     precision: str = "fp16"
+    # ---- engine option (not a detectron2 key): how both NMS stages read ``torchvision.ops.batched_nms``.  "per_category" = one NMS per
+    # category (RPN: FPN level; box head: class) on the boxes as they are; "torchvision" = torchvision 0.11's size rule, per image: at
+    # most 1000 boxes in the call (``boxes.numel() <= 4000``) -> ONE NMS over boxes shifted by category * (boxes.max() + 1) in fp32,
+    # otherwise per category.  The two differ only where the rounding of the shifted coordinates moves an IoU across the threshold.
+    batched_nms: str = "per_category"
     # ---- derived constants
     scale_clamp: float = field(default=math.log(1000.0 / 16.0))   # Box2BoxTransform default
+
+    def __post_init__(self) -> None:
+        if self.batched_nms not in BATCHED_NMS_MODES:
+            raise ValueError(f"batched_nms={self.batched_nms!r}: one of {BATCHED_NMS_MODES}")
 
     # ------------------------------------------------------------------ helpers
     @property

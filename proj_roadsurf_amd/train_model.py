@@ -36,7 +36,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import yaml
 
-from .spec import load_d2_yaml, resize_shortest_edge_shape
+from .spec import BATCHED_NMS_HELP, load_d2_yaml, resize_shortest_edge_shape
 from .weights import infer_num_classes, load_checkpoint, synthetic_weights
 
 log = logging.getLogger("train_model")
@@ -207,7 +207,7 @@ def training_sampler(n: int, seed: int, rank: int, world: int):
             k += 1
 
 
-def main(argv: Optional[Sequence[str]] = None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("config_file", help="YAML with a 'train_model.py' section (R:config/config_obj_detec.yaml)")
     ap.add_argument("--synthetic-weights", action="store_true", help="start from seeded synthetic weights (no checkpoint available offline)")
@@ -222,7 +222,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--log-period", type=int, default=20)
     ap.add_argument("--tagged-samples", type=int, default=3, help="tagged ground-truth PNGs per dataset in sample_tagged_img_subfolder (0 = none)")
     ap.add_argument("--val-max-images", type=int, default=0, help="cap on the validation images per evaluation (0 = all)")
-    args = ap.parse_args(argv)
+    ap.add_argument("--batched-nms", choices=("per-category", "torchvision"), default="per-category",
+                    help="the training proposal stage and the validation inference: " + BATCHED_NMS_HELP)
+    return ap
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    args = build_parser().parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s", stream=sys.stderr)
     with open(args.config_file) as f:
         cfg = yaml.safe_load(f)[SECTION]
@@ -301,9 +307,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         raise SystemExit("model_weights needs pth_file or model_zoo_checkpoint_url (or --synthetic-weights)")
 
     precision = args.precision if args.precision != "auto" else ("fp16" if sv["amp"] else "fp32")
-    spec = spec.replace(precision=precision)
+    spec = spec.replace(precision=precision, batched_nms=args.batched_nms.replace("-", "_"))
     if precision == "fp32":
         args.loss_scale, args.scale_window = 1.0, 0     # nothing to protect from underflow; the overflow check stays on (it also catches a diverged run)
+    log.info("batched_nms: %s", {"per_category": "per-category (one NMS per FPN level)",
+                                 "torchvision": "torchvision (size rule: shifted coordinates at <= 1000 boxes per image)"}[spec.batched_nms])
     log.info("precision: %s (%s)", precision, "--precision" if args.precision != "auto" else f"SOLVER.AMP.ENABLED {sv['amp']}")
     from .engine import MultiScaleTrainer      # fails loudly without librs_engine.so / a HIP device
     from .make_detections import read_tile

@@ -47,6 +47,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--objects", type=int, nargs=2, default=[3, 8], help="objects per evaluation scene (min max)")
     ap.add_argument("--out", default="bisect_stages.json")
+    ap.add_argument("--batched-nms", choices=("per-category", "torchvision"), default="per-category",
+                    help="engine mode (EngineSpec.batched_nms); with torchvision the oracle follows torchvision's size rule too (nms_trick=None)")
     args = ap.parse_args()
     from oracle import maskrcnn_oracle as O
     from proj_roadsurf_amd.engine import Engine
@@ -57,7 +59,8 @@ def main():
     # a one-GPU box's CPU share is 16 cores whatever the host shows: torch's default (one thread per visible core) oversubscribes
     # them and the oracle runs ~5x slower
     torch.set_num_threads(max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 16)))
-    spec = EngineSpec(num_classes=2)
+    spec = EngineSpec(num_classes=2, batched_nms=args.batched_nms.replace("-", "_"))
+    nms_trick = None if spec.batched_nms == "torchvision" else False        # the oracle's batched_nms branch that the engine's mode states
     K = spec.num_classes
     A_ = spec.num_anchors
     T = 512
@@ -77,7 +80,7 @@ def main():
             cls, reg = clsreg
         probs = F.softmax(cls, dim=-1)
         dec = O.apply_deltas(reg, pb, spec.box_reg_weights, spec.scale_clamp)
-        det = O.fast_rcnn_inference_single_image(spec, dec, probs, size, nms_trick=False)
+        det = O.fast_rcnn_inference_single_image(spec, dec, probs, size, nms_trick=nms_trick)
         mp = O.roi_pooler(fn, scales, [det["boxes"]], spec.mask_pooler_resolution)
         _, mprob = O.mask_head(spec, m.W, mp, det["classes"])
         det["mask_probs"] = mprob
@@ -123,7 +126,7 @@ def main():
         log(f"seed {seed}: trained {args.steps} steps in {time.time() - t0:.1f} s, loss {curve[0]:.3f} -> {np.mean(curve[-20:]):.3f}")
         tiles, gtb, gtc, _ = synthetic_scenes(args.tiles, T, T, 3, seed=987654 + seed, objects=tuple(args.objects))
         eng = Engine(spec, W, (T, T, 3), max_batch=args.batch)
-        m = O.OracleModel(spec, W)
+        m = O.OracleModel(spec, W, nms_trick=nms_trick)
         seed_tot = {k: {"fw_n": 0, "fw_m": 0, "bw_n": 0, "bw_m": 0} for k in pooled}
         n_bisected = 0
         for b0 in range(0, args.tiles, args.batch):
@@ -158,7 +161,7 @@ def main():
                 fn = [fB[n] for n in spec.roi_in_features]
                 lg = [h[i:i + 1, ..., :A_].permute(0, 3, 1, 2).contiguous() for h in cut["heads"]]
                 dl = [h[i:i + 1, ..., A_:5 * A_].permute(0, 3, 1, 2).contiguous() for h in cut["heads"]]
-                props = O.rpn_proposals(spec, lg, dl, sizes, nms_trick=False)
+                props = O.rpn_proposals(spec, lg, dl, sizes, nms_trick=nms_trick)
                 R["C"] = tail(m, fn, props[0]["boxes"], sizes[0])
                 n = int(cut["pc"][i])
                 pbe = torch.from_numpy(cut["pb"][i, :n].copy())
