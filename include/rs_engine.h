@@ -29,6 +29,8 @@ extern "C" {
 #define RS_SPEC_MAX_ANCHORS 8
 #define RS_NUM_PHASES 3 /* rs_engine_infer_phase: 0 preprocess..RPN proposals, 1 box head..detections, 2 mask head + paste */
 #define RS_MASK_SIDE 28 /* 2 * ROI_MASK_HEAD.POOLER_RESOLUTION (R:219) */
+#define RS_MAX_CLASSES 80 /* rs_spec.num_classes an inference engine accepts (the COCO model zoo's heads) */
+#define RS_TRAIN_MAX_CLASSES 8 /* rs_spec.num_classes rs_trainer_create accepts (RS_ERR_UNSUPPORTED above) */
 
 /* POD mirror of the detectron2 YAML fields the inference path reads
  * (R:config/detectron2_config_3bands.yaml; line numbers per field). */
@@ -325,6 +327,19 @@ int rs_op_batched_nms(const float* boxes, const int32_t* counts, const uint8_t* 
                       int segments_per_image, int cap, float thresh, int rule, void* stream);
 int rs_op_batched_nms_decision(const float* boxes, const int32_t* counts, const uint8_t* valid, uint8_t* keep, int images,
                                int segments_per_image, int cap, float thresh, int rule, int32_t* rule_out, float* unit_out, void* stream);
+
+/* The engine's box.merge_postprocess stage alone (fast_rcnn_inference's top-k over the NMS survivors of all classes, then
+ * detector_postprocess's box part), on device buffers laid out as the engine's: dec_boxes [images][cap][num_classes][4] and dec_scores
+ * [images][cap][num_classes] (cap <= 1024 RoI slots per image), seg_roi / keep [images][num_classes][1024] (candidates of a class in
+ * NMS order: RoI slot, keep flag), seg_count [images][num_classes].  Per image the kept entries are ordered by score descending, ties by
+ * lower roi * num_classes + class first, and the first dets_per_image (<= 1024) are taken; each box is scaled by (scale_x, scale_y),
+ * clipped to [0, out_w] x [0, out_h] and dropped when empty.  Outputs per image, packed to the front: det_boxes_net (unscaled boxes),
+ * det_boxes, det_scores, det_classes, det_roi (optional), det_count.  1 <= num_classes <= RS_MAX_CLASSES: up to 8 classes one launch,
+ * above it the two-launch form of the engine (groups of 8 classes, then their partial winners). */
+int rs_op_det_merge(const float* dec_boxes, const float* dec_scores, const int32_t* seg_roi, const int32_t* seg_count, const uint8_t* keep,
+                    int images, int num_classes, int cap, int dets_per_image, float scale_x, float scale_y, float out_w, float out_h,
+                    float* det_boxes_net, float* det_boxes, float* det_scores, int32_t* det_classes, int32_t* det_roi, int32_t* det_count,
+                    void* stream);
 
 /* ROIPooler + ROIAlign(aligned=True, sampling_ratio=0) over up to 4 NHWC fp16 levels (halo 1,
  * 256 channels). rois: [n_rois][4] image coordinates, batch_index = roi / rois_per_image.

@@ -102,7 +102,17 @@ struct BoxCandParams {
   float* seg_boxes;         // [N][K][1024][4]
   int* seg_roi;             // [N][K][1024]
   int* seg_count;           // [N][K]
+  float* roi_stat;          // K > RS_DET_GROUP only: [N][cap][2] softmax max and sum of every RoI, computed once for all classes
 };
+
+// Classes whose NMS survivors one workgroup can sort: RS_DET_GROUP * 1024 keys are the 64 KB LDS list of det_merge_kernel.  Up to
+// RS_DET_GROUP classes the detection tail is one launch per stage; above, launch_box_candidates and launch_det_merge take their
+// many-class forms and need the scratch buffers named here.
+#define RS_DET_GROUP 8
+#define RS_DET_FINAL_KEYS 16384   // partial winners the final sort of the many-class merge holds in LDS (128 KB)
+static inline int det_merge_groups(int K) { return (K + RS_DET_GROUP - 1) / RS_DET_GROUP; }
+// RS_OK where the merge can hold NUM_CLASSES K with DETECTIONS_PER_IMAGE D, else RS_ERR_UNSUPPORTED with a message naming both
+int det_merge_check(int K, int D);
 
 struct DetMergeParams {
   const float* dec_boxes;
@@ -118,6 +128,10 @@ struct DetMergeParams {
   int* det_classes;         // [N][D]
   int* det_roi;             // optional [N][D]
   int* det_count;           // [N]
+  // K > RS_DET_GROUP only: the first D sorted keys of every group of RS_DET_GROUP classes, handed from det_merge_part_kernel to
+  // det_merge_final_kernel (two launches)
+  unsigned long long* part_keys;   // [N][det_merge_groups(K)][D]
+  int* part_count;                 // [N][det_merge_groups(K)]
 };
 
 struct MaskPredictParams {

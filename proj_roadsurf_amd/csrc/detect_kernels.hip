@@ -363,6 +363,10 @@ __global__ __launch_bounds__(1024) void nms_kernel(const NmsParams p) {
   const uint8_t* valid = p.valid ? p.valid + (long long)s * p.cap : nullptr;
   uint8_t* keep = p.keep + (long long)s * p.cap;
   if (!(GM && p.mode == 1)) for (int i = tid; i < p.cap; i += 1024) keep[i] = 0;
+  // An empty segment has nothing to build or scan and its keep flags are zero already: with many classes most segments of a trained
+  // detector are empty, and a workgroup that holds 148 KB of LDS should not queue behind them.  Under the size rule the first
+  // segment of an image still writes the image's decision out.
+  if (n <= 0 && !(p.rule && !(GM && p.mode == 2) && s % p.group == 0 && blockIdx.y == 0)) return;
   if (tid < WPR) sremoved[tid] = 0ull;
   __syncthreads();
   // batched_nms's coordinate offsets (NmsParams::rule): `idxs.to(boxes) * (max_coordinate + 1)` is one rounded product, `boxes + offsets[:, None]`
@@ -1406,34 +1410,75 @@ __global__ __launch_bounds__(1024) void box_candidates_kernel(const BoxCandParam
   }
 }
 
-// Gather NMS survivors of all classes, order by score (ties: lower roi*K+class first), keep the
-// first dets_per_image, then detector_postprocess's box part (scale to tile, clip, drop empty).
-__global__ __launch_bounds__(1024) void det_merge_kernel(const DetMergeParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned long long* list = (unsigned long long*)smem;   // 8192
+// More than RS_DET_GROUP classes: the softmax statistics of every RoI once (BoxCandParams::roi_stat), in the summation order of
+// box_candidates_kernel, so that the scores carry the same bits; the per-class kernel then costs one expf per RoI instead of K + 2.
+__global__ __launch_bounds__(256) void box_softmax_stat_kernel(const BoxCandParams p) {
+  const int n = blockIdx.y, r = blockIdx.x * 256 + threadIdx.x, K = p.K;
+  if (r >= p.prop_count[n] || r >= p.cap) return;
+  const float* pr = p.pred + ((long long)n * p.cap + r) * p.cs;
+  float mx = pr[0];
+  for (int c = 1; c <= K; ++c) mx = fmaxf(mx, pr[c]);
+  float sum = 0.f;
+  for (int c = 0; c <= K; ++c) sum += expf(pr[c] - mx);
+  float* st = p.roi_stat + ((long long)n * p.cap + r) * 2;
+  st[0] = mx; st[1] = sum;
+}
+
+// box_candidates_kernel on the statistics above.  The candidates are compacted before the sort (the keys are unique, so the order they
+// arrive in changes nothing) and the sort runs over the entries that exist: most classes of a trained detector hold none.
+__global__ __launch_bounds__(1024) void box_candidates_mc_kernel(const BoxCandParams p) {
+  __shared__ unsigned long long list[1024];
   __shared__ unsigned int cnt;
-  __shared__ unsigned char flag[1024];
-  __shared__ int dst[1024];
-  const int n = blockIdx.x, tid = threadIdx.x, K = p.K;
+  const int k = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
+  const int K = p.K;
+  const int np = p.prop_count[n];
   if (tid == 0) cnt = 0;
-  for (int i = tid; i < 8192; i += 1024) list[i] = 0ull;
+  list[tid] = 0ull;
   __syncthreads();
-  for (int k = 0; k < K; ++k) {
-    const int c = p.seg_count[n * K + k];
-    const long long sb = ((long long)n * K + k) * 1024;
-    for (int i = tid; i < c; i += 1024) {
-      if (p.keep[sb + i]) {
-        const int r = p.seg_roi[sb + i];
-        const float sc = p.dec_scores[((long long)n * p.cap + r) * K + k];
-        const unsigned pos = atomicAdd(&cnt, 1u);
-        list[pos] = ((unsigned long long)fkey(sc) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)(r * K + k));
-      }
-    }
+  if (tid < np && tid < p.cap) {
+    const float* pr = p.pred + ((long long)n * p.cap + tid) * p.cs;
+    const float* st = p.roi_stat + ((long long)n * p.cap + tid) * 2;
+    const float score = rs_fdiv(expf(pr[k] - st[0]), st[1]);
+    const float* pb = p.prop_boxes + ((long long)n * p.cap + tid) * 4;
+    float b[4] = {pb[0], pb[1], pb[2], pb[3]};
+    const float* dp = pr + (K + 1) + k * 4;
+    float d[4] = {dp[0], dp[1], dp[2], dp[3]};
+    float box[4];
+    apply_deltas(b, d, p.wx, p.wy, p.ww, p.wh, p.scale_clamp, box);
+    box[0] = clampf(box[0], 0.f, p.img_w);
+    box[1] = clampf(box[1], 0.f, p.img_h);
+    box[2] = clampf(box[2], 0.f, p.img_w);
+    box[3] = clampf(box[3], 0.f, p.img_h);
+    float* db = p.dec_boxes + (((long long)n * p.cap + tid) * K + k) * 4;
+    db[0] = box[0]; db[1] = box[1]; db[2] = box[2]; db[3] = box[3];
+    p.dec_scores[((long long)n * p.cap + tid) * K + k] = score;
+    if (score > p.score_thresh)
+      list[atomicAdd(&cnt, 1u)] = ((unsigned long long)fkey(score) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)tid);
   }
   __syncthreads();
-  bitonic_sort_desc<1024>(list, sort_size(cnt, 1024, 8192), tid);
+  const int c = (int)cnt;
+  const long long sb = ((long long)n * K + k) * 1024;
+  if (tid == 0) p.seg_count[n * K + k] = c;
+  if (c == 0) return;                            // uniform
+  bitonic_sort_desc<1024>(list, sort_size(c, 64, 1024), tid);
+  if (tid < c) {
+    const int r = (int)(0xFFFFFFFFu - (uint32_t)(list[tid] & 0xFFFFFFFFull));
+    const float* db = p.dec_boxes + (((long long)n * p.cap + r) * K + k) * 4;   // this workgroup's own stores, ordered by the __syncthreads() above (in front of the count), not by the sort
+    float* o = p.seg_boxes + (sb + tid) * 4;
+    o[0] = db[0]; o[1] = db[1]; o[2] = db[2]; o[3] = db[3];
+    p.seg_roi[sb + tid] = r;
+  }
+}
+
+// Gather NMS survivors of all classes, order by score (ties: lower roi*K+class first), keep the
+// first dets_per_image, then detector_postprocess's box part (scale to tile, clip, drop empty).
+// det_finish is that last part, by all 1024 threads: `list` holds an image's keys in final order, `total` of them real.
+__device__ __forceinline__ void det_finish(const DetMergeParams& p, int n, const unsigned long long* list, int total) {
+  __shared__ unsigned char flag[1024];
+  __shared__ int dst[1024];
+  const int tid = threadIdx.x, K = p.K;
   const int D = p.dets_per_image;
-  const int nd = (int)cnt < D ? (int)cnt : D;
+  const int nd = total < D ? total : D;
   float bn[4] = {0, 0, 0, 0}, bo[4] = {0, 0, 0, 0};
   float sc = 0.f;
   int cls = 0, roi = 0;
@@ -1469,6 +1514,89 @@ __global__ __launch_bounds__(1024) void det_merge_kernel(const DetMergeParams p)
     p.det_classes[s] = cls;
     if (p.det_roi) p.det_roi[s] = roi;
   }
+}
+
+// NMS survivors of classes [k0, k1) of image n into `list` (zeroed, room for 1024 per class) as sort keys; *cnt counts them
+__device__ __forceinline__ void det_gather(const DetMergeParams& p, int n, int k0, int k1, unsigned long long* list, unsigned int* cnt) {
+  const int tid = threadIdx.x, K = p.K;
+  for (int k = k0; k < k1; ++k) {
+    int c = p.seg_count[n * K + k];
+    if (c > 1024) c = 1024;                       // a segment has 1024 slots
+    const long long sb = ((long long)n * K + k) * 1024;
+    for (int i = tid; i < c; i += 1024) {
+      if (p.keep[sb + i]) {
+        const int r = p.seg_roi[sb + i];
+        const float sc = p.dec_scores[((long long)n * p.cap + r) * K + k];
+        const unsigned pos = atomicAdd(cnt, 1u);
+        list[pos] = ((unsigned long long)fkey(sc) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)(r * K + k));
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(1024) void det_merge_kernel(const DetMergeParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* list = (unsigned long long*)smem;   // 8192
+  __shared__ unsigned int cnt;
+  const int n = blockIdx.x, tid = threadIdx.x;
+  if (tid == 0) cnt = 0;
+  for (int i = tid; i < 8192; i += 1024) list[i] = 0ull;
+  __syncthreads();
+  det_gather(p, n, 0, p.K, list, &cnt);
+  __syncthreads();
+  bitonic_sort_desc<1024>(list, sort_size(cnt, 1024, 8192), tid);
+  det_finish(p, n, list, (int)cnt);
+}
+
+// More than RS_DET_GROUP classes: up to K * 1024 survivors per image do not fit one LDS list.  The keys are unique, so the first D of
+// an image are among the first D of every group of RS_DET_GROUP classes: one workgroup per (group, image) sorts its group as
+// det_merge_kernel does and hands its first D keys on through global memory; a second LAUNCH (not a hand-off inside one: nothing
+// orders one workgroup's stores before another's loads across XCDs short of a kernel boundary) sorts an image's partial winners.
+__global__ __launch_bounds__(1024) void det_merge_part_kernel(const DetMergeParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* list = (unsigned long long*)smem;   // 8192
+  __shared__ unsigned int cnt;
+  const int g = blockIdx.x, G = gridDim.x, n = blockIdx.y, tid = threadIdx.x, K = p.K, D = p.dets_per_image;
+  const int k0 = g * RS_DET_GROUP, k1 = k0 + RS_DET_GROUP < K ? k0 + RS_DET_GROUP : K;
+  int bound = 0;                                          // candidates of the group: at least its survivors
+  for (int k = k0; k < k1; ++k) { const int c = p.seg_count[n * K + k]; bound += c < 0 ? 0 : (c > 1024 ? 1024 : c); }
+  if (bound <= 0) {                                       // uniform
+    if (tid == 0) p.part_count[n * G + g] = 0;
+    return;
+  }
+  const int room = sort_size((unsigned)bound, 1024, 8192);
+  if (tid == 0) cnt = 0;
+  for (int i = tid; i < room; i += 1024) list[i] = 0ull;
+  __syncthreads();
+  det_gather(p, n, k0, k1, list, &cnt);
+  __syncthreads();
+  bitonic_sort_desc<1024>(list, sort_size(cnt, 1024, 8192), tid);
+  const int m = (int)cnt < D ? (int)cnt : D;
+  if (tid == 0) p.part_count[n * G + g] = m;
+  if (tid < m) p.part_keys[((long long)n * G + g) * D + tid] = list[tid];
+}
+
+// room: keys of the LDS list, a power of two >= G * D
+__global__ __launch_bounds__(1024) void det_merge_final_kernel(const DetMergeParams p, int G, int room) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* list = (unsigned long long*)smem;
+  __shared__ int off[RS_DET_FINAL_KEYS / 1024 + 1];
+  const int n = blockIdx.x, tid = threadIdx.x, D = p.dets_per_image;
+  if (tid == 0) {
+    int c = 0;
+    for (int g = 0; g < G; ++g) { off[g] = c; c += p.part_count[n * G + g]; }
+    off[G] = c;
+  }
+  for (int i = tid; i < room; i += 1024) list[i] = 0ull;
+  __syncthreads();
+  const int total = off[G];
+  for (int g = 0; g < G; ++g) {
+    const int m = off[g + 1] - off[g];
+    if (tid < m) list[off[g] + tid] = p.part_keys[((long long)n * G + g) * D + tid];
+  }
+  __syncthreads();
+  bitonic_sort_desc<1024>(list, sort_size((unsigned)total, 1024, room), tid);
+  det_finish(p, n, list, total);
 }
 
 // exclusive scan of per-image detection counts -> compact entry list for the mask head
@@ -1784,20 +1912,42 @@ int launch_roi_align_bwd(const RoiAlignParams& p_in, hipStream_t s) {
 
 int launch_box_candidates(const BoxCandParams& p, int N, hipStream_t s) {
   RS_CHECK(p.cap <= 1024, RS_ERR_UNSUPPORTED, "box head: more than 1024 proposals per image");
-  hipLaunchKernelGGL(box_candidates_kernel, dim3(p.K, N), dim3(1024), 0, s, p);
+  if (p.K <= RS_DET_GROUP) hipLaunchKernelGGL(box_candidates_kernel, dim3(p.K, N), dim3(1024), 0, s, p);
+  else {
+    RS_CHECK(p.roi_stat, RS_ERR_ARG, "box head: %d classes need BoxCandParams::roi_stat", p.K);
+    hipLaunchKernelGGL(box_softmax_stat_kernel, dim3(cdiv(p.cap, 256), N), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(box_candidates_mc_kernel, dim3(p.K, N), dim3(1024), 0, s, p);
+  }
   RS_HIP(hipGetLastError());
   return RS_OK;
 }
 
+int det_merge_check(int K, int D) {
+  RS_CHECK(K >= 1 && D <= 1024 &&
+               (K <= RS_DET_GROUP || (D >= 1 && det_merge_groups(K) <= RS_DET_FINAL_KEYS / 1024 && det_merge_groups(K) * D <= RS_DET_FINAL_KEYS)), RS_ERR_UNSUPPORTED,
+           "det merge: NUM_CLASSES %d with DETECTIONS_PER_IMAGE %d -- at most 1024 detections per image, and above %d classes "
+           "ceil(NUM_CLASSES / %d) * DETECTIONS_PER_IMAGE <= %d partial winners", K, D, RS_DET_GROUP, RS_DET_GROUP, RS_DET_FINAL_KEYS);
+  return RS_OK;
+}
+
 int launch_det_merge(const DetMergeParams& p, int N, hipStream_t s) {
-  RS_CHECK(p.K * 1024 <= 8192, RS_ERR_UNSUPPORTED, "det merge: NUM_CLASSES %d > 8 not supported yet", p.K);
-  RS_CHECK(p.dets_per_image <= 1024, RS_ERR_UNSUPPORTED, "det merge: DETECTIONS_PER_IMAGE > 1024");
+  { const int rc = det_merge_check(p.K, p.dets_per_image); if (rc) return rc; }
   static bool done = false;
   if (!done) {
     RS_HIP(hipFuncSetAttribute((const void*)det_merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+    RS_HIP(hipFuncSetAttribute((const void*)det_merge_part_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+    RS_HIP(hipFuncSetAttribute((const void*)det_merge_final_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RS_DET_FINAL_KEYS * 8));
     done = true;
   }
-  hipLaunchKernelGGL(det_merge_kernel, dim3(N), dim3(1024), 65536, s, p);
+  if (p.K <= RS_DET_GROUP) hipLaunchKernelGGL(det_merge_kernel, dim3(N), dim3(1024), 65536, s, p);
+  else {
+    RS_CHECK(p.part_keys && p.part_count, RS_ERR_ARG, "det merge: %d classes need DetMergeParams::part_keys / part_count", p.K);
+    const int G = det_merge_groups(p.K);
+    int room = 1024;
+    while (room < G * p.dets_per_image) room <<= 1;
+    hipLaunchKernelGGL(det_merge_part_kernel, dim3(G, N), dim3(1024), 65536, s, p);
+    hipLaunchKernelGGL(det_merge_final_kernel, dim3(N), dim3(1024), room * 8, s, p, G, room);
+  }
   RS_HIP(hipGetLastError());
   return RS_OK;
 }

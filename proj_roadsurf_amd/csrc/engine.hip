@@ -487,7 +487,9 @@ int rs_engine::build() {
   RS_CHECK(S.fpn_out_channels == 256 && S.mask_conv_dim == 256, RS_ERR_UNSUPPORTED, "FPN/mask width must be 256");
   RS_CHECK(S.num_levels == 5, RS_ERR_UNSUPPORTED, "RPN must use p2..p6");
   RS_CHECK(S.rpn_pre_nms_topk <= 1024 && S.rpn_post_nms_topk <= 1024, RS_ERR_UNSUPPORTED, "RPN top-k > 1024");
-  RS_CHECK(S.num_classes >= 1 && S.num_classes <= 8, RS_ERR_UNSUPPORTED, "NUM_CLASSES %d outside [1,8]", S.num_classes);
+  RS_CHECK(S.num_classes >= 1 && S.num_classes <= RS_MAX_CLASSES, RS_ERR_UNSUPPORTED, "NUM_CLASSES %d outside [1,%d]", S.num_classes, RS_MAX_CLASSES);
+  // the many-class merge is checked here, with both numbers in the message; up to RS_DET_GROUP classes the launcher's own check stands as before
+  if (S.num_classes > RS_DET_GROUP) { const int rc0 = det_merge_check(S.num_classes, S.detections_per_image); if (rc0) return rc0; }
   RS_CHECK(S.in_channels >= 1 && S.in_channels <= 4 && S.in_channels == tile_c, RS_ERR_ARG, "tile channels %d vs PIXEL_MEAN %d", tile_c, S.in_channels);
   RS_CHECK(!S.mask_on || S.mask_pooler_resolution * 2 == RS_MASK_SIDE, RS_ERR_UNSUPPORTED, "mask side must be 28");
   int rc;
@@ -1009,6 +1011,10 @@ int rs_engine::build() {
   if ((rc = alloc((void**)&bc.seg_roi, (size_t)NB * K * 1024 * 4))) return rc;
   if ((rc = alloc((void**)&bc.seg_count, (size_t)NB * K * 4))) return rc;
   if ((rc = alloc((void**)&seg_keep, (size_t)NB * K * 1024))) return rc;
+  if (K > RS_DET_GROUP) {   // many classes: softmax statistics per RoI, computed once (launch_box_candidates)
+    if ((rc = alloc((void**)&bc.roi_stat, (size_t)NB * PC * 8))) return rc;
+    reg("box_roi_stat", bc.roi_stat, DT_F32, {NB, PC, 2}, 0);
+  }
   reg("box_dec_boxes", bc.dec_boxes, DT_F32, {NB, PC, K, 4}, 0);
   reg("box_dec_scores", bc.dec_scores, DT_F32, {NB, PC, K}, 0);
   reg("box_seg_boxes", bc.seg_boxes, DT_F32, {NB, K, 1024, 4}, 0);
@@ -1054,6 +1060,11 @@ int rs_engine::build() {
     dm.out_w = (float)tile_w; dm.out_h = (float)tile_h;
     dm.det_boxes_net = det_boxes_net; dm.det_boxes = det_boxes; dm.det_scores = det_scores; dm.det_classes = det_classes;
     dm.det_roi = det_roi; dm.det_count = det_count;
+    if (K > RS_DET_GROUP) {   // many classes: the groups' partial winners between the merge's two launches (launch_det_merge)
+      const int G = det_merge_groups(K);
+      if ((rc = alloc((void**)&dm.part_keys, (size_t)NB * G * D * 8))) return rc;
+      if ((rc = alloc((void**)&dm.part_count, (size_t)NB * G * 4))) return rc;
+    }
     Stage st;
     st.name = "box.merge_postprocess";
     st.fn = [dm](int n, hipStream_t s) { return launch_det_merge(dm, n, s); };
@@ -1985,6 +1996,35 @@ int rs_op_batched_nms_decision(const float* boxes, const int32_t* counts, const 
   (void)hipStreamSynchronize(s);
   (void)hipFree(dec);
   if (scratch) (void)hipFree(scratch);
+  return rc;
+}
+
+int rs_op_det_merge(const float* dec_boxes, const float* dec_scores, const int32_t* seg_roi, const int32_t* seg_count, const uint8_t* keep,
+                    int images, int num_classes, int cap, int dets_per_image, float scale_x, float scale_y, float out_w, float out_h,
+                    float* det_boxes_net, float* det_boxes, float* det_scores, int32_t* det_classes, int32_t* det_roi, int32_t* det_count,
+                    void* stream) {
+  RS_CHECK(dec_boxes && dec_scores && seg_roi && seg_count && keep && det_boxes_net && det_boxes && det_scores && det_classes && det_count &&
+               images > 0, RS_ERR_ARG, "bad argument");
+  RS_CHECK(num_classes >= 1 && num_classes <= RS_MAX_CLASSES, RS_ERR_UNSUPPORTED, "NUM_CLASSES %d outside [1,%d]", num_classes, RS_MAX_CLASSES);
+  RS_CHECK(cap >= 1 && cap <= 1024, RS_ERR_ARG, "cap %d outside [1,1024]", cap);
+  { const int rc0 = det_merge_check(num_classes, dets_per_image); if (rc0) return rc0; }
+  hipStream_t s = (hipStream_t)stream;
+  DetMergeParams p;
+  memset(&p, 0, sizeof p);
+  p.dec_boxes = dec_boxes; p.dec_scores = dec_scores; p.seg_roi = seg_roi; p.seg_count = seg_count; p.keep = keep;
+  p.K = num_classes; p.cap = cap; p.dets_per_image = dets_per_image;
+  p.scale_x = scale_x; p.scale_y = scale_y; p.out_w = out_w; p.out_h = out_h;
+  p.det_boxes_net = det_boxes_net; p.det_boxes = det_boxes; p.det_scores = det_scores; p.det_classes = det_classes; p.det_roi = det_roi;
+  p.det_count = det_count;
+  void* ws = nullptr;
+  if (num_classes > RS_DET_GROUP) {    // the partial winners between the two launches, for the time of this call (the engine owns its own)
+    const size_t G = (size_t)det_merge_groups(num_classes);
+    const size_t kb = (size_t)images * G * dets_per_image * 8;
+    RS_HIP(hipMalloc(&ws, kb + (size_t)images * G * 4));
+    p.part_keys = (unsigned long long*)ws; p.part_count = (int*)((char*)ws + kb);
+  }
+  int rc = launch_det_merge(p, images, s);
+  if (ws) { (void)hipStreamSynchronize(s); (void)hipFree(ws); }
   return rc;
 }
 

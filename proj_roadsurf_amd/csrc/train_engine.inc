@@ -1085,6 +1085,8 @@ int rs_trainer_create(const rs_spec* spec, const void* weights, size_t nbytes, i
                       int tile_c, float loss_scale, rs_trainer** out) {
   RS_CHECK(spec && weights && out && loss_scale > 0.f, RS_ERR_ARG, "bad argument");
   RS_CHECK(spec->precision == 0 || spec->precision == 1, RS_ERR_UNSUPPORTED, "trainer: precision %d", spec->precision);
+  RS_CHECK(spec->num_classes <= RS_TRAIN_MAX_CLASSES, RS_ERR_UNSUPPORTED, "trainer: NUM_CLASSES %d > %d (more classes, up to %d, run in inference engines only)",
+           spec->num_classes, RS_TRAIN_MAX_CLASSES, RS_MAX_CLASSES);
   rs_trainer* t = new rs_trainer();
   t->f32 = spec->precision == 1;
   t->N = batch;

@@ -149,6 +149,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.rs_op_nms.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, vp]
     lib.rs_op_batched_nms.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_float, i32, vp]
     lib.rs_op_batched_nms_decision.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_float, i32, vp, vp, vp]
+    lib.rs_op_det_merge.argtypes = [vp] * 5 + [i32] * 4 + [C.c_float] * 4 + [vp] * 7
     lib.rs_spec_batched_nms.argtypes = [C.POINTER(RsSpec)]
     lib.rs_op_roi_align.argtypes = [C.POINTER(vp), i32p, i32p, f32p, i32, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.rs_op_roi_align_bwd.argtypes = [C.POINTER(vp), i32p, i32p, f32p, i32, vp, i32, i32, i32, i32, vp, vp]

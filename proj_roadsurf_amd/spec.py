@@ -48,6 +48,10 @@ BATCHED_NMS_HELP = ("how both NMS stages read torchvision.ops.batched_nms.  per-
                     "are; torchvision: torchvision 0.11's size rule as the reference runs it -- an image with at most 1000 boxes in the call gets ONE "
                     "NMS over boxes shifted by category * (largest coordinate + 1) in fp32, which can decide a pair at the IoU threshold the other way "
                     "(DESIGN.md section 4)")
+# include/rs_engine.h's RS_MAX_CLASSES and RS_TRAIN_MAX_CLASSES (tests/test_many_classes_cpu.py holds each pair equal): the classes an
+# inference engine runs, and the classes the trainer accepts.
+MAX_CLASSES = 80
+TRAIN_MAX_CLASSES = 8
 
 
 @dataclass(frozen=True)
@@ -166,6 +170,8 @@ class EngineSpec:
             errs.append("class-agnostic heads")
         if self.depth != 50:
             errs.append(f"DEPTH={self.depth}")
+        if not 1 <= self.num_classes <= MAX_CLASSES:
+            errs.append(f"ROI_HEADS.NUM_CLASSES={self.num_classes} (the engine runs 1 to {MAX_CLASSES} classes)")
         if errs:
             raise NotImplementedError("unsupported detectron2 config: " + "; ".join(errs))
 

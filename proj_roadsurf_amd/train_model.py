@@ -36,7 +36,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import yaml
 
-from .spec import BATCHED_NMS_HELP, load_d2_yaml, resize_shortest_edge_shape
+from .spec import BATCHED_NMS_HELP, MAX_CLASSES, TRAIN_MAX_CLASSES, load_d2_yaml, resize_shortest_edge_shape
 from .weights import infer_num_classes, load_checkpoint, synthetic_weights
 
 log = logging.getLogger("train_model")
@@ -80,11 +80,16 @@ def load_solver(d2_yaml: str) -> Dict[str, Any]:
 GT_CAP, MASK_ENTRIES_CAP, ROI_CAP, RPN_PRE_TOPK_CAP, RPN_POST_TOPK_CAP = 128, 256, 1024, 2048, 1024
 
 
-def validate_solver(sv: Dict[str, Any]) -> None:
+def validate_solver(sv: Dict[str, Any], num_classes: Optional[int] = None) -> None:
     """Reject, up front, every solver / sampler value the training engine does not implement -- never clamp or ignore one
     silently (the same rule as ``EngineSpec.check_supported`` for the model keys).  Values of the reference YAML
-    (R:config/detectron2_config_3bands.yaml:268-305, :29, :178, :192, :248-250) all pass."""
+    (R:config/detectron2_config_3bands.yaml:268-305, :29, :178, :192, :248-250) all pass.  ``num_classes``: the classes of the
+    run where known (COCO categories / checkpoint heads) -- inference engines run up to spec.MAX_CLASSES, the trainer's losses and
+    its box-head backward stop at TRAIN_MAX_CLASSES (rs_trainer_create returns RS_ERR_UNSUPPORTED above)."""
     errs = []
+    if num_classes is not None and num_classes > TRAIN_MAX_CLASSES:
+        errs.append(f"ROI_HEADS.NUM_CLASSES {num_classes} > {TRAIN_MAX_CLASSES}: more than {TRAIN_MAX_CLASSES} classes run in inference only "
+                    f"(make_detections, up to {MAX_CLASSES}); the training engine is not built for them")
     if sv["lr_scheduler"] != "WarmupMultiStepLR":
         errs.append(f"SOLVER.LR_SCHEDULER_NAME {sv['lr_scheduler']!r} (only WarmupMultiStepLR)")
     if sv["warmup_method"] != "linear":
@@ -277,7 +282,6 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 draw_annotations(rgb, anns, {k: k for k in range(len(dcats))}, names or None).save(png)
         log.info("tagged sample training images -> %s/", sub)
     sv = load_solver(cfg["detectron2_config_file"])
-    validate_solver(sv)
     check_gt_capacity(recs, "training set")
     max_iter = args.max_iter or sv["max_iter"]
     mw = cfg.get("model_weights", {}) or {}
@@ -305,6 +309,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         spec = load_d2_yaml(cfg["detectron2_config_file"], num_classes=k)
     else:
         raise SystemExit("model_weights needs pth_file or model_zoo_checkpoint_url (or --synthetic-weights)")
+    validate_solver(sv, num_classes=spec.num_classes)     # the class count is known here: COCO categories, or the checkpoint's heads
 
     precision = args.precision if args.precision != "auto" else ("fp16" if sv["amp"] else "fp32")
     spec = spec.replace(precision=precision, batched_nms=args.batched_nms.replace("-", "_"))
