@@ -427,7 +427,9 @@ int rs_trainer_backward_trunk(rs_trainer* t, int n);
  * largest size of the batch), the canvas is zero beyond it, and its proposals are clipped to that size.  n = 0 restores one size
  * for all.  Ground truth passed to rs_trainer_set_targets is in each image's own resized pixels. */
 int rs_trainer_set_image_sizes(rs_trainer* t, const int32_t* new_h, const int32_t* new_w, int n);
-/* Ground truth of the batch (host pointers): boxes in network-input pixels [n][cap][4], classes [n][cap], counts [n]. */
+/* Ground truth of the batch (host pointers): boxes in network-input pixels [n][cap][4], classes [n][cap], counts [n].
+ * The classes of the counted boxes are validated: one outside [0, rs_spec.num_classes) returns RS_ERR_ARG (the message names the
+ * image, the box index, the class and the range) and leaves the previous targets in place.  Slots beyond gt_count[i] are ignored. */
 int rs_trainer_set_targets(rs_trainer* t, const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_count, int n, int cap);
 /* RPN of the training forward + RPN.losses + its backward: heads on the current FPN maps, anchor Matcher (0.3/0.7, low-quality
  * matches) and subsample_labels (256 @ 0.5) keyed by `seed`, loss_rpn_cls / loss_rpn_loc into tensor "losses"[0..1], gradients of

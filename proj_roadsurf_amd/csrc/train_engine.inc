@@ -1208,11 +1208,21 @@ int rs_trainer_backward_trunk(rs_trainer* t, int n) {
   return RS_OK;
 }
 
-// ground truth of the batch: boxes in NETWORK-INPUT pixels [n][cap][4], classes [n][cap], counts [n] (host pointers)
+// ground truth of the batch: boxes in NETWORK-INPUT pixels [n][cap][4], classes [n][cap], counts [n] (host pointers).
+// The classes of the counted boxes (j < gt_count[i]) are VALIDATED: one outside [0, NUM_CLASSES) is RS_ERR_ARG and nothing is
+// copied (detectron2 fails in cross_entropy on such a target; the loss kernels would drop the RoI from loss_cls while still counting
+// it, and the mask loss would train a padding channel of predictor16).  The padding slots beyond gt_count[i] are not looked at.
 int rs_trainer_set_targets(rs_trainer* t, const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_count, int n, int cap) {
   RS_CHECK(t && gt_boxes && gt_classes && gt_count && n >= 1 && n <= t->N && cap >= 1 && cap <= rs_trainer::GT_CAP, RS_ERR_ARG, "bad argument (at most %d boxes per image)", rs_trainer::GT_CAP);
+  const int K = t->eng->spec.num_classes;
   for (int i = 0; i < n; ++i) {
     RS_CHECK(gt_count[i] >= 0 && gt_count[i] <= cap, RS_ERR_ARG, "gt_count[%d] = %d", i, gt_count[i]);
+    for (int j = 0; j < gt_count[i]; ++j) {
+      const int c = gt_classes[(size_t)i * cap + j];
+      RS_CHECK(c >= 0 && c < K, RS_ERR_ARG, "image %d, box %d: ground-truth class %d outside [0, %d)", i, j, c, K);
+    }
+  }
+  for (int i = 0; i < n; ++i) {
     RS_HIP(hipMemcpyAsync(t->gt_boxes + (size_t)i * rs_trainer::GT_CAP * 4, gt_boxes + (size_t)i * cap * 4, (size_t)cap * 16, hipMemcpyHostToDevice, t->stream));
     RS_HIP(hipMemcpyAsync(t->gt_classes + (size_t)i * rs_trainer::GT_CAP, gt_classes + (size_t)i * cap, (size_t)cap * 4, hipMemcpyHostToDevice, t->stream));
   }

@@ -649,3 +649,260 @@ def test_nms_operator_both_capacities(gpu_required, cap):
             want[np.nonzero(v)[0][O.nms_sorted_np(b[v], 0.7)]] = True
             assert np.array_equal(k[s_, :c].astype(bool), want), (cap, S, s_, c)
             assert (k[s_, c:] == 0).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Loss operators at their edges, per element, against float64 autograd on the same fp32 inputs.
+#
+# The tests above hold the gradients to 2e-3 of the LARGEST entry, on randn logits (|x| < 5): a wrong small entry -- a rare
+# class' column, a saturated softmax -- passes.  Here every element is held to
+#     |got / scale - ref| <= 2^-10 |ref| + 2^-22 / norm + 2^-24 / scale
+# * 2^-10 |ref|: the stored gradient is fp16 (rounding unit 2^-11), doubled for the fp32 arithmetic ahead of it;
+# * 2^-22 / norm: a few ulp of 1 (2^-24 each) in the cancelling `softmax - 1` / `sigmoid - t` of saturated entries;
+# * 2^-24 / scale: fp16's subnormal spacing (scaled gradients below 2^-14);
+# norm = n_valid (box), n_masks * S^2 (mask), normalizer (RPN).  The loss values keep the 1e-5 relative bound of the tests above.
+# ---------------------------------------------------------------------------------------------------------------------
+def _scale_for(norm):
+    """Largest power-of-two loss scale <= 2^15 whose largest possible scaled gradient, scale / norm, stays <= 2^10 (fp16 max 65504)."""
+    s = 2.0 ** 15
+    while s / norm > 1024.0:
+        s /= 2
+    return s
+
+
+def _assert_per_element(got16, ref64, norm, scale, what):
+    got = got16.double() / scale
+    assert bool(torch.isfinite(got16.float()).all()), f"{what}: non-finite gradient"
+    err = (got - ref64).abs()
+    bound = 2.0 ** -10 * ref64.abs() + 2.0 ** -22 / norm + 2.0 ** -24 / scale
+    ratio = float((err / bound).max())
+    print(f"{what}: worst per-element error / bound = {ratio:.3f}")
+    bad = torch.nonzero(err > bound)
+    assert bad.numel() == 0, (what, ratio, bad[:5].tolist(), [float(got[tuple(b)]) for b in bad[:5]], [float(ref64[tuple(b)]) for b in bad[:5]])
+
+
+def _loss_close(got, ref, what):
+    got, ref = float(got), float(ref.detach())
+    print(f"{what}: engine {got:.9g} reference {ref:.9g} rel err {abs(got - ref) / max(abs(ref), 1e-30):.2e}")
+    assert abs(got - ref) <= 1e-5 * abs(ref) + 1e-6, (what, got, ref)
+
+
+def _run_box_loss(pred, cls, props, gts, K, cs, n_valid, w, scale):
+    lib = load_library()
+    R = pred.shape[0]
+    loss = _dev(torch.zeros(2))
+    pd = _dev(pred)
+    dp = torch.full((R, cs), float("nan"), dtype=torch.float16, device=pd.device)
+    cd, prd, gd = _dev(cls), _dev(props), _dev(gts)
+    _check(lib, lib.rs_op_box_loss(_ptr(pd), _ptr(dp), _ptr(cd), _ptr(prd), _ptr(gd), _ptr(loss), R, K, cs, n_valid,
+                                   (C.c_float * 4)(*w), scale, None), "rs_op_box_loss")
+    torch.cuda.synchronize()
+    return dp.cpu(), loss.cpu()
+
+
+@pytest.mark.parametrize("R", [1, 257, 700])
+@pytest.mark.parametrize("K", [1, 3, 4, 8])
+def test_box_loss_edges_per_class_count(gpu_required, K, R):
+    """rs_op_box_loss at every predictor width of the trainer (cs = round16(5K+1): 16 / 16 with no padding column / 32 / 48), one
+    RoI, two blocks and three: a block of saturated rows (one class at +60, the rest at -60, the gt class NOT the dominant one),
+    rows whose proposal IS the gt box with zero predicted deltas (L1 residual exactly 0 -> gradient exactly 0), -1 slots, every
+    class 0..K present; per element against float64."""
+    g = torch.Generator().manual_seed(1000 * K + R)
+    cs = (5 * K + 1 + 15) // 16 * 16
+    w = (10.0, 10.0, 5.0, 5.0)
+    pred = torch.randn(R, cs, generator=g)
+    cls = torch.randint(0, K + 1, (R,), generator=g, dtype=torch.int32)
+    props, gts = _rand_boxes(R, g), _rand_boxes(R, g)
+    sat, zero = slice(0, 0), slice(0, 0)
+    if R == 1:
+        cls[0] = K - 1
+    else:
+        sat, zero = slice(0, 32), slice(32, 48)
+        cls[48:48 + K + 1] = torch.arange(K + 1, dtype=torch.int32)          # every class, background included
+        cls[60::23] = -1
+        dom = torch.randint(0, K + 1, (32,), generator=g)
+        cls[sat] = ((dom + 1 + torch.randint(0, K, (32,), generator=g)) % (K + 1)).to(torch.int32)      # any class but the dominant one
+        assert bool((cls[sat].long() != dom).all())
+        pred[sat, :K + 1] = -60.0
+        pred[torch.arange(32), dom] = 60.0
+        cls[zero] = torch.randint(0, K, (16,), generator=g, dtype=torch.int32)
+        cls[zero][:1] = K - 1
+        gts[zero] = props[zero]
+        for r in range(32, 48):
+            c = int(cls[r])
+            pred[r, K + 1 + 4 * c:K + 5 + 4 * c] = 0.0
+    valid = cls >= 0
+    n_valid = float(valid.sum())
+    scale = _scale_for(n_valid)
+    # float64 reference on the same fp32 inputs
+    pr = pred.double().requires_grad_(True)
+    l_cls = F.cross_entropy(pr[valid][:, :K + 1], cls[valid].long(), reduction="sum") / n_valid
+    fg_idx = torch.nonzero(valid & (cls < K))[:, 0]
+    d = pr[:, K + 1:5 * K + 1].view(R, K, 4)[fg_idx, cls[fg_idx].long()]
+    l_reg = (d - _get_deltas(props[fg_idx].double(), gts[fg_idx].double(), w)).abs().sum() / n_valid
+    (l_cls + l_reg).backward()
+    got, lo = _run_box_loss(pred, cls, props, gts, K, cs, n_valid, w, scale)
+    _assert_per_element(got, pr.grad, n_valid, scale, f"box loss K={K} R={R}")
+    assert not got[:, 5 * K + 1:].any(), "padding columns of the fused predictor received a gradient"
+    assert not got[~valid].any(), "-1 slots received a gradient"
+    for r in range(zero.start, zero.stop):
+        c = int(cls[r])
+        assert not got[r, K + 1 + 4 * c:K + 5 + 4 * c].any(), (r, c, got[r])          # exact-zero residual: exact-zero gradient
+    if R > 1:
+        fgc = cls[fg_idx].long()
+        for c in range(K):            # every class' four delta columns carry gradient from its own rows only
+            cols = got[:, K + 1 + 4 * c:K + 5 + 4 * c]
+            assert cols[fg_idx[fgc == c]].any() and not cols[cls.long() != c].any(), c
+    _loss_close(lo[0], l_cls, f"loss_cls K={K} R={R}")
+    _loss_close(lo[1], l_reg, f"loss_box_reg K={K} R={R}")
+
+
+def test_box_loss_all_slots_ignored(gpu_required):
+    """Every row -1 (an image batch whose sampler returned nothing): the losses gain exactly 0, dpred is written as zeros (the
+    buffer starts as NaN), nothing non-finite."""
+    g = torch.Generator().manual_seed(77)
+    R, K, cs = 257, 3, 16
+    pred = torch.randn(R, cs, generator=g) * 30
+    cls = torch.full((R,), -1, dtype=torch.int32)
+    got, lo = _run_box_loss(pred, cls, _rand_boxes(R, g), _rand_boxes(R, g), K, cs, 1.0, (10.0, 10.0, 5.0, 5.0), 1024.0)
+    assert bool(torch.isfinite(got.float()).all()) and not got.any()
+    assert float(lo[0]) == 0.0 and float(lo[1]) == 0.0
+
+
+@pytest.mark.parametrize("M", [1, 37])
+def test_mask_loss_edges_eight_classes(gpu_required, M):
+    """rs_op_mask_loss with the gt channel drawn from all eight classes of the 16-channel predictor (7 present), logits up to +-80
+    (saturated sigmoid both ways, on both target values), one mask with all-0 and one with all-1 targets; per element against
+    float64, every channel but the gt class' exactly 0."""
+    lib = load_library()
+    g = torch.Generator().manual_seed(500 + M)
+    S, cs = 28, 16
+    logits = (torch.randn(M, S * S, cs, generator=g) * 25).clamp(-80, 80)
+    logits[:, ::7] = torch.where(torch.rand(M, len(range(0, S * S, 7)), cs, generator=g) > 0.5, 80.0, -80.0)
+    tgt = (torch.rand(M, S * S, generator=g) > 0.5).to(torch.uint8)
+    cls = torch.randint(0, 8, (M,), generator=g, dtype=torch.int32)
+    cls[0] = 7
+    if M > 1:
+        cls[1:9] = torch.arange(8, dtype=torch.int32)
+        tgt[0], tgt[1] = 0, 1
+    else:
+        tgt[0] = 1
+    norm = float(M * S * S)
+    scale = _scale_for(norm)
+    lr = logits.double().requires_grad_(True)
+    sel = lr[torch.arange(M), :, cls.long()]
+    l = F.binary_cross_entropy_with_logits(sel, tgt.double(), reduction="sum") / norm
+    l.backward()
+    loss = _dev(torch.zeros(1))
+    ld = _dev(logits)
+    dl = torch.full((M, S * S, cs), float("nan"), dtype=torch.float16, device=ld.device)
+    td, cd = _dev(tgt), _dev(cls)
+    _check(lib, lib.rs_op_mask_loss(_ptr(ld), _ptr(dl), _ptr(td), _ptr(cd), _ptr(loss), M, S, cs, scale, None), "rs_op_mask_loss")
+    torch.cuda.synchronize()
+    got = dl.cpu()
+    _assert_per_element(got, lr.grad, norm, scale, f"mask loss M={M}")
+    other = torch.ones(M, 1, cs, dtype=torch.bool)
+    other[torch.arange(M), 0, cls.long()] = False
+    assert not got[other.expand(M, S * S, cs)].any(), "a channel other than the gt class received a gradient"
+    assert all(bool(got[m, :, int(cls[m])].any()) for m in range(M))
+    _loss_close(loss.cpu()[0], l, f"loss_mask M={M}")
+
+
+@pytest.mark.parametrize("hw", [1, 35])
+def test_rpn_loss_edges(gpu_required, hw):
+    """rs_op_rpn_loss on a level of 1 pixel and of 35 (3 anchors each): image 0 ordinary, image 1 without a positive anchor, image 2
+    with every label -1; objectness logits up to +-80; a positive anchor that EQUALS its matched box with zero predicted deltas
+    (gradient exactly 0).  Per element against float64."""
+    lib = load_library()
+    g = torch.Generator().manual_seed(600 + hw)
+    N, A, cs = 3, 3, 16
+    total = hw * A + 5                                   # this level starts 5 anchors into the table
+    off = 5
+    anchors = _rand_boxes(total, g)
+    matched = _rand_boxes(N * total, g).view(N, total, 4).clone()
+    labels = torch.randint(-1, 2, (N, total), generator=g, dtype=torch.int32)
+    labels[0, off] = 1                                   # anchor 0 of pixel 0: positive, equal to its gt, zero deltas
+    labels[1] = labels[1].clamp(max=0)
+    labels[2] = -1
+    matched[0, off] = anchors[off]
+    head = torch.randn(N, hw, cs, generator=g)
+    head[:, :, :A] = (head[:, :, :A] * 30).clamp(-80, 80)
+    head[0, 0, 0] = 80.0
+    head[0, 0, A:A + 4] = 0.0
+    if hw > 1:
+        labels[0, off + A], labels[0, off + 2 * A] = 1, 0
+        head[0, 1, 0], head[0, 2, 0] = -80.0, 80.0       # a positive at -80, a negative at +80: |gradient| = 1 / normalizer
+    normalizer = 256.0 * N
+    scale = _scale_for(normalizer)
+    hr = head.double().requires_grad_(True)
+    lab = labels[:, off:]
+    logits = hr[:, :, :A].reshape(N, -1)
+    deltas = hr[:, :, A:5 * A].reshape(N, -1, 4)
+    valid, pos = lab >= 0, lab == 1
+    l_cls = F.binary_cross_entropy_with_logits(logits[valid], lab[valid].double(), reduction="sum") / normalizer
+    tg = torch.stack([_get_deltas(anchors[off:].double(), matched[i, off:].double(), (1, 1, 1, 1)) for i in range(N)])
+    l_loc = (deltas[pos] - tg[pos]).abs().sum() / normalizer
+    (l_cls + l_loc).backward()
+    loss = _dev(torch.zeros(2))
+    ad, md, ld, hd = _dev(anchors), _dev(matched), _dev(labels), _dev(head)
+    dh = torch.full((N, hw, cs), float("nan"), dtype=torch.float16, device=hd.device)
+    _check(lib, lib.rs_op_rpn_loss(_ptr(hd), _ptr(dh), _ptr(ld), _ptr(ad), _ptr(md), _ptr(loss), N, hw, A, cs, off, total,
+                                   normalizer, scale, None), "rs_op_rpn_loss")
+    torch.cuda.synchronize()
+    got = dh.cpu()
+    _assert_per_element(got, hr.grad, normalizer, scale, f"rpn loss hw={hw}")
+    assert not got[:, :, 5 * A:].any(), "padding columns of the fused head received a gradient"
+    assert not got[2].any(), "an image whose labels are all -1 received a gradient"
+    assert not got[1, :, A:].any(), "an image without a positive anchor received a box gradient"
+    assert not got[0, 0, A:A + 4].any(), "exact-zero L1 residual: the gradient must be exactly 0"
+    assert bool(got[0, :, :A].any()) and (hw == 1 or bool(got[1, :, :A].any()))
+    lo = loss.cpu()
+    _loss_close(lo[0], l_cls, f"loss_rpn_cls hw={hw}")
+    _loss_close(lo[1], l_loc, f"loss_rpn_loc hw={hw}")
+
+
+@pytest.mark.parametrize("cout,cin,k", [(16, 256, 1), (32, 1024, 1), (48, 1024, 1), (256, 256, 3)])
+def test_fold_weights_head_shapes_bit_equal(gpu_required, cout, cin, k):
+    """rs_op_fold_weights at the shapes of the trainer's narrow heads -- the 16-row mask predictor / RPN heads, the 32- and 48-row box
+    predictor of 4..6 and 7..8 classes (half a 32 x 32 tile; one and a half) -- and a 3x3 layer: forward operand and the transposed,
+    tap-flipped operand (kpad_t = k*k*round64(cout)) are BIT-equal to the numpy layout, padding columns included (the caller zeroes
+    the buffers: the kernel writes no padding)."""
+    lib = load_library()
+    g = torch.Generator().manual_seed(cout + cin + k)
+    w = torch.randn(cout, cin, k, k, generator=g) * 0.1
+    scale = torch.rand(cout, generator=g) + 0.5
+    master = w.permute(0, 2, 3, 1).reshape(cout, k * k * cin).contiguous()
+    kpad, kpad_t = k * k * cin, k * k * ((cout + 63) // 64 * 64)
+    md, sd = _dev(master), _dev(scale)
+    fwd = torch.zeros(cout, kpad, dtype=torch.float16, device=md.device)
+    bwd = torch.zeros(cin, kpad_t, dtype=torch.float16, device=md.device)
+    _check(lib, lib.rs_op_fold_weights(_ptr(md), _ptr(sd), _ptr(fwd), _ptr(bwd), cout, cin, k, k, kpad, kpad_t, None), "fold")
+    torch.cuda.synchronize()
+    folded = (master.numpy() * scale.numpy()[:, None]).astype(np.float32).astype(np.float16)          # fp32 product, then one rounding
+    want_f = folded
+    want_b = np.zeros((cin, kpad_t), np.float16)
+    t = folded.reshape(cout, k, k, cin)[:, ::-1, ::-1].transpose(3, 1, 2, 0).reshape(cin, k * k * cout)      # [ci][(k-1-i, k-1-j, co)]
+    want_b[:, :k * k * cout] = t
+    assert kpad_t > k * k * cout or cout % 64 == 0
+    gf, gb = fwd.cpu().numpy(), bwd.cpu().numpy()
+    assert np.array_equal(gf.view(np.uint16), want_f.view(np.uint16)), int((gf != want_f).sum())
+    assert np.array_equal(gb.view(np.uint16), want_b.view(np.uint16)), int((gb != want_b).sum())
+
+
+@pytest.mark.parametrize("f32", [False, True])
+@pytest.mark.parametrize("cout", [16, 48])
+def test_conv_wgrad_predictor_shapes(gpu_required, cout, f32):
+    """The box predictor's weight gradient as the trainer runs it -- a linear layer over an (M x 1) image, M = 333 RoIs, 1024 inputs,
+    16 (K <= 3) and 48 (K = 7, 8) output rows, a per-channel scale -- in both precisions, at the bounds of the wgrad tests above."""
+    g = torch.Generator().manual_seed(900 + cout)
+    m, kin = 333, 1024
+    a = torch.randn(m, kin, generator=g)
+    dy = torch.randn(m, cout, generator=g) * 0.05
+    if not f32:
+        a, dy = _r16(a), _r16(dy)
+    scale = torch.rand(cout, generator=g) + 0.5
+    ref = ((dy.double().t() @ a.double()) * scale.double()[:, None]).float()
+    got = run_wgrad(a.t().reshape(1, kin, m, 1), dy.t().reshape(1, cout, m, 1), 1, 1, 0, scale=scale, in_halo=0, dy_halo=0, f32=f32)[:, :, 0, 0]
+    err = float((got - ref).abs().max())
+    print(f"wgrad {m}x{kin}->{cout} {'fp32' if f32 else 'fp16'}: max err {err:.3e}, ref max {float(ref.abs().max()):.3f}")
+    assert err <= (1e-5 if f32 else 2e-3) * max(1.0, float(ref.abs().max())), err

@@ -280,7 +280,8 @@ def test_box_head_training_step_matches_autograd(gpu_required):
         p = "roi_heads."
         w_pred = np.concatenate([W[p + "box_predictor.cls_score.weight"].grad.numpy(), W[p + "box_predictor.bbox_pred.weight"].grad.numpy()], 0)
         got = tr.tensor("g:" + p + "box_predictor.w") / scale
-        assert np.linalg.norm(got[:11] - w_pred) / np.linalg.norm(w_pred) <= 3e-2 and float(np.abs(got[11:]).max()) == 0.0
+        assert got.shape[0] == (5 * K + 1 + 15) // 16 * 16 and w_pred.shape[0] == 5 * K + 1
+        assert np.linalg.norm(got[:5 * K + 1] - w_pred) / np.linalg.norm(w_pred) <= 3e-2 and float(np.abs(got[5 * K + 1:]).max()) == 0.0
         assert rel("g:" + p + "box_head.fc2.w", W[p + "box_head.fc2.weight"].grad.numpy()) <= 3e-2
         g1 = W[p + "box_head.fc1.weight"].grad.reshape(1024, 256, 7, 7).permute(0, 2, 3, 1).reshape(1024, -1).numpy()
         assert rel("g:" + p + "box_head.fc1.w", g1) <= 3e-2
@@ -441,9 +442,10 @@ def _engine_step(tr, tiles, gt_boxes, gt_classes, polys, seed):
     return targets, where
 
 
-def _d2_grad(W, layer):
-    """autograd's gradient of engine layer ``layer`` in the engine's GEMM layout (the layout of the flat gradient buffer)."""
-    A, K = 3, 2
+def _d2_grad(W, layer, spec=None):
+    """autograd's gradient of engine layer ``layer`` in the engine's GEMM layout (the layout of the flat gradient buffer): the fused RPN
+    heads are 5A rows inside 16, the fused box predictor 5K+1 rows inside round16(5K+1), the mask predictor K rows inside 16."""
+    A, K = (3, 2) if spec is None else (spec.num_anchors, spec.num_classes)
     if layer == "proposal_generator.rpn_head.heads":
         p = "proposal_generator.rpn_head."
         g = torch.cat([W[p + "objectness_logits.weight"].grad, W[p + "anchor_deltas.weight"].grad], 0)[:, :, 0, 0].numpy()
@@ -451,7 +453,8 @@ def _d2_grad(W, layer):
         return out
     if layer == "roi_heads.box_predictor":
         g = torch.cat([W[layer + ".cls_score.weight"].grad, W[layer + ".bbox_pred.weight"].grad], 0).numpy()
-        out = np.zeros((16, g.shape[1]), np.float32); out[:5 * K + 1] = g
+        assert g.shape[0] == 5 * K + 1
+        out = np.zeros(((5 * K + 1 + 15) // 16 * 16, g.shape[1]), np.float32); out[:5 * K + 1] = g
         return out
     if layer == "roi_heads.box_head.fc1":
         g = W[layer + ".weight"].grad
@@ -460,6 +463,7 @@ def _d2_grad(W, layer):
         return W[layer + ".weight"].grad.permute(0, 2, 3, 1).reshape(256, 1024).numpy()
     if layer == "roi_heads.mask_head.predictor16":
         g = W["roi_heads.mask_head.predictor.weight"].grad[:, :, 0, 0].numpy()
+        assert g.shape[0] == K
         out = np.zeros((16, g.shape[1]), np.float32); out[:K] = g
         return out
     g = W[layer + ".weight"].grad
@@ -492,7 +496,7 @@ def test_reference_precision_training_step_matches_autograd(gpu_required):
             assert abs(float(losses[i]) - r) <= 1e-4 * abs(r) + 1e-7, (n, float(losses[i]), r)
         worst = {}
         for layer in trainable_layers(spec):
-            want = _d2_grad(W, layer)
+            want = _d2_grad(W, layer, spec)
             got = tr.tensor(f"g:{layer}.w")
             assert got.shape == want.shape, (layer, got.shape, want.shape)
             worst[layer] = float(np.linalg.norm(got - want) / max(np.linalg.norm(want), 1e-30))

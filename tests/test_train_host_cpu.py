@@ -25,11 +25,13 @@ def test_solver_values_come_from_the_reference_yaml():
         assert TM.lr_at(sv, it) == pytest.approx(T.lr_at(ts, it))
 
 
-def test_master_layouts_round_trip_to_detectron2_keys():
+@pytest.mark.parametrize("K", [1, 2, 3, 4, 8])
+def test_master_layouts_round_trip_to_detectron2_keys(K):
     """train_tensors (detectron2 tensors -> engine master layouts) followed by master_to_d2 returns every trainable tensor
     unchanged -- conv OHWI, fused RPN heads, fc1's (h,w,c) K order, fused predictor, transposed deconv, padded mask predictor --
-    and leaves the frozen stem / res2 / FrozenBN tensors alone."""
-    spec = EngineSpec(num_classes=2)
+    and leaves the frozen stem / res2 / FrozenBN tensors alone.  At every class count the trainer accepts the fused box predictor is
+    5K+1 rows inside round16(5K+1) (16 / 32 / 48; K = 3 fills its 16 rows) and the mask predictor K rows inside 16, padding rows zero."""
+    spec = EngineSpec(num_classes=K)
     W = Wt.synthetic_weights(spec, 0)
     T = Wt.train_tensors(spec, W)
     raw = Wt.engine_tensors(spec, W, w_dtype=np.float32, fold_bn=False)
@@ -48,7 +50,17 @@ def test_master_layouts_round_trip_to_detectron2_keys():
     assert set(back) == set(W)
     for k in W:
         assert back[k].shape == W[k].shape and np.array_equal(back[k], W[k].astype(np.float32)), k
-    assert sum(T[k].size for k in T if k.endswith(".m32")) == pytest.approx(43.7e6, rel=0.01)       # 43.7 M trainable
+    rows = (5 * K + 1 + 15) // 16 * 16
+    assert rows == {1: 16, 2: 16, 3: 16, 4: 32, 8: 48}[K]
+    bw, bb = T["roi_heads.box_predictor.m32"], raw["roi_heads.box_predictor.b"]
+    assert bw.shape == (rows, 1024) and bb.shape == (rows,)
+    assert not bw[5 * K + 1:].any() and not bb[5 * K + 1:].any() and bw[:5 * K + 1].any(axis=1).all()
+    mw, mb = T["roi_heads.mask_head.predictor16.m32"], T["roi_heads.mask_head.predictor16.b"]
+    assert mw.shape == (16, 256) and mb.shape == (16,)
+    assert not mw[K:].any() and not mb[K:].any() and mw[:K].any(axis=1).all()
+    assert not T["roi_heads.mask_head.predictor16.w"][K:].any()
+    if K == 2:
+        assert sum(T[k].size for k in T if k.endswith(".m32")) == pytest.approx(43.7e6, rel=0.01)       # 43.7 M trainable
 
 
 def test_coco_mapper_flip_scale_and_sampler(tmp_path):
