@@ -18,7 +18,6 @@
 
 // ------------------------------------------------------------------------------------- errors
 static thread_local char g_err[1024] = "";
-static bool g_trainer_unfused_shortcut = false;   // set by rs_trainer_create while it builds its forward engine
 
 // ---------------------------------------------------------------- debug switches: the one place that reads the environment
 static RsDebug g_debug;
@@ -200,6 +199,11 @@ struct rs_engine {
   unsigned long long* h_crop_total = nullptr;   // pinned
   hipEvent_t ev_crop_hdr = nullptr;
 
+  // the precision of the activations, as the launchers take it (PreprocParams::out_f32, RoiAlignParams::f32, MaskPredictParams::f32)
+  int prec_code() const { return f32 ? 1 : (split ? 2 : 0); }
+  int planes() const { return split ? 2 : 1; }        // fp16 planes per activation / weight
+  size_t esize() const { return f32 ? 4 : 2; }        // bytes per element of one plane
+
   int alloc(void** p, size_t bytes) {
     if (bytes == 0) bytes = 16;
     bytes = (bytes + 255) & ~(size_t)255;
@@ -208,22 +212,34 @@ struct rs_engine {
     RS_HIP(hipMemsetAsync(*p, 0, bytes, stream));
     return RS_OK;
   }
-  void reg(const std::string& name, void* p, int dtype, std::vector<int64_t> dims, int halo) {
+  // A zeroed device buffer of the given shape, entered in the tensor table (rs_engine_tensor); buffers nobody inspects take plain alloc
+  template <class T>
+  int new_tensor(T** p, const std::string& name, int dtype, std::vector<int64_t> dims, int halo = 0) {
     TensorInfo t;
-    t.name = name; t.p = p; t.dtype = dtype; t.ndim = (int)dims.size(); t.halo = halo;
+    t.name = name; t.dtype = dtype; t.ndim = (int)dims.size(); t.halo = halo;
     size_t nb = dt_size(dtype);
     for (size_t i = 0; i < dims.size(); ++i) { t.dims[i] = dims[i]; nb *= (size_t)dims[i]; }
     t.bytes = dtype == DT_SPLIT16 ? 2 * nb : nb;
+    int rc = alloc((void**)p, t.bytes);
+    if (rc) return rc;
+    t.p = *p;
     tensors.push_back(t);
+    return RS_OK;
   }
   int new_act(Act* a, const std::string& name, int N, int H, int W, int C, int pad) {
     a->N = N; a->H = H; a->W = W; a->C = C; a->pad = pad;
-    const size_t bytes = (size_t)N * a->Hp() * a->Wp() * C * (f32 ? 4 : 2) * (split ? 2 : 1);
-    int rc = alloc((void**)&a->p, bytes);
-    if (rc) return rc;
     a->lo = split ? (long long)N * a->Hp() * a->Wp() * C : 0;
-    reg(name, a->p, f32 ? DT_F32 : (split ? DT_SPLIT16 : DT_F16), {N, a->Hp(), a->Wp(), C}, pad);
-    return RS_OK;
+    return new_tensor(&a->p, name, f32 ? DT_F32 : (split ? DT_SPLIT16 : DT_F16), {N, a->Hp(), a->Wp(), C}, pad);
+  }
+  // Appends a stage and returns it for its `fn`.  A stage that counts saturated values passes the address of its launch parameters'
+  // `sat` field and gets the counter of its own position in `stages` (null in a trainer's forward engine).  Call it in a statement of
+  // its own, before the lambda that copies the parameters: in `add_stage(..).fn = [p]..` the right-hand side is evaluated first.
+  Stage& add_stage(const std::string& name, double flops_per_image, double bytes_per_image, unsigned long long** sat = nullptr) {
+    if (sat) *sat = sat_dev ? sat_dev + stages.size() : nullptr;
+    stages.emplace_back();
+    Stage& st = stages.back();
+    st.name = name; st.flops_per_image = flops_per_image; st.bytes_per_image = bytes_per_image;
+    return st;
   }
   const BlobEntry* find(const std::string& n) {
     auto it = blob.find(n);
@@ -249,12 +265,52 @@ struct rs_engine {
     return RS_OK;
   }
   int parse_blob(const void* data, size_t nbytes);
-  int build();
   struct DeferredConv { ConvParams p; int m_per_image = 0; double flops = 0, bytes = 0; };
-  int add_conv(const std::string& name, const std::string& wname, const Act& in, const Act& out, int k, int stride,
-               int pad, bool relu, const Act* res, const Act* up, int cin_real, int units_per_tile = 1,
-               const int* m_count = nullptr, const Act* in2 = nullptr, int stride2 = 1, DeferredConv* defer = nullptr);
+  struct ConvDesc {                  // one conv / linear stage (add_conv): ConvDesc{k, stride, pad, relu}, the rest by name
+    int k = 1, stride = 1, pad = 0;
+    bool relu = false;
+    const Act* res = nullptr;        // residual added before the ReLU
+    const Act* up = nullptr;         // coarser map added 2x-upsampled (FPN top-down path)
+    int cin_real = 0;                // input channels in the FLOP count (stem: 3 of 8 padded channels); 0 = in.C
+    int units_per_tile = 1;          // images of the conv per input tile (1 for feature maps, D for per-RoI maps)
+    const int* m_count = nullptr;    // device-side count of units actually present
+    const Act* in2 = nullptr;        // second K source: 1x1 taps at stride2 (projection shortcut folded into conv3)
+    int stride2 = 1;
+    DeferredConv* defer = nullptr;   // filled instead of a stage: the caller merges it into a multi-map launch (add_merged_convs)
+  };
+  int add_conv(const std::string& name, const std::string& wname, const Act& in, const Act& out, const ConvDesc& d);
   int add_merged_convs(const std::string& name, const std::vector<DeferredConv>& d);
+  // ---- the graph builder: build() runs the sections below in order; `Graph` is what one section hands to the next
+  // (the detections a forward returns are the det_* members above)
+  struct Graph {
+    Act x0, c1, res_out[4], P[5];
+    Act rpn_t[RS_MAX_LEVELS];          // 3x3 RPN conv outputs (written only where the heads are not fused into it)
+    float* rpn_ho[RS_MAX_LEVELS];      // RPN head outputs (objectness + deltas)
+    float* prop_boxes = nullptr;
+    int *prop_count = nullptr, *prop_level = nullptr, *prop_order = nullptr;
+    float* pred = nullptr;             // box predictor output
+    int *slot_list = nullptr, *det_total = nullptr;   // compacted detection slots of the batch, for the mask head
+  };
+  struct ResCursor {                   // running state of the residual stages, block to block
+    Act cur;
+    Act t1_pre;                        // conv1 output of the NEXT block when the previous block's fused tail already produced it
+    bool have_t1 = false;
+    int bott = 64, cout = 0;
+  };
+  int build();
+  int build_input(Graph& g);
+  int build_stem(Graph& g);
+  int build_res_stages(Graph& g);
+  int build_bottleneck(ResCursor& r, int si, int bi);
+  int add_fused_tail(const std::string& nm, const std::string& next, const Act& t1, const Act& x, const Act& out, const Act* t1n, bool proj);
+  int build_fpn(Graph& g);
+  int build_rpn(Graph& g);
+  int build_box_head(Graph& g);
+  int build_mask_head(Graph& g);
+  // FPN output convs / RPN 3x3 of all levels as one multi-map launch each
+  bool merge_maps() const { return merge_levels && !f32 && rs_debug().conv_deep && use_glds > 0; }
+  int add_nms_rule(const char* head, NmsParams* np, int group);
+  RoiAlignParams roi_align_levels(const Graph& g) const;
   int run(const uint8_t* tiles, int n, int phase = -1);
   int run_stages(int n, bool record, int phase = -1, bool all_wide = false);
   int assign_phases();
@@ -274,7 +330,6 @@ struct rs_engine {
   unsigned long long* h_sat_copy = nullptr;  // pinned target of the fetch copies
   bool sat_copy_pending = false;
   std::vector<int64_t> h_sat;                // the most recent fetched forward's
-  unsigned long long* sat_slot() const { return sat_dev ? sat_dev + stages.size() : nullptr; }   // counter of the stage pushed next
   int sat_copy(hipStream_t s) {
     if (!sat_dev) return RS_OK;
     RS_HIP(hipMemcpyAsync(h_sat_copy, sat_snap, stages.size() * 8, hipMemcpyDeviceToHost, s));
@@ -325,12 +380,11 @@ int rs_engine::parse_blob(const void* data, size_t nbytes) {
   return RS_OK;
 }
 
-// One conv / linear stage.  `cin_real` only feeds the FLOP count (stem: 3 of 8 padded channels).
-// `units_per_tile` = images of the conv per input tile (1 for feature maps, D for per-RoI maps);
-// `m_count` = optional device-side count of units actually present.
-int rs_engine::add_conv(const std::string& name, const std::string& wname, const Act& in, const Act& out, int k,
-                        int stride, int pad, bool relu, const Act* res, const Act* up, int cin_real, int units_per_tile,
-                        const int* m_count, const Act* in2, int stride2, DeferredConv* defer) {
+// One conv / linear stage (ConvDesc).
+int rs_engine::add_conv(const std::string& name, const std::string& wname, const Act& in, const Act& out, const ConvDesc& d) {
+  const int k = d.k, stride = d.stride, pad = d.pad, stride2 = d.stride2, units_per_tile = d.units_per_tile;
+  const int cin_real = d.cin_real ? d.cin_real : in.C;
+  const Act *res = d.res, *up = d.up, *in2 = d.in2;
   const BlobEntry* w = findw(wname);
   const BlobEntry* b = find(wname + ".b");
   RS_CHECK(w && b, RS_ERR_BLOB, "weights for %s missing from blob", wname.c_str());
@@ -348,7 +402,7 @@ int rs_engine::add_conv(const std::string& name, const std::string& wname, const
   p.Cout = out.C;
   p.out_Hp = out.Hp(); p.out_Wp = out.Wp(); p.out_Cs = out.C; p.out_pad = out.pad;
   if (up) { p.up_Hp = up->Hp(); p.up_Wp = up->Wp(); p.up_Cs = up->C; p.up_pad = up->pad; }
-  p.relu = relu ? 1 : 0;
+  p.relu = d.relu ? 1 : 0;
   if (in2) {   // second K source: 1x1 taps at stride2 (projection shortcut folded into conv3)
     RS_CHECK((out.H - 1) * stride2 < in2->H && (out.W - 1) * stride2 < in2->W && in2->C % 64 == 0, RS_ERR_ARG, "%s: second source geometry", name.c_str());
     p.in2 = in2->p; p.in2_Hp = in2->Hp(); p.in2_Wp = in2->Wp(); p.in2_Cs = in2->C; p.in2_off = in2->pad;
@@ -371,35 +425,32 @@ int rs_engine::add_conv(const std::string& name, const std::string& wname, const
       p.KW = 8;
       for (int t = 0; t < k * 4 && t < (int)koff.size(); ++t) koff[t] = ((t / 4) * p.in_Wp + (t % 4) * 2) * in.C;
     }
-    int* d = nullptr;
-    int rc = alloc((void**)&d, koff.size() * 4);
+    int* dk = nullptr;
+    int rc = alloc((void**)&dk, koff.size() * 4);
     if (rc) return rc;
-    RS_HIP(hipMemcpyAsync(d, koff.data(), koff.size() * 4, hipMemcpyHostToDevice, stream));
+    RS_HIP(hipMemcpyAsync(dk, koff.data(), koff.size() * 4, hipMemcpyHostToDevice, stream));
     RS_HIP(hipStreamSynchronize(stream));
-    p.koff = d;
+    p.koff = dk;
   }
   const int m_per_image = out.H * out.W * units_per_tile;
-  p.m_count = m_count;
+  p.m_count = d.m_count;
   p.m_mul = out.H * out.W;
-  Stage st;
-  st.name = name;
-  st.flops_per_image = 2.0 * m_per_image * ((double)k * k * cin_real + (in2 ? in2->C : 0)) * out.C;
+  const double flops = 2.0 * m_per_image * ((double)k * k * cin_real + (in2 ? in2->C : 0)) * out.C;
   // algorithmic bytes: the input pixels the convolution actually reads (a stride-s 1x1 touches every s-th pixel of every
   // s-th row only), the output once, the residual once, the second K source at the output's pixel count
   const double in_px = k >= stride ? (double)in.H * in.W : (double)out.H * out.W * k * k;
-  st.bytes_per_image = (split ? 4.0 : 2.0) * (in_px * in.C * units_per_tile + (double)m_per_image * out.C * (1 + (res ? 1 : 0)) +
-                              (in2 ? (double)m_per_image * in2->C : 0.0));
-  const int glds = use_glds;
-  if (defer) {           // the caller merges this convolution into a multi-map launch (add_merged_convs)
-    defer->p = p; defer->m_per_image = m_per_image; defer->flops = st.flops_per_image; defer->bytes = st.bytes_per_image;
+  const double bytes = 2.0 * planes() * (in_px * in.C * units_per_tile + (double)m_per_image * out.C * (1 + (res ? 1 : 0)) +
+                                        (in2 ? (double)m_per_image * in2->C : 0.0));
+  if (d.defer) {
+    d.defer->p = p; d.defer->m_per_image = m_per_image; d.defer->flops = flops; d.defer->bytes = bytes;
     return RS_OK;
   }
-  p.sat = sat_slot();
+  const int glds = use_glds;
+  Stage& st = add_stage(name, flops, bytes, &p.sat);   // before the lambda copies p
   st.fn = [p, m_per_image, glds](int n, hipStream_t s) mutable {
     p.M = n * m_per_image;
     return launch_conv(p, s, -1, glds);
   };
-  stages.push_back(st);
   return RS_OK;
 }
 
@@ -409,8 +460,7 @@ int rs_engine::add_merged_convs(const std::string& name, const std::vector<Defer
   ConvParams common = d[0].p;
   std::vector<ConvSeg> segs(d.size());
   std::vector<int> mpi(d.size());
-  Stage st;
-  st.name = name;
+  double flops = 0, bytes = 0;
   for (size_t i = 0; i < d.size(); ++i) {
     const ConvParams& q = d[i].p;
     RS_CHECK(q.Cin == common.Cin && q.Cout == common.Cout && q.KH == common.KH && q.KW == common.KW && q.stride == 1 && q.in_Cs == common.in_Cs &&
@@ -423,15 +473,14 @@ int rs_engine::add_merged_convs(const std::string& name, const std::vector<Defer
     segs[i].in_lo = q.in_lo; segs[i].out_lo = q.out_lo; segs[i].wscale = q.wscale;
     segs[i].Ho = q.Ho; segs[i].Wo = q.Wo; segs[i].in_Hp = q.in_Hp; segs[i].in_Wp = q.in_Wp; segs[i].out_Hp = q.out_Hp; segs[i].out_Wp = q.out_Wp;
     mpi[i] = d[i].m_per_image;
-    st.flops_per_image += d[i].flops;
-    st.bytes_per_image += d[i].bytes;
+    flops += d[i].flops;
+    bytes += d[i].bytes;
   }
-  common.sat = sat_slot();
+  Stage& st = add_stage(name, flops, bytes, &common.sat);
   st.fn = [common, segs, mpi](int n, hipStream_t s) {
     g_last_conv_variant = 12;
     return launch_conv_deep_multi(common, segs.data(), mpi.data(), (int)segs.size(), n, s);
   };
-  stages.push_back(st);
   return RS_OK;
 }
 
@@ -477,9 +526,10 @@ int rs_engine::set_image_sizes(const int32_t* new_h, const int32_t* new_w, int n
   return RS_OK;
 }
 
+static const std::string kBottomUp = "backbone.bottom_up.";
+
 int rs_engine::build() {
   const rs_spec& S = spec;
-  const int NB = max_batch;
   rs_resize_shape(tile_h, tile_w, S.min_size_test, S.max_size_test, &net_h, &net_w);
   const int dv = S.size_divisibility;
   pad_h = (net_h + dv - 1) / dv * dv;
@@ -498,10 +548,26 @@ int rs_engine::build() {
     if ((rc = alloc((void**)&sat_snap, kSatCap * 8))) return rc;
     RS_HIP(hipHostMalloc((void**)&h_sat_copy, kSatCap * 8, hipHostMallocDefault));
   }
+  Graph g;
+  if ((rc = build_input(g))) return rc;
+  if ((rc = build_stem(g))) return rc;
+  if ((rc = build_res_stages(g))) return rc;
+  if ((rc = build_fpn(g))) return rc;
+  if ((rc = build_rpn(g))) return rc;
+  if ((rc = build_box_head(g))) return rc;
+  if (S.mask_on && (rc = build_mask_head(g))) return rc;
+  RS_CHECK(stages.size() <= (size_t)kSatCap, RS_ERR_UNSUPPORTED, "%d stages: more than the %d saturation counters", (int)stages.size(), kSatCap);
+  h_sat.assign(stages.size(), 0);
+  RS_HIP(hipStreamSynchronize(stream));
+  return RS_OK;
+}
 
-  // ---- resize tables + input staging
-  RS_CHECK(alloc((void**)&tiles_dev, (size_t)NB * tile_h * tile_w * tile_c) == RS_OK, RS_ERR_HIP, "alloc tiles");
-  reg("tiles", tiles_dev, DT_U8, {NB, tile_h, tile_w, tile_c}, 0);
+// ---- resize tables + input staging + preprocess
+int rs_engine::build_input(Graph& g) {
+  const rs_spec& S = spec;
+  const int NB = max_batch;
+  int rc;
+  if ((rc = new_tensor(&tiles_dev, "tiles", DT_U8, {NB, tile_h, tile_w, tile_c}))) return rc;
   PreprocParams pp;
   memset(&pp, 0, sizeof pp);
   pp.need_h = net_w != tile_w;
@@ -524,278 +590,288 @@ int rs_engine::build() {
     RS_HIP(hipStreamSynchronize(stream));
     pp.hb = dhb; pp.hk = dhk; pp.vb = dvb; pp.vk = dvk; pp.ksh = ksh; pp.ksv = ksv;
   }
-  Act x0;
+  Act& x0 = g.x0;
   if ((rc = new_act(&x0, "net_input", NB, pad_h, pad_w, 4, 3))) return rc;
   pp.out = x0.p; pp.H = tile_h; pp.W = tile_w; pp.C = tile_c; pp.new_h = net_h; pp.new_w = net_w;
-  pp.out_Hp = x0.Hp(); pp.out_Wp = x0.Wp(); pp.flip = S.flip_channels; pp.out_f32 = f32 ? 1 : (split ? 2 : 0);
+  pp.out_Hp = x0.Hp(); pp.out_Wp = x0.Wp(); pp.flip = S.flip_channels; pp.out_f32 = prec_code();
   pp.out_lo = x0.lo;
   for (int c = 0; c < 4; ++c) { pp.mean[c] = S.pixel_mean[c]; pp.stdv[c] = S.pixel_std[c] == 0.f ? 1.f : S.pixel_std[c]; }
-  {
-    Stage st;
-    st.name = "preprocess";
-    st.bytes_per_image = (double)tile_h * tile_w * tile_c + (double)net_h * net_w * 8;
-    pp.tiles = tiles_dev;
-    pp.sat = sat_slot();
-    const size_t x0_bytes = (size_t)NB * x0.Hp() * x0.Wp() * 4 * (f32 ? 4 : 2);       // one plane
-    const int planes = split ? 2 : 1;
-    st.fn = [this, pp, x0_bytes, planes](int n, hipStream_t s) mutable {
-      if (img_new_h.empty()) {
-        pp.N = n;
-        return launch_preprocess(pp, s);
-      }
-      // images of different sizes in one canvas: zeros (the padding value of ImageList.from_tensors) outside each image
-      RS_CHECK((int)img_new_h.size() >= n, RS_ERR_ARG, "per-image sizes set for %d images, batch of %d", (int)img_new_h.size(), n);
-      RS_HIP(hipMemsetAsync((void*)pp.out, 0, x0_bytes * planes, s));
-      for (int i = 0; i < n; ++i) {
-        PreprocParams q = pp;
-        ResizeTab th, tv;
-        int rc;
-        if ((rc = resize_tab(tile_w, img_new_w[i], tab_h, &th))) return rc;
-        if ((rc = resize_tab(tile_h, img_new_h[i], tab_v, &tv))) return rc;
-        q.N = 1;
-        q.tiles = pp.tiles + (size_t)i * tile_h * tile_w * tile_c;
-        q.out = (half_t*)((char*)pp.out + (size_t)i * (x0_bytes / max_batch));
-        q.new_h = img_new_h[i]; q.new_w = img_new_w[i];
-        q.need_h = q.new_w != tile_w; q.need_v = q.new_h != tile_h;
-        q.hb = th.b; q.hk = th.k; q.ksh = th.ks; q.vb = tv.b; q.vk = tv.k; q.ksv = tv.ks;
-        if ((rc = launch_preprocess(q, s))) return rc;
-      }
-      return RS_OK;
-    };
-    stages.push_back(st);
-    if ((rc = alloc((void**)&img_hw_dev, (size_t)NB * 8))) return rc;
-    if ((rc = set_image_sizes(nullptr, nullptr, 0))) return rc;
-  }
+  pp.tiles = tiles_dev;
+  Stage& st = add_stage("preprocess", 0, (double)tile_h * tile_w * tile_c + (double)net_h * net_w * 8, &pp.sat);
+  const size_t x0_bytes = (size_t)NB * x0.Hp() * x0.Wp() * 4 * esize();       // one plane
+  const int planes = this->planes();
+  st.fn = [this, pp, x0_bytes, planes](int n, hipStream_t s) mutable {
+    if (img_new_h.empty()) {
+      pp.N = n;
+      return launch_preprocess(pp, s);
+    }
+    // images of different sizes in one canvas: zeros (the padding value of ImageList.from_tensors) outside each image
+    RS_CHECK((int)img_new_h.size() >= n, RS_ERR_ARG, "per-image sizes set for %d images, batch of %d", (int)img_new_h.size(), n);
+    RS_HIP(hipMemsetAsync((void*)pp.out, 0, x0_bytes * planes, s));
+    for (int i = 0; i < n; ++i) {
+      PreprocParams q = pp;
+      ResizeTab th, tv;
+      int rc;
+      if ((rc = resize_tab(tile_w, img_new_w[i], tab_h, &th))) return rc;
+      if ((rc = resize_tab(tile_h, img_new_h[i], tab_v, &tv))) return rc;
+      q.N = 1;
+      q.tiles = pp.tiles + (size_t)i * tile_h * tile_w * tile_c;
+      q.out = (half_t*)((char*)pp.out + (size_t)i * (x0_bytes / max_batch));
+      q.new_h = img_new_h[i]; q.new_w = img_new_w[i];
+      q.need_h = q.new_w != tile_w; q.need_v = q.new_h != tile_h;
+      q.hb = th.b; q.hk = th.k; q.ksh = th.ks; q.vb = tv.b; q.vk = tv.k; q.ksv = tv.ks;
+      if ((rc = launch_preprocess(q, s))) return rc;
+    }
+    return RS_OK;
+  };
+  if ((rc = alloc((void**)&img_hw_dev, (size_t)NB * 8))) return rc;
+  return set_image_sizes(nullptr, nullptr, 0);
+}
 
-  // ---- stem
-  const std::string bu = "backbone.bottom_up.";
+// ---- stem: conv 7x7 s2 + FrozenBN + ReLU, max-pool 3x3 s2
+int rs_engine::build_stem(Graph& g) {
+  const rs_spec& S = spec;
+  const std::string& bu = kBottomUp;
+  const Act& x0 = g.x0;
   const int h2 = pad_h / 2, w2 = pad_w / 2, h4 = pad_h / 4, w4 = pad_w / 4;
-  Act stem, c1;
-  if ((rc = new_act(&stem, "stem_conv", NB, h2, w2, S.stem_out_channels, 1))) return rc;
-  if ((rc = new_act(&c1, "stem", NB, h4, w4, S.stem_out_channels, 1))) return rc;
+  Act stem;
+  Act& c1 = g.c1;
+  int rc;
+  if ((rc = new_act(&stem, "stem_conv", max_batch, h2, w2, S.stem_out_channels, 1))) return rc;
+  if ((rc = new_act(&c1, "stem", max_batch, h4, w4, S.stem_out_channels, 1))) return rc;
   const BlobEntry* stem_w = findw(bu + "stem.conv1f");          // fragment-ordered copy of the 64 x 256 stem matrix
   const BlobEntry* stem_b = find(bu + "stem.conv1.b");
-  if (fuse_stem && !f32 && !split && use_glds > 0 && S.stem_out_channels == 64 && x0.C == 4 && x0.pad == 3 && stem_w && stem_b &&
-      (long long)stem_w->dims[0] * stem_w->dims[1] == 7 * 4 * 64 * 8 && (pad_h & 3) == 0 && (pad_w & 3) == 0) {
+  const BlobEntry* stem_si = split ? find(bu + "stem.conv1.wsi") : nullptr;
+  if (fuse_stem && !f32 && use_glds > 0 && S.stem_out_channels == 64 && x0.C == 4 && x0.pad == 3 && stem_w && stem_b && (!split || stem_si) &&
+      (long long)stem_w->dims[0] * stem_w->dims[1] == planes() * 7 * 4 * 64 * 8 && (pad_h & 3) == 0 && (pad_w & 3) == 0) {
     // conv 7x7 s2 + FrozenBN + ReLU + max-pool 3x3 s2 in one launch (stem_fused.hip): the 400 x 400 x 64 map never reaches HBM
-    StemPoolParams sp;
-    memset(&sp, 0, sizeof sp);
-    sp.in = x0.p; sp.wf = (const half_t*)stem_w->dev; sp.bias = (const float*)stem_b->dev; sp.out = c1.p;
-    sp.in_Hp = x0.Hp(); sp.in_Wp = x0.Wp();
-    sp.Hc = h2; sp.Wc = w2; sp.Hq = h4; sp.Wq = w4;
-    Stage st;
-    st.name = "stem.conv1+maxpool";
-    st.flops_per_image = 2.0 * h2 * w2 * 49.0 * S.in_channels * 64;
-    st.bytes_per_image = 2.0 * ((double)pad_h * pad_w * 4 + (double)h4 * w4 * 64);
-    sp.sat = sat_slot();
-    st.fn = [sp](int n, hipStream_t s) mutable { sp.N = n; g_last_conv_variant = 21; return launch_stem_pool(sp, s); };
-    stages.push_back(st);
-  } else if (fuse_stem && split && use_glds > 0 && S.stem_out_channels == 64 && x0.C == 4 && x0.pad == 3 && stem_w && stem_b && find(bu + "stem.conv1.wsi") &&
-             (long long)stem_w->dims[0] * stem_w->dims[1] == 2 * 7 * 4 * 64 * 8 && (pad_h & 3) == 0 && (pad_w & 3) == 0) {
-    // the same launch on hi + lo planes (stem_fused.hip stem_pool_split_kernel): bit-identical to the stand-alone split stem + split max-pool
-    StemPoolSplitParams sp;
-    memset(&sp, 0, sizeof sp);
-    sp.in = x0.p; sp.in_lo = x0.lo; sp.wf = (const half_t*)stem_w->dev; sp.wscale = (const float*)find(bu + "stem.conv1.wsi")->dev;
-    sp.bias = (const float*)stem_b->dev; sp.out = c1.p; sp.out_lo = c1.lo;
-    sp.in_Hp = x0.Hp(); sp.in_Wp = x0.Wp();
-    sp.Hc = h2; sp.Wc = w2; sp.Hq = h4; sp.Wq = w4;
-    Stage st;
-    st.name = "stem.conv1+maxpool";
-    st.flops_per_image = 2.0 * h2 * w2 * 49.0 * S.in_channels * 64;
-    st.bytes_per_image = 4.0 * ((double)pad_h * pad_w * 4 + (double)h4 * w4 * 64);
-    sp.sat = sat_slot();
-    st.fn = [sp](int n, hipStream_t s) mutable { sp.N = n; g_last_conv_variant = 21; return launch_stem_pool_split(sp, s); };
-    stages.push_back(st);
-  } else {
-  if ((rc = add_conv("stem.conv1", bu + "stem.conv1", x0, stem, 7, 2, 3, true, nullptr, nullptr, S.in_channels))) return rc;
-  {
-    Stage st;
-    st.name = "stem.maxpool";
-    st.bytes_per_image = 2.0 * ((double)h2 * w2 + (double)h4 * w4) * S.stem_out_channels;
-    const bool f = f32, sp = split;
-    st.fn = [stem, c1, f, sp](int n, hipStream_t s) {
-      if (sp) return launch_maxpool_split(stem.p, stem.lo, c1.p, c1.lo, n, stem.H, stem.W, c1.H, c1.W, c1.C, s);
-      return f ? launch_maxpool_f32((const float*)stem.p, (float*)c1.p, n, stem.H, stem.W, c1.H, c1.W, c1.C, s)
-               : launch_maxpool(stem.p, c1.p, n, stem.H, stem.W, c1.H, c1.W, c1.C, s);
-    };
-    stages.push_back(st);
-  }
-  }
-
-  // ---- res2..res5
-  Act cur = c1;
-  Act res_out[4];
-  Act t1_pre;              // conv1 output of the NEXT block when the previous block's fused tail already produced it
-  bool have_t1 = false;
-  int bott = 64, cout = S.res2_out_channels;
-  int ch = h4, cw = w4;
-  for (int si = 0; si < 4; ++si) {
-    for (int bi = 0; bi < S.res_blocks[si]; ++bi) {
-      const std::string nm = "res" + std::to_string(si + 2) + "." + std::to_string(bi);
-      const std::string wn = bu + nm;
-      const int stride = (bi == 0 && si > 0) ? 2 : 1;
-      const int s1 = S.stride_in_1x1 ? stride : 1, s3 = S.stride_in_1x1 ? 1 : stride;
-      const int oh = ch / stride, ow = cw / stride;
-      Act t1, t2, sc, out;
-      // Fused tail (bneck_fused.hip): identity-shortcut blocks of the 64- and 128-wide stages run conv2 + conv3 (+ the next block's conv1)
-      // in one launch -- t2 is never materialised and the next conv1 reads `out` from registers.  fp16 inference engine only.
-      // Block 0 of the stage has a projection shortcut from the 64-channel stem output at the same resolution: the tail then adds
-      // Wsc . x0 as two more K steps instead of the identity residual (needs the folded conv3sc bias = conv3's + the shortcut's).
-      const bool may_fuse = !frozen_fusions_only || si == 0;          // a trainer fuses only inside the frozen res2
-      const bool fuse_bneck = this->fuse_bneck && may_fuse, fuse_shortcut = this->fuse_shortcut && may_fuse;
-      const bool tail0 = !f32 && !split && fuse_bneck && fuse_shortcut && bi == 0 && bott == 64 && cout == 256 && stride == 1 && cur.C == 64 &&
-                         findw(wn + ".conv3p") != nullptr && findw(wn + ".shortcut") != nullptr && find(wn + ".conv3sc.b") != nullptr;
-      const bool tail = tail0 || (!f32 && !split && fuse_bneck && bi > 0 && (bott == 64 || bott == 128) && cout == 4 * bott && stride == 1 && findw(wn + ".conv3p") != nullptr);
-      // Split-operand mode: the same chain on hi + lo planes (bneck_split.hip), identity-shortcut blocks only.
-      const bool tail_s = split && fuse_bneck && rs_debug().conv_deep && use_glds > 0 && bi > 0 && (bott == 64 || bott == 128) && cout == 4 * bott && stride == 1 &&
-                          findw(wn + ".conv3p") != nullptr && find(wn + ".conv3p.wsi") != nullptr;
-      // ... and res2.0, whose projection shortcut reads the 64-channel stem output at the same resolution (conv3 | shortcut as one [256][128] operand)
-      const bool tail0_s = split && fuse_bneck && fuse_shortcut && rs_debug().conv_deep && use_glds > 0 && bi == 0 && bott == 64 && cout == 256 && stride == 1 &&
-                           cur.C == 64 && findw(wn + ".conv3scp") != nullptr && find(wn + ".conv3scp.wsi") != nullptr && find(wn + ".conv3sc.b") != nullptr;
-      const bool tail_next = (tail || tail_s || tail0_s) && bi + 1 < S.res_blocks[si] &&
-                             findw(bu + "res" + std::to_string(si + 2) + "." + std::to_string(bi + 1) + ".conv1p") != nullptr;
-      if (have_t1) t1 = t1_pre;
-      else if ((rc = new_act(&t1, nm + ".conv1", NB, ch / s1, cw / s1, bott, 1))) return rc;
-      if (!tail && !tail_s && !tail0_s) { if ((rc = new_act(&t2, nm + ".conv2", NB, oh, ow, bott, 1))) return rc; }
-      if ((rc = new_act(&out, bi == S.res_blocks[si] - 1 ? "res" + std::to_string(si + 2) : nm + ".out", NB, oh, ow, cout, 1))) return rc;
-      const Act* resid = &cur;
-      // Projection shortcut: in the fp16 path it is folded into conv3 as a second K source (one GEMM over
-      // [conv2 out ; block input], no shortcut tensor written or re-read); the fp32 validation path and
-      // RS_FUSE_SHORTCUT=0 keep the reference's two-convolution form.
-      const bool proj = cur.C != cout;
-      const bool fuse_sc = proj && !tail0 && !tail0_s && !f32 && fuse_shortcut && s3 == 1 && cur.C % 64 == 0 && findw(wn + ".conv3sc") != nullptr;
-      if (proj && !fuse_sc && !tail0 && !tail0_s) {
-        if ((rc = new_act(&sc, nm + ".shortcut", NB, oh, ow, cout, 1))) return rc;
-        if ((rc = add_conv(nm + ".shortcut", wn + ".shortcut", cur, sc, 1, stride, 0, false, nullptr, nullptr, cur.C))) return rc;
-        resid = &sc;
-      }
-      if (!have_t1) { if ((rc = add_conv(nm + ".conv1", wn + ".conv1", cur, t1, 1, s1, 0, true, nullptr, nullptr, cur.C))) return rc; }
-      have_t1 = false;
-      if (tail) {
-        const std::string nn = "res" + std::to_string(si + 2) + "." + std::to_string(bi + 1);
-        if (tail_next) { if ((rc = new_act(&t1_pre, nn + ".conv1", NB, oh, ow, bott, 1))) return rc; }
-        const BlobEntry *w2 = findw(wn + ".conv2"), *b2 = find(wn + ".conv2.b"), *w3 = findw(wn + ".conv3p"), *b3 = find(wn + (tail0 ? ".conv3sc.b" : ".conv3.b"));
-        const BlobEntry* wsc = tail0 ? findw(wn + ".shortcut") : nullptr;
-        const BlobEntry *w1 = tail_next ? findw(bu + nn + ".conv1p") : nullptr, *b1 = tail_next ? find(bu + nn + ".conv1.b") : nullptr;
-        RS_CHECK(w2 && b2 && w3 && b3 && (!tail_next || (w1 && b1)), RS_ERR_BLOB, "weights of the fused tail of %s missing", nm.c_str());
-        RS_CHECK(w2->dims[0] == bott && w2->dims[1] == 9 * bott && w3->dims[0] == cout && w3->dims[1] == bott && (!w1 || (w1->dims[0] == bott && w1->dims[1] == cout)),
-                 RS_ERR_BLOB, "fused tail of %s: weight shapes", nm.c_str());
-        BneckParams bp;
-        memset(&bp, 0, sizeof bp);
-        bp.t1 = t1.p; bp.w2 = (const half_t*)w2->dev; bp.b2 = (const float*)b2->dev; bp.w3p = (const half_t*)w3->dev; bp.b3 = (const float*)b3->dev;
-        bp.out = out.p;
-        if (tail0) {
-          RS_CHECK(wsc && wsc->dims[0] == 256 && wsc->dims[1] == 64, RS_ERR_BLOB, "fused tail of %s: shortcut weight shape", nm.c_str());
-          bp.x0 = cur.p; bp.wsc = (const half_t*)wsc->dev;
-        } else {
-          bp.x = cur.p;
-        }
-        if (tail_next) { bp.w1p = (const half_t*)w1->dev; bp.b1 = (const float*)b1->dev; bp.t1n = t1_pre.p; }
-        bp.H = oh; bp.W = ow; bp.Hp = out.Hp(); bp.Wp = out.Wp(); bp.CB = bott / 64;
-        RS_CHECK(t1.pad == 1 && cur.pad == 1 && out.pad == 1 && t1.H == oh && cur.H == oh && t1.C == bott && cur.C == (tail0 ? 64 : cout), RS_ERR_ARG, "fused tail of %s: geometry", nm.c_str());
-        const int mpi = oh * ow;
-        Stage st;
-        st.name = nm + (tail_next ? ".conv2+conv3+next.conv1" : ".conv2+conv3");
-        st.flops_per_image = 2.0 * mpi * (9.0 * bott * bott + (double)bott * cout + (tail0 ? 64.0 * cout : 0.0) + (tail_next ? (double)cout * bott : 0.0));
-        st.bytes_per_image = 2.0 * mpi * ((double)bott + (tail0 ? 64.0 : (double)cout) + cout + (tail_next ? (double)bott : 0.0));       // t1 + x (or x0) in, out (+ t1n) out
-        bp.sat = sat_slot();
-        st.fn = [bp, mpi](int n, hipStream_t s) mutable { bp.M = n * mpi; g_last_conv_variant = 13; return launch_bneck_tail(bp, s); };
-        stages.push_back(st);
-        have_t1 = tail_next;
-      } else if (tail_s || tail0_s) {
-        const std::string nn = "res" + std::to_string(si + 2) + "." + std::to_string(bi + 1);
-        if (tail_next) { if ((rc = new_act(&t1_pre, nn + ".conv1", NB, oh, ow, bott, 1))) return rc; }
-        const BlobEntry *w2 = findw(wn + ".conv2"), *b2 = find(wn + ".conv2.b"), *s2 = find(wn + ".conv2.wsi");
-        const BlobEntry *w3 = findw(wn + (tail0_s ? ".conv3scp" : ".conv3p")), *b3 = find(wn + (tail0_s ? ".conv3sc.b" : ".conv3.b")),
-                        *sc3 = find(wn + (tail0_s ? ".conv3scp.wsi" : ".conv3p.wsi"));
-        const BlobEntry *w1 = tail_next ? findw(bu + nn + ".conv1p") : nullptr, *b1 = tail_next ? find(bu + nn + ".conv1.b") : nullptr,
-                        *sc1 = tail_next ? find(bu + nn + ".conv1p.wsi") : nullptr;
-        RS_CHECK(w2 && b2 && s2 && w3 && b3 && sc3 && (!tail_next || (w1 && b1 && sc1)), RS_ERR_BLOB, "weights of the fused split tail of %s missing", nm.c_str());
-        const int k3 = tail0_s ? bott + 64 : bott;
-        RS_CHECK(wrows(w2) == bott && w2->dims[1] == 9 * bott && wrows(w3) == cout && w3->dims[1] == k3 && (!w1 || (wrows(w1) == bott && w1->dims[1] == cout)),
-                 RS_ERR_BLOB, "fused split tail of %s: weight shapes", nm.c_str());
-        RS_CHECK(t1.pad == 1 && cur.pad == 1 && out.pad == 1 && t1.H == oh && cur.H == oh && t1.C == bott && cur.C == (tail0_s ? 64 : cout), RS_ERR_ARG, "fused split tail of %s: geometry", nm.c_str());
-        BneckSplitParams bp;
-        memset(&bp, 0, sizeof bp);
-        bp.t1 = t1.p; bp.t1_lo = t1.lo;
-        bp.w2 = (const half_t*)w2->dev; bp.w2_lo = (long long)bott * 9 * bott; bp.b2 = (const float*)b2->dev; bp.s2 = (const float*)s2->dev;
-        bp.w3p = (const half_t*)w3->dev; bp.w3_lo = (long long)cout * k3; bp.b3 = (const float*)b3->dev; bp.s3 = (const float*)sc3->dev;
-        if (tail0_s) { bp.x0 = cur.p; bp.x0_lo = cur.lo; } else { bp.x = cur.p; bp.x_lo = cur.lo; }
-        bp.out = out.p; bp.out_lo = out.lo;
-        if (tail_next) {
-          bp.w1p = (const half_t*)w1->dev; bp.w1_lo = (long long)bott * cout; bp.b1 = (const float*)b1->dev; bp.s1 = (const float*)sc1->dev;
-          bp.t1n = t1_pre.p; bp.t1n_lo = t1_pre.lo;
-        }
-        bp.H = oh; bp.W = ow; bp.Hp = out.Hp(); bp.Wp = out.Wp(); bp.CB = bott / 64;
-        const int mpi = oh * ow;
-        Stage st;
-        st.name = nm + (tail_next ? ".conv2+conv3+next.conv1" : ".conv2+conv3");
-        st.flops_per_image = 2.0 * mpi * (9.0 * bott * bott + (double)k3 * cout + (tail_next ? (double)cout * bott : 0.0));
-        st.bytes_per_image = 4.0 * mpi * ((double)bott + (tail0_s ? 64.0 : (double)cout) + cout + (tail_next ? (double)bott : 0.0));       // two planes of t1 + x (or x0) in, out (+ t1n) out
-        bp.sat = sat_slot();
-        st.fn = [bp, mpi](int n, hipStream_t s) mutable { bp.M = n * mpi; g_last_conv_variant = 23; return launch_bneck_tail_split(bp, s); };
-        stages.push_back(st);
-        have_t1 = tail_next;
-      } else if (fuse_sc) {
-        if ((rc = add_conv(nm + ".conv2", wn + ".conv2", t1, t2, 3, s3, 1, true, nullptr, nullptr, bott))) return rc;
-        if ((rc = add_conv(nm + ".conv3", wn + ".conv3sc", t2, out, 1, 1, 0, true, nullptr, nullptr, bott, 1, nullptr, &cur, stride))) return rc;
-      } else {
-        if ((rc = add_conv(nm + ".conv2", wn + ".conv2", t1, t2, 3, s3, 1, true, nullptr, nullptr, bott))) return rc;
-        if ((rc = add_conv(nm + ".conv3", wn + ".conv3", t2, out, 1, 1, 0, true, resid, nullptr, bott))) return rc;
-      }
-      cur = out;
-      ch = oh; cw = ow;
+    const double flops = 2.0 * h2 * w2 * 49.0 * S.in_channels * 64;
+    const double bytes = 2.0 * planes() * ((double)pad_h * pad_w * 4 + (double)h4 * w4 * 64);
+    if (!split) {
+      StemPoolParams sp;
+      memset(&sp, 0, sizeof sp);
+      sp.in = x0.p; sp.wf = (const half_t*)stem_w->dev; sp.bias = (const float*)stem_b->dev; sp.out = c1.p;
+      sp.in_Hp = x0.Hp(); sp.in_Wp = x0.Wp();
+      sp.Hc = h2; sp.Wc = w2; sp.Hq = h4; sp.Wq = w4;
+      Stage& st = add_stage("stem.conv1+maxpool", flops, bytes, &sp.sat);
+      st.fn = [sp](int n, hipStream_t s) mutable { sp.N = n; g_last_conv_variant = 21; return launch_stem_pool(sp, s); };
+    } else {
+      // the same launch on hi + lo planes (stem_fused.hip stem_pool_split_kernel): bit-identical to the stand-alone split stem + split max-pool
+      StemPoolSplitParams sp;
+      memset(&sp, 0, sizeof sp);
+      sp.in = x0.p; sp.in_lo = x0.lo; sp.wf = (const half_t*)stem_w->dev; sp.wscale = (const float*)stem_si->dev;
+      sp.bias = (const float*)stem_b->dev; sp.out = c1.p; sp.out_lo = c1.lo;
+      sp.in_Hp = x0.Hp(); sp.in_Wp = x0.Wp();
+      sp.Hc = h2; sp.Wc = w2; sp.Hq = h4; sp.Wq = w4;
+      Stage& st = add_stage("stem.conv1+maxpool", flops, bytes, &sp.sat);
+      st.fn = [sp](int n, hipStream_t s) mutable { sp.N = n; g_last_conv_variant = 21; return launch_stem_pool_split(sp, s); };
     }
-    res_out[si] = cur;
-    bott *= 2;
-    cout *= 2;
+    return RS_OK;
   }
+  ConvDesc d{7, 2, 3, true};
+  d.cin_real = S.in_channels;
+  if ((rc = add_conv("stem.conv1", bu + "stem.conv1", x0, stem, d))) return rc;
+  const bool f = f32, sp = split;
+  add_stage("stem.maxpool", 0, 2.0 * ((double)h2 * w2 + (double)h4 * w4) * S.stem_out_channels).fn = [stem, c1, f, sp](int n, hipStream_t s) {
+    if (sp) return launch_maxpool_split(stem.p, stem.lo, c1.p, c1.lo, n, stem.H, stem.W, c1.H, c1.W, c1.C, s);
+    return f ? launch_maxpool_f32((const float*)stem.p, (float*)c1.p, n, stem.H, stem.W, c1.H, c1.W, c1.C, s)
+             : launch_maxpool(stem.p, c1.p, n, stem.H, stem.W, c1.H, c1.W, c1.C, s);
+  };
+  return RS_OK;
+}
 
-  // ---- FPN
-  Act inner[4], P[5];
-  const bool merge = merge_levels && !f32 && rs_debug().conv_deep && use_glds > 0;
-  std::vector<DeferredConv> fpn_out(4), rpn_conv(S.num_levels);
+// ---- res2..res5
+int rs_engine::build_res_stages(Graph& g) {
+  ResCursor r;
+  r.cur = g.c1;
+  r.cout = spec.res2_out_channels;
+  for (int si = 0; si < 4; ++si) {
+    for (int bi = 0; bi < spec.res_blocks[si]; ++bi) {
+      int rc = build_bottleneck(r, si, bi);
+      if (rc) return rc;
+    }
+    g.res_out[si] = r.cur;
+    r.bott *= 2;
+    r.cout *= 2;
+  }
+  return RS_OK;
+}
+
+// One bottleneck block: conv1 1x1, conv2 3x3, conv3 1x1 + shortcut + ReLU, with whatever of it this engine fuses
+int rs_engine::build_bottleneck(ResCursor& r, int si, int bi) {
+  const rs_spec& S = spec;
+  const std::string& bu = kBottomUp;
+  const int NB = max_batch, bott = r.bott, cout = r.cout;
+  const Act cur = r.cur;
+  const std::string stage = "res" + std::to_string(si + 2);
+  const std::string nm = stage + "." + std::to_string(bi), next = stage + "." + std::to_string(bi + 1);
+  const std::string wn = bu + nm;
+  const int stride = (bi == 0 && si > 0) ? 2 : 1;
+  const int s1 = S.stride_in_1x1 ? stride : 1, s3 = S.stride_in_1x1 ? 1 : stride;
+  const int oh = cur.H / stride, ow = cur.W / stride;
+  int rc;
+  Act t1, t2, sc, out;
+  // Fused tail (bneck_fused.hip): identity-shortcut blocks of the 64- and 128-wide stages run conv2 + conv3 (+ the next block's conv1)
+  // in one launch -- t2 is never materialised and the next conv1 reads `out` from registers.  Inference engines, fp16 and split-operand
+  // mode (bneck_split.hip: the same chain on hi + lo planes, on the deep-K loop with LDS-DMA staging).
+  // Block 0 of the stage has a projection shortcut from the 64-channel stem output at the same resolution: the tail then adds
+  // Wsc . x0 as two more K steps instead of the identity residual (needs the folded conv3sc bias = conv3's + the shortcut's; the split
+  // mode takes conv3 | shortcut as one [256][128] operand, conv3scp).
+  const bool may_fuse = !frozen_fusions_only || si == 0;          // a trainer fuses only inside the frozen res2
+  const bool fuse_bneck = this->fuse_bneck && may_fuse, fuse_shortcut = this->fuse_shortcut && may_fuse;
+  const bool can_tail = !f32 && fuse_bneck && stride == 1 && (!split || (rs_debug().conv_deep && use_glds > 0));
+  const bool tail_proj = can_tail && fuse_shortcut && bi == 0 && bott == 64 && cout == 256 && cur.C == 64 && find(wn + ".conv3sc.b") != nullptr &&
+                         (split ? findw(wn + ".conv3scp") != nullptr && find(wn + ".conv3scp.wsi") != nullptr
+                                : findw(wn + ".conv3p") != nullptr && findw(wn + ".shortcut") != nullptr);
+  const bool tail_id = can_tail && bi > 0 && (bott == 64 || bott == 128) && cout == 4 * bott && findw(wn + ".conv3p") != nullptr &&
+                       (!split || find(wn + ".conv3p.wsi") != nullptr);
+  const bool tail = tail_proj || tail_id;
+  const bool tail_next = tail && bi + 1 < S.res_blocks[si] && findw(bu + next + ".conv1p") != nullptr;
+  if (r.have_t1) t1 = r.t1_pre;
+  else if ((rc = new_act(&t1, nm + ".conv1", NB, cur.H / s1, cur.W / s1, bott, 1))) return rc;
+  if (!tail) { if ((rc = new_act(&t2, nm + ".conv2", NB, oh, ow, bott, 1))) return rc; }
+  if ((rc = new_act(&out, bi == S.res_blocks[si] - 1 ? stage : nm + ".out", NB, oh, ow, cout, 1))) return rc;
+  const Act* resid = &cur;
+  // Projection shortcut: in the fp16 path it is folded into conv3 as a second K source (one GEMM over
+  // [conv2 out ; block input], no shortcut tensor written or re-read); the fp32 validation path and
+  // RS_FUSE_SHORTCUT=0 keep the reference's two-convolution form.
+  const bool proj = cur.C != cout;
+  const bool fuse_sc = proj && !tail_proj && !f32 && fuse_shortcut && s3 == 1 && cur.C % 64 == 0 && findw(wn + ".conv3sc") != nullptr;
+  if (proj && !fuse_sc && !tail_proj) {
+    if ((rc = new_act(&sc, nm + ".shortcut", NB, oh, ow, cout, 1))) return rc;
+    if ((rc = add_conv(nm + ".shortcut", wn + ".shortcut", cur, sc, ConvDesc{1, stride, 0, false}))) return rc;
+    resid = &sc;
+  }
+  if (!r.have_t1) { if ((rc = add_conv(nm + ".conv1", wn + ".conv1", cur, t1, ConvDesc{1, s1, 0, true}))) return rc; }
+  r.have_t1 = false;
+  if (tail) {
+    if (tail_next) { if ((rc = new_act(&r.t1_pre, next + ".conv1", NB, oh, ow, bott, 1))) return rc; }
+    if ((rc = add_fused_tail(nm, next, t1, cur, out, tail_next ? &r.t1_pre : nullptr, tail_proj))) return rc;
+    r.have_t1 = tail_next;
+  } else {
+    if ((rc = add_conv(nm + ".conv2", wn + ".conv2", t1, t2, ConvDesc{3, s3, 1, true}))) return rc;
+    ConvDesc d3{1, 1, 0, true};
+    if (fuse_sc) { d3.in2 = &cur; d3.stride2 = stride; } else { d3.res = resid; }
+    if ((rc = add_conv(nm + ".conv3", wn + (fuse_sc ? ".conv3sc" : ".conv3"), t2, out, d3))) return rc;
+  }
+  r.cur = out;
+  return RS_OK;
+}
+
+// The fused tail of block `nm`: conv2 + conv3 + shortcut (+ conv1 of block `next` into *t1n) in one launch.  `x` is the block input:
+// the identity residual, or with `proj` the 64-channel source of res2.0's projection shortcut.
+int rs_engine::add_fused_tail(const std::string& nm, const std::string& next, const Act& t1, const Act& x, const Act& out, const Act* t1n, bool proj) {
+  const std::string wn = kBottomUp + nm, wnn = kBottomUp + next;
+  const char* kind = split ? "fused split tail" : "fused tail";
+  const int bott = t1.C, cout = out.C, oh = out.H, ow = out.W;
+  const std::string w3n = wn + (proj && split ? ".conv3scp" : ".conv3p");
+  const int k3 = proj && split ? bott + 64 : bott;               // K of the conv3 operand
+  const BlobEntry *w2 = findw(wn + ".conv2"), *b2 = find(wn + ".conv2.b"), *w3 = findw(w3n), *b3 = find(wn + (proj ? ".conv3sc.b" : ".conv3.b"));
+  const BlobEntry *w1 = t1n ? findw(wnn + ".conv1p") : nullptr, *b1 = t1n ? find(wnn + ".conv1.b") : nullptr;
+  // split-operand mode: the inverse row scales of the three operands
+  const BlobEntry *s2 = split ? find(wn + ".conv2.wsi") : nullptr, *s3 = split ? find(w3n + ".wsi") : nullptr,
+                  *s1 = split && t1n ? find(wnn + ".conv1p.wsi") : nullptr;
+  RS_CHECK(w2 && b2 && w3 && b3 && (!t1n || (w1 && b1)) && (!split || (s2 && s3 && (!t1n || s1))), RS_ERR_BLOB, "weights of the %s of %s missing", kind, nm.c_str());
+  RS_CHECK(wrows(w2) == bott && w2->dims[1] == 9 * bott && wrows(w3) == cout && w3->dims[1] == k3 && (!w1 || (wrows(w1) == bott && w1->dims[1] == cout)),
+           RS_ERR_BLOB, "%s of %s: weight shapes", kind, nm.c_str());
+  RS_CHECK(t1.pad == 1 && x.pad == 1 && out.pad == 1 && t1.H == oh && x.H == oh && t1.C == bott && x.C == (proj ? 64 : cout), RS_ERR_ARG, "%s of %s: geometry", kind, nm.c_str());
+  const int mpi = oh * ow;
+  const std::string name = nm + (t1n ? ".conv2+conv3+next.conv1" : ".conv2+conv3");
+  const double flops = 2.0 * mpi * (9.0 * bott * bott + (double)(bott + (proj ? 64 : 0)) * cout + (t1n ? (double)cout * bott : 0.0));
+  const double bytes = 2.0 * planes() * mpi * ((double)bott + (proj ? 64.0 : (double)cout) + cout + (t1n ? (double)bott : 0.0));   // t1 + x in, out (+ t1n) out
+  if (!split) {
+    BneckParams bp;
+    memset(&bp, 0, sizeof bp);
+    bp.t1 = t1.p; bp.w2 = (const half_t*)w2->dev; bp.b2 = (const float*)b2->dev; bp.w3p = (const half_t*)w3->dev; bp.b3 = (const float*)b3->dev;
+    bp.out = out.p;
+    if (proj) {
+      const BlobEntry* wsc = findw(wn + ".shortcut");
+      RS_CHECK(wsc && wsc->dims[0] == 256 && wsc->dims[1] == 64, RS_ERR_BLOB, "fused tail of %s: shortcut weight shape", nm.c_str());
+      bp.x0 = x.p; bp.wsc = (const half_t*)wsc->dev;
+    } else {
+      bp.x = x.p;
+    }
+    if (t1n) { bp.w1p = (const half_t*)w1->dev; bp.b1 = (const float*)b1->dev; bp.t1n = t1n->p; }
+    bp.H = oh; bp.W = ow; bp.Hp = out.Hp(); bp.Wp = out.Wp(); bp.CB = bott / 64;
+    Stage& st = add_stage(name, flops, bytes, &bp.sat);
+    st.fn = [bp, mpi](int n, hipStream_t s) mutable { bp.M = n * mpi; g_last_conv_variant = 13; return launch_bneck_tail(bp, s); };
+  } else {
+    BneckSplitParams bp;
+    memset(&bp, 0, sizeof bp);
+    bp.t1 = t1.p; bp.t1_lo = t1.lo;
+    bp.w2 = (const half_t*)w2->dev; bp.w2_lo = (long long)bott * 9 * bott; bp.b2 = (const float*)b2->dev; bp.s2 = (const float*)s2->dev;
+    bp.w3p = (const half_t*)w3->dev; bp.w3_lo = (long long)cout * k3; bp.b3 = (const float*)b3->dev; bp.s3 = (const float*)s3->dev;
+    if (proj) { bp.x0 = x.p; bp.x0_lo = x.lo; } else { bp.x = x.p; bp.x_lo = x.lo; }
+    bp.out = out.p; bp.out_lo = out.lo;
+    if (t1n) {
+      bp.w1p = (const half_t*)w1->dev; bp.w1_lo = (long long)bott * cout; bp.b1 = (const float*)b1->dev; bp.s1 = (const float*)s1->dev;
+      bp.t1n = t1n->p; bp.t1n_lo = t1n->lo;
+    }
+    bp.H = oh; bp.W = ow; bp.Hp = out.Hp(); bp.Wp = out.Wp(); bp.CB = bott / 64;
+    Stage& st = add_stage(name, flops, bytes, &bp.sat);
+    st.fn = [bp, mpi](int n, hipStream_t s) mutable { bp.M = n * mpi; g_last_conv_variant = 23; return launch_bneck_tail_split(bp, s); };
+  }
+  return RS_OK;
+}
+
+// ---- FPN: laterals + top-down path, output convs, p6
+int rs_engine::build_fpn(Graph& g) {
+  const int NB = max_batch;
+  Act inner[4];
+  Act* P = g.P;
+  const Act* res_out = g.res_out;
+  const bool merge = merge_maps();
+  std::vector<DeferredConv> fpn_out(4);
+  int rc;
   for (int l = 3; l >= 0; --l) {
     const std::string ln = std::to_string(l + 2);
     if ((rc = new_act(&inner[l], "inner" + ln, NB, res_out[l].H, res_out[l].W, 256, 1))) return rc;
     if ((rc = new_act(&P[l], "p" + ln, NB, res_out[l].H, res_out[l].W, 256, 1))) return rc;
-    if ((rc = add_conv("fpn_lateral" + ln, "backbone.fpn_lateral" + ln, res_out[l], inner[l], 1, 1, 0, false, nullptr,
-                       l < 3 ? &inner[l + 1] : nullptr, res_out[l].C))) return rc;
-    if (merge) {
-      if ((rc = add_conv("fpn_output" + ln, "backbone.fpn_output" + ln, inner[l], P[l], 3, 1, 1, false, nullptr, nullptr, 256, 1, nullptr, nullptr, 1, &fpn_out[l]))) return rc;
-    } else {
-      if ((rc = add_conv("fpn_output" + ln, "backbone.fpn_output" + ln, inner[l], P[l], 3, 1, 1, false, nullptr, nullptr, 256))) return rc;
-    }
+    ConvDesc lat{1, 1, 0, false};
+    lat.up = l < 3 ? &inner[l + 1] : nullptr;
+    if ((rc = add_conv("fpn_lateral" + ln, "backbone.fpn_lateral" + ln, res_out[l], inner[l], lat))) return rc;
+    ConvDesc o{3, 1, 1, false};
+    o.defer = merge ? &fpn_out[l] : nullptr;
+    if ((rc = add_conv("fpn_output" + ln, "backbone.fpn_output" + ln, inner[l], P[l], o))) return rc;
   }
   // the four output convolutions depend on the laterals only: one launch, largest map first
   if (merge && (rc = add_merged_convs("fpn_output2-5", fpn_out))) return rc;
-  {
-    const int h6 = (P[3].H - 1) / 2 + 1, w6 = (P[3].W - 1) / 2 + 1;
-    if ((rc = new_act(&P[4], "p6", NB, h6, w6, 256, 1))) return rc;
-    Stage st;
-    st.name = "fpn.p6";
-    Act a = P[3], b = P[4];
-    const bool f = f32, sp = split;
-    st.fn = [a, b, f, sp](int n, hipStream_t s) {
-      if (sp) return launch_subsample2_split(a.p, a.lo, b.p, b.lo, n, a.H, a.W, b.H, b.W, 256, s);
-      return f ? launch_subsample2_f32((const float*)a.p, (float*)b.p, n, a.H, a.W, b.H, b.W, 256, s)
-               : launch_subsample2(a.p, b.p, n, a.H, a.W, b.H, b.W, 256, s);
-    };
-    stages.push_back(st);
-  }
+  const int h6 = (P[3].H - 1) / 2 + 1, w6 = (P[3].W - 1) / 2 + 1;
+  if ((rc = new_act(&P[4], "p6", NB, h6, w6, 256, 1))) return rc;
+  const Act a = P[3], b = P[4];
+  const bool f = f32, sp = split;
+  add_stage("fpn.p6", 0, 0).fn = [a, b, f, sp](int n, hipStream_t s) {
+    if (sp) return launch_subsample2_split(a.p, a.lo, b.p, b.lo, n, a.H, a.W, b.H, b.W, 256, s);
+    return f ? launch_subsample2_f32((const float*)a.p, (float*)b.p, n, a.H, a.W, b.H, b.W, 256, s)
+             : launch_subsample2(a.p, b.p, n, a.H, a.W, b.H, b.W, 256, s);
+  };
+  return RS_OK;
+}
 
-  // ---- RPN head
+// rs_spec.batched_nms = 1: the NMS stage decides torchvision's size rule per image in its own prologue (NmsParams::rule) and leaves the decision
+// in two tensors.  Decided on the device: launches, grids and a captured graph are the same for both outcomes and for both modes.
+int rs_engine::add_nms_rule(const char* head, NmsParams* np, int group) {
+  int rc;
+  if ((rc = new_tensor(&np->rule, std::string(head) + "_nms_rule", DT_I32, {max_batch, 2}))) return rc;
+  if ((rc = new_tensor(&np->unit, std::string(head) + "_nms_unit", DT_F32, {max_batch}))) return rc;
+  np->group = group;
+  return RS_OK;
+}
+
+// ---- RPN head + proposals
+int rs_engine::build_rpn(Graph& g) {
+  const rs_spec& S = spec;
+  const int NB = max_batch;
+  const Act* P = g.P;
+  const bool merge = merge_maps();
   const int A = S.num_anchors, L = S.num_levels;
   const int head_cs = (5 * A + 15) / 16 * 16;
+  int rc;
   RpnParams rp;
   memset(&rp, 0, sizeof rp);
-  Act rpn_t[RS_MAX_LEVELS];
-  float* rpn_ho[RS_MAX_LEVELS];
+  std::vector<DeferredConv> rpn_conv(L);
   for (int l = 0; l < L; ++l) {
-    float* ho = nullptr;
-    if ((rc = alloc((void**)&ho, (size_t)NB * P[l].H * P[l].W * head_cs * 4))) return rc;
-    reg("rpn_head" + std::to_string(l + 2), ho, DT_F32, {NB, P[l].H, P[l].W, head_cs}, 0);
-    rpn_ho[l] = ho;
+    if ((rc = new_tensor(&g.rpn_ho[l], "rpn_head" + std::to_string(l + 2), DT_F32, {NB, P[l].H, P[l].W, head_cs}))) return rc;
   }
   // inference engines: the 16-row head runs inside the epilogue of the merged 3x3 launch (conv_deep.hip, ConvParams::head_w), so the
   // 256-channel "rpn_conv" maps are never written
@@ -804,29 +880,24 @@ int rs_engine::build() {
   const bool fuse_heads = merge && !frozen_fusions_only && rs_debug().fuse_rpn_heads && head_cs == 16 && headsp != nullptr && (!split || headsp_si != nullptr);
   for (int l = 0; l < L; ++l) {
     const std::string ln = std::to_string(l + 2);
-    Act t;
+    Act& t = g.rpn_t[l];
     if ((rc = new_act(&t, "rpn_conv" + ln, NB, P[l].H, P[l].W, 256, 1))) return rc;   // halo 1: its gradient is the input of a 3x3 (training)
-    if (merge) {
-      if ((rc = add_conv("rpn.conv" + ln, "proposal_generator.rpn_head.conv", P[l], t, 3, 1, 1, true, nullptr, nullptr, 256, 1, nullptr, nullptr, 1, &rpn_conv[l]))) return rc;
-      if (fuse_heads) {
-        const BlobEntry* hb = find("proposal_generator.rpn_head.heads.b");
-        RS_CHECK(hb && wrows(headsp) == 16 && (int)headsp->dims[1] == 256, RS_ERR_BLOB, "rpn head weights (chained order) missing or not 16 x 256");
-        rpn_conv[l].p.head_w = (const half_t*)headsp->dev; rpn_conv[l].p.head_b = (const float*)hb->dev; rpn_conv[l].p.head_out = rpn_ho[l];
-        if (split) { rpn_conv[l].p.head_w_lo = 16 * 256; rpn_conv[l].p.head_scale = (const float*)headsp_si->dev; }
-        rpn_conv[l].flops += 2.0 * P[l].H * P[l].W * 256 * 5 * A;
-        rpn_conv[l].bytes += (double)P[l].H * P[l].W * (head_cs * 4 - 256 * 2 * (split ? 2 : 1));       // the heads' output instead of the 256-channel map
-      }
-      if (l == L - 1 && (rc = add_merged_convs(fuse_heads ? "rpn.conv+heads2-6" : "rpn.conv2-6", rpn_conv))) return rc;
-      rpn_t[l] = t;
-      continue;
+    ConvDesc d{3, 1, 1, true};
+    d.defer = merge ? &rpn_conv[l] : nullptr;
+    if ((rc = add_conv("rpn.conv" + ln, "proposal_generator.rpn_head.conv", P[l], t, d))) return rc;
+    if (merge && fuse_heads) {
+      const BlobEntry* hb = find("proposal_generator.rpn_head.heads.b");
+      RS_CHECK(hb && wrows(headsp) == 16 && (int)headsp->dims[1] == 256, RS_ERR_BLOB, "rpn head weights (chained order) missing or not 16 x 256");
+      rpn_conv[l].p.head_w = (const half_t*)headsp->dev; rpn_conv[l].p.head_b = (const float*)hb->dev; rpn_conv[l].p.head_out = g.rpn_ho[l];
+      if (split) { rpn_conv[l].p.head_w_lo = 16 * 256; rpn_conv[l].p.head_scale = (const float*)headsp_si->dev; }
+      rpn_conv[l].flops += 2.0 * P[l].H * P[l].W * 256 * 5 * A;
+      rpn_conv[l].bytes += (double)P[l].H * P[l].W * (head_cs * 4 - 256 * 2 * planes());       // the heads' output instead of the 256-channel map
     }
-    if ((rc = add_conv("rpn.conv" + ln, "proposal_generator.rpn_head.conv", P[l], t, 3, 1, 1, true, nullptr, nullptr, 256))) return rc;
-    rpn_t[l] = t;
+    if (merge && l == L - 1 && (rc = add_merged_convs(fuse_heads ? "rpn.conv+heads2-6" : "rpn.conv2-6", rpn_conv))) return rc;
   }
   for (int l = 0; l < L; ++l) {
-    const std::string ln = std::to_string(l + 2);
-    const Act t = rpn_t[l];
-    float* ho = rpn_ho[l];
+    const Act t = g.rpn_t[l];
+    float* ho = g.rpn_ho[l];
     // 1x1 heads (objectness + deltas fused), fp32 out
     if (!fuse_heads) {
       const BlobEntry* w = findw("proposal_generator.rpn_head.heads");
@@ -842,12 +913,8 @@ int rs_engine::build() {
       p.out_Hp = t.H; p.out_Wp = t.W; p.out_Cs = head_cs; p.out_pad = 0; p.out_f32 = 1;
       const int mpi = t.H * t.W;
       const int glds = use_glds;
-      Stage st;
-      st.name = "rpn.heads" + ln;
-      st.flops_per_image = 2.0 * mpi * 256 * 5 * A;
-      st.bytes_per_image = (double)mpi * (256 * 2 + head_cs * 4);
-      st.fn = [p, mpi, glds](int n, hipStream_t s) mutable { p.M = n * mpi; return launch_conv(p, s, 2, glds); };
-      stages.push_back(st);
+      add_stage("rpn.heads" + std::to_string(l + 2), 2.0 * mpi * 256 * 5 * A, (double)mpi * (256 * 2 + head_cs * 4)).fn =
+          [p, mpi, glds](int n, hipStream_t s) mutable { p.M = n * mpi; return launch_conv(p, s, 2, glds); };
     }
     rp.head[l] = ho;
     rp.H[l] = P[l].H; rp.W[l] = P[l].W; rp.stride[l] = 4 << l;
@@ -862,36 +929,14 @@ int rs_engine::build() {
   rp.img_h = (float)net_h; rp.img_w = (float)net_w;
   rp.wx = S.rpn_bbox_reg_weights[0]; rp.wy = S.rpn_bbox_reg_weights[1]; rp.ww = S.rpn_bbox_reg_weights[2]; rp.wh = S.rpn_bbox_reg_weights[3];
   rp.scale_clamp = S.scale_clamp; rp.min_size = S.rpn_min_size;
-  // rs_spec.batched_nms = 1: the NMS stage decides torchvision's size rule per image in its own prologue (NmsParams::rule) and leaves the decision
-  // in two tensors.  Decided on the device: launches, grids and a captured graph are the same for both outcomes and for both modes.
-  auto add_nms_rule = [&](const char* head, NmsParams* np, int group) -> int {
-    int rc2;
-    if ((rc2 = alloc((void**)&np->rule, (size_t)NB * 2 * 4))) return rc2;
-    if ((rc2 = alloc((void**)&np->unit, (size_t)NB * 4))) return rc2;
-    reg(std::string(head) + "_nms_rule", np->rule, DT_I32, {NB, 2}, 0);
-    reg(std::string(head) + "_nms_unit", np->unit, DT_F32, {NB}, 0);
-    np->group = group;
-    return RS_OK;
-  };
   uint8_t* cand_keep = nullptr;
-  if ((rc = alloc((void**)&rp.cand_boxes, (size_t)NB * L * 1024 * 16))) return rc;
-  if ((rc = alloc((void**)&rp.cand_scores, (size_t)NB * L * 1024 * 4))) return rc;
-  if ((rc = alloc((void**)&rp.cand_valid, (size_t)NB * L * 1024))) return rc;
-  if ((rc = alloc((void**)&rp.cand_count, (size_t)NB * L * 4))) return rc;
-  if ((rc = alloc((void**)&rp.cand_index, (size_t)NB * L * 1024 * 4))) return rc;
-  if ((rc = alloc((void**)&cand_keep, (size_t)NB * L * 1024))) return rc;
-  reg("rpn_cand_boxes", rp.cand_boxes, DT_F32, {NB, L, 1024, 4}, 0);
-  reg("rpn_cand_scores", rp.cand_scores, DT_F32, {NB, L, 1024}, 0);
-  reg("rpn_cand_valid", rp.cand_valid, DT_U8, {NB, L, 1024}, 0);
-  reg("rpn_cand_count", rp.cand_count, DT_I32, {NB, L}, 0);
-  reg("rpn_cand_index", rp.cand_index, DT_I32, {NB, L, 1024}, 0);
-  reg("rpn_cand_keep", cand_keep, DT_U8, {NB, L, 1024}, 0);
-  {
-    Stage st;
-    st.name = "rpn.select_decode";
-    st.fn = [rp](int n, hipStream_t s) mutable { rp.N = n; return launch_rpn_select(rp, s); };
-    stages.push_back(st);
-  }
+  if ((rc = new_tensor(&rp.cand_boxes, "rpn_cand_boxes", DT_F32, {NB, L, 1024, 4}))) return rc;
+  if ((rc = new_tensor(&rp.cand_scores, "rpn_cand_scores", DT_F32, {NB, L, 1024}))) return rc;
+  if ((rc = new_tensor(&rp.cand_valid, "rpn_cand_valid", DT_U8, {NB, L, 1024}))) return rc;
+  if ((rc = new_tensor(&rp.cand_count, "rpn_cand_count", DT_I32, {NB, L}))) return rc;
+  if ((rc = new_tensor(&rp.cand_index, "rpn_cand_index", DT_I32, {NB, L, 1024}))) return rc;
+  if ((rc = new_tensor(&cand_keep, "rpn_cand_keep", DT_U8, {NB, L, 1024}))) return rc;
+  add_stage("rpn.select_decode", 0, 0).fn = [rp](int n, hipStream_t s) mutable { rp.N = n; return launch_rpn_select(rp, s); };
   {
     NmsParams np = {};
     np.boxes = rp.cand_boxes; np.count = rp.cand_count; np.valid = rp.cand_valid; np.keep = cand_keep; np.cap = 1024;
@@ -899,64 +944,56 @@ int rs_engine::build() {
     // suppression masks in global memory for launches of few segments (batch 1-3: launch_nms shares a segment's mask build between workgroups)
     if ((rc = alloc((void**)&np.scratch, (size_t)(NB * L < 32 ? NB * L : 32) * 1024 * 16 * 8))) return rc;
     if (S.batched_nms) { if ((rc = add_nms_rule("rpn", &np, L))) return rc; }
-    Stage st;
-    st.name = "rpn.nms";
-    st.fn = [np, L](int n, hipStream_t s) { return launch_nms(np, n * L, s); };
-    stages.push_back(st);
+    add_stage("rpn.nms", 0, 0).fn = [np, L](int n, hipStream_t s) { return launch_nms(np, n * L, s); };
   }
   const int PC = 1024;   // proposal slots per image
-  float *prop_boxes, *prop_scores;
-  int *prop_count, *prop_level;
-  if ((rc = alloc((void**)&prop_boxes, (size_t)NB * PC * 16))) return rc;
-  if ((rc = alloc((void**)&prop_scores, (size_t)NB * PC * 4))) return rc;
-  if ((rc = alloc((void**)&prop_level, (size_t)NB * PC * 4))) return rc;
-  if ((rc = alloc((void**)&prop_count, (size_t)NB * 4))) return rc;
-  reg("proposal_boxes", prop_boxes, DT_F32, {NB, PC, 4}, 0);
-  reg("proposal_logits", prop_scores, DT_F32, {NB, PC}, 0);
-  reg("proposal_level", prop_level, DT_I32, {NB, PC}, 0);
-  reg("proposal_count", prop_count, DT_I32, {NB}, 0);
+  float* prop_scores;
+  if ((rc = new_tensor(&g.prop_boxes, "proposal_boxes", DT_F32, {NB, PC, 4}))) return rc;
+  if ((rc = new_tensor(&prop_scores, "proposal_logits", DT_F32, {NB, PC}))) return rc;
+  if ((rc = new_tensor(&g.prop_level, "proposal_level", DT_I32, {NB, PC}))) return rc;
+  if ((rc = new_tensor(&g.prop_count, "proposal_count", DT_I32, {NB}))) return rc;
   // visiting order of box.roi_align (RpnMergeParams::prop_order): inference engines on the windowed fp16 kernel only -- a training
   // engine overwrites the proposal buffer with its sampled RoIs after this stage
-  int* prop_order = nullptr;
-  const bool roi_order = !f32 && !(split && rs_debug().roi_window != 1) && !g_trainer_unfused_shortcut && rs_debug().roi_order != 0;
+  const bool roi_order = !f32 && !(split && rs_debug().roi_window != 1) && !frozen_fusions_only && rs_debug().roi_order != 0;
   if (roi_order) {
-    if ((rc = alloc((void**)&prop_order, (size_t)NB * PC * 4))) return rc;
-    reg("proposal_order", prop_order, DT_I32, {NB, PC}, 0);
+    if ((rc = new_tensor(&g.prop_order, "proposal_order", DT_I32, {NB, PC}))) return rc;
   }
-  {
-    RpnMergeParams mp = {};
-    mp.cand_boxes = rp.cand_boxes; mp.cand_scores = rp.cand_scores; mp.keep = cand_keep; mp.cand_count = rp.cand_count;
-    mp.L = L; mp.post_topk = S.rpn_post_nms_topk; mp.cap = PC;
-    mp.prop_boxes = prop_boxes; mp.prop_scores = prop_scores; mp.prop_level = prop_level; mp.prop_count = prop_count;
-    mp.prop_order = prop_order;
-    Stage st;
-    st.name = "rpn.merge";
-    st.fn = [mp](int n, hipStream_t s) { return launch_rpn_merge(mp, n, s); };
-    stages.push_back(st);
-  }
+  RpnMergeParams mp = {};
+  mp.cand_boxes = rp.cand_boxes; mp.cand_scores = rp.cand_scores; mp.keep = cand_keep; mp.cand_count = rp.cand_count;
+  mp.L = L; mp.post_topk = S.rpn_post_nms_topk; mp.cap = PC;
+  mp.prop_boxes = g.prop_boxes; mp.prop_scores = prop_scores; mp.prop_level = g.prop_level; mp.prop_count = g.prop_count;
+  mp.prop_order = g.prop_order;
+  add_stage("rpn.merge", 0, 0).fn = [mp](int n, hipStream_t s) { return launch_rpn_merge(mp, n, s); };
+  return RS_OK;
+}
 
-  // ---- box head
-  const int PR = S.box_pooler_resolution;
+// the pyramid levels both RoIAligns read
+RoiAlignParams rs_engine::roi_align_levels(const Graph& g) const {
   RoiAlignParams ra;
   memset(&ra, 0, sizeof ra);
-  for (int l = 0; l < 4; ++l) { ra.feat[l] = P[l].p; ra.H[l] = P[l].H; ra.W[l] = P[l].W; ra.scale[l] = 1.0f / (float)(4 << l); }
-  ra.nlevels = 4; ra.C = 256; ra.f32 = f32 ? 1 : (split ? 2 : 0);
-  for (int l = 0; l < 4; ++l) ra.feat_lo[l] = P[l].lo;
+  for (int l = 0; l < 4; ++l) { ra.feat[l] = g.P[l].p; ra.H[l] = g.P[l].H; ra.W[l] = g.P[l].W; ra.scale[l] = 1.0f / (float)(4 << l); }
+  ra.nlevels = 4; ra.C = 256; ra.f32 = prec_code();
+  for (int l = 0; l < 4; ++l) ra.feat_lo[l] = g.P[l].lo;
+  return ra;
+}
+
+// ---- box head + detections
+int rs_engine::build_box_head(Graph& g) {
+  const rs_spec& S = spec;
+  const int NB = max_batch, PC = 1024;
+  const int PR = S.box_pooler_resolution;
+  int rc;
   Act boxfeat;   // [NB*PC] "images" of PR x PR x 256
   if ((rc = new_act(&boxfeat, "box_pooled", NB * PC, PR, PR, 256, 0))) return rc;
   int* box_level = nullptr;
-  if ((rc = alloc((void**)&box_level, (size_t)NB * PC * 4))) return rc;
-  reg("box_roi_level", box_level, DT_I32, {NB, PC}, 0);
+  if ((rc = new_tensor(&box_level, "box_roi_level", DT_I32, {NB, PC}))) return rc;
   {
-    RoiAlignParams q = ra;
-    q.rois = prop_boxes; q.per_image_count = prop_count; q.slots_per_image = PC; q.out = boxfeat.p; q.out_lo = boxfeat.lo; q.P = PR; q.out_pad = 0;
+    RoiAlignParams q = roi_align_levels(g);
+    q.rois = g.prop_boxes; q.per_image_count = g.prop_count; q.slots_per_image = PC; q.out = boxfeat.p; q.out_lo = boxfeat.lo; q.P = PR; q.out_pad = 0;
     q.out_level = box_level;
-    q.order = prop_order;
-    Stage st;
-    st.name = "box.roi_align";
-    st.bytes_per_image = (double)PC * PR * PR * 256 * 2 * 2 * (split ? 2 : 1);
-    st.fn = [q](int n, hipStream_t s) mutable { q.S = n * PC; return launch_roi_align(q, s); };
-    stages.push_back(st);
+    q.order = g.prop_order;
+    add_stage("box.roi_align", 0, (double)PC * PR * PR * 256 * 2 * 2 * planes()).fn =
+        [q](int n, hipStream_t s) mutable { q.S = n * PC; return launch_roi_align(q, s); };
   }
   // FC layers as 1x1 "convs" over a (M x 1) image
   const int FC = S.box_fc_dim;
@@ -980,228 +1017,161 @@ int rs_engine::build() {
     RS_CHECK(wrows(w) >= p.Cout && p.Kpad >= in.C, RS_ERR_BLOB, "%s: weight shape", wn.c_str());
     const int glds = use_glds;
     const int variant = out32 ? 2 : -1;
-    Stage st;
-    st.name = name;
-    st.flops_per_image = 2.0 * PC * (double)in.C * p.Cout;
-    st.bytes_per_image = (double)PC * (in.C * 2 * (split ? 2 : 1) + p.Cout * (out32 ? 4 : (split ? 4 : 2)));
-    p.sat = out32 ? nullptr : sat_slot();
+    Stage& st = add_stage(name, 2.0 * PC * (double)in.C * p.Cout, (double)PC * (in.C * 2 * planes() + p.Cout * (out32 ? 4 : 2 * planes())),
+                          out32 ? nullptr : &p.sat);
     st.fn = [p, glds, variant](int n, hipStream_t s) mutable { p.M = n * PC; return launch_conv(p, s, variant, glds); };
-    stages.push_back(st);
     return RS_OK;
   };
   if ((rc = add_fc("box.fc1", "roi_heads.box_head.fc1", fin, f1, true, nullptr, 0))) return rc;
   if ((rc = add_fc("box.fc2", "roi_heads.box_head.fc2", f1, f2, true, nullptr, 0))) return rc;
   const int K = S.num_classes;
   const int pred_cs = (5 * K + 1 + 15) / 16 * 16;
-  float* pred = nullptr;
-  if ((rc = alloc((void**)&pred, (size_t)NB * PC * pred_cs * 4))) return rc;
-  reg("box_pred", pred, DT_F32, {NB, PC, pred_cs}, 0);
-  if ((rc = add_fc("box.predictor", "roi_heads.box_predictor", f2, f2, false, pred, pred_cs))) return rc;
+  if ((rc = new_tensor(&g.pred, "box_pred", DT_F32, {NB, PC, pred_cs}))) return rc;
+  if ((rc = add_fc("box.predictor", "roi_heads.box_predictor", f2, f2, false, g.pred, pred_cs))) return rc;
 
   D = S.detections_per_image;
   BoxCandParams bc;
   memset(&bc, 0, sizeof bc);
-  bc.pred = pred; bc.prop_boxes = prop_boxes; bc.prop_count = prop_count; bc.K = K; bc.cap = PC; bc.cs = pred_cs;
+  bc.pred = g.pred; bc.prop_boxes = g.prop_boxes; bc.prop_count = g.prop_count; bc.K = K; bc.cap = PC; bc.cs = pred_cs;
   bc.wx = S.box_reg_weights[0]; bc.wy = S.box_reg_weights[1]; bc.ww = S.box_reg_weights[2]; bc.wh = S.box_reg_weights[3];
   bc.scale_clamp = S.scale_clamp; bc.img_h = (float)net_h; bc.img_w = (float)net_w; bc.score_thresh = S.score_thresh_test;
   uint8_t* seg_keep = nullptr;
-  if ((rc = alloc((void**)&bc.dec_boxes, (size_t)NB * PC * K * 16))) return rc;
-  if ((rc = alloc((void**)&bc.dec_scores, (size_t)NB * PC * K * 4))) return rc;
-  if ((rc = alloc((void**)&bc.seg_boxes, (size_t)NB * K * 1024 * 16))) return rc;
-  if ((rc = alloc((void**)&bc.seg_roi, (size_t)NB * K * 1024 * 4))) return rc;
-  if ((rc = alloc((void**)&bc.seg_count, (size_t)NB * K * 4))) return rc;
-  if ((rc = alloc((void**)&seg_keep, (size_t)NB * K * 1024))) return rc;
   if (K > RS_DET_GROUP) {   // many classes: softmax statistics per RoI, computed once (launch_box_candidates)
-    if ((rc = alloc((void**)&bc.roi_stat, (size_t)NB * PC * 8))) return rc;
-    reg("box_roi_stat", bc.roi_stat, DT_F32, {NB, PC, 2}, 0);
+    if ((rc = new_tensor(&bc.roi_stat, "box_roi_stat", DT_F32, {NB, PC, 2}))) return rc;
   }
-  reg("box_dec_boxes", bc.dec_boxes, DT_F32, {NB, PC, K, 4}, 0);
-  reg("box_dec_scores", bc.dec_scores, DT_F32, {NB, PC, K}, 0);
-  reg("box_seg_boxes", bc.seg_boxes, DT_F32, {NB, K, 1024, 4}, 0);
-  reg("box_seg_roi", bc.seg_roi, DT_I32, {NB, K, 1024}, 0);
-  reg("box_seg_count", bc.seg_count, DT_I32, {NB, K}, 0);
-  reg("box_seg_keep", seg_keep, DT_U8, {NB, K, 1024}, 0);
-  {
-    Stage st;
-    st.name = "box.candidates";
-    st.fn = [bc](int n, hipStream_t s) { return launch_box_candidates(bc, n, s); };
-    stages.push_back(st);
-  }
+  if ((rc = new_tensor(&bc.dec_boxes, "box_dec_boxes", DT_F32, {NB, PC, K, 4}))) return rc;
+  if ((rc = new_tensor(&bc.dec_scores, "box_dec_scores", DT_F32, {NB, PC, K}))) return rc;
+  if ((rc = new_tensor(&bc.seg_boxes, "box_seg_boxes", DT_F32, {NB, K, 1024, 4}))) return rc;
+  if ((rc = new_tensor(&bc.seg_roi, "box_seg_roi", DT_I32, {NB, K, 1024}))) return rc;
+  if ((rc = new_tensor(&bc.seg_count, "box_seg_count", DT_I32, {NB, K}))) return rc;
+  if ((rc = new_tensor(&seg_keep, "box_seg_keep", DT_U8, {NB, K, 1024}))) return rc;
+  add_stage("box.candidates", 0, 0).fn = [bc](int n, hipStream_t s) { return launch_box_candidates(bc, n, s); };
   {
     NmsParams np = {};
     np.boxes = bc.seg_boxes; np.count = bc.seg_count; np.valid = nullptr; np.keep = seg_keep; np.cap = 1024; np.thresh = S.nms_thresh_test;
     if ((rc = alloc((void**)&np.scratch, (size_t)(NB * K < 32 ? NB * K : 32) * 1024 * 16 * 8))) return rc;
     if (S.batched_nms) { if ((rc = add_nms_rule("box", &np, K))) return rc; }
-    Stage st;
-    st.name = "box.nms";
-    st.fn = [np, K](int n, hipStream_t s) { return launch_nms(np, n * K, s); };
-    stages.push_back(st);
+    add_stage("box.nms", 0, 0).fn = [np, K](int n, hipStream_t s) { return launch_nms(np, n * K, s); };
   }
   int* det_roi = nullptr;
-  if ((rc = alloc((void**)&det_boxes_net, (size_t)NB * D * 16))) return rc;
-  if ((rc = alloc((void**)&det_boxes, (size_t)NB * D * 16))) return rc;
-  if ((rc = alloc((void**)&det_scores, (size_t)NB * D * 4))) return rc;
-  if ((rc = alloc((void**)&det_classes, (size_t)NB * D * 4))) return rc;
-  if ((rc = alloc((void**)&det_roi, (size_t)NB * D * 4))) return rc;
-  if ((rc = alloc((void**)&det_count, (size_t)NB * 4))) return rc;
-  reg("det_boxes_net", det_boxes_net, DT_F32, {NB, D, 4}, 0);
-  reg("det_boxes", det_boxes, DT_F32, {NB, D, 4}, 0);
-  reg("det_scores", det_scores, DT_F32, {NB, D}, 0);
-  reg("det_classes", det_classes, DT_I32, {NB, D}, 0);
-  reg("det_roi", det_roi, DT_I32, {NB, D}, 0);
-  reg("det_count", det_count, DT_I32, {NB}, 0);
-  {
-    DetMergeParams dm;
-    memset(&dm, 0, sizeof dm);
-    dm.dec_boxes = bc.dec_boxes; dm.dec_scores = bc.dec_scores; dm.seg_roi = bc.seg_roi; dm.seg_count = bc.seg_count; dm.keep = seg_keep;
-    dm.K = K; dm.cap = PC; dm.dets_per_image = D;
-    dm.scale_x = (float)((double)tile_w / (double)net_w);
-    dm.scale_y = (float)((double)tile_h / (double)net_h);
-    dm.out_w = (float)tile_w; dm.out_h = (float)tile_h;
-    dm.det_boxes_net = det_boxes_net; dm.det_boxes = det_boxes; dm.det_scores = det_scores; dm.det_classes = det_classes;
-    dm.det_roi = det_roi; dm.det_count = det_count;
-    if (K > RS_DET_GROUP) {   // many classes: the groups' partial winners between the merge's two launches (launch_det_merge)
-      const int G = det_merge_groups(K);
-      if ((rc = alloc((void**)&dm.part_keys, (size_t)NB * G * D * 8))) return rc;
-      if ((rc = alloc((void**)&dm.part_count, (size_t)NB * G * 4))) return rc;
-    }
-    Stage st;
-    st.name = "box.merge_postprocess";
-    st.fn = [dm](int n, hipStream_t s) { return launch_det_merge(dm, n, s); };
-    stages.push_back(st);
+  if ((rc = new_tensor(&det_boxes_net, "det_boxes_net", DT_F32, {NB, D, 4}))) return rc;
+  if ((rc = new_tensor(&det_boxes, "det_boxes", DT_F32, {NB, D, 4}))) return rc;
+  if ((rc = new_tensor(&det_scores, "det_scores", DT_F32, {NB, D}))) return rc;
+  if ((rc = new_tensor(&det_classes, "det_classes", DT_I32, {NB, D}))) return rc;
+  if ((rc = new_tensor(&det_roi, "det_roi", DT_I32, {NB, D}))) return rc;
+  if ((rc = new_tensor(&det_count, "det_count", DT_I32, {NB}))) return rc;
+  DetMergeParams dm;
+  memset(&dm, 0, sizeof dm);
+  dm.dec_boxes = bc.dec_boxes; dm.dec_scores = bc.dec_scores; dm.seg_roi = bc.seg_roi; dm.seg_count = bc.seg_count; dm.keep = seg_keep;
+  dm.K = K; dm.cap = PC; dm.dets_per_image = D;
+  dm.scale_x = (float)((double)tile_w / (double)net_w);
+  dm.scale_y = (float)((double)tile_h / (double)net_h);
+  dm.out_w = (float)tile_w; dm.out_h = (float)tile_h;
+  dm.det_boxes_net = det_boxes_net; dm.det_boxes = det_boxes; dm.det_scores = det_scores; dm.det_classes = det_classes;
+  dm.det_roi = det_roi; dm.det_count = det_count;
+  if (K > RS_DET_GROUP) {   // many classes: the groups' partial winners between the merge's two launches (launch_det_merge)
+    const int G = det_merge_groups(K);
+    if ((rc = alloc((void**)&dm.part_keys, (size_t)NB * G * D * 8))) return rc;
+    if ((rc = alloc((void**)&dm.part_count, (size_t)NB * G * 4))) return rc;
   }
+  add_stage("box.merge_postprocess", 0, 0).fn = [dm](int n, hipStream_t s) { return launch_det_merge(dm, n, s); };
+  return RS_OK;
+}
 
-  // ---- mask head
-  if (S.mask_on) {
-    const int MR = S.mask_pooler_resolution, R = NB * D;
-    int *slot_list, *det_total;
-    if ((rc = alloc((void**)&slot_list, (size_t)R * 4))) return rc;
-    if ((rc = alloc((void**)&det_total, 16))) return rc;
-    reg("det_slot_list", slot_list, DT_I32, {R}, 0);
-    reg("det_total", det_total, DT_I32, {1}, 0);
-    {
-      Stage st;
-      st.name = "mask.compact";
-      int* dc = det_count;
-      const int Dc = D;
-      st.fn = [dc, Dc, slot_list, det_total](int n, hipStream_t s) { return launch_det_compact(dc, n, Dc, slot_list, det_total, s); };
-      stages.push_back(st);
-    }
-    Act mx;
-    if ((rc = new_act(&mx, "mask_pooled", R, MR, MR, 256, 1))) return rc;
-    {
-      RoiAlignParams q = ra;
-      q.rois = det_boxes_net; q.slot_list = slot_list; q.n_entries = det_total; q.slots_per_image = D;
-      q.out = mx.p; q.out_lo = mx.lo; q.P = MR; q.out_pad = 1;
-      Stage st;
-      st.name = "mask.roi_align";
-      st.bytes_per_image = (double)D * MR * MR * 256 * 2 * 2 * (split ? 2 : 1);
-      const int Dc = D;
-      st.fn = [q, Dc](int n, hipStream_t s) mutable { q.S = n * Dc; return launch_roi_align(q, s); };
-      stages.push_back(st);
-    }
-    Act curm = mx;
-    for (int i = 0; i < S.mask_num_conv; ++i) {
-      Act o;
-      const std::string nm = "mask_fcn" + std::to_string(i + 1);
-      if ((rc = new_act(&o, nm, R, MR, MR, 256, 1))) return rc;
-      if ((rc = add_conv("mask.fcn" + std::to_string(i + 1), "roi_heads.mask_head." + nm, curm, o, 3, 1, 1, true, nullptr, nullptr, 256, D, det_total))) return rc;
-      curm = o;
-    }
-    if ((rc = alloc((void**)&mask_probs, (size_t)R * RS_MASK_SIDE * RS_MASK_SIDE * 4))) return rc;
-    reg("mask_probs", mask_probs, DT_F32, {NB, D, RS_MASK_SIDE, RS_MASK_SIDE}, 0);
-    const BlobEntry* dw = findw("roi_heads.mask_head.deconv");
-    const BlobEntry* db = find("roi_heads.mask_head.deconv.b");
-    const BlobEntry* pw = find("roi_heads.mask_head.predictor.w");
-    const BlobEntry* pb = find("roi_heads.mask_head.predictor.b");
-    RS_CHECK(dw && db && wrows(dw) == 1024, RS_ERR_BLOB, "deconv weights missing / wrong rows");
-    RS_CHECK(pw && pb && pw->dtype == DT_F32, RS_ERR_BLOB, "mask predictor weights missing");
-    const bool fuse = f32 ? false : rs_debug().fuse_mask_predictor != 0;
-    ConvParams dp;
-    memset(&dp, 0, sizeof dp);
-    if ((rc = set_split(&dp, "roi_heads.mask_head.deconv", dw, &curm, nullptr, nullptr, nullptr, nullptr))) return rc;
-    dp.in = curm.p; dp.w = (const half_t*)dw->dev; dp.bias = (const float*)db->dev;
-    dp.Ho = MR; dp.Wo = MR; dp.in_Hp = curm.Hp(); dp.in_Wp = curm.Wp(); dp.in_Cs = 256; dp.in_off = 1; dp.stride = 1; dp.KH = dp.KW = 1;
-    dp.Cin = 256; dp.Kpad = (int)dw->dims[1]; dp.Cout = 256; dp.out_Hp = 2 * MR; dp.out_Wp = 2 * MR; dp.out_Cs = 256; dp.out_pad = 0; dp.relu = 1;
-    dp.m_count = det_total; dp.m_mul = MR * MR;
-    const int per_roi = MR * MR;
-    if (fuse) {
-      // deconv 2x2 s2 + ReLU + predictor 1x1 (predicted class only) in one launch: the 28x28x256 map (40 MB per
-      // tile) is never written; a small kernel then adds the class bias and applies the sigmoid in place.
-      dp.mode = 2; dp.out = nullptr;
-      dp.dot_w = (const float*)pw->dev; dp.dot_cls = det_classes; dp.dot_slot = slot_list; dp.dot_out = mask_probs;
-      dp.dot_k = (int)pw->dims[0];
-      const int glds = use_glds, Dc = D;
-      const bool sp = split;
-      float* probs = mask_probs;
-      const size_t zero_per_tile = (size_t)D * RS_MASK_SIDE * RS_MASK_SIDE * 4;
-      Stage st;
-      st.name = "mask.deconv_predict";
-      st.flops_per_image = 2.0 * D * per_roi * 256 * 1024 + 2.0 * D * RS_MASK_SIDE * RS_MASK_SIDE * 256;
-      st.bytes_per_image = (double)D * per_roi * 256 * 2 * (split ? 2 : 1) + (double)D * RS_MASK_SIDE * RS_MASK_SIDE * 4;
-      st.fn = [dp, per_roi, Dc, glds, probs, zero_per_tile, sp](int n, hipStream_t s) mutable {
-        RS_HIP(hipMemsetAsync(probs, 0, zero_per_tile * n, s));
-        dp.M = n * Dc * per_roi;
-        // conv_wreg.hip (22: persistent, a (dy, dx) group's weights in registers) or conv_igemm's tile where one workgroup holds all 256
-        // channels of a group (14 / 10); the two give the same bits
-        const int dv = rs_debug().deconv_variant;
-        return launch_conv(dp, s, (dv == 22 && (sp || !(rs_debug().conv_wreg && glds > 0))) ? 14 : dv, glds);
-      };
-      stages.push_back(st);
-      MaskPredictParams mp;
-      mp.f32 = 0;
-      mp.in = nullptr; mp.w = nullptr; mp.b = (const float*)pb->dev; mp.slot_list = slot_list; mp.det_classes = det_classes;
-      mp.n_entries = det_total; mp.out = mask_probs; mp.S = RS_MASK_SIDE;
-      Stage st2;
-      st2.name = "mask.bias_sigmoid";
-      st2.fn = [mp, Dc](int n, hipStream_t s) { return launch_mask_sigmoid(mp, n * Dc, s); };
-      stages.push_back(st2);
-    } else {
-      Act dec;
-      if ((rc = new_act(&dec, "mask_deconv", R, 2 * MR, 2 * MR, 256, 0))) return rc;
-      dp.mode = 1; dp.out = dec.p; dp.out_lo = dec.lo;
-      {
-        const int glds = use_glds, Dc = D;
-        Stage st;
-        st.name = "mask.deconv";
-        st.flops_per_image = 2.0 * D * per_roi * 256 * 1024;
-        st.bytes_per_image = (double)D * per_roi * 256 * 2 * 5;
-        dp.sat = sat_slot();
-        st.fn = [dp, per_roi, Dc, glds](int n, hipStream_t s) mutable { dp.M = n * Dc * per_roi; return launch_conv(dp, s, -1, glds); };
-        stages.push_back(st);
-      }
-      MaskPredictParams mp;
-      mp.in = dec.p; mp.w = (const float*)pw->dev; mp.b = (const float*)pb->dev; mp.slot_list = slot_list; mp.det_classes = det_classes;
-      mp.n_entries = det_total; mp.out = mask_probs; mp.S = RS_MASK_SIDE; mp.f32 = f32 ? 1 : (split ? 2 : 0); mp.in_lo = dec.lo;
-      Stage st;
-      st.name = "mask.predict_sigmoid";
-      st.bytes_per_image = (double)D * RS_MASK_SIDE * RS_MASK_SIDE * (256 * 2 + 4);
-      const int Dc = D;
-      st.fn = [mp, Dc](int n, hipStream_t s) { return launch_mask_predict(mp, n * Dc, s); };
-      stages.push_back(st);
-    }
-    const int Wb = (tile_w + 7) / 8;
-    if ((rc = alloc((void**)&masks, (size_t)R * tile_h * Wb))) return rc;
-    reg("masks", masks, DT_U8, {NB, D, tile_h, Wb}, 0);
-    if ((rc = alloc((void**)&crop_data, (size_t)R * tile_h * Wb))) return rc;
-    if ((rc = alloc((void**)&crop_rects, (size_t)R * 16))) return rc;
-    if ((rc = alloc((void**)&crop_offsets, (size_t)R * 4))) return rc;
-    if ((rc = alloc((void**)&crop_total, 16))) return rc;
-    {
-      PasteParams pm;
-      pm.probs = mask_probs; pm.det_boxes = det_boxes; pm.slot_list = slot_list; pm.n_entries = det_total; pm.out = masks;
-      pm.S = RS_MASK_SIDE; pm.out_h = tile_h; pm.out_w = tile_w; pm.threshold = S.mask_threshold;
-      Stage st;
-      st.name = "mask.paste";
-      st.bytes_per_image = (double)D * tile_h * Wb;
-      const int Dc = D;
-      st.fn = [pm, Dc](int n, hipStream_t s) { return launch_paste_masks(pm, n * Dc, s); };
-      stages.push_back(st);
-    }
+// ---- mask head: RoIAlign of the detections, 4 x conv 3x3, deconv 2x2 s2 + predictor + sigmoid, paste into the tile
+int rs_engine::build_mask_head(Graph& g) {
+  const rs_spec& S = spec;
+  const int NB = max_batch, Dc = D;
+  const int MR = S.mask_pooler_resolution, R = NB * D;
+  int rc;
+  if ((rc = new_tensor(&g.slot_list, "det_slot_list", DT_I32, {R}))) return rc;
+  if ((rc = new_tensor(&g.det_total, "det_total", DT_I32, {1}))) return rc;
+  int *slot_list = g.slot_list, *det_total = g.det_total;
+  {
+    int* dc = det_count;
+    add_stage("mask.compact", 0, 0).fn = [dc, Dc, slot_list, det_total](int n, hipStream_t s) { return launch_det_compact(dc, n, Dc, slot_list, det_total, s); };
   }
-  RS_CHECK(stages.size() <= (size_t)kSatCap, RS_ERR_UNSUPPORTED, "%d stages: more than the %d saturation counters", (int)stages.size(), kSatCap);
-  h_sat.assign(stages.size(), 0);
-  RS_HIP(hipStreamSynchronize(stream));
+  Act mx;
+  if ((rc = new_act(&mx, "mask_pooled", R, MR, MR, 256, 1))) return rc;
+  {
+    RoiAlignParams q = roi_align_levels(g);
+    q.rois = det_boxes_net; q.slot_list = slot_list; q.n_entries = det_total; q.slots_per_image = D;
+    q.out = mx.p; q.out_lo = mx.lo; q.P = MR; q.out_pad = 1;
+    add_stage("mask.roi_align", 0, (double)D * MR * MR * 256 * 2 * 2 * planes()).fn =
+        [q, Dc](int n, hipStream_t s) mutable { q.S = n * Dc; return launch_roi_align(q, s); };
+  }
+  Act curm = mx;
+  for (int i = 0; i < S.mask_num_conv; ++i) {
+    Act o;
+    const std::string nm = "mask_fcn" + std::to_string(i + 1);
+    if ((rc = new_act(&o, nm, R, MR, MR, 256, 1))) return rc;
+    ConvDesc d{3, 1, 1, true};
+    d.units_per_tile = D; d.m_count = det_total;
+    if ((rc = add_conv("mask.fcn" + std::to_string(i + 1), "roi_heads.mask_head." + nm, curm, o, d))) return rc;
+    curm = o;
+  }
+  if ((rc = new_tensor(&mask_probs, "mask_probs", DT_F32, {NB, D, RS_MASK_SIDE, RS_MASK_SIDE}))) return rc;
+  const BlobEntry* dw = findw("roi_heads.mask_head.deconv");
+  const BlobEntry* db = find("roi_heads.mask_head.deconv.b");
+  const BlobEntry* pw = find("roi_heads.mask_head.predictor.w");
+  const BlobEntry* pb = find("roi_heads.mask_head.predictor.b");
+  RS_CHECK(dw && db && wrows(dw) == 1024, RS_ERR_BLOB, "deconv weights missing / wrong rows");
+  RS_CHECK(pw && pb && pw->dtype == DT_F32, RS_ERR_BLOB, "mask predictor weights missing");
+  const bool fuse = f32 ? false : rs_debug().fuse_mask_predictor != 0;
+  ConvParams dp;
+  memset(&dp, 0, sizeof dp);
+  if ((rc = set_split(&dp, "roi_heads.mask_head.deconv", dw, &curm, nullptr, nullptr, nullptr, nullptr))) return rc;
+  dp.in = curm.p; dp.w = (const half_t*)dw->dev; dp.bias = (const float*)db->dev;
+  dp.Ho = MR; dp.Wo = MR; dp.in_Hp = curm.Hp(); dp.in_Wp = curm.Wp(); dp.in_Cs = 256; dp.in_off = 1; dp.stride = 1; dp.KH = dp.KW = 1;
+  dp.Cin = 256; dp.Kpad = (int)dw->dims[1]; dp.Cout = 256; dp.out_Hp = 2 * MR; dp.out_Wp = 2 * MR; dp.out_Cs = 256; dp.out_pad = 0; dp.relu = 1;
+  dp.m_count = det_total; dp.m_mul = MR * MR;
+  const int per_roi = MR * MR;
+  const int glds = use_glds;
+  MaskPredictParams mp = {};
+  mp.b = (const float*)pb->dev; mp.slot_list = slot_list; mp.det_classes = det_classes;
+  mp.n_entries = det_total; mp.out = mask_probs; mp.S = RS_MASK_SIDE;
+  if (fuse) {
+    // deconv 2x2 s2 + ReLU + predictor 1x1 (predicted class only) in one launch: the 28x28x256 map (40 MB per
+    // tile) is never written; a small kernel then adds the class bias and applies the sigmoid in place.
+    dp.mode = 2; dp.out = nullptr;
+    dp.dot_w = (const float*)pw->dev; dp.dot_cls = det_classes; dp.dot_slot = slot_list; dp.dot_out = mask_probs;
+    dp.dot_k = (int)pw->dims[0];
+    const bool sp = split;
+    float* probs = mask_probs;
+    const size_t zero_per_tile = (size_t)D * RS_MASK_SIDE * RS_MASK_SIDE * 4;
+    add_stage("mask.deconv_predict", 2.0 * D * per_roi * 256 * 1024 + 2.0 * D * RS_MASK_SIDE * RS_MASK_SIDE * 256,
+              (double)D * per_roi * 256 * 2 * planes() + (double)D * RS_MASK_SIDE * RS_MASK_SIDE * 4).fn =
+        [dp, per_roi, Dc, glds, probs, zero_per_tile, sp](int n, hipStream_t s) mutable {
+      RS_HIP(hipMemsetAsync(probs, 0, zero_per_tile * n, s));
+      dp.M = n * Dc * per_roi;
+      // conv_wreg.hip (22: persistent, a (dy, dx) group's weights in registers) or conv_igemm's tile where one workgroup holds all 256
+      // channels of a group (14 / 10); the two give the same bits
+      const int dv = rs_debug().deconv_variant;
+      return launch_conv(dp, s, (dv == 22 && (sp || !(rs_debug().conv_wreg && glds > 0))) ? 14 : dv, glds);
+    };
+    mp.f32 = 0;
+    mp.in = nullptr; mp.w = nullptr;
+    add_stage("mask.bias_sigmoid", 0, 0).fn = [mp, Dc](int n, hipStream_t s) { return launch_mask_sigmoid(mp, n * Dc, s); };
+  } else {
+    Act dec;
+    if ((rc = new_act(&dec, "mask_deconv", R, 2 * MR, 2 * MR, 256, 0))) return rc;
+    dp.mode = 1; dp.out = dec.p; dp.out_lo = dec.lo;
+    Stage& st = add_stage("mask.deconv", 2.0 * D * per_roi * 256 * 1024, (double)D * per_roi * 256 * 2 * 5, &dp.sat);
+    st.fn = [dp, per_roi, Dc, glds](int n, hipStream_t s) mutable { dp.M = n * Dc * per_roi; return launch_conv(dp, s, -1, glds); };
+    mp.in = dec.p; mp.w = (const float*)pw->dev; mp.f32 = prec_code(); mp.in_lo = dec.lo;
+    add_stage("mask.predict_sigmoid", 0, (double)D * RS_MASK_SIDE * RS_MASK_SIDE * (256 * 2 + 4)).fn =
+        [mp, Dc](int n, hipStream_t s) { return launch_mask_predict(mp, n * Dc, s); };
+  }
+  const int Wb = (tile_w + 7) / 8;
+  if ((rc = new_tensor(&masks, "masks", DT_U8, {NB, D, tile_h, Wb}))) return rc;
+  if ((rc = alloc((void**)&crop_data, (size_t)R * tile_h * Wb))) return rc;
+  if ((rc = alloc((void**)&crop_rects, (size_t)R * 16))) return rc;
+  if ((rc = alloc((void**)&crop_offsets, (size_t)R * 4))) return rc;
+  if ((rc = alloc((void**)&crop_total, 16))) return rc;
+  PasteParams pm;
+  pm.probs = mask_probs; pm.det_boxes = det_boxes; pm.slot_list = slot_list; pm.n_entries = det_total; pm.out = masks;
+  pm.S = RS_MASK_SIDE; pm.out_h = tile_h; pm.out_w = tile_w; pm.threshold = S.mask_threshold;
+  add_stage("mask.paste", 0, (double)D * tile_h * Wb).fn = [pm, Dc](int n, hipStream_t s) { return launch_paste_masks(pm, n * Dc, s); };
   return RS_OK;
 }
 
@@ -1389,8 +1359,11 @@ int rs_spec_batched_nms(const rs_spec* spec) {
   return spec->batched_nms;
 }
 
-int rs_engine_create(const rs_spec* spec, const void* weights, size_t nbytes, int device_ordinal, int max_batch,
-                     int tile_h, int tile_w, int tile_c, void* stream, rs_engine** out) {
+}  // extern "C"
+
+// rs_engine_create, or with `for_trainer` the forward engine of an rs_trainer (rs_engine::frozen_fusions_only)
+static int engine_create(const rs_spec* spec, const void* weights, size_t nbytes, int device_ordinal, int max_batch,
+                         int tile_h, int tile_w, int tile_c, void* stream, bool for_trainer, rs_engine** out) {
   RS_CHECK(spec && weights && out, RS_ERR_ARG, "null argument");
   const int nms_mode = rs_spec_batched_nms(spec);     // checks struct_size: the current struct, or the one that ends before batched_nms (mode 0)
   if (nms_mode < 0) return nms_mode;
@@ -1411,7 +1384,7 @@ int rs_engine_create(const rs_spec* spec, const void* weights, size_t nbytes, in
   e->f32 = spec->precision == 1;
   e->split = spec->precision == 2;
   if (e->f32) e->use_glds = -1;
-  if (e->split && (e->use_glds <= 0 || g_trainer_unfused_shortcut)) {
+  if (e->split && (e->use_glds <= 0 || for_trainer)) {
     rs_set_error("precision 2 (split operands) needs LDS-DMA staging and is an inference mode");
     delete e;
     return RS_ERR_UNSUPPORTED;
@@ -1424,7 +1397,7 @@ int rs_engine_create(const rs_spec* spec, const void* weights, size_t nbytes, in
   // stem and res2 (FREEZE_AT 2, what rs_trainer implements) keep the inference engine's fused stem and fused bottleneck tails
   // (the multi-map launches of the FPN output convolutions and of the RPN 3x3 stay: every map still gets its own output tensor; only the RPN heads
   //  leave the 3x3's epilogue, because the trainer differentiates through the 256-channel rpn_conv maps)
-  if (g_trainer_unfused_shortcut) e->frozen_fusions_only = true;
+  e->frozen_fusions_only = for_trainer;
   e->use_graph = rs_debug().use_graph;   // measured: replay == eager (11.54 ms/step either way), so off by default
   if (stream) { e->stream = (hipStream_t)stream; e->own_stream = false; }
   else {
@@ -1440,6 +1413,13 @@ int rs_engine_create(const rs_spec* spec, const void* weights, size_t nbytes, in
   if (rc) { rs_engine_destroy(e); return rc; }
   *out = e;
   return RS_OK;
+}
+
+extern "C" {
+
+int rs_engine_create(const rs_spec* spec, const void* weights, size_t nbytes, int device_ordinal, int max_batch,
+                     int tile_h, int tile_w, int tile_c, void* stream, rs_engine** out) {
+  return engine_create(spec, weights, nbytes, device_ordinal, max_batch, tile_h, tile_w, tile_c, stream, /*for_trainer=*/false, out);
 }
 
 void rs_engine_destroy(rs_engine* e) {

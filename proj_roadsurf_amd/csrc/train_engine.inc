@@ -1091,9 +1091,7 @@ int rs_trainer_create(const rs_spec* spec, const void* weights, size_t nbytes, i
   t->f32 = spec->precision == 1;
   t->N = batch;
   t->loss_scale = loss_scale;
-  g_trainer_unfused_shortcut = true;
-  int rc = rs_engine_create(spec, weights, nbytes, device_ordinal, batch, tile_h, tile_w, tile_c, nullptr, &t->eng);
-  g_trainer_unfused_shortcut = false;
+  int rc = engine_create(spec, weights, nbytes, device_ordinal, batch, tile_h, tile_w, tile_c, nullptr, /*for_trainer=*/true, &t->eng);
   if (rc) { delete t; return rc; }
   t->stream = t->eng->stream;
   {
