@@ -550,6 +550,48 @@ void rs_vec_free(rs_vec_result* r);
 int64_t rs_vec_gpkg_blobs(const rs_vec_result* r, const double* xform, int32_t srs_id, uint8_t* out, int64_t out_cap,
                           int64_t* offsets, double bbox[4]);
 
+/* ------------------------------------------------------------------ detections -> polygons on the device (csrc/polygonize.hip)
+ * The same mask -> polygon -> Ramer-Douglas-Peucker tail as rs_vectorize_masks, vertex for vertex, as HIP kernels: one workgroup per
+ * instance, its working set in LDS.  An instance whose mask needs more than the per-instance capacities (directed
+ * edges, rings, ring vertices before simplification: rs_polygonize_caps) is FLAGGED and produces no rows; the caller vectorises it on
+ * the host (rs_vectorize_masks / rs_vectorize_mask_crops) and rs_vec_from_tables merges the two, so nothing is dropped or truncated.
+ * Tables: header [n][RS_POLY_HDR] int32 = {flagged, polygons, rings, vertices, first polygon, first ring, first vertex, 0} per instance;
+ * poly_ring_count / ring_len as in rs_vec_result over the instances that are not flagged, in order; xy = int16 (x, y) pairs in tile
+ * pixels (integers by construction; canvases up to 1024 x 1024).  totals [4] = {polygons, rings, vertices, flagged instances}. */
+#define RS_POLY_HDR 8
+void rs_polygonize_caps(int* edge_cap, int* vertex_cap, int* ring_cap, int* max_side);
+/* Stand-alone operator on caller-owned device memory: masks_dev [n][h][(w+7)/8]; edge_cap / vertex_cap 0 = the default (the maximum).
+ * Output device buffers sized for the worst case: header n * RS_POLY_HDR, poly_ring_count and ring_len n * ring_cap each, xy n *
+ * vertex_cap pairs, totals 4.  Waits for the stream. */
+int rs_op_polygonize(const uint8_t* masks_dev, int n, int h, int w, double rdp_epsilon, int edge_cap, int vertex_cap, int32_t* header_dev,
+                     int32_t* poly_ring_count_dev, int32_t* ring_len_dev, int16_t* xy_dev, int32_t* totals_dev, void* stream);
+/* Host only: an rs_vec_result over n instances from the tables above.  `fallback` holds the host-vectorised flagged instances, one
+ * per flagged header in slot order (NULL when none is flagged); NULL is returned when the tables and the fallback do not fit together.
+ * rs_vec_counts / rs_vec_copy / rs_vec_gpkg_blobs serve the result as any other. */
+rs_vec_result* rs_vec_from_tables(const int32_t* header, int n, const int32_t* poly_ring_count, const int32_t* ring_len, const int16_t* xy,
+                                  const rs_vec_result* fallback);
+
+/* Polygons of the last forward, the counterpart of rs_engine_fetch_crops_*: caller-allocated (rs_host_alloc) tables for n tiles of D
+ * slots each; poly_cap / ring_cap / vertex_cap = elements available (n * D * ring_cap, the same, n * D * vertex_cap always suffice). */
+typedef struct rs_polygons {
+  int32_t* header;            /* [n][D][RS_POLY_HDR] */
+  int32_t* poly_ring_count;
+  int32_t* ring_len;
+  int16_t* xy;
+  uint64_t poly_cap, ring_cap, vertex_cap;
+  uint64_t n_polygons, n_rings, n_vertices, n_flagged;  /* out (rs_engine_fetch_polygons_wait) */
+  rs_mask_crops* crops;       /* crop table (always filled) and data (copied only when an instance was flagged or want_masks) */
+  int32_t want_masks;         /* in: copy the crop bytes in any case */
+  int32_t masks_copied;       /* out: crops->data / crops->used are valid */
+} rs_polygons;
+/* rs_engine_fetch_polygons_async enqueues, on the copy stream behind the forward, the crop planning, the polygoniser (rdp_epsilon <= 0:
+ * no simplification) and the copies of count / boxes / scores / classes, the crop table and the polygon headers;
+ * rs_engine_fetch_polygons_wait waits for them, copies exactly the rows in use and -- only when an instance was flagged or masks were
+ * asked for -- the crop bytes.  The engine's result buffers are free for the next forward after the first step.  MASK_ON false:
+ * RS_ERR_ARG.  The device buffers are allocated on the first call. */
+int rs_engine_fetch_polygons_async(rs_engine* e, int n, rs_dets* dets_host, rs_polygons* polys_host, double rdp_epsilon);
+int rs_engine_fetch_polygons_wait(rs_engine* e, rs_polygons* polys_host);
+
 /* Training targets of the mask head (host code): the polygons of ONE ground-truth instance cropped to `box` and rasterised at
  * mask_size x mask_size -- PolygonMasks.crop_and_resize ([EXT d2: structures/masks.py rasterize_polygons_within_box]; rasteriser =
  * pycocotools' rleFrPoly restated, parity unpinned).  polys: concatenated [x0,y0,x1,y1,...] of the polygons, poly_len[i] doubles

@@ -14,6 +14,7 @@
 
 #include "../../include/rs_engine.h"
 #include "detect.h"
+#include "polygonize.h"
 #include "train.h"
 
 // ------------------------------------------------------------------------------------- errors
@@ -198,6 +199,11 @@ struct rs_engine {
   uint8_t* crop_data = nullptr;
   unsigned long long* h_crop_total = nullptr;   // pinned
   hipEvent_t ev_crop_hdr = nullptr;
+  // polygons for the host (rs_engine_fetch_polygons_*): allocated on the first call, an engine that never asks keeps none of it
+  PolyParams poly;                              // scratch + compacted tables on the device
+  bool poly_ready = false;
+  int* h_poly_totals = nullptr;                 // pinned [4]
+  hipEvent_t ev_poly_hdr = nullptr;
 
   // the precision of the activations, as the launchers take it (PreprocParams::out_f32, RoiAlignParams::f32, MaskPredictParams::f32)
   int prec_code() const { return f32 ? 1 : (split ? 2 : 0); }
@@ -1430,6 +1436,8 @@ void rs_engine_destroy(rs_engine* e) {
   if (e->copy_stream) { (void)hipStreamSynchronize(e->copy_stream); (void)hipStreamDestroy(e->copy_stream); }
   if (e->ev_crop_hdr) (void)hipEventDestroy(e->ev_crop_hdr);
   if (e->h_crop_total) (void)hipHostFree(e->h_crop_total);
+  if (e->ev_poly_hdr) (void)hipEventDestroy(e->ev_poly_hdr);
+  if (e->h_poly_totals) (void)hipHostFree(e->h_poly_totals);
   if (e->h_sat_copy) (void)hipHostFree(e->h_sat_copy);
   if (e->ev_results) (void)hipEventDestroy(e->ev_results);
   if (e->ev_copied) (void)hipEventDestroy(e->ev_copied);
@@ -1593,6 +1601,97 @@ int rs_engine_fetch_crops_wait(rs_engine* e, rs_mask_crops* c) {
   c->used = used;
   if (used) RS_HIP(hipMemcpyAsync(c->data, e->crop_data, (size_t)used, hipMemcpyDeviceToHost, e->copy_stream));
   RS_HIP(hipStreamSynchronize(e->copy_stream));
+  e->sat_publish();
+  return RS_OK;
+}
+
+int rs_engine_fetch_polygons_async(rs_engine* e, int n, rs_dets* o, rs_polygons* g, double rdp_epsilon) {
+  RS_CHECK(e && o && o->count && g && g->header && g->poly_ring_count && g->ring_len && g->xy && n >= 1 && n <= e->max_batch, RS_ERR_ARG, "bad argument");
+  rs_mask_crops* c = g->crops;
+  RS_CHECK(c && c->rects && c->offsets && c->data, RS_ERR_ARG, "rs_polygons.crops is incomplete");
+  RS_CHECK(e->masks && e->crop_data, RS_ERR_ARG, "polygons requested but MASK_ON is false");
+  RS_CHECK(e->tile_h <= PG_MAX_SIDE && e->tile_w <= PG_MAX_SIDE, RS_ERR_UNSUPPORTED, "polygons on the device need tiles up to %d x %d", PG_MAX_SIDE, PG_MAX_SIDE);
+  const int D = e->D;
+  if (!e->copy_stream) {
+    RS_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
+    RS_HIP(hipEventCreateWithFlags(&e->ev_results, hipEventDisableTiming));
+    RS_HIP(hipEventCreateWithFlags(&e->ev_copied, hipEventDisableTiming));
+  }
+  if (!e->ev_crop_hdr) {
+    RS_HIP(hipEventCreateWithFlags(&e->ev_crop_hdr, hipEventDisableTiming));
+    RS_HIP(hipHostMalloc((void**)&e->h_crop_total, 16, hipHostMallocDefault));
+  }
+  if (!e->poly_ready) {
+    const int inst = e->max_batch * D;
+    size_t b_hdr, b_prc, b_rlen, b_xy;
+    polygonize_scratch_bytes(inst, &b_hdr, &b_prc, &b_rlen, &b_xy);
+    PolyParams& q = e->poly;
+    memset(&q, 0, sizeof q);
+    int rc;
+    if ((rc = e->alloc((void**)&q.s_hdr, b_hdr))) return rc;
+    if ((rc = e->alloc((void**)&q.s_prc, b_prc))) return rc;
+    if ((rc = e->alloc((void**)&q.s_rlen, b_rlen))) return rc;
+    if ((rc = e->alloc((void**)&q.s_xy, b_xy))) return rc;
+    if ((rc = e->alloc((void**)&q.header, (size_t)inst * PG_HDR * 4))) return rc;
+    if ((rc = e->alloc((void**)&q.poly_ring_count, (size_t)inst * PG_RING_CAP * 4))) return rc;
+    if ((rc = e->alloc((void**)&q.ring_len, (size_t)inst * PG_RING_CAP * 4))) return rc;
+    if ((rc = e->alloc((void**)&q.xy, (size_t)inst * PG_VERTEX_CAP * 4))) return rc;
+    if ((rc = e->alloc((void**)&q.totals, 16))) return rc;
+    RS_HIP(hipEventCreateWithFlags(&e->ev_poly_hdr, hipEventDisableTiming));
+    RS_HIP(hipHostMalloc((void**)&e->h_poly_totals, 16, hipHostMallocDefault));
+    e->poly_ready = true;
+  }
+  hipStream_t s = e->copy_stream;
+  RS_HIP(hipEventRecord(e->ev_results, e->stream));
+  RS_HIP(hipStreamWaitEvent(s, e->ev_results, 0));
+  CropParams cp;
+  memset(&cp, 0, sizeof cp);
+  cp.det_boxes = e->det_boxes; cp.det_count = e->det_count; cp.masks = e->masks; cp.n = n; cp.D = D; cp.h = e->tile_h; cp.w = e->tile_w;
+  cp.Wb = (e->tile_w + 7) / 8; cp.rects = e->crop_rects; cp.offsets = e->crop_offsets; cp.total = e->crop_total; cp.data = e->crop_data;
+  { int rc = launch_mask_crops(cp, s); if (rc) return rc; }
+  PolyParams pp = e->poly;
+  pp.masks = e->masks; pp.rects = e->crop_rects; pp.det_count = e->det_count; pp.instances = n * D; pp.D = D; pp.h = e->tile_h; pp.w = e->tile_w;
+  pp.Wb = cp.Wb; pp.eps = rdp_epsilon; pp.edge_cap = PG_EDGE_CAP; pp.vertex_cap = PG_VERTEX_CAP;
+  { int rc = launch_polygonize(pp, s); if (rc) return rc; }
+  RS_HIP(hipMemcpyAsync(o->count, e->det_count, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  if (o->boxes) RS_HIP(hipMemcpyAsync(o->boxes, e->det_boxes, (size_t)n * D * 16, hipMemcpyDeviceToHost, s));
+  if (o->scores) RS_HIP(hipMemcpyAsync(o->scores, e->det_scores, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
+  if (o->classes) RS_HIP(hipMemcpyAsync(o->classes, e->det_classes, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(c->rects, e->crop_rects, (size_t)n * D * 16, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(c->offsets, e->crop_offsets, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(e->h_crop_total, e->crop_total, 8, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(g->header, pp.header, (size_t)n * D * PG_HDR * 4, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(e->h_poly_totals, pp.totals, 16, hipMemcpyDeviceToHost, s));
+  { int rc = e->sat_copy(s); if (rc) return rc; }
+  RS_HIP(hipEventRecord(e->ev_copied, s));       // detections and canvases are free for the next forward: crops and polygons live in their own buffers
+  RS_HIP(hipEventRecord(e->ev_poly_hdr, s));
+  e->copy_pending = true;
+  return RS_OK;
+}
+
+int rs_engine_fetch_polygons_wait(rs_engine* e, rs_polygons* g) {
+  RS_CHECK(e && g && g->crops && g->crops->data && e->ev_poly_hdr, RS_ERR_ARG, "rs_engine_fetch_polygons_wait without rs_engine_fetch_polygons_async");
+  RS_HIP(hipEventSynchronize(e->ev_poly_hdr));
+  const int* t = e->h_poly_totals;
+  RS_CHECK((uint64_t)t[0] <= g->poly_cap && (uint64_t)t[1] <= g->ring_cap && (uint64_t)t[2] <= g->vertex_cap, RS_ERR_ARG,
+           "polygons need %d / %d / %d rows, the caller's buffers hold %llu / %llu / %llu", t[0], t[1], t[2], (unsigned long long)g->poly_cap,
+           (unsigned long long)g->ring_cap, (unsigned long long)g->vertex_cap);
+  g->n_polygons = (uint64_t)t[0]; g->n_rings = (uint64_t)t[1]; g->n_vertices = (uint64_t)t[2]; g->n_flagged = (uint64_t)t[3];
+  hipStream_t s = e->copy_stream;
+  if (t[0]) RS_HIP(hipMemcpyAsync(g->poly_ring_count, e->poly.poly_ring_count, (size_t)t[0] * 4, hipMemcpyDeviceToHost, s));
+  if (t[1]) RS_HIP(hipMemcpyAsync(g->ring_len, e->poly.ring_len, (size_t)t[1] * 4, hipMemcpyDeviceToHost, s));
+  if (t[2]) RS_HIP(hipMemcpyAsync(g->xy, e->poly.xy, (size_t)t[2] * 4, hipMemcpyDeviceToHost, s));
+  rs_mask_crops* c = g->crops;
+  g->masks_copied = 0;
+  c->used = 0;
+  if (t[3] > 0 || g->want_masks) {
+    const unsigned long long used = *e->h_crop_total;
+    RS_CHECK(used <= c->capacity, RS_ERR_ARG, "mask crops need %llu bytes, the caller's buffer holds %llu", used, (unsigned long long)c->capacity);
+    c->used = used;
+    if (used) RS_HIP(hipMemcpyAsync(c->data, e->crop_data, (size_t)used, hipMemcpyDeviceToHost, s));
+    g->masks_copied = 1;
+  }
+  RS_HIP(hipStreamSynchronize(s));
   e->sat_publish();
   return RS_OK;
 }

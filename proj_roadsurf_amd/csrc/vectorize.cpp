@@ -320,6 +320,49 @@ rs_vec_result* rs_vectorize_mask_crops(const uint8_t* data, const int32_t* rects
   return r;
 }
 
+// Device tables (csrc/polygonize.hip; include/rs_engine.h) -> rs_vec_result.  Flagged instances take their rows from `fallback`, which holds
+// exactly those instances in slot order, so a polygon reaches rs_vec_gpkg_blobs through the same structure whichever side traced it.
+rs_vec_result* rs_vec_from_tables(const int32_t* header, int n, const int32_t* poly_ring_count, const int32_t* ring_len, const int16_t* xy,
+                                  const rs_vec_result* fallback) {
+  if (n < 0 || (n > 0 && !header)) return nullptr;
+  rs_vec_result* r = new rs_vec_result();
+  size_t fi = 0, fp = 0, fr = 0, fv = 0;          // cursors into the fallback: instance, polygon, ring, vertex
+  bool ok = true;
+  for (int i = 0; i < n && ok; ++i) {
+    const int32_t* h = header + (size_t)i * RS_POLY_HDR;
+    if (h[0]) {
+      if (!fallback || fi >= fallback->inst_poly_count.size()) { ok = false; break; }
+      const int32_t np = fallback->inst_poly_count[fi++];
+      r->inst_poly_count.push_back(np);
+      for (int32_t q = 0; q < np; ++q) {
+        const int32_t nr = fallback->poly_ring_count[fp++];
+        r->poly_ring_count.push_back(nr);
+        for (int32_t k = 0; k < nr; ++k) {
+          const int32_t len = fallback->ring_len[fr++];
+          r->ring_len.push_back(len);
+          r->xy.insert(r->xy.end(), fallback->xy.begin() + 2 * fv, fallback->xy.begin() + 2 * (fv + len));
+          fv += (size_t)len;
+        }
+      }
+      continue;
+    }
+    const int32_t np = h[1], nr = h[2], nv = h[3];
+    if (np < 0 || nr < 0 || nv < 0 || ((np || nr || nv) && (!poly_ring_count || !ring_len || !xy))) { ok = false; break; }
+    r->inst_poly_count.push_back(np);
+    int64_t rings = 0, verts = 0;
+    for (int32_t q = 0; q < np; ++q) rings += poly_ring_count[h[4] + q];
+    for (int32_t k = 0; k < nr; ++k) verts += ring_len[h[5] + k];
+    if (rings != nr || verts != nv) { ok = false; break; }
+    r->poly_ring_count.insert(r->poly_ring_count.end(), poly_ring_count + h[4], poly_ring_count + h[4] + np);
+    r->ring_len.insert(r->ring_len.end(), ring_len + h[5], ring_len + h[5] + nr);
+    const int16_t* v = xy + 2 * (size_t)h[6];
+    for (int32_t k = 0; k < 2 * nv; ++k) r->xy.push_back((double)v[k]);
+  }
+  if (ok && fallback && fi != fallback->inst_poly_count.size()) ok = false;
+  if (!ok) { delete r; return nullptr; }
+  return r;
+}
+
 void rs_vec_counts(const rs_vec_result* r, int64_t* n_instances, int64_t* n_polygons, int64_t* n_rings, int64_t* n_vertices) {
   if (n_instances) *n_instances = r ? (int64_t)r->inst_poly_count.size() : 0;
   if (n_polygons) *n_polygons = r ? (int64_t)r->poly_ring_count.size() : 0;

@@ -85,6 +85,35 @@ class RsMaskCrops(C.Structure):
                 ("capacity", C.c_uint64), ("used", C.c_uint64)]
 
 
+class RsPolygons(C.Structure):
+    _fields_ = [("header", C.POINTER(C.c_int32)), ("poly_ring_count", C.POINTER(C.c_int32)), ("ring_len", C.POINTER(C.c_int32)),
+                ("xy", C.POINTER(C.c_int16)), ("poly_cap", C.c_uint64), ("ring_cap", C.c_uint64), ("vertex_cap", C.c_uint64),
+                ("n_polygons", C.c_uint64), ("n_rings", C.c_uint64), ("n_vertices", C.c_uint64), ("n_flagged", C.c_uint64),
+                ("crops", C.POINTER(RsMaskCrops)), ("want_masks", C.c_int32), ("masks_copied", C.c_int32)]
+
+
+POLY_HDR = 8       # RS_POLY_HDR: flagged, polygons, rings, vertices, first polygon, first ring, first vertex, 0
+
+
+class PolygonTables:
+    """Polygons of the instances of one tile as the device polygoniser leaves them (include/rs_engine.h, ``rs_op_polygonize``):
+    ``header`` (n, 8) int32 per instance [flagged, polygons, rings, vertices, first polygon, first ring, first vertex, 0] with the
+    offsets pointing into ``poly_ring_count`` / ``ring_len`` / ``xy`` ((nv, 2) int16, tile pixels); ``rdp_epsilon`` is the tolerance
+    they were simplified with (0.0 = not simplified).  A flagged instance has no rows here: its mask exceeded the kernel's
+    capacities and is vectorised on the host from its crop (``proj_roadsurf_amd.vectorize``)."""
+
+    def __init__(self, header: np.ndarray, poly_ring_count: np.ndarray, ring_len: np.ndarray, xy: np.ndarray, rdp_epsilon: float):
+        self.header = np.ascontiguousarray(header, np.int32).reshape(-1, POLY_HDR)
+        self.poly_ring_count = np.ascontiguousarray(poly_ring_count, np.int32)
+        self.ring_len = np.ascontiguousarray(ring_len, np.int32)
+        self.xy = np.ascontiguousarray(xy, np.int16).reshape(-1, 2)
+        self.rdp_epsilon = max(float(rdp_epsilon), 0.0)
+
+    @property
+    def flagged(self) -> np.ndarray:
+        return np.nonzero(self.header[:, 0])[0]
+
+
 def load_library(path: Optional[str] = None) -> C.CDLL:
     """Load librs_engine.so (built in-tree by ``__graft_entry__.build()`` / csrc/Makefile)."""
     global _LIB
@@ -122,6 +151,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.rs_engine_fetch_wait.argtypes = [vp]
     lib.rs_engine_fetch_crops_async.argtypes = [vp, i32, C.POINTER(RsDets), C.POINTER(RsMaskCrops)]
     lib.rs_engine_fetch_crops_wait.argtypes = [vp, C.POINTER(RsMaskCrops)]
+    lib.rs_engine_fetch_polygons_async.argtypes = [vp, i32, C.POINTER(RsDets), C.POINTER(RsPolygons), C.c_double]
+    lib.rs_engine_fetch_polygons_wait.argtypes = [vp, C.POINTER(RsPolygons)]
     lib.rs_engine_fetch.argtypes = [vp, i32, C.POINTER(RsDets)]
     lib.rs_engine_stream.argtypes = [vp]
     lib.rs_engine_stream.restype = vp
@@ -172,6 +203,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.rs_vec_copy.argtypes = [vp, i32p, i32p, i32p, f64p]
     lib.rs_vec_free.argtypes = [vp]
     lib.rs_vec_free.restype = None
+    lib.rs_vectorize_mask_crops.argtypes = [vp, vp, vp, i32, i32, i32, C.c_double, i32]
+    lib.rs_vectorize_mask_crops.restype = vp
+    lib.rs_vec_from_tables.argtypes = [vp, i32, vp, vp, vp, vp]
+    lib.rs_vec_from_tables.restype = vp
+    lib.rs_polygonize_caps.argtypes = [i32p, i32p, i32p, i32p]
+    lib.rs_polygonize_caps.restype = None
+    lib.rs_op_polygonize.argtypes = [vp, i32, i32, i32, C.c_double, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.rs_rasterize_polygons_within_box.argtypes = [f64p, i32p, i32, f64p, i32, u8p]
     lib.rs_memcpy_d2h.argtypes = [vp, vp, C.c_size_t]
     lib.rs_op_fdiv.argtypes = [vp, vp, vp, C.c_int64, vp]
@@ -261,7 +299,7 @@ class Instances:
 
     def __init__(self, image_size: Tuple[int, int], pred_boxes: np.ndarray, scores: np.ndarray, pred_classes: np.ndarray,
                  packed_masks: Optional[np.ndarray], mask_probs: Optional[np.ndarray],
-                 crops: Optional[Tuple[np.ndarray, np.ndarray, np.ndarray]] = None):
+                 crops: Optional[Tuple[np.ndarray, np.ndarray, np.ndarray]] = None, polygons: Optional[PolygonTables] = None):
         self.image_size = image_size
         self.pred_boxes = pred_boxes
         self.scores = scores
@@ -271,6 +309,9 @@ class Instances:
         # masks as crops of their boxes (rs_mask_crops): (rects (n,4) int32 [first byte column, first row, bytes per row, rows],
         # offsets (n,) uint32 into data, data uint8); the full canvases are rebuilt on demand
         self._crops = crops
+        # polygons traced on the device (Engine.fetch_async(polygons=True)) with the epsilon they were simplified with; masks come
+        # along only when the caller asked for them or an instance of the batch was left to the host vectoriser
+        self._polygons = polygons
 
     @property
     def _packed(self) -> Optional[np.ndarray]:
@@ -418,6 +459,11 @@ class Engine:
         self._crop_data: Optional[np.ndarray] = None
         self._crops_struct: Optional[RsMaskCrops] = None
         self._crops_pending = False
+        # polygons (rs_engine_fetch_polygons_*): pinned tables, allocated on the first polygon fetch
+        self._poly_struct: Optional[RsPolygons] = None
+        self._poly_pending = False
+        self._poly_landed = False
+        self._poly_eps = 0.0
 
     def _dets_struct(self, want_probs: bool) -> RsDets:
         d = RsDets()
@@ -431,11 +477,28 @@ class Engine:
                 d.mask_probs = self._probs.ctypes.data_as(C.POINTER(C.c_float))
         return d
 
-    def _collect(self, n: int, want_probs: bool, crops: bool = False) -> List[Instances]:
+    def _collect(self, n: int, want_probs: bool, crops: bool = False, polygons: bool = False) -> List[Instances]:
         out = []
-        if crops:
+        if polygons:
+            crops = bool(self._poly_struct.masks_copied)
+        if crops or polygons:
             for i in range(n):
                 c = int(self._count[i])
+                tables = None
+                if polygons:
+                    hdr = self._poly_header[i, :c].copy()
+                    if c:
+                        lo = hdr[0, 4:7].copy()
+                        hi = hdr[c - 1, 4:7] + hdr[c - 1, 1:4]
+                        hdr[:, 4:7] -= lo
+                    else:
+                        lo = hi = np.zeros(3, np.int32)
+                    tables = PolygonTables(hdr, self._poly_prc[lo[0]:hi[0]].copy(), self._poly_rlen[lo[1]:hi[1]].copy(),
+                                           self._poly_xy[lo[2]:hi[2]].copy(), self._poly_eps)
+                if not crops:
+                    out.append(Instances((self.tile_h, self.tile_w), self._boxes[i, :c].copy(), self._scores[i, :c].copy(),
+                                         self._classes[i, :c].astype(np.int64), None, None, polygons=tables))
+                    continue
                 rects = self._crop_rects[i, :c].copy()
                 offs = self._crop_offsets[i, :c].astype(np.int64)
                 if c:
@@ -446,7 +509,7 @@ class Engine:
                 else:
                     data, offs = np.zeros(0, np.uint8), np.zeros(0, np.uint32)
                 out.append(Instances((self.tile_h, self.tile_w), self._boxes[i, :c].copy(), self._scores[i, :c].copy(),
-                                     self._classes[i, :c].astype(np.int64), None, None, crops=(rects, offs, data)))
+                                     self._classes[i, :c].astype(np.int64), None, None, crops=(rects, offs, data), polygons=tables))
             return out
         for i in range(n):
             c = int(self._count[i])
@@ -485,30 +548,66 @@ class Engine:
         _check(self.lib, self.lib.rs_engine_upload_async(self._h, self._stage_tiles.ctypes.data_as(C.c_void_p), n), "rs_engine_upload_async")
         return self.tensor_ptr("tiles")[0]
 
-    def fetch_async(self, n: int, crops: bool = True) -> None:
+    def _crops_buffers(self) -> RsMaskCrops:
+        if self._crop_data is None:
+            self._crop_data = self._pinned((self.max_batch * self.D * self.tile_h * ((self.tile_w + 7) // 8),), np.uint8)
+            c = RsMaskCrops()
+            c.rects = self._crop_rects.ctypes.data_as(C.POINTER(C.c_int32))
+            c.offsets = self._crop_offsets.ctypes.data_as(C.POINTER(C.c_uint32))
+            c.data = self._crop_data.ctypes.data_as(C.POINTER(C.c_uint8))
+            c.capacity = self._crop_data.nbytes
+            self._crops_struct = c
+        return self._crops_struct
+
+    def fetch_async(self, n: int, crops: bool = True, polygons: bool = False, rdp_epsilon: float = 0.75, masks: bool = False) -> None:
         """Enqueue the copy of the last forward's results to the host behind it.  ``crops`` (default, with MASK_ON): the masks
         travel as crops of their boxes (``rs_mask_crops``) instead of full canvases -- 100 x h x w/8 bytes per tile shrink to
-        the boxes' area, on the PCIe link and in the host-side copies."""
+        the boxes' area, on the PCIe link and in the host-side copies.  ``polygons``: the masks are polygonised and simplified
+        (``rdp_epsilon`` in pixels, <= 0: not simplified) on the device (csrc/polygonize.hip) and only the polygon tables come
+        back; the ``Instances`` carry them (and the epsilon), and carry masks only with ``masks=True`` or when an instance of
+        the batch exceeded the kernel's capacities and is left to the host vectoriser."""
         d = self._dets_struct(False)
-        if crops and self._masks is not None:
-            if self._crop_data is None:
-                self._crop_data = self._pinned((self.max_batch * self.D * self.tile_h * ((self.tile_w + 7) // 8),), np.uint8)
-                c = RsMaskCrops()
-                c.rects = self._crop_rects.ctypes.data_as(C.POINTER(C.c_int32))
-                c.offsets = self._crop_offsets.ctypes.data_as(C.POINTER(C.c_uint32))
-                c.data = self._crop_data.ctypes.data_as(C.POINTER(C.c_uint8))
-                c.capacity = self._crop_data.nbytes
-                self._crops_struct = c
+        if polygons:
+            if self._masks is None:
+                raise RsError("polygons requested but MASK_ON is false")
+            if self._poly_struct is None:
+                caps = [C.c_int32() for _ in range(4)]
+                self.lib.rs_polygonize_caps(*[C.byref(x) for x in caps])
+                inst = self.max_batch * self.D
+                self._poly_header = self._pinned((self.max_batch, self.D, POLY_HDR), np.int32)
+                self._poly_prc = self._pinned((inst * caps[2].value,), np.int32)
+                self._poly_rlen = self._pinned((inst * caps[2].value,), np.int32)
+                self._poly_xy = self._pinned((inst * caps[1].value, 2), np.int16)
+                g = RsPolygons()
+                g.header = self._poly_header.ctypes.data_as(C.POINTER(C.c_int32))
+                g.poly_ring_count = self._poly_prc.ctypes.data_as(C.POINTER(C.c_int32))
+                g.ring_len = self._poly_rlen.ctypes.data_as(C.POINTER(C.c_int32))
+                g.xy = self._poly_xy.ctypes.data_as(C.POINTER(C.c_int16))
+                g.poly_cap, g.ring_cap, g.vertex_cap = self._poly_prc.size, self._poly_rlen.size, self._poly_xy.shape[0]
+                g.crops = C.pointer(self._crops_buffers())
+                self._poly_struct = g
+            self._poly_struct.want_masks = int(bool(masks))
+            self._poly_eps = max(float(rdp_epsilon), 0.0)
             d.masks = None
-            _check(self.lib, self.lib.rs_engine_fetch_crops_async(self._h, n, C.byref(d), C.byref(self._crops_struct)), "rs_engine_fetch_crops_async")
+            _check(self.lib, self.lib.rs_engine_fetch_polygons_async(self._h, n, C.byref(d), C.byref(self._poly_struct), float(rdp_epsilon)),
+                   "rs_engine_fetch_polygons_async")
+            self._poly_pending = True
+            return
+        if crops and self._masks is not None:
+            d.masks = None
+            _check(self.lib, self.lib.rs_engine_fetch_crops_async(self._h, n, C.byref(d), C.byref(self._crops_buffers())), "rs_engine_fetch_crops_async")
             self._crops_pending = True
             return
         _check(self.lib, self.lib.rs_engine_fetch_async(self._h, n, C.byref(d)), "rs_engine_fetch_async")
 
     def wait_results(self) -> None:
         """Block until the copies of the last ``fetch_async`` have landed (for crops: wait for the crop table, copy exactly the
-        bytes in use, wait for them)."""
-        if self._crops_pending:
+        bytes in use, wait for them; for polygons the same with the polygon headers and rows)."""
+        self._poly_landed = False
+        if self._poly_pending:
+            _check(self.lib, self.lib.rs_engine_fetch_polygons_wait(self._h, C.byref(self._poly_struct)), "rs_engine_fetch_polygons_wait")
+            self._poly_pending, self._poly_landed, self._crops_landed = False, True, False
+        elif self._crops_pending:
             _check(self.lib, self.lib.rs_engine_fetch_crops_wait(self._h, C.byref(self._crops_struct)), "rs_engine_fetch_crops_wait")
             self._crops_pending, self._crops_landed = False, True
         else:
@@ -517,7 +616,7 @@ class Engine:
 
     def collect_results(self, n: int) -> List[Instances]:
         """``Instances`` of the results ``wait_results`` waited for (copies out of the pinned buffers)."""
-        return self._collect(n, False, crops=getattr(self, "_crops_landed", False))
+        return self._collect(n, False, crops=getattr(self, "_crops_landed", False), polygons=self._poly_landed)
 
     def fetch_wait(self, n: int) -> List[Instances]:
         self.wait_results()
@@ -665,6 +764,9 @@ class Engine:
             pass
 
 
+VECTORIZE_MODES = ("host", "device")
+
+
 class LanePipeline:
     """Several engines ("lanes") fed alternately so that consecutive batches overlap on one GPU.  The reference processes one tile at a time
     and has no counterpart ([EXT d2: engine/defaults.py]).  Two forms:
@@ -686,9 +788,14 @@ class LanePipeline:
       Results of batch k are complete once phase2(k) has run, i.e. after ``submit`` of batch k+1 or ``flush``."""
 
     def __init__(self, spec: EngineSpec, weights: Dict[str, np.ndarray], tile_shape: Tuple[int, int, int], max_batch: int = 16,
-                 device: int = 0, lanes: int = 2, shared_stream: bool = False):
+                 device: int = 0, lanes: int = 2, shared_stream: bool = False, vectorize: str = "host", rdp_epsilon: float = 0.75):
         if lanes not in (1, 2, 3, 4):
             raise ValueError("lanes must be 1..4")
+        if vectorize not in VECTORIZE_MODES:
+            raise ValueError(f"vectorize must be one of {VECTORIZE_MODES}, got {vectorize!r}")
+        # "device": ``run`` fetches polygons traced and simplified on the GPU (Engine.fetch_async(polygons=True)) instead of mask crops;
+        # ``want_masks`` makes those batches bring their masks too
+        self.vectorize, self.rdp_epsilon, self.want_masks = vectorize, float(rdp_epsilon), False
         blob = pack_weights(spec, weights)           # folding + fragment orders once, not once per lane (0.3 s of host time each)
         self.shared = bool(shared_stream) and lanes > 1
         first = Engine(spec, weights, tile_shape, max_batch, device, blob=blob)
@@ -698,6 +805,12 @@ class LanePipeline:
         self._pending: Optional[Tuple[int, int, int]] = None     # shared form: (lane, tiles ptr, n) whose phase 2 is still to be enqueued
         # saturation counts (Engine.saturation) of the batch ``run`` yielded last: set before the batch is yielded
         self.last_saturation: Dict[str, int] = {}
+
+    def _fetch_async(self, e: Engine, n: int) -> None:
+        if self.vectorize == "device" and e.spec.mask_on:
+            e.fetch_async(n, polygons=True, rdp_epsilon=self.rdp_epsilon, masks=self.want_masks)
+        else:
+            e.fetch_async(n)
 
     def lane_of_next(self) -> Engine:
         return self.engines[self.k % len(self.engines)]
@@ -756,7 +869,7 @@ class LanePipeline:
             self.k += 1
             if L == 1:                              # one lane has one set of host buffers: no look-ahead
                 e.infer_device(e.upload_async(np.ascontiguousarray(tiles)), n)
-                e.fetch_async(n)
+                self._fetch_async(e, n)
                 yield counted(e, e.fetch_wait(n))
                 continue
             done = None
@@ -781,7 +894,7 @@ class LanePipeline:
                     res = counted(self.engines[done[0]], self.engines[done[0]].collect_results(done[1]))
                     T["collect"] += clock() - t0
                 t1 = clock()
-                e.fetch_async(n)
+                self._fetch_async(e, n)
                 T["enqueue"] += clock() - t1
                 inflight.append((lane, n))
                 if res is not None:
@@ -791,7 +904,7 @@ class LanePipeline:
             if self._pending is not None:
                 pl, pp, pn = self._pending
                 self.engines[pl].infer_phase(pp, pn, 2)
-                self.engines[pl].fetch_async(pn)
+                self._fetch_async(self.engines[pl], pn)
                 self._pending = None
             e.infer_phase(ptr, n, 1)
             T["enqueue"] += clock() - t1
@@ -805,7 +918,7 @@ class LanePipeline:
         if self._pending is not None:
             pl, pp, pn = self._pending
             self.engines[pl].infer_phase(pp, pn, 2)
-            self.engines[pl].fetch_async(pn)
+            self._fetch_async(self.engines[pl], pn)
             self._pending = None
         for ol, on in inflight:
             yield counted(self.engines[ol], self.engines[ol].fetch_wait(on))
@@ -831,9 +944,14 @@ class Predictor:
     the image of ``__call__``, the whole ``predict_batch`` call (summed over its batches), the batch ``predict_stream`` yielded."""
 
     def __init__(self, spec: EngineSpec, weights: Dict[str, np.ndarray], max_batch: int = 16, device: int = 0, lanes: int = 2,
-                 on_saturation: str = "warn"):
+                 on_saturation: str = "warn", vectorize: str = "host", rdp_epsilon: float = 0.75):
         if on_saturation not in ("warn", "raise", "ignore"):
             raise ValueError(f"on_saturation must be 'warn', 'raise' or 'ignore', got {on_saturation!r}")
+        if vectorize not in VECTORIZE_MODES:
+            raise ValueError(f"vectorize must be one of {VECTORIZE_MODES}, got {vectorize!r}")
+        # "device": the streaming forms (predict_batch, predict_stream) return Instances that carry polygons made on the GPU with
+        # ``rdp_epsilon`` (<= 0: not simplified) and no masks; ``__call__`` always returns masks
+        self.vectorize, self.rdp_epsilon = vectorize, float(rdp_epsilon)
         self.spec, self.weights, self.max_batch, self.device, self.lanes = spec, weights, max_batch, device, lanes
         self.on_saturation = on_saturation
         self.last_saturation: Dict[str, int] = {}
@@ -851,7 +969,8 @@ class Predictor:
 
     def _pipe(self, shape: Tuple[int, int, int]) -> LanePipeline:
         if shape not in self._pipes:
-            self._pipes[shape] = LanePipeline(self.spec, self.weights, shape, self.max_batch, self.device, self.lanes)
+            self._pipes[shape] = LanePipeline(self.spec, self.weights, shape, self.max_batch, self.device, self.lanes,
+                                              vectorize=self.vectorize, rdp_epsilon=self.rdp_epsilon)
         return self._pipes[shape]
 
     def prepare(self, shape: Tuple[int, int, int], warm: bool = True) -> None:

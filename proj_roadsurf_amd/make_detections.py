@@ -113,6 +113,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--decode-procs", type=int, default=None,
                     help="worker PROCESSES that decode tiles into shared memory (decode_pool.DecodePool); 0 = decode on the --host-workers threads (default: as --host-workers)")
     ap.add_argument("--vector-threads", type=int, default=None, help="threads inside one rs_vectorize_masks call (default: as --host-workers)")
+    ap.add_argument("--vectorize", choices=("host", "device"), default="host",
+                    help="where detection masks become polygons: 'host' = csrc/vectorize.cpp on the vectoriser threads (masks cross PCIe as crops); "
+                         "'device' = csrc/polygonize.hip behind the forward, only polygon tables come back, and only instances beyond the kernel's "
+                         "capacities are vectorised on the host (same polygons either way; DESIGN.md 3.7)")
     ap.add_argument("--precision", choices=("fp16", "split", "fp32"), default="fp16",
                     help="fp16: fp16 operands / fp32 accumulate on the matrix cores (fastest; meets the SURVEY 8d tolerance on a trained detector); "
                          "split: the reference's fp32 results on the fp16 matrix cores -- every operand as hi + lo fp16 planes, three products, about 2.7x "
@@ -178,7 +182,17 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                                  "torchvision": "torchvision (size rule: shifted coordinates at <= 1000 boxes per image)"}[spec.batched_nms])
     from .engine import Predictor      # fails loudly without librs_engine.so / a HIP device
     # saturation (activations clamped to the fp16 range) is reported once per dataset below, not per batch
-    predictor = Predictor(spec, W, max_batch=args.batch, device=local_rank, lanes=args.lanes, on_saturation="ignore")
+    # the epsilon the device polygoniser simplifies with is the YAML's, as on the host path (rdp_simplification: enabled / epsilon)
+    dev_eps = float(rdp_cfg.get("epsilon", 0.75)) if bool(rdp_cfg.get("enabled", False)) else 0.0
+    pred_kw = dict(max_batch=args.batch, device=local_rank, lanes=args.lanes, on_saturation="ignore", vectorize=args.vectorize, rdp_epsilon=dev_eps)
+    if args.vectorize == "device":
+        # polygons come back with the detections; the tagged previews below run their own forward (Predictor.__call__), which always
+        # returns masks, so no streamed batch has to bring masks along.  No vectoriser pool: the few instances the kernel leaves to
+        # the host are traced on the thread that finishes their batch.
+        args.vector_threads = 1
+        log.info("polygons on the device (rdp epsilon %s); the vectoriser threads are not started", dev_eps if dev_eps > 0 else "off")
+    predictor = Predictor(spec, W, **pred_kw)
+    fell_back = {"instances": 0, "of": 0}          # device mode: instances the polygoniser left to the host vectoriser
 
     class _Batch(list):       # one batch's results with the saturation counts of its forward, for finish()
         saturation: Dict[str, int] = {}
@@ -226,6 +240,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             ext, epsg_t = tile_extent(meta, e["file_name"])
             name = os.path.basename(e["file_name"])
             rdp_on, eps = bool(rdp_cfg.get("enabled", False)), float(rdp_cfg.get("epsilon", 0.75))
+            carried = getattr(o["instances"], "_polygons", None)
+            if carried is not None:
+                fell_back["instances"] += int(len(carried.flagged))
+                fell_back["of"] += len(o["instances"])
             rows, bbox = instances_to_gpkg_rows(o["instances"], name, ext, rdp_on, eps, srs_id=cur_srs["id"], threads=args.vector_threads)
             feats = instances_to_features(o["instances"], name, ext, rdp_on, eps, threads=args.vector_threads) if args.geojson else None
             res.append((rows, bbox, feats))
@@ -287,7 +305,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 log.warning("%s: %s -- running the dataset again with thread decoding", dataset, ex)
                 predictor.close()
                 saturated.clear()
-                predictor = Predictor(spec, W, max_batch=args.batch, device=local_rank, lanes=args.lanes, on_saturation="ignore")
+                predictor = Predictor(spec, W, **pred_kw)
+                fell_back.update(instances=0, of=0)
                 per_tile = run_sharded(images, predict_batch, args.batch, rank, world, gather=False, prepare=prepare, finish=finish,
                                        workers=args.host_workers, predict_stream=predict_stream, prepared_source=None)
         except BaseException:
@@ -343,8 +362,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             with open(base + ".geojson", "w") as f:
                 f.write(json.dumps({"type": "FeatureCollection", "features": feats}))   # dumps() = C encoder; dump() streams through the slow Python one
         dt = time.time() - t0
-        log.info("%s: %d tiles -> %d features in %.1f s (%.1f tiles/s) -> %s.gpkg", dataset, len(images), n, dt,
-                 len(images) / max(dt, 1e-9), base)
+        if args.vectorize == "device":
+            log.info("%s: %d tiles -> %d features in %.1f s (%.1f tiles/s) -> %s.gpkg; %d of %d instances fell back to the host vectoriser",
+                     dataset, len(images), n, dt, len(images) / max(dt, 1e-9), base, fell_back["instances"], fell_back["of"])
+            fell_back.update(instances=0, of=0)
+        else:
+            log.info("%s: %d tiles -> %d features in %.1f s (%.1f tiles/s) -> %s.gpkg", dataset, len(images), n, dt,
+                     len(images) / max(dt, 1e-9), base)
         log.info("%s: stage busy time (summed over threads) decode %.2f s, predict %.2f s, vectorise %.2f s, write %.2f s",
                  dataset, busy["decode"], busy["predict"], busy["vectorise"], dt_write)
         for shp, pl in getattr(predictor, "_pipes", {}).items():

@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--train-steps", type=int, default=300)
     ap.add_argument("--precision", choices=["fp16", "split", "fp32"], default="fp16", help="make_detections --precision")
     ap.add_argument("--lanes", type=int, default=2)
+    ap.add_argument("--vectorize", choices=["host", "device"], default="host", help="make_detections --vectorize")
     args = ap.parse_args()
     import yaml
     from PIL import Image
@@ -70,11 +71,12 @@ def main():
         t0 = time.time()
         rc = make_detections.main([os.path.join(td, "config.yaml"), *extra, "--batch", str(args.batch),
                                    "--host-workers", str(args.host_workers), "--vector-threads", str(args.vector_threads),
-                                   "--decode-procs", str(args.decode_procs), "--precision", args.precision, "--lanes", str(args.lanes)])
+                                   "--decode-procs", str(args.decode_procs), "--precision", args.precision, "--lanes", str(args.lanes),
+                                   "--vectorize", args.vectorize])
         dt = time.time() - t0
         os.chdir(cwd)
         size = os.path.getsize(os.path.join(wd, "oth_detections_at_0dot05_threshold.gpkg"))
-    print(json.dumps({"cli_tiles": args.tiles, "weights": args.weights, "precision": args.precision, "seconds_total_incl_engine_build": dt, "rc": rc, "gpkg_bytes": size}))
+    print(json.dumps({"cli_tiles": args.tiles, "weights": args.weights, "precision": args.precision, "vectorize": args.vectorize, "seconds_total_incl_engine_build": dt, "rc": rc, "gpkg_bytes": size}))
 
 
 if __name__ == "__main__":
