@@ -458,6 +458,22 @@ int rs_trainer_mask_backward(rs_trainer* t, int n, const uint8_t* targets_host, 
  * [n][1024], counts [n][2] (foreground, total).  Waits for the sampling only (own copy stream, event recorded in roi_step): the
  * box head and an already enqueued rs_trainer_mask_forward keep running while the host rasterises. */
 int rs_trainer_fetch_rois(rs_trainer* t, int n, float* boxes_host, int32_t* gt_index_host, int32_t* counts_host);
+/* Mask targets rasterised on the device (opt-in; the host path above is untouched).  rs_trainer_set_polygons, after
+ * rs_trainer_set_targets, packs the ground-truth polygons of the batch into pinned staging and uploads them on the trainer's stream
+ * (no host wait): the flat layout of rs_rasterize_entries -- polygon q = poly_len[q] doubles at polys + poly_off[q], instance g owns
+ * polygons inst_first[g] .. inst_first[g+1]-1 -- plus image_first[n + 1], the first instance of every image (gt j of image i is
+ * instance image_first[i] + j); coordinates in network-input pixels.  The device pool holds, for a trainer of batch capacity N, at
+ * most N * 512 polygons and N * 65536 doubles (32768 vertices per image on average): a batch beyond it returns
+ * RS_POLYGONS_DO_NOT_FIT (positive, not an error: nothing was copied, the trainer is as before, run this step through
+ * rs_trainer_fetch_rois + rs_trainer_mask_backward).  rs_trainer_mask_backward_device replaces rs_trainer_mask_backward: it
+ * rasterises entry e (the order of "mask_slots") from "roi_boxes" / "roi_gt_index" into the tensor "mask_targets" [N*256][28][28]
+ * on the chain stream -- the same bytes the host path uploads; a gt index outside the image's instances gives an all-zero mask --
+ * and runs the loss and the backward, with no read-back, host wait or upload.  RS_ERR_ARG when no polygons were set since the last
+ * rs_trainer_set_targets.  The stage "mask.targets" is listed by rs_trainer_stage_info once the pool exists. */
+#define RS_POLYGONS_DO_NOT_FIT 1
+int rs_trainer_set_polygons(rs_trainer* t, const double* polys, const int64_t* poly_off, const int32_t* poly_len, const int32_t* inst_first,
+                            const int32_t* image_first, int n);
+int rs_trainer_mask_backward_device(rs_trainer* t, int n);
 int rs_trainer_set_rpn_topk(rs_trainer* t, int pre_nms_topk_train, int post_nms_topk_train);
 /* Sampler sizes (defaults = the reference YAML: 256 @ 0.5 anchors, 1024 @ 0.25 RoIs per image). */
 int rs_trainer_set_sampling(rs_trainer* t, int rpn_batch, float rpn_positive_fraction, int roi_batch, float roi_positive_fraction);
@@ -603,6 +619,13 @@ int rs_rasterize_polygons_within_box(const double* polys, const int32_t* poly_le
  * entry e rasterises instance entry_inst[e] inside boxes[e] (x1,y1,x2,y2 as read back from "roi_boxes") -> out[e][S*S]. */
 int rs_rasterize_entries(const double* polys, const int64_t* poly_off, const int32_t* poly_len, const int32_t* inst_first, int n_inst,
                          const int32_t* entry_inst, const float* boxes, int n_entries, int mask_size, uint8_t* out, int threads);
+
+/* rs_rasterize_entries on the GPU (mask_targets_kernel, the kernel behind rs_trainer_mask_backward_device): same arguments (host
+ * pointers) without `threads`, same bytes out.  Uploads the polygons, rasterises the n_entries (instance, box) pairs, one workgroup
+ * each, and copies the masks back.  mask_size even, up to RS_MASK_SIDE.  Unlike the host call, an entry whose instance is outside
+ * [0, n_inst) is not an error: its mask is all zero. */
+int rs_op_mask_targets(const double* polys, const int64_t* poly_off, const int32_t* poly_len, const int32_t* inst_first, int n_inst,
+                       const int32_t* entry_inst, const float* boxes, int n_entries, int mask_size, uint8_t* out);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,16 @@
 // Training-path kernels (train_kernels.hip): parameter blocks and launchers.
 #pragma once
 #include "common.h"
+#include "mask_targets.h"
 
+// Optional scratch of a loss kernel: with it the logged loss is summed in a fixed order (one slot per workgroup, the last workgroup adds
+// them) instead of one float atomic per wave, so that two runs of a step report the same bits.  Null partial = the atomics.  One
+// scratch per stream of launches: the counter is left at 0 by every launch.
+struct LossScratch {
+  float* partial;           // [2][cap]
+  unsigned int* counter;    // [1], zero before the launch
+  int cap;                  // workgroups a launch may have
+};
 struct RpnLossParams {
   const float* head;        // one level's fused RPN head output [N][HW][cs] fp32: [0,A) logits, [A,5A) deltas
   half_t* dhead;            // gradient, same layout, fp16 (times loss_scale)
@@ -15,6 +24,7 @@ struct RpnLossParams {
   float normalizer;         // BATCH_SIZE_PER_IMAGE * N
   float loss_scale;
   int d32;                  // 1: dhead points to fp32 (reference-precision trainer)
+  LossScratch scratch;
 };
 struct BoxLossParams {
   const float* pred;        // [n_rois][cs] fp32: [0,K] logits (K = background), then 4K deltas
@@ -30,6 +40,7 @@ struct BoxLossParams {
   float wx, wy, ww, wh;
   float loss_scale;
   int d32;                  // 1: dpred points to fp32
+  LossScratch scratch;
 };
 struct MaskLossParams {
   const float* logits;      // [n_masks][S*S][cs] fp32, channel = class
@@ -41,6 +52,7 @@ struct MaskLossParams {
   int n_masks, S, cs, dcs;  // dcs: row stride of dlogits (0 = cs)
   float loss_scale;
   int d32;                  // 1: dlogits points to fp32
+  LossScratch scratch;
 };
 int launch_rpn_loss(const RpnLossParams& p, int N, hipStream_t s);
 int launch_box_loss(const BoxLossParams& p, hipStream_t s);
@@ -128,3 +140,22 @@ struct MaskEntriesParams {
   int N, slots_per_image, per_image_cap, cap;
 };
 int launch_mask_entries(const MaskEntriesParams& p, hipStream_t s);
+
+// ground-truth masks of the mask-head entries on the device (mask_targets.h): one workgroup per entry.
+// Trainer form (slots != null): entry e < *total is slot slots[e] of the sampled RoI list -- box boxes[slot], instance
+// image_first[slot / slots_per_image] + gt_index[slot].  Explicit form (slots == null): entry e is instance gt_index[e] of n_inst
+// inside boxes[e].  An instance index outside its range gives an all-zero mask and reads no polygon.
+struct MaskTargetsParams {
+  const float* boxes;       // [..][4] x1, y1, x2, y2
+  const int* gt_index;
+  const int* slots;         // [n_entries] or null
+  const int* total;         // [1] device entry count (trainer form)
+  const int* image_first;   // [images + 1] first instance of every image (trainer form)
+  const double* polys;      // polygon pool: polygon q = poly_len[q] doubles (x0, y0, x1, y1, ...) at polys + poly_off[q]
+  const int* poly_off;
+  const int* poly_len;
+  const int* inst_first;    // [instances + 1] first polygon of every instance
+  uint8_t* out;             // [n_entries][S*S] 0/1, row-major, 4-byte aligned
+  int n_entries, n_inst, slots_per_image, S;
+};
+int launch_mask_targets(const MaskTargetsParams& p, hipStream_t s);

@@ -28,6 +28,45 @@ struct TrainLayer {
   int bias_tile = 1;             // forward bias = master bias repeated this many times (the 2x2 deconv as 4 GEMMs)
 };
 
+// Polygon pool of the device mask targets, one contiguous block (one upload): int32 image_first[n_img + 1] | inst_first[n_inst + 1] |
+// poly_off[n_poly] | poly_len[n_poly] | padding to 8 bytes | double xy[n_doubles].  poly_off counts doubles inside xy (the polygons are
+// packed back to back in polygon order, whatever the caller's offsets were).
+struct MtLayout {
+  int n_img = 0, n_inst = 0, n_poly = 0;
+  size_t n_doubles = 0, o_inst = 0, o_off = 0, o_len = 0, o_xy = 0, bytes = 0;
+};
+int mt_measure(const double* polys, const int64_t* poly_off, const int32_t* poly_len, const int32_t* inst_first, int n_inst, int n_img, MtLayout* L) {
+  RS_CHECK(inst_first && n_inst >= 0 && inst_first[0] == 0, RS_ERR_ARG, "polygons: inst_first must start at 0");
+  for (int g = 0; g < n_inst; ++g) RS_CHECK(inst_first[g + 1] >= inst_first[g], RS_ERR_ARG, "polygons: inst_first decreases at instance %d", g);
+  L->n_img = n_img; L->n_inst = n_inst; L->n_poly = inst_first[n_inst];
+  RS_CHECK(L->n_poly == 0 || (polys && poly_off && poly_len), RS_ERR_ARG, "polygons: null table");
+  L->n_doubles = 0;
+  for (int q = 0; q < L->n_poly; ++q) {
+    RS_CHECK(poly_len[q] >= 2 && !(poly_len[q] & 1) && poly_off[q] >= 0, RS_ERR_ARG, "polygon %d: %d doubles at offset %lld", q, poly_len[q], (long long)poly_off[q]);
+    L->n_doubles += (size_t)poly_len[q];
+  }
+  L->o_inst = 4 * ((size_t)n_img + 1);
+  L->o_off = L->o_inst + 4 * ((size_t)n_inst + 1);
+  L->o_len = L->o_off + 4 * (size_t)L->n_poly;
+  L->o_xy = (L->o_len + 4 * (size_t)L->n_poly + 7) & ~(size_t)7;
+  L->bytes = L->o_xy + 8 * L->n_doubles;
+  return RS_OK;
+}
+void mt_pack(uint8_t* dst, const MtLayout& L, const double* polys, const int64_t* poly_off, const int32_t* poly_len, const int32_t* inst_first,
+             const int32_t* image_first) {
+  memcpy(dst, image_first, 4 * ((size_t)L.n_img + 1));
+  memcpy(dst + L.o_inst, inst_first, 4 * ((size_t)L.n_inst + 1));
+  int32_t* off = (int32_t*)(dst + L.o_off);
+  double* xy = (double*)(dst + L.o_xy);
+  size_t at = 0;
+  for (int q = 0; q < L.n_poly; ++q) {
+    off[q] = (int32_t)at;
+    memcpy(xy + at, polys + poly_off[q], 8 * (size_t)poly_len[q]);
+    at += (size_t)poly_len[q];
+  }
+  if (L.n_poly) memcpy(dst + L.o_len, poly_len, 4 * (size_t)L.n_poly);
+}
+
 }  // namespace
 
 struct rs_trainer {
@@ -83,6 +122,7 @@ struct rs_trainer {
   int* rpn_labels = nullptr;     // [N][A_total] 1 / 0 / -1 (after subsampling)
   unsigned int* gt_best = nullptr;
   float* losses = nullptr;       // [8]: rpn_cls, rpn_loc, cls, box_reg, mask
+  LossScratch loss_scratch[3] = {};   // rpn / box / mask loss: the logged sums in a fixed order (train.h), so that two runs of a step log the same bits
   int rpn_first_stage = -1, rpn_last_stage = -1;
   unsigned int seed = 1;
   bool external_rpn_labels = false;   // parity tests: keep the labels the caller wrote into rpn_labels
@@ -116,6 +156,20 @@ struct rs_trainer {
   hipStream_t copy = nullptr;            // read-back of the sampled RoIs while the box head runs
   hipEvent_t ev_rois = nullptr;          // sampled RoIs written (recorded inside rs_trainer_roi_step)
   float* h_boxes = nullptr; int32_t* h_gti = nullptr; int32_t* h_cnt = nullptr;   // pinned read-back buffers
+  // ---- mask targets rasterised on the device (opt-in: rs_trainer_set_polygons + rs_trainer_mask_backward_device).  The polygon pool
+  // holds the ground-truth polygons of ONE batch: at most N * MT_POLYS_PER_IMAGE polygons and N * MT_DOUBLES_PER_IMAGE doubles
+  // (N = the trainer's batch capacity; 32 768 vertices and 512 KiB per image on average); a batch beyond that is the caller's to
+  // rasterise on the host (RS_POLYGONS_DO_NOT_FIT).  Pool and staging are allocated by the first rs_trainer_set_polygons.
+  static constexpr int MT_POLYS_PER_IMAGE = 512, MT_DOUBLES_PER_IMAGE = 65536;
+  uint8_t* mt_pool = nullptr;            // device, MtLayout of the current batch
+  uint8_t* mt_pinned = nullptr;          // host staging of the pool
+  hipEvent_t ev_polys = nullptr;         // the staging buffer's last upload
+  MtLayout mt_layout;
+  bool mt_set = false;                   // polygons of the current targets are in the pool (cleared by rs_trainer_set_targets)
+  int mt_n = 0;
+  Stage mt_stage;                        // "mask.targets": listed by rs_trainer_stage_info once the pool exists
+  bool mt_listed = false;
+  std::vector<TensorInfo> named;         // readable through rs_trainer_tensor by name, not part of the enumerated table
   const int* ctx_m_count = nullptr;   // while set, add_dgrad / add_wgrad bound their rows by this device counter (entries)
   int build_mask_training();
   std::vector<std::pair<void*, size_t>> clear_list;   // gradient buffers that must be zero before a backward pass
@@ -686,6 +740,7 @@ int rs_trainer::build_rpn_training() {
       q.loss_out = self->losses; q.A = A; q.cs = head_cs; q.dcs = 64; q.HW = hw; q.n_anchors = hw * A; q.level_off = loff;
       q.total_anchors = self->A_total; q.gt_cap = GT_CAP; q.normalizer = (float)self->rpn_batch * (float)n; q.loss_scale = self->loss_scale;
       q.d32 = self->f32 ? 1 : 0;
+      q.scratch = self->loss_scratch[0];
       return launch_rpn_loss(q, n, s);
     };
     rpn_bwd.push_back(st);
@@ -823,6 +878,7 @@ int rs_trainer::build_box_training() {
       q.ww = self->eng->spec.box_reg_weights[2]; q.wh = self->eng->spec.box_reg_weights[3];
       q.loss_scale = self->loss_scale;
       q.d32 = self->f32 ? 1 : 0;
+      q.scratch = self->loss_scratch[1];
       return launch_box_loss(q, s);
     };
     roi_bwd.push_back(st);
@@ -909,6 +965,28 @@ int rs_trainer::build_mask_training() {
   reg("mask_slots", m_slots, DT_I32, {ME}, 0);
   reg("mask_classes", m_cls, DT_I32, {ME}, 0);
   reg("mask_total", m_total, DT_I32, {1}, 0);
+  {
+    TensorInfo ti;
+    ti.name = "mask_targets"; ti.p = m_targets; ti.dtype = DT_U8; ti.ndim = 3; ti.halo = 0;
+    ti.dims[0] = ME; ti.dims[1] = SD; ti.dims[2] = SD;
+    ti.bytes = (size_t)ME * SD * SD;
+    named.push_back(ti);
+  }
+  {
+    rs_trainer* me = this;
+    mt_stage.name = "mask.targets";
+    mt_stage.fn = [me, SD](int n, hipStream_t s) {
+      const MtLayout& L = me->mt_layout;
+      MaskTargetsParams q;
+      memset(&q, 0, sizeof q);
+      q.boxes = me->rsp.out_boxes; q.gt_index = me->rsp.out_gt_index; q.slots = me->m_slots; q.total = me->m_total;
+      q.image_first = (const int*)me->mt_pool; q.inst_first = (const int*)(me->mt_pool + L.o_inst);
+      q.poly_off = (const int*)(me->mt_pool + L.o_off); q.poly_len = (const int*)(me->mt_pool + L.o_len);
+      q.polys = (const double*)(me->mt_pool + L.o_xy);
+      q.out = me->m_targets; q.n_entries = n * MEI; q.n_inst = L.n_inst; q.slots_per_image = PC; q.S = SD;
+      return launch_mask_targets(q, s);
+    };
+  }
   // ---- forward buffers
   auto mk = [&](Act* a, const std::string& name, int H, int W, int C, int pad) -> int {
     a->N = ME; a->H = H; a->W = W; a->C = C; a->pad = pad;
@@ -1013,6 +1091,7 @@ int rs_trainer::build_mask_training() {
         q2.n_masks_ptr = self->m_total; q2.n_masks = n * MEI; q2.S = SD; q2.cs = 16; q2.dcs = 64; q2.loss_scale = self->loss_scale;
         q2.d32 = self->f32 ? 1 : 0;
         (void)ME;
+        q2.scratch = self->loss_scratch[2];
         return launch_mask_loss(q2, s);
       };
       mask_bwd.push_back(sl);
@@ -1120,6 +1199,17 @@ int rs_trainer_create(const rs_spec* spec, const void* weights, size_t nbytes, i
   if (!rc) rc = t->build_rpn_training();
   if (!rc) rc = t->build_box_training();
   if (!rc) rc = t->build_mask_training();
+  if (!rc) {
+    // the three loss stages run on the chain stream, one after the other; each kind has its own slots and counter
+    const int SDm = 2 * spec->mask_pooler_resolution;
+    const int caps[3] = {batch * (cdiv(t->A_total, 256) + 8), cdiv((long long)batch * rs_trainer::PC, 256) + 1,
+                         cdiv((long long)batch * rs_trainer::MEI * SDm * SDm, 256) + 1};
+    for (int k = 0; k < 3 && !rc; ++k) {
+      t->loss_scratch[k].cap = caps[k];
+      rc = t->alloc((void**)&t->loss_scratch[k].partial, (size_t)2 * caps[k] * 4);
+      if (!rc) rc = t->alloc((void**)&t->loss_scratch[k].counter, 16);
+    }
+  }
   if (!rc) rc = t->alloc((void**)&t->master, t->n_params * 4);
   if (!rc) rc = t->alloc((void**)&t->grad, t->n_params * 4);
   if (!rc) rc = t->alloc((void**)&t->mom, t->n_params * 4);
@@ -1158,6 +1248,8 @@ void rs_trainer_destroy(rs_trainer* t) {
   if (t->copy) { (void)hipStreamSynchronize(t->copy); (void)hipStreamDestroy(t->copy); }
   if (t->ev_rois) (void)hipEventDestroy(t->ev_rois);
   if (t->ev_targets) (void)hipEventDestroy(t->ev_targets);
+  if (t->ev_polys) (void)hipEventDestroy(t->ev_polys);
+  if (t->mt_pinned) (void)hipHostFree(t->mt_pinned);
   if (t->m_targets_pinned) (void)hipHostFree(t->m_targets_pinned);
   if (t->h_boxes) (void)hipHostFree(t->h_boxes);
   if (t->h_gti) (void)hipHostFree(t->h_gti);
@@ -1226,6 +1318,46 @@ int rs_trainer_set_targets(rs_trainer* t, const float* gt_boxes, const int32_t* 
   }
   RS_HIP(hipMemcpyAsync(t->gt_count, gt_count, (size_t)n * 4, hipMemcpyHostToDevice, t->stream));
   RS_HIP(hipStreamSynchronize(t->stream));
+  t->mt_set = false;                     // the pool holds the previous batch's polygons
+  return RS_OK;
+}
+
+// Ground-truth polygons of the batch for mask targets rasterised on the device: the flat layout of rs_rasterize_entries (polygon q =
+// poly_len[q] doubles at polys + poly_off[q], instance g owns polygons inst_first[g] .. inst_first[g+1]-1) plus image_first[n + 1], the
+// first instance of every image (instance of image i's gt j = image_first[i] + j).  Coordinates in network-input pixels.  Packed into
+// pinned staging and uploaded on the trainer's stream without a host wait; the staging buffer is guarded by an event like the
+// targets' own.  A batch beyond the pool (rs_trainer: MT_POLYS_PER_IMAGE, MT_DOUBLES_PER_IMAGE) returns RS_POLYGONS_DO_NOT_FIT, copies
+// nothing and leaves the trainer as it was: that step takes rs_trainer_fetch_rois + rs_trainer_mask_backward.
+int rs_trainer_set_polygons(rs_trainer* t, const double* polys, const int64_t* poly_off, const int32_t* poly_len, const int32_t* inst_first,
+                            const int32_t* image_first, int n) {
+  RS_CHECK(t && n >= 1 && n <= t->N && !t->mask_bwd.empty(), RS_ERR_ARG, "bad argument / MASK_ON false");
+  RS_CHECK(2 * t->eng->spec.mask_pooler_resolution <= MT_MAX_SIDE, RS_ERR_UNSUPPORTED, "device mask targets: mask side above %d", MT_MAX_SIDE);
+  RS_CHECK(image_first && image_first[0] == 0, RS_ERR_ARG, "image_first must start at 0");
+  for (int i = 0; i < n; ++i) RS_CHECK(image_first[i + 1] >= image_first[i], RS_ERR_ARG, "image_first decreases at image %d", i);
+  t->mt_set = false;
+  MtLayout L;
+  { int rc = mt_measure(polys, poly_off, poly_len, inst_first, image_first[n], n, &L); if (rc) return rc; }
+  const size_t cap_poly = (size_t)t->N * rs_trainer::MT_POLYS_PER_IMAGE, cap_dbl = (size_t)t->N * rs_trainer::MT_DOUBLES_PER_IMAGE;
+  const size_t cap_inst = (size_t)t->N * rs_trainer::GT_CAP;
+  if ((size_t)L.n_poly > cap_poly || L.n_doubles > cap_dbl || (size_t)L.n_inst > cap_inst) {
+    rs_set_error("trainer: %d polygons / %zu doubles / %d instances do not fit the device pool (%zu / %zu / %zu)", L.n_poly, L.n_doubles,
+                 L.n_inst, cap_poly, cap_dbl, cap_inst);
+    return RS_POLYGONS_DO_NOT_FIT;
+  }
+  if (!t->mt_pool) {
+    const size_t bytes = 4 * ((size_t)t->N + 1 + cap_inst + 1 + 2 * cap_poly) + 8 + 8 * cap_dbl;
+    if (!t->ev_polys) RS_HIP(hipEventCreateWithFlags(&t->ev_polys, hipEventDisableTiming));
+    if (!t->mt_pinned) RS_HIP(hipHostMalloc((void**)&t->mt_pinned, bytes, hipHostMallocDefault));
+    { int rc = t->alloc((void**)&t->mt_pool, bytes); if (rc) return rc; }
+  } else {
+    RS_HIP(hipEventSynchronize(t->ev_polys));      // the previous upload has left the staging buffer
+  }
+  mt_pack(t->mt_pinned, L, polys, poly_off, poly_len, inst_first, image_first);
+  RS_HIP(hipMemcpyAsync(t->mt_pool, t->mt_pinned, L.bytes, hipMemcpyHostToDevice, t->stream));
+  RS_HIP(hipEventRecord(t->ev_polys, t->stream));
+  t->mt_layout = L;
+  t->mt_n = n;
+  t->mt_set = true;
   return RS_OK;
 }
 
@@ -1347,6 +1479,15 @@ int rs_trainer_mask_backward(rs_trainer* t, int n, const uint8_t* targets_host, 
   return t->run_list(t->mask_bwd, n);
 }
 
+// rs_trainer_mask_backward with the targets rasterised on the device (mask_targets_kernel on the chain stream, behind mask.entries and
+// the sampling): no read-back, no host wait, no upload.  Needs the batch's polygons (rs_trainer_set_polygons after rs_trainer_set_targets).
+int rs_trainer_mask_backward_device(rs_trainer* t, int n) {
+  RS_CHECK(t && n >= 1 && n <= t->N && !t->mask_bwd.empty(), RS_ERR_ARG, "bad argument / MASK_ON false");
+  RS_CHECK(t->mt_set && t->mt_n == n, RS_ERR_ARG, "no polygons of this batch on the device: call rs_trainer_set_polygons after rs_trainer_set_targets");
+  { int rc = t->run_stage(t->mt_stage, n, t->stream); if (rc) return rc; }
+  return t->run_list(t->mask_bwd, n);
+}
+
 // The sampled RoIs of the current rs_trainer_roi_step for the host-side mask targets: "roi_boxes" [n][1024][4], "roi_gt_index"
 // [n][1024], "roi_sampled_count" [n][2] -> host.  Waits only for the sampling (an event recorded inside rs_trainer_roi_step),
 // on its own copy stream: the box head's forward / backward and the mask head's forward keep the GPU busy meanwhile.
@@ -1432,6 +1573,16 @@ int rs_trainer_tensor(rs_trainer* t, const char* name, void** dev_ptr, int* dtyp
       return RS_OK;
     }
   }
+  for (const TensorInfo& ti : t->named) {
+    if (ti.name == name) {
+      if (dev_ptr) *dev_ptr = ti.p;
+      if (dtype) *dtype = ti.dtype;
+      if (ndim) *ndim = ti.ndim;
+      if (dims) for (int i = 0; i < 5; ++i) dims[i] = ti.dims[i];
+      if (halo) *halo = ti.halo;
+      return RS_OK;
+    }
+  }
   rs_set_error("trainer: no tensor named %s", name);
   return RS_ERR_ARG;
 }
@@ -1502,6 +1653,7 @@ int rs_trainer_set_profiling(rs_trainer* t, int on) {
     for (auto* l : {&t->roi_bwd, &t->mask_fwd, &t->mask_bwd, &t->rpn_bwd, &t->bwd})
       for (Stage& st : *l) t->all_stages.push_back(&st);
   }
+  if (t->mt_pool && !t->mt_listed) { t->all_stages.push_back(&t->mt_stage); t->mt_listed = true; }   // last: the other indices stay
   if (on) {
     for (Stage* st : t->all_stages) { st->ms_total = 0; st->calls = 0; st->last_flops = 0; }
     if (t->pev.empty()) {
@@ -1525,6 +1677,43 @@ int rs_trainer_stage_info(rs_trainer* t, int i, char* name_out, double* ms_total
   if (flops) *flops = st.last_flops;
   if (on_side_stream) *on_side_stream = (st.grad_side && t->side) ? 1 : 0;
   return RS_OK;
+}
+
+// Operator-level entry of mask_targets_kernel: the arguments of rs_rasterize_entries (host pointers) without `threads`; packs and
+// uploads the polygons, rasterises the n_entries explicit (instance, box) pairs on the device and copies the masks back.  An entry
+// whose instance is outside [0, n_inst) comes back all zero.
+int rs_op_mask_targets(const double* polys, const int64_t* poly_off, const int32_t* poly_len, const int32_t* inst_first, int n_inst,
+                       const int32_t* entry_inst, const float* boxes, int n_entries, int mask_size, uint8_t* out) {
+  if (n_entries == 0) return RS_OK;
+  RS_CHECK(entry_inst && boxes && out && n_inst > 0 && n_entries > 0, RS_ERR_ARG, "bad argument");
+  RS_CHECK(mask_size >= 2 && mask_size <= MT_MAX_SIDE && mask_size % 2 == 0, RS_ERR_UNSUPPORTED, "mask_targets: even mask side up to %d", MT_MAX_SIDE);
+  MtLayout L;
+  { int rc = mt_measure(polys, poly_off, poly_len, inst_first, n_inst, 0, &L); if (rc) return rc; }
+  RS_CHECK(L.n_doubles <= (size_t)MT_MAX_DOUBLES, RS_ERR_UNSUPPORTED, "mask_targets: more than %d doubles of polygons", MT_MAX_DOUBLES);
+  std::vector<uint8_t> host(L.bytes);
+  const int32_t zero = 0;
+  mt_pack(host.data(), L, polys, poly_off, poly_len, inst_first, &zero);
+  const size_t SS = (size_t)mask_size * mask_size;
+  uint8_t* pool = nullptr; float* bx = nullptr; int* ei = nullptr; uint8_t* m = nullptr;
+  int rc = RS_OK;
+  if (hipMalloc((void**)&pool, L.bytes) != hipSuccess || hipMalloc((void**)&bx, (size_t)n_entries * 16) != hipSuccess ||
+      hipMalloc((void**)&ei, (size_t)n_entries * 4) != hipSuccess || hipMalloc((void**)&m, (size_t)n_entries * SS) != hipSuccess ||
+      hipMemcpy(pool, host.data(), L.bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(bx, boxes, (size_t)n_entries * 16, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(ei, entry_inst, (size_t)n_entries * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    rs_set_error("mask_targets: device buffers"); rc = RS_ERR_HIP;
+  }
+  if (!rc) {
+    MaskTargetsParams q;
+    memset(&q, 0, sizeof q);
+    q.boxes = bx; q.gt_index = ei; q.inst_first = (const int*)(pool + L.o_inst); q.poly_off = (const int*)(pool + L.o_off);
+    q.poly_len = (const int*)(pool + L.o_len); q.polys = (const double*)(pool + L.o_xy);
+    q.out = m; q.n_entries = n_entries; q.n_inst = n_inst; q.S = mask_size;
+    rc = launch_mask_targets(q, nullptr);
+    if (!rc && hipMemcpy(out, m, (size_t)n_entries * SS, hipMemcpyDeviceToHost) != hipSuccess) { rs_set_error("mask_targets: read-back"); rc = RS_ERR_HIP; }
+  }
+  (void)hipFree(pool); (void)hipFree(bx); (void)hipFree(ei); (void)hipFree(m);
+  return rc;
 }
 
 void* rs_trainer_master_buffer(rs_trainer* t) { return t ? (void*)t->master : nullptr; }

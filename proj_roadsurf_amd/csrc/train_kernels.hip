@@ -16,8 +16,10 @@
 //                          [Cout][(kh,kw,ci)] with the FrozenBN scale folded in, and its transposed, tap-flipped copy
 //                          [Cin][(kh',kw',co)] for the input-gradient convolution
 // Each loss kernel writes the GRADIENT of the (weighted) total loss w.r.t. its logits/deltas, scaled by `loss_scale`
-// (fp16 loss scaling), and accumulates the loss value itself into an fp32 scalar for logging.
+// (fp16 loss scaling), and accumulates the loss value itself into an fp32 scalar for logging (one float atomic per wave, or, given a
+// LossScratch, in a fixed order: grid_sum_to).
 #include "common.h"
+#include "mask_targets.h"
 #include "train.h"
 
 namespace {
@@ -44,6 +46,44 @@ __device__ __forceinline__ void block_sum_to(float v, float* dst) {
   // wave reduction, then one atomic per wave (loss logging only; gradients never go through atomics here)
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   if ((threadIdx.x & 63) == 0 && v != 0.f) atomicAdd(dst, v);
+}
+
+// The same sums in an order that does not depend on the scheduling (LossScratch, the trainer's steps): every workgroup stores its
+// two sums (waves added in wave order) into its own slot; the workgroup that arrives last -- a counter, behind a fence -- adds the slots in
+// a fixed order and accumulates into dst with a plain store.  Two runs of a step then log the same bits.  All 256 threads must call it.
+__device__ __forceinline__ void grid_sum_to(float v0, float v1, float* dst0, float* dst1, const LossScratch& sc, unsigned bid, unsigned nblocks) {
+  __shared__ float s_part[2][256];
+  __shared__ int s_last;
+  const int tid = threadIdx.x;
+  for (int o = 32; o > 0; o >>= 1) { v0 += __shfl_xor(v0, o); v1 += __shfl_xor(v1, o); }
+  if ((tid & 63) == 0) { s_part[0][tid >> 6] = v0; s_part[1][tid >> 6] = v1; }
+  __syncthreads();
+  if (tid == 0) {
+    sc.partial[bid] = ((s_part[0][0] + s_part[0][1]) + s_part[0][2]) + s_part[0][3];
+    sc.partial[sc.cap + bid] = ((s_part[1][0] + s_part[1][1]) + s_part[1][2]) + s_part[1][3];
+    __threadfence();
+    s_last = atomicAdd(sc.counter, 1u) == nblocks - 1u;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  __threadfence();
+  float a = 0.f, b = 0.f;
+  for (unsigned i = tid; i < nblocks; i += 256) {
+    a += __hip_atomic_load(sc.partial + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    b += __hip_atomic_load(sc.partial + sc.cap + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  s_part[0][tid] = a; s_part[1][tid] = b;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) { s_part[0][tid] += s_part[0][tid + o]; s_part[1][tid] += s_part[1][tid + o]; }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    *dst0 += s_part[0][0];
+    if (dst1) *dst1 += s_part[1][0];
+    *sc.counter = 0u;                            // ready for the next launch on the stream
+  }
 }
 
 // one thread per anchor of one level; head output rows are [pixel][cs] fp32: columns [0,A) logits, [A,5A) deltas (a*4+d)
@@ -81,6 +121,7 @@ __global__ __launch_bounds__(256) void rpn_loss_kernel(const RpnLossParams p) {
     for (int d = 0; d < 4; ++d) g[p.A + a * 4 + d] = (G)(gd[d] * p.loss_scale);
     if (a == 0) for (int c = 5 * p.A; c < dcs; ++c) g[c] = (G)0.f;       // padding columns of the fused head
   }
+  if (p.scratch.partial) { grid_sum_to(lc, ll, p.loss_out, p.loss_out + 1, p.scratch, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y); return; }
   block_sum_to(lc, p.loss_out);
   block_sum_to(ll, p.loss_out + 1);
 }
@@ -128,6 +169,7 @@ __global__ __launch_bounds__(256) void box_loss_kernel(const BoxLossParams p) {
       }
     }
   }
+  if (p.scratch.partial) { grid_sum_to(lc, ll, p.loss_out, p.loss_out + 1, p.scratch, blockIdx.x, gridDim.x); return; }
   block_sum_to(lc, p.loss_out);
   block_sum_to(ll, p.loss_out + 1);
 }
@@ -153,6 +195,7 @@ __global__ __launch_bounds__(256) void mask_loss_kernel(const MaskLossParams p) 
       g[cls] = (G)(rs_fdiv(sigmoidf(x) - t, norm) * p.loss_scale);
     }
   }
+  if (p.scratch.partial) { grid_sum_to(l, 0.f, p.loss_out, nullptr, p.scratch, blockIdx.x, gridDim.x); return; }
   block_sum_to(l, p.loss_out);
 }
 
@@ -603,10 +646,80 @@ __global__ __launch_bounds__(256) void mask_entries_kernel(const MaskEntriesPara
   }
 }
 
+// Ground-truth mask of one mask-head entry (PolygonMasks.crop_and_resize), bit for bit the host's rs_rasterize_polygons_within_box:
+// mask_targets.h locates, per (edge, column), the one point rleFrPoly would emit; here one 64-lane workgroup per entry strides over
+// the (edge, column) pairs of a polygon, counts the points per column-major cell with integer LDS atomics, turns the counts into the
+// run-length decode's fill (cell q is set when the number of points <= q is odd) with a wave prefix parity, ORs the polygons of the
+// instance and stores the mask transposed to row-major.  fp64 only; no float atomics; every loop bound is known before the loop.
+constexpr int MT_CELLS = MT_MAX_SIDE * MT_MAX_SIDE + MT_MAX_SIDE + 1;   // a point may land on row S of the last column
+constexpr int MT_PER_LANE = (MT_MAX_SIDE * MT_MAX_SIDE + 63) / 64;       // consecutive cells per lane in the prefix (13)
+__global__ __launch_bounds__(64) void mask_targets_kernel(const MaskTargetsParams p) {
+  __shared__ int s_cnt[MT_CELLS];
+  __shared__ uint32_t s_out[MT_MAX_SIDE * MT_MAX_SIDE / 4];
+  const int e = blockIdx.x, lane = threadIdx.x, S = p.S, SS = S * S;
+  int inst = -1;
+  const float* bp;
+  if (p.slots) {                                // trainer: entry -> slot of the sampled RoI list, instance = image's first + gt index
+    if (e >= *p.total) return;
+    const int slot = p.slots[e], img = slot / p.slots_per_image;
+    bp = p.boxes + (long long)slot * 4;
+    const int gi = p.gt_index[slot], i0 = p.image_first[img], i1 = p.image_first[img + 1];
+    if (gi >= 0 && gi < i1 - i0) inst = i0 + gi;
+  } else {
+    bp = p.boxes + (long long)e * 4;
+    const int g = p.gt_index[e];
+    if (g >= 0 && g < p.n_inst) inst = g;
+  }
+  uint32_t acc = 0;                             // bit i: cell lane * MT_PER_LANE + i
+  if (inst >= 0) {                              // an index outside the instances reads nothing and leaves the mask zero
+    const MtBox box = mt_box(bp[0], bp[1], bp[2], bp[3], S);
+    const int q0 = p.inst_first[inst], q1 = p.inst_first[inst + 1];
+    for (int q = q0; q < q1; ++q) {
+      const double* xy = p.polys + p.poly_off[q];
+      const int k = p.poly_len[q] >> 1;
+      for (int c = lane; c < MT_CELLS; c += 64) s_cnt[c] = 0;
+      __syncthreads();
+      const unsigned items = (unsigned)k * (unsigned)S;       // the pool holds fewer than 2^26 doubles (MT_MAX_DOUBLES)
+      for (unsigned it = lane; it < items; it += 64) {
+        const int j = (int)(it / (unsigned)S), m = (int)(it - (unsigned)j * (unsigned)S), j2 = j + 1 == k ? 0 : j + 1;
+        int xs, ys, xe, ye;
+        mt_vertex(box, xy[2 * j], xy[2 * j + 1], &xs, &ys);
+        mt_vertex(box, xy[2 * j2], xy[2 * j2 + 1], &xe, &ye);
+        const int pt = mt_edge_point(xs, ys, xe, ye, m, S);
+        if (pt >= 0) atomicAdd(&s_cnt[pt], 1);
+      }
+      __syncthreads();
+      uint32_t odd = 0;                         // parity of the points of this lane's cells, then of everything before them
+      for (int i = 0; i < MT_PER_LANE; ++i) {
+        const int c = lane * MT_PER_LANE + i;
+        if (c < SS) odd ^= (uint32_t)(s_cnt[c] & 1) << i;
+      }
+      const unsigned long long ball = __ballot(__popc(odd) & 1);
+      uint32_t par = (uint32_t)__popcll(ball & ((1ull << lane) - 1ull)) & 1u;
+      uint32_t fill = 0;
+      for (int i = 0; i < MT_PER_LANE; ++i) {
+        par ^= (odd >> i) & 1u;
+        fill |= par << i;
+      }
+      acc |= fill;
+      __syncthreads();                          // the counters are cleared again for the next polygon
+    }
+  }
+  uint8_t* ob = (uint8_t*)s_out;
+  for (int i = 0; i < MT_PER_LANE; ++i) {
+    const int c = lane * MT_PER_LANE + i;       // column-major cell: column c / S, row c % S
+    if (c < SS) ob[(c % S) * S + c / S] = (uint8_t)((acc >> i) & 1u);
+  }
+  __syncthreads();
+  uint32_t* o = (uint32_t*)(p.out + (long long)e * SS);      // SS is a multiple of 4 (launcher) and the buffer is 256-byte aligned
+  for (int i = lane; i < SS / 4; i += 64) o[i] = s_out[i];
+}
+
 }  // namespace
 
 int launch_rpn_loss(const RpnLossParams& p, int N, hipStream_t s) {
   RS_CHECK(p.head && p.dhead && p.labels && p.anchors && (p.matched_gt || (p.gt && p.matched)) && p.loss_out && p.n_anchors > 0 && p.cs >= 5 * p.A, RS_ERR_ARG, "rpn_loss: bad arguments");
+  RS_CHECK(!p.scratch.partial || (p.scratch.counter && (long long)cdiv(p.n_anchors, 256) * N <= p.scratch.cap), RS_ERR_ARG, "rpn_loss: loss scratch too small");
   if (p.d32) hipLaunchKernelGGL(rpn_loss_kernel<float>, dim3(cdiv(p.n_anchors, 256), N), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(rpn_loss_kernel<half_t>, dim3(cdiv(p.n_anchors, 256), N), dim3(256), 0, s, p);
   RS_HIP(hipGetLastError());
@@ -614,6 +727,7 @@ int launch_rpn_loss(const RpnLossParams& p, int N, hipStream_t s) {
 }
 int launch_box_loss(const BoxLossParams& p, hipStream_t s) {
   RS_CHECK(p.pred && p.dpred && p.gt_classes && p.proposals && p.gt_boxes && p.loss_out && p.n_rois > 0 && p.cs >= 5 * p.K + 1 && (p.n_valid > 0 || p.n_valid_counts), RS_ERR_ARG, "box_loss: bad arguments");
+  RS_CHECK(!p.scratch.partial || (p.scratch.counter && cdiv(p.n_rois, 256) <= p.scratch.cap), RS_ERR_ARG, "box_loss: loss scratch too small");
   if (p.d32) hipLaunchKernelGGL(box_loss_kernel<float>, dim3(cdiv(p.n_rois, 256)), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(box_loss_kernel<half_t>, dim3(cdiv(p.n_rois, 256)), dim3(256), 0, s, p);
   RS_HIP(hipGetLastError());
@@ -621,6 +735,7 @@ int launch_box_loss(const BoxLossParams& p, hipStream_t s) {
 }
 int launch_mask_loss(const MaskLossParams& p, hipStream_t s) {
   RS_CHECK(p.logits && p.dlogits && p.targets && p.gt_classes && p.loss_out && p.n_masks > 0 && p.S > 0, RS_ERR_ARG, "mask_loss: bad arguments");
+  RS_CHECK(!p.scratch.partial || (p.scratch.counter && cdiv((long long)p.n_masks * p.S * p.S, 256) <= p.scratch.cap), RS_ERR_ARG, "mask_loss: loss scratch too small");
   if (p.d32) hipLaunchKernelGGL(mask_loss_kernel<float>, dim3((unsigned)cdiv((long long)p.n_masks * p.S * p.S, 256)), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(mask_loss_kernel<half_t>, dim3((unsigned)cdiv((long long)p.n_masks * p.S * p.S, 256)), dim3(256), 0, s, p);
   RS_HIP(hipGetLastError());
@@ -722,6 +837,16 @@ int launch_roi_gather(const RoiSampleParams& p, int N, hipStream_t s) {
 int launch_mask_entries(const MaskEntriesParams& p, hipStream_t s) {
   RS_CHECK(p.sampled_count && p.roi_classes && p.slots && p.classes && p.total && p.N >= 1 && p.N <= 64, RS_ERR_ARG, "mask_entries: bad arguments");
   hipLaunchKernelGGL(mask_entries_kernel, dim3(1), dim3(256), 0, s, p);
+  RS_HIP(hipGetLastError());
+  return RS_OK;
+}
+
+int launch_mask_targets(const MaskTargetsParams& p, hipStream_t s) {
+  RS_CHECK(p.boxes && p.gt_index && p.polys && p.poly_off && p.poly_len && p.inst_first && p.out && p.n_entries >= 0 && p.S >= 2 &&
+           p.S <= MT_MAX_SIDE && p.S % 2 == 0 && (p.slots ? (p.total && p.image_first && p.slots_per_image > 0) : p.n_inst >= 0),
+           RS_ERR_ARG, "mask_targets: bad arguments (even mask side up to %d)", MT_MAX_SIDE);
+  if (p.n_entries == 0) return RS_OK;
+  hipLaunchKernelGGL(mask_targets_kernel, dim3((unsigned)p.n_entries), dim3(64), 0, s, p);
   RS_HIP(hipGetLastError());
   return RS_OK;
 }

@@ -1057,6 +1057,10 @@ class Predictor:
         self._pipes.clear()
 
 
+MASK_TARGET_MODES = ("host", "device")
+RS_POLYGONS_DO_NOT_FIT = 1     # include/rs_engine.h: rs_trainer_set_polygons, the batch's polygons exceed the device pool
+
+
 class Trainer:
     """Training engine (include/rs_engine.h ``rs_trainer_*``): forward engine + flat fp32
     master / gradient / momentum buffers + backward stage list.  ``train_step`` = ``SimpleTrainer.run_step`` up to
@@ -1064,7 +1068,16 @@ class Trainer:
     ``apply_sgd`` = the optimiser step; ``allreduce_gradients`` = DDP's gradient averaging over RCCL."""
 
     def __init__(self, spec: EngineSpec, weights: Dict[str, np.ndarray], tile_shape: Tuple[int, int, int], batch: int = 2,
-                 device: int = 0, loss_scale: float = 1.0, lib_path: Optional[str] = None):
+                 device: int = 0, loss_scale: float = 1.0, lib_path: Optional[str] = None, mask_targets: str = "host"):
+        """``mask_targets``: where ``train_step`` rasterises the mask head's ground-truth crops.  "host" (default): read the sampled
+        RoIs back, rasterise on host threads, upload (``mask_entries`` + ``mask_backward``).  "device": upload the batch's polygons
+        with the targets and rasterise on the GPU (``set_polygons`` + ``mask_backward_device``) -- the same bytes, no host wait
+        inside the step; a batch whose polygons do not fit the device pool runs the host path for that step
+        (``mask_target_fallbacks`` counts them)."""
+        if mask_targets not in MASK_TARGET_MODES:
+            raise ValueError(f"mask_targets must be one of {MASK_TARGET_MODES}, got {mask_targets!r}")
+        self.mask_targets = mask_targets
+        self.mask_target_fallbacks = 0
         self.lib = lib = load_library(lib_path)
         vp, i32 = C.c_void_p, C.c_int
         lib.rs_trainer_create.argtypes = [C.POINTER(RsSpec), vp, C.c_size_t, i32, i32, i32, i32, i32, C.c_float, C.POINTER(vp)]
@@ -1098,6 +1111,8 @@ class Trainer:
         lib.rs_trainer_wait_stream.argtypes = [vp, vp]
         lib.rs_trainer_mask_forward.argtypes = [vp, i32]
         lib.rs_trainer_mask_backward.argtypes = [vp, i32, vp, i32]
+        lib.rs_trainer_set_polygons.argtypes = [vp, vp, vp, vp, vp, vp, i32]
+        lib.rs_trainer_mask_backward_device.argtypes = [vp, i32]
         lib.rs_trainer_sync.argtypes = [vp]
         lib.rs_trainer_set_profiling.argtypes = [vp, i32]
         lib.rs_trainer_stage_count.argtypes = [vp]
@@ -1219,6 +1234,33 @@ class Trainer:
         _check(self.lib, self.lib.rs_trainer_mask_backward(self._h, n, t.ctypes.data_as(C.c_void_p) if t.size else None, int(t.shape[0])),
                "rs_trainer_mask_backward")
 
+    def set_polygons(self, gt_polygons: Sequence[Sequence[Sequence[np.ndarray]]]) -> bool:
+        """Device mask targets: upload the batch's ground-truth polygons (gt_polygons[image][gt index] = list of polygons, network-input
+        pixels, as ``mask_entries`` takes them).  Call after ``set_targets``.  False: they do not fit the device pool (include/rs_engine.h
+        ``rs_trainer_set_polygons``) and nothing was uploaded -- run this step through ``mask_entries`` + ``mask_backward``."""
+        n = len(gt_polygons)
+        arrs = [np.asarray(p, np.float64).reshape(-1) for img in gt_polygons for polys in img for p in polys]
+        lens = np.array([a.size for a in arrs], np.int32)
+        off = np.zeros(max(len(arrs), 1), np.int64)
+        if len(arrs) > 1:
+            off[1:] = np.cumsum(lens[:-1], dtype=np.int64)
+        flat = np.ascontiguousarray(np.concatenate(arrs)) if arrs else np.zeros(1)
+        inst_first = np.zeros(sum(len(img) for img in gt_polygons) + 1, np.int32)
+        inst_first[1:] = np.cumsum([len(polys) for img in gt_polygons for polys in img])
+        image_first = np.zeros(n + 1, np.int32)
+        image_first[1:] = np.cumsum([len(img) for img in gt_polygons])
+        lens = np.ascontiguousarray(lens) if lens.size else np.zeros(1, np.int32)
+        rc = self.lib.rs_trainer_set_polygons(self._h, flat.ctypes.data, off.ctypes.data, lens.ctypes.data, inst_first.ctypes.data,
+                                              image_first.ctypes.data, n)
+        if rc == RS_POLYGONS_DO_NOT_FIT:
+            return False
+        _check(self.lib, rc, "rs_trainer_set_polygons")
+        return True
+
+    def mask_backward_device(self, n: int) -> None:
+        """``mask_backward`` with the targets rasterised on the GPU from the polygons of ``set_polygons`` (tensor "mask_targets")."""
+        _check(self.lib, self.lib.rs_trainer_mask_backward_device(self._h, n), "rs_trainer_mask_backward_device")
+
     def mask_entries(self, gt_polygons: Sequence[Sequence[Sequence[np.ndarray]]], n: int) -> Tuple[np.ndarray, List[Tuple[int, int]]]:
         """Host part of the mask branch: gt masks of the sampled foreground RoIs (``PolygonMasks.crop_and_resize``).
         gt_polygons[image][gt index] = list of polygons ([x0,y0,...], network-input pixels).  Returns (targets, [(image, slot)])."""
@@ -1251,6 +1293,11 @@ class Trainer:
         if sizes is not None:
             self.set_image_sizes(sizes if any(int(s) != self.spec.min_size_test for s in sizes) else None)
         self.set_targets(gt_boxes, gt_classes)
+        on_device = False
+        if self.spec.mask_on and self.mask_targets == "device":
+            on_device = self.set_polygons(gt_polygons[:n])
+            if not on_device:
+                self.mask_target_fallbacks += 1          # this step alone takes the host path; nothing is truncated
         # the RPN's targets depend on the ground truth and the seed only: on the side stream, ahead of the forward pass
         _check(self.lib, self.lib.rs_trainer_rpn_targets_async(self._h, n, seed & 0xFFFFFFFF), "rs_trainer_rpn_targets_async")
         self.forward_trunk(self.upload_tiles(tiles), n)
@@ -1258,8 +1305,11 @@ class Trainer:
         self.roi_step(n, seed)
         if self.spec.mask_on:
             self.mask_forward(n)
-            targets, _ = self.mask_entries(gt_polygons, n)
-            self.mask_backward(n, targets)
+            if on_device:
+                self.mask_backward_device(n)
+            else:
+                targets, _ = self.mask_entries(gt_polygons, n)
+                self.mask_backward(n, targets)
         self.rpn_step(n, seed)
         self.backward_trunk(n)
         if allreduce:
@@ -1426,7 +1476,10 @@ class MultiScaleTrainer:
     (``rs_trainer_copy_state``)."""
 
     def __init__(self, spec: EngineSpec, weights: Dict[str, np.ndarray], tile_shape: Tuple[int, int, int], sizes: Sequence[int], batch: int = 1,
-                 device: int = 0, loss_scale: float = 1024.0):
+                 device: int = 0, loss_scale: float = 1024.0, mask_targets: str = "host"):
+        if mask_targets not in MASK_TARGET_MODES:
+            raise ValueError(f"mask_targets must be one of {MASK_TARGET_MODES}, got {mask_targets!r}")
+        self.mask_targets = mask_targets
         self.spec, self.weights, self.tile_shape, self.batch, self.device, self.loss_scale = spec, weights, tile_shape, batch, device, loss_scale
         self.sizes = [int(s) for s in sizes]
         self._t: Dict[int, Trainer] = {}
@@ -1452,7 +1505,8 @@ class MultiScaleTrainer:
     def select(self, size: int) -> Trainer:
         """The trainer for shortest-edge ``size``, holding the up-to-date optimiser state."""
         if size not in self._t:
-            t = Trainer(self.spec.replace(min_size_test=int(size)), self.weights, self.tile_shape, self.batch, self.device, self.loss_scale)
+            t = Trainer(self.spec.replace(min_size_test=int(size)), self.weights, self.tile_shape, self.batch, self.device, self.loss_scale,
+                        mask_targets=self.mask_targets)
             if self._sampling:
                 t.set_sampling(*self._sampling)
             if getattr(self, "_rpn_topk", None):
@@ -1471,6 +1525,11 @@ class MultiScaleTrainer:
         t = self.select(max(int(s) for s in sizes))
         t.set_image_sizes(list(sizes) if len(set(int(s) for s in sizes)) > 1 else None)
         return t
+
+    @property
+    def mask_target_fallbacks(self) -> int:
+        """Steps of all the trainers that took the host path because their polygons did not fit the device pool."""
+        return sum(t.mask_target_fallbacks for t in self._t.values())
 
     def net_shape(self, size: int) -> Tuple[int, int]:
         from .spec import resize_shortest_edge_shape

@@ -229,6 +229,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--val-max-images", type=int, default=0, help="cap on the validation images per evaluation (0 = all)")
     ap.add_argument("--batched-nms", choices=("per-category", "torchvision"), default="per-category",
                     help="the training proposal stage and the validation inference: " + BATCHED_NMS_HELP)
+    ap.add_argument("--mask-targets", choices=("host", "device"), default="host",
+                    help="where the mask head's ground-truth crops are rasterised in every step.  host (default): the sampled RoIs are read "
+                         "back, rasterised on host threads and uploaded.  device: the batch's polygons are uploaded with the targets and "
+                         "rasterised on the GPU, the same bytes without a host wait inside the step; a batch whose polygons do not fit the "
+                         "device pool runs the host path for that step")
     return ap
 
 
@@ -327,7 +332,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     sizes = list(sv["min_size_train"]) or [spec.min_size_test]
     if sv["min_size_sampling"] == "range" and len(sizes) == 2:
         sizes = list(range(sizes[0], sizes[1] + 1, 32))
-    ms = MultiScaleTrainer(spec, W, first.shape, sizes, batch=per_rank, device=local_rank, loss_scale=args.loss_scale)
+    ms = MultiScaleTrainer(spec, W, first.shape, sizes, batch=per_rank, device=local_rank, loss_scale=args.loss_scale,
+                           mask_targets=args.mask_targets)
+    log.info("mask_targets: %s", {"host": "host (sampled RoIs read back, rasterised on host threads)",
+                                  "device": "device (polygons uploaded with the targets, rasterised on the GPU)"}[args.mask_targets])
     ms.set_sampling(sv["rpn_batch"], sv["rpn_pos"], sv["roi_batch"], sv["roi_pos"])
     ms.set_rpn_topk(sv["pre_nms_topk_train"], sv["post_nms_topk_train"])
     size_rng = np.random.default_rng(args.seed * 104729 + rank)
@@ -516,6 +524,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             save(f"model_{it:07d}.pth", it)
     save("model_final.pth", max_iter - 1)
     loader.shutdown(wait=True)
+    if ms.mask_target_fallbacks:
+        log.info("mask_targets: %d steps rasterised on the host (their polygons did not fit the device pool)", ms.mask_target_fallbacks)
     ms.close()
     if metrics:
         metrics.close()

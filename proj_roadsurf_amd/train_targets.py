@@ -39,6 +39,32 @@ def rasterize_entries(instances: Sequence[Sequence[np.ndarray]], entry_instance:
     return out.astype(bool)
 
 
+def rasterize_entries_device(instances: Sequence[Sequence[np.ndarray]], entry_instance: np.ndarray, boxes: np.ndarray, mask_size: int) -> np.ndarray:
+    """``rasterize_entries`` on the GPU (``rs_op_mask_targets``: the kernel behind ``Trainer(mask_targets="device")``, one workgroup
+    per entry): same arguments, the same (n_entries, mask_size, mask_size) bool, bit for bit.  Needs a HIP device."""
+    from .engine import load_library, _check
+    lib = load_library()
+    ne = int(len(entry_instance))
+    out = np.zeros((ne, mask_size, mask_size), np.uint8)
+    if ne == 0:
+        return out.astype(bool)
+    arrs = [np.asarray(p, np.float64).reshape(-1) for polys in instances for p in polys]
+    lens = np.array([a.size for a in arrs] or [0], np.int32)
+    off = np.zeros(max(len(arrs), 1), np.int64)
+    if len(arrs) > 1:
+        off[1:] = np.cumsum(lens[:-1], dtype=np.int64)
+    flat = np.ascontiguousarray(np.concatenate(arrs)) if arrs else np.zeros(1)
+    first = np.zeros(len(instances) + 1, np.int32)
+    first[1:] = np.cumsum([len(polys) for polys in instances])
+    ei = np.ascontiguousarray(np.asarray(entry_instance, np.int32))
+    bx = np.ascontiguousarray(np.asarray(boxes, np.float32).reshape(ne, 4))
+    lib.rs_op_mask_targets.restype = C.c_int
+    lib.rs_op_mask_targets.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    _check(lib, lib.rs_op_mask_targets(flat.ctypes.data, off.ctypes.data, lens.ctypes.data, first.ctypes.data, len(instances), ei.ctypes.data,
+                                       bx.ctypes.data, ne, mask_size, out.ctypes.data), "rs_op_mask_targets")
+    return out.astype(bool)
+
+
 def rasterize_polygons_within_box(polygons: Sequence[np.ndarray], box: np.ndarray, mask_size: int) -> np.ndarray:
     """Polygons ([x0,y0,x1,y1,...] each, image coordinates) of one instance -> (mask_size, mask_size) bool target inside ``box``."""
     from .engine import load_library, RsError
