@@ -581,6 +581,14 @@ void rs_polygonize_caps(int* edge_cap, int* vertex_cap, int* ring_cap, int* max_
  * vertex_cap pairs, totals 4.  Waits for the stream. */
 int rs_op_polygonize(const uint8_t* masks_dev, int n, int h, int w, double rdp_epsilon, int edge_cap, int vertex_cap, int32_t* header_dev,
                      int32_t* poly_ring_count_dev, int32_t* ring_len_dev, int16_t* xy_dev, int32_t* totals_dev, void* stream);
+/* The same in the form the engine calls it: masks_dev [tiles * slots][h][(w+7)/8] canvases, instance = tile * slots + slot.
+ * det_count_dev [tiles] (NULL: every slot is valid): slots at or past a tile's count give an all-zero header.  rects_dev
+ * [tiles * slots][4] as rs_mask_crops.rects (NULL: whole canvases): only the rectangle is read, as a mask of its own with background
+ * around it, and the vertices stay in tile pixels; a rectangle with a negative field or one that leaves the canvas flags its
+ * instance.  Output buffers sized for tiles * slots instances. */
+int rs_op_polygonize_crops(const uint8_t* masks_dev, int tiles, int slots, const int32_t* det_count_dev, const int32_t* rects_dev, int h, int w,
+                           double rdp_epsilon, int edge_cap, int vertex_cap, int32_t* header_dev, int32_t* poly_ring_count_dev, int32_t* ring_len_dev,
+                           int16_t* xy_dev, int32_t* totals_dev, void* stream);
 /* Host only: an rs_vec_result over n instances from the tables above.  `fallback` holds the host-vectorised flagged instances, one
  * per flagged header in slot order (NULL when none is flagged); NULL is returned when the tables and the fallback do not fit together.
  * rs_vec_counts / rs_vec_copy / rs_vec_gpkg_blobs serve the result as any other. */

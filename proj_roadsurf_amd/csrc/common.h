@@ -108,6 +108,8 @@ struct RsDebug {
   int roi_window = 1;             // RS_ROI_WINDOW
   int roi_bwd_atomic = 0;         // RS_ROI_BWD_ATOMIC        1: RoIAlign backward by float atomics for every RoI (rounds 1-2) instead of owner-computes regions
   int roi_order = 1;              // RS_ROI_ORDER             box.roi_align visits the proposals sorted by (level, row, column) instead of by score
+  int poly_edge_cap = 0;          // RS_POLY_EDGE_CAP         rs_engine_fetch_polygons_*: edges above which an instance is left to the host (0: the kernel's capacity)
+  int poly_vertex_cap = 0;        // RS_POLY_VERTEX_CAP       the same for ring vertices before simplification
 };
 const RsDebug& rs_debug();
 void rs_debug_reload();

@@ -33,6 +33,7 @@ void rs_debug_reload() {
   rd("RS_USE_GRAPH", &d.use_graph); rd("RS_GRAPH_SMALL", &d.graph_small); rd("RS_TRAIN_ROI_SIDE", &d.train_roi_side);
   rd("RS_TRAIN_SIDE", &d.train_side); rd("RS_WGRAD_TARGET", &d.wgrad_target); rd("RS_WGRAD_CB", &d.wgrad_cb);
   rd("RS_SELECT_DEBUG", &d.select_debug); rd("RS_NMS_DEBUG", &d.nms_debug); rd("RS_ROI_WINDOW", &d.roi_window); rd("RS_ROI_ORDER", &d.roi_order);
+  rd("RS_POLY_EDGE_CAP", &d.poly_edge_cap); rd("RS_POLY_VERTEX_CAP", &d.poly_vertex_cap);
   g_debug = d;
   g_debug_loaded = true;
 }
@@ -1651,7 +1652,9 @@ int rs_engine_fetch_polygons_async(rs_engine* e, int n, rs_dets* o, rs_polygons*
   { int rc = launch_mask_crops(cp, s); if (rc) return rc; }
   PolyParams pp = e->poly;
   pp.masks = e->masks; pp.rects = e->crop_rects; pp.det_count = e->det_count; pp.instances = n * D; pp.D = D; pp.h = e->tile_h; pp.w = e->tile_w;
-  pp.Wb = cp.Wb; pp.eps = rdp_epsilon; pp.edge_cap = PG_EDGE_CAP; pp.vertex_cap = PG_VERTEX_CAP;
+  pp.Wb = cp.Wb; pp.eps = rdp_epsilon;
+  pp.edge_cap = rs_debug().poly_edge_cap ? rs_debug().poly_edge_cap : PG_EDGE_CAP;
+  pp.vertex_cap = rs_debug().poly_vertex_cap ? rs_debug().poly_vertex_cap : PG_VERTEX_CAP;
   { int rc = launch_polygonize(pp, s); if (rc) return rc; }
   RS_HIP(hipMemcpyAsync(o->count, e->det_count, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   if (o->boxes) RS_HIP(hipMemcpyAsync(o->boxes, e->det_boxes, (size_t)n * D * 16, hipMemcpyDeviceToHost, s));

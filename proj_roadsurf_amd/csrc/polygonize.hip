@@ -566,10 +566,12 @@ void rs_polygonize_caps(int* edge_cap, int* vertex_cap, int* ring_cap, int* max_
   if (max_side) *max_side = PG_MAX_SIDE;
 }
 
-int rs_op_polygonize(const uint8_t* masks_dev, int n, int h, int w, double rdp_epsilon, int edge_cap, int vertex_cap, int32_t* header_dev,
-                     int32_t* poly_ring_count_dev, int32_t* ring_len_dev, int16_t* xy_dev, int32_t* totals_dev, void* stream) {
-  RS_CHECK(masks_dev && n > 0 && header_dev && poly_ring_count_dev && ring_len_dev && xy_dev && totals_dev, RS_ERR_ARG, "rs_op_polygonize: bad argument");
-  RS_CHECK(edge_cap >= 0 && vertex_cap >= 0, RS_ERR_ARG, "rs_op_polygonize: negative cap");
+// the two stand-alone forms: scratch of the call's own, one launch_polygonize, wait
+static int op_polygonize(const char* who, const uint8_t* masks_dev, int n, int slots, const int32_t* det_count_dev, const int32_t* rects_dev, int h, int w,
+                         double rdp_epsilon, int edge_cap, int vertex_cap, int32_t* header_dev, int32_t* poly_ring_count_dev, int32_t* ring_len_dev,
+                         int16_t* xy_dev, int32_t* totals_dev, void* stream) {
+  RS_CHECK(masks_dev && n > 0 && slots > 0 && header_dev && poly_ring_count_dev && ring_len_dev && xy_dev && totals_dev, RS_ERR_ARG, "%s: bad argument", who);
+  RS_CHECK(edge_cap >= 0 && vertex_cap >= 0, RS_ERR_ARG, "%s: negative cap", who);
   hipStream_t s = (hipStream_t)stream;
   size_t b_hdr, b_prc, b_rlen, b_xy;
   const size_t total = polygonize_scratch_bytes(n, &b_hdr, &b_prc, &b_rlen, &b_xy);
@@ -577,7 +579,7 @@ int rs_op_polygonize(const uint8_t* masks_dev, int n, int h, int w, double rdp_e
   RS_HIP(hipMalloc((void**)&scratch, total));
   PolyParams p;
   memset(&p, 0, sizeof p);
-  p.masks = masks_dev; p.instances = n; p.D = 1; p.h = h; p.w = w; p.Wb = (w + 7) / 8; p.eps = rdp_epsilon;
+  p.masks = masks_dev; p.rects = rects_dev; p.det_count = det_count_dev; p.instances = n; p.D = slots; p.h = h; p.w = w; p.Wb = (w + 7) / 8; p.eps = rdp_epsilon;
   p.edge_cap = edge_cap ? edge_cap : PG_EDGE_CAP; p.vertex_cap = vertex_cap ? vertex_cap : PG_VERTEX_CAP;
   p.s_hdr = (int*)scratch; p.s_prc = (uint16_t*)(scratch + b_hdr); p.s_rlen = (uint16_t*)(scratch + b_hdr + b_prc);
   p.s_xy = (uint32_t*)(scratch + b_hdr + b_prc + b_rlen);
@@ -588,6 +590,20 @@ int rs_op_polygonize(const uint8_t* masks_dev, int n, int h, int w, double rdp_e
   if (rc) return rc;
   RS_HIP(he);
   return RS_OK;
+}
+
+int rs_op_polygonize(const uint8_t* masks_dev, int n, int h, int w, double rdp_epsilon, int edge_cap, int vertex_cap, int32_t* header_dev,
+                     int32_t* poly_ring_count_dev, int32_t* ring_len_dev, int16_t* xy_dev, int32_t* totals_dev, void* stream) {
+  return op_polygonize("rs_op_polygonize", masks_dev, n, 1, nullptr, nullptr, h, w, rdp_epsilon, edge_cap, vertex_cap, header_dev, poly_ring_count_dev,
+                       ring_len_dev, xy_dev, totals_dev, stream);
+}
+
+int rs_op_polygonize_crops(const uint8_t* masks_dev, int tiles, int slots, const int32_t* det_count_dev, const int32_t* rects_dev, int h, int w,
+                           double rdp_epsilon, int edge_cap, int vertex_cap, int32_t* header_dev, int32_t* poly_ring_count_dev, int32_t* ring_len_dev,
+                           int16_t* xy_dev, int32_t* totals_dev, void* stream) {
+  RS_CHECK(tiles > 0 && slots > 0 && (long long)tiles * slots <= 0x7FFFFFFF, RS_ERR_ARG, "rs_op_polygonize_crops: %d tiles of %d slots", tiles, slots);
+  return op_polygonize("rs_op_polygonize_crops", masks_dev, tiles * slots, slots, det_count_dev, rects_dev, h, w, rdp_epsilon, edge_cap, vertex_cap, header_dev,
+                       poly_ring_count_dev, ring_len_dev, xy_dev, totals_dev, stream);
 }
 
 }  // extern "C"

@@ -102,12 +102,15 @@ class PolygonTables:
     they were simplified with (0.0 = not simplified).  A flagged instance has no rows here: its mask exceeded the kernel's
     capacities and is vectorised on the host from its crop (``proj_roadsurf_amd.vectorize``)."""
 
-    def __init__(self, header: np.ndarray, poly_ring_count: np.ndarray, ring_len: np.ndarray, xy: np.ndarray, rdp_epsilon: float):
+    def __init__(self, header: np.ndarray, poly_ring_count: np.ndarray, ring_len: np.ndarray, xy: np.ndarray, rdp_epsilon: float,
+                 totals: Optional[np.ndarray] = None):
         self.header = np.ascontiguousarray(header, np.int32).reshape(-1, POLY_HDR)
         self.poly_ring_count = np.ascontiguousarray(poly_ring_count, np.int32)
         self.ring_len = np.ascontiguousarray(ring_len, np.int32)
         self.xy = np.ascontiguousarray(xy, np.int16).reshape(-1, 2)
         self.rdp_epsilon = max(float(rdp_epsilon), 0.0)
+        # the stand-alone operator's totals [polygons, rings, vertices, flagged instances] as the device summed them (None: not carried)
+        self.totals = None if totals is None else np.asarray(totals, np.int32).copy()
 
     @property
     def flagged(self) -> np.ndarray:
@@ -210,6 +213,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.rs_polygonize_caps.argtypes = [i32p, i32p, i32p, i32p]
     lib.rs_polygonize_caps.restype = None
     lib.rs_op_polygonize.argtypes = [vp, i32, i32, i32, C.c_double, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.rs_op_polygonize_crops.argtypes = [vp, i32, i32, vp, vp, i32, i32, C.c_double, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.rs_rasterize_polygons_within_box.argtypes = [f64p, i32p, i32, f64p, i32, u8p]
     lib.rs_memcpy_d2h.argtypes = [vp, vp, C.c_size_t]
     lib.rs_op_fdiv.argtypes = [vp, vp, vp, C.c_int64, vp]

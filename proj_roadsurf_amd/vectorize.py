@@ -93,10 +93,14 @@ def _nested_polygons(lib, r) -> List[List[Polygon]]:
     return out
 
 
-def polygonize_masks_device(packed: np.ndarray, h: int, w: int, rdp_epsilon: float = 0.0, edge_cap: int = 0, vertex_cap: int = 0):
+def polygonize_masks_device(packed: np.ndarray, h: int, w: int, rdp_epsilon: float = 0.0, edge_cap: int = 0, vertex_cap: int = 0,
+                            rects: Optional[np.ndarray] = None, det_count: Optional[np.ndarray] = None, slots: Optional[int] = None):
     """``rs_op_polygonize`` on n bit-packed masks (n, h, ceil(w/8)) uint8: uploads them, runs the device polygoniser
     (csrc/polygonize.hip) and returns ``engine.PolygonTables`` -- header flags included, nothing merged.  Caps of 0 = the
-    kernel's defaults; smaller caps flag more instances (tests reach the fallback with small masks this way)."""
+    kernel's defaults; smaller caps flag more instances (tests reach the fallback with small masks this way).
+    ``rects`` (n, 4) int32 [first byte column, first row, bytes per row, rows], ``det_count`` (n / slots,) and ``slots``: the form
+    the engine calls (``rs_op_polygonize_crops``) -- instance = tile * slots + slot, only the rectangle of a canvas is read, slots at
+    or past their tile's count give all-zero headers."""
     import ctypes as C
     import torch
     from .engine import load_library, _check, PolygonTables, POLY_HDR
@@ -107,21 +111,40 @@ def polygonize_masks_device(packed: np.ndarray, h: int, w: int, rdp_epsilon: flo
         raise ValueError(f"packed masks must be (n,{h},{(w + 7) // 8}), got {packed.shape}")
     if n == 0:
         return PolygonTables(np.zeros((0, POLY_HDR), np.int32), np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros((0, 2), np.int16), rdp_epsilon)
+    crop_form = rects is not None or det_count is not None or slots is not None
+    slots = 1 if slots is None else int(slots)
+    if slots < 1 or n % slots:
+        raise ValueError(f"{n} masks are no whole number of tiles of {slots} slots")
+    if rects is not None:
+        rects = np.ascontiguousarray(rects, dtype=np.int32)
+        if rects.shape != (n, 4):
+            raise ValueError(f"rects must be ({n},4), got {rects.shape}")
+    if det_count is not None:
+        det_count = np.ascontiguousarray(det_count, dtype=np.int32)
+        if det_count.shape != (n // slots,):
+            raise ValueError(f"det_count must be ({n // slots},), got {det_count.shape}")
     caps = [C.c_int32() for _ in range(4)]
     lib.rs_polygonize_caps(*[C.byref(x) for x in caps])
     vcap, rcap = caps[1].value, caps[2].value
     dev = torch.device("cuda")
     m = torch.from_numpy(packed).to(dev)
+    r_dev = torch.from_numpy(rects).to(dev) if rects is not None else None
+    c_dev = torch.from_numpy(det_count).to(dev) if det_count is not None else None
     hdr = torch.zeros((n, POLY_HDR), dtype=torch.int32, device=dev)
     prc = torch.zeros(n * rcap, dtype=torch.int32, device=dev)
     rl = torch.zeros(n * rcap, dtype=torch.int32, device=dev)
     xy = torch.zeros((n * vcap, 2), dtype=torch.int16, device=dev)
     tot = torch.zeros(4, dtype=torch.int32, device=dev)
     torch.cuda.synchronize()
-    _check(lib, lib.rs_op_polygonize(m.data_ptr(), n, h, w, float(rdp_epsilon), int(edge_cap), int(vertex_cap), hdr.data_ptr(), prc.data_ptr(),
-                                     rl.data_ptr(), xy.data_ptr(), tot.data_ptr(), None), "rs_op_polygonize")
+    if crop_form:
+        _check(lib, lib.rs_op_polygonize_crops(m.data_ptr(), n // slots, slots, c_dev.data_ptr() if c_dev is not None else None,
+                                               r_dev.data_ptr() if r_dev is not None else None, h, w, float(rdp_epsilon), int(edge_cap), int(vertex_cap),
+                                               hdr.data_ptr(), prc.data_ptr(), rl.data_ptr(), xy.data_ptr(), tot.data_ptr(), None), "rs_op_polygonize_crops")
+    else:
+        _check(lib, lib.rs_op_polygonize(m.data_ptr(), n, h, w, float(rdp_epsilon), int(edge_cap), int(vertex_cap), hdr.data_ptr(), prc.data_ptr(),
+                                         rl.data_ptr(), xy.data_ptr(), tot.data_ptr(), None), "rs_op_polygonize")
     t = tot.cpu().numpy()
-    return PolygonTables(hdr.cpu().numpy(), prc[:int(t[0])].cpu().numpy(), rl[:int(t[1])].cpu().numpy(), xy[:int(t[2])].cpu().numpy(), rdp_epsilon)
+    return PolygonTables(hdr.cpu().numpy(), prc[:int(t[0])].cpu().numpy(), rl[:int(t[1])].cpu().numpy(), xy[:int(t[2])].cpu().numpy(), rdp_epsilon, totals=t)
 
 
 def polygon_tables_to_lists(polygons, packed: Optional[np.ndarray], h: int, w: int, threads: int = 0) -> List[List[Polygon]]:

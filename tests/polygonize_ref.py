@@ -1,6 +1,7 @@
 """Plain-Python statement of the formulation the device polygoniser implements (csrc/polygonize.hip): a tracer
 without the sequential "remove edges as you walk" state of oracle/host_tail_oracle.py, and Ramer-Douglas-Peucker with an integer
-argmax.  tests/test_polygonize_cpu.py compares it with the oracle; the masks below are shared with tests/test_gpu_polygonize.py.
+argmax.  tests/test_polygonize_cpu.py compares it with the oracle; the masks below are shared with tests/test_gpu_polygonize.py and
+tests/test_gpu_polygonize_limits.py.
 
   1 edges      every foreground pixel, row-major, emits top (E), right (S), bottom (W), left (N) edges, foreground on the right;
                emission index t = 4 * (y * w + x) + k.  A vertex's rank is the smaller t of its (at most two) outgoing edges, an
@@ -30,18 +31,17 @@ def edges_of(mask: np.ndarray) -> List[Tuple[int, int, int]]:
     m = np.zeros((h + 2, w + 2), bool)
     m[1:-1, 1:-1] = mask.astype(bool)
     out = []
-    for y in range(h):
-        for x in range(w):
-            if not m[y + 1, x + 1]:
-                continue
-            if not m[y, x + 1]:
-                out.append((x, y, 0))
-            if not m[y + 1, x + 2]:
-                out.append((x + 1, y, 1))
-            if not m[y + 2, x + 1]:
-                out.append((x + 1, y + 1, 2))
-            if not m[y + 1, x]:
-                out.append((x, y + 1, 3))
+    c = m[1:-1, 1:-1]
+    emits = c & ~(m[:-2, 1:-1] & m[2:, 1:-1] & m[1:-1, :-2] & m[1:-1, 2:])       # foreground with a background neighbour, visited row-major
+    for y, x in zip(*(a.tolist() for a in np.nonzero(emits))):
+        if not m[y, x + 1]:
+            out.append((x, y, 0))
+        if not m[y + 1, x + 2]:
+            out.append((x + 1, y, 1))
+        if not m[y + 2, x + 1]:
+            out.append((x + 1, y + 1, 2))
+        if not m[y + 1, x]:
+            out.append((x, y + 1, 3))
     return out
 
 
@@ -227,3 +227,154 @@ def random_masks(n: int, h: int, w: int, density: float, seed: int) -> np.ndarra
 def pack(masks: np.ndarray) -> np.ndarray:
     """(n, h, w) bool -> (n, h, ceil(w/8)) uint8, the engine's layout (bit b of a byte = pixel 8 * byte + b)."""
     return np.packbits(np.asarray(masks, bool), axis=2, bitorder="little")
+
+
+# ------------------------------------------------------------------------------------------------ masks at the kernel's capacities
+EDGE_CAP, RING_CAP, VERTEX_CAP, MAX_SIDE = 4096, 512, 4096, 1024       # csrc/polygonize.h; the GPU tests compare them with rs_polygonize_caps
+
+
+def edge_count(mask: np.ndarray) -> int:
+    """E: (foreground pixel, 4-neighbour that is background or outside the canvas) pairs."""
+    m = np.pad(np.asarray(mask, bool), 1)
+    c = m[1:-1, 1:-1]
+    return int((c & ~m[:-2, 1:-1]).sum() + (c & ~m[2:, 1:-1]).sum() + (c & ~m[1:-1, :-2]).sum() + (c & ~m[1:-1, 2:]).sum())
+
+
+def counts(mask: np.ndarray) -> Tuple[int, int, int]:
+    """(E, R, V) of a mask by the formulation above: directed edges, rings of mask_to_polygons, closed ring lengths before simplification."""
+    mask = np.asarray(mask, bool)
+    polys = mask_to_polygons(mask)
+    e = edge_count(mask)
+    assert e == len(edges_of(mask))
+    return e, sum(len(p) for p in polys), sum(len(r) for p in polys for r in p)
+
+
+def over_a_cap(c: Tuple[int, int, int]) -> bool:
+    """What the kernel must flag, from the counts alone."""
+    return c[0] > EDGE_CAP or c[1] > RING_CAP or c[2] > VERTEX_CAP
+
+
+def stripes_mask(extra: bool = False) -> np.ndarray:
+    """63 x 64: rows 0, 2, .., 62 set in columns 0..62 -- 32 rectangles of 128 edges; ``extra`` adds pixel (0, 63)."""
+    m = np.zeros((63, 64), bool)
+    m[0::2, 0:63] = True
+    if extra:
+        m[0, 63] = True
+    return m
+
+
+def dots_mask(extra: bool = False) -> np.ndarray:
+    """31 x 63 (33 x 63 with ``extra``): isolated pixels at even row and even column of rows 0..30 -- 512 rings; ``extra`` adds (32, 0)."""
+    m = np.zeros((33 if extra else 31, 63), bool)
+    m[0:31:2, 0::2] = True
+    if extra:
+        m[32, 0] = True
+    return m
+
+
+def vertex_mask(dots: int) -> np.ndarray:
+    """72 x 152: nine diagonal bands two pixels wide (0 <= x - y - 4b <= 1: 4 * 72 + 1 vertices each), two empty columns, then a
+    72 x 40 block of isolated pixels at (even row, odd column) filled row-major (5 vertices each)."""
+    h, w = 72, 152
+    yy, xx = np.mgrid[0:h, 0:w]
+    m = np.zeros((h, w), bool)
+    for b in range(9):
+        m |= (xx - yy - 4 * b >= 0) & (xx - yy - 4 * b <= 1)
+    x0 = int(np.nonzero(m.any(axis=0))[0].max()) + 3
+    assert x0 + 40 <= w and 0 <= dots <= 36 * 20
+    for k in range(dots):
+        m[2 * (k // 20), x0 + 1 + 2 * (k % 20)] = True
+    return m
+
+
+def full_canvas_mask(cleared: bool = False) -> np.ndarray:
+    m = np.ones((MAX_SIDE, MAX_SIDE), bool)
+    if cleared:
+        m[500, 300] = False
+    return m
+
+
+def staircase_mask(n: int = 200) -> np.ndarray:
+    yy, xx = np.mgrid[0:n, 0:n]
+    return xx <= yy
+
+
+def road_mask() -> np.ndarray:
+    """A road three pixels wide across the whole 1024 x 1024 canvas: y = 100 + 0.23 x + 30 sin(x / 160)."""
+    m = np.zeros((MAX_SIDE, MAX_SIDE), bool)
+    x = np.arange(MAX_SIDE)
+    y = np.floor(100.0 + 0.23 * x + 30.0 * np.sin(x / 160.0)).astype(int)
+    for d in (-1, 0, 1):
+        m[y + d, x] = True
+    return m
+
+
+def far_corner_mask() -> np.ndarray:
+    m = np.zeros((MAX_SIDE, MAX_SIDE), bool)
+    m[1000:1024, 1001:1024] = True
+    m[1005:1010, 1005:1012] = False
+    return m
+
+
+# name -> (builder, (E, R, V)): the counts are asserted on the CPU (tests/test_polygonize_cpu.py); the GPU tests predict the flag from them
+CAPACITY_MASKS = {
+    "stripes": (stripes_mask, (4096, 32, 160)),
+    "stripes_plus_pixel": (lambda: stripes_mask(True), (4098, 32, 160)),
+    "dots": (dots_mask, (2048, 512, 2560)),
+    "dots_plus_pixel": (lambda: dots_mask(True), (2052, 513, 2565)),
+    "vertices_299": (lambda: vertex_mask(299), (3806, 308, 4096)),
+    "vertices_300": (lambda: vertex_mask(300), (3810, 309, 4101)),
+    "full_canvas": (full_canvas_mask, (4096, 1, 5)),
+    "full_canvas_cleared_pixel": (lambda: full_canvas_mask(True), (4100, 2, 10)),
+    "staircase_200": (staircase_mask, (800, 1, 403)),
+    "road": (road_mask, (2530, 1, 957)),
+    "far_corner_hole": (far_corner_mask, (118, 2, 10)),
+}
+
+# random 64 x 64 masks that straddle one cap with the other two counts under theirs: (density, seeds, cap straddled)
+RANDOM_POPULATIONS = {"edges": (0.5, tuple(range(8)), 0), "rings": (0.35, tuple(range(8)), 1)}
+
+
+def random_population(which: str) -> List[np.ndarray]:
+    dens, seeds, _ = RANDOM_POPULATIONS[which]
+    return [random_masks(1, 64, 64, dens, s)[0] for s in seeds]
+
+
+# ------------------------------------------------------------------------------------------------ the engine's form of the call: crops
+def pad_to(mask: np.ndarray, h: int, w: int, y0: int = 0, x0: int = 0) -> np.ndarray:
+    """``mask`` placed at (y0, x0) of an empty h x w canvas."""
+    m = np.zeros((h, w), bool)
+    m[y0:y0 + mask.shape[0], x0:x0 + mask.shape[1]] = mask
+    return m
+
+
+def crop_bits(canvas: np.ndarray, rect) -> np.ndarray:
+    """The pixels a rect [first byte column, first row, bytes per row, rows] covers, cut at the canvas width."""
+    x0b, oy, wb, rows = (int(v) for v in rect)
+    return np.asarray(canvas, bool)[oy:oy + rows, 8 * x0b:min(8 * (x0b + wb), canvas.shape[1])]
+
+
+def crop_cases(h: int, w: int) -> Dict[str, Tuple[np.ndarray, Tuple[int, int, int, int], bool]]:
+    """name -> (canvas, rect, the rect holds the whole mask) on a 24 x 40 or 45 x 45 canvas.  Every rect starts at a byte column > 0
+    and a row > 0, so a kernel that forgets an offset gives other vertices, and the hole probes run at shifted coordinates."""
+    assert (h, w) in ((24, 40), (45, 45))
+    x0b, oy = (1, 3) if w == 40 else (2, 20)
+    out: Dict[str, Tuple[np.ndarray, Tuple[int, int, int, int], bool]] = {}
+    small = structured_masks(11, 13)
+    for k in ("ring_with_hole", "nested_rings_island", "exteriors_after_hole"):
+        out[k] = (pad_to(small[k], h, w, oy + 1, 8 * x0b + 2), (x0b, oy, 2, 12), True)
+    # the same masks against the rect's first row and column: vertices on the rect's own border
+    out["nested_at_rect_origin"] = (pad_to(small["nested_rings_island"], h, w, oy, 8 * x0b), (x0b, oy, 2, 12), True)
+    # foreground of a random canvas cut by the rect on all four sides
+    m = random_masks(1, h, w, 0.6, 11 + w)[0]
+    rect = (x0b, oy, 2, 10)
+    y1, xa, xb = oy + 10, 8 * x0b, 8 * x0b + 16
+    m[oy - 1:oy + 1, xa + 3:xa + 6] = True; m[y1 - 1:y1 + 1, xa + 9:xa + 12] = True          # across the first and the last row
+    m[oy + 4:oy + 6, xa - 1:xa + 1] = True; m[oy + 6:oy + 8, xb - 1:xb + 1] = True          # across the first and the last column
+    out["cut_on_four_sides"] = (m, rect, False)
+    if w == 45:
+        # the rect's last byte crosses the canvas width: bytes 3..5 = columns 24..47, of which 24..44 exist
+        m = np.zeros((h, w), bool)
+        m[5:30, 38:45] = True; m[10:20, 40:43] = False; m[12, 41] = True; m[35, 44] = True; m[33:38, 26:30] = True
+        out["last_byte_partial"] = (m, (3, 2, 3, 40), True)
+    return out

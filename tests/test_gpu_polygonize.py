@@ -202,6 +202,75 @@ def test_engine_polygons_equal_crops_plus_host_vectoriser(small, n):
         assert g.has("pred_masks") and np.array_equal(g._packed, r._packed)
 
 
+def _crop_edge_counts(inst):
+    """E of every instance of a tile from its crop bytes, the crop taken as a mask of its own (what the kernel counts)."""
+    rects, offs, data = inst._crops
+    w = inst.image_size[1]
+    out = []
+    for (x0b, oy, wb, rows), o in zip(np.asarray(rects).tolist(), np.asarray(offs).tolist()):
+        bits = np.unpackbits(np.asarray(data[o:o + wb * rows], np.uint8).reshape(rows, wb), axis=1, bitorder="little").astype(bool)
+        out.append(R.edge_count(bits[:, :min(8 * wb, w - 8 * x0b)]))
+    return out
+
+
+def test_engine_fallback_forced_by_the_edge_cap_switch(small, monkeypatch):
+    """RS_POLY_EDGE_CAP at the median edge count of the batch's own crops: about half of the instances are left to the host, their
+    crops come along, and polygons and GeoPackage rows are those of crops + host vectoriser.  Without the switch, no crop travels
+    unless an instance is over the kernel's real capacities."""
+    spec, W, tiles, eng = small
+    ref = _run(eng, tiles, crops=True)
+    counts = [_crop_edge_counts(r) for r in ref]
+    flat = np.array([e for c in counts for e in c])
+    cap = int(np.median(flat))
+    assert len(flat) > 1 and cap >= 1 and flat.max() > cap, f"the edge counts of the crops do not straddle their median: {sorted(flat.tolist())}"
+
+    def check(e2, eps, want_flags):
+        got = _run(e2, tiles, polygons=True, rdp_epsilon=eps)
+        traced = flagged = 0
+        any_flagged = any(len(g._polygons.flagged) for g in got)
+        for i, (g, r) in enumerate(zip(got, ref)):
+            assert _same_dets(g, r), f"tile {i}: detections differ"
+            flags = g._polygons.header[:, 0] != 0
+            ec = np.array(counts[i])
+            if want_flags:
+                assert flags[ec > cap].all(), f"tile {i}: an instance over the cap was traced"
+                assert not flags[ec <= min(cap, 2048)].any(), f"tile {i}: an instance under every cap was flagged"     # R <= E / 4, V <= E + R
+            assert (g._crops is not None) == any_flagged                     # the batch's crops travel exactly when one of its instances needs them
+            assert not g._polygons.header[flags, 1:4].any()
+            assert _lists(g, eps) == _lists(r, eps), f"tile {i} eps {eps}: polygons differ"
+            rows_g = V.instances_to_gpkg_rows(g, f"t{i}.tif", (0.0, 0.0, 64.0, 64.0), eps > 0, eps, srs_id=3857)
+            assert rows_g == V.instances_to_gpkg_rows(r, f"t{i}.tif", (0.0, 0.0, 64.0, 64.0), eps > 0, eps, srs_id=3857)
+            flagged += int(flags.sum())
+            traced += len(g) - int(flags.sum())
+        return traced, flagged, got
+
+    try:
+        with monkeypatch.context() as mp:
+            mp.setenv("RS_POLY_EDGE_CAP", str(cap))
+            e2 = Engine(spec, W, (128, 128, 3), max_batch=3)                 # the switches are read when an engine is created
+            try:
+                for eps in (0.0, 0.75):
+                    traced, flagged, got = check(e2, eps, True)
+                    print(f"engine fallback, edge cap {cap} (median of {len(flat)} crops, E {int(flat.min())}..{int(flat.max())}), eps {eps}: {traced} traced, {flagged} left to the host")
+                    assert flagged > 0 and traced > 0
+                    assert flagged >= int((flat > cap).sum())
+                    assert all(g._crops is not None for g in got if len(g))
+            finally:
+                e2.close()
+    finally:
+        monkeypatch.delenv("RS_POLY_EDGE_CAP", raising=False)
+        e3 = Engine(spec, W, (128, 128, 3), max_batch=3)                     # reads the switches again: the kernel's own caps
+    try:
+        traced, flagged, got = check(e3, 0.75, False)
+        assert traced > 0
+        if flagged:
+            print(f"engine fallback: {flagged} instance(s) are over the kernel's capacities without the switch; the no-crops assertion is not made")
+        else:
+            assert all(g._crops is None for g in got)
+    finally:
+        e3.close()
+
+
 def test_forward_after_a_polygon_fetch_repeats_the_first(small):
     """The engine's result buffers are free once the polygon fetch says so: another forward gives the first one's bits."""
     spec, W, tiles, eng = small

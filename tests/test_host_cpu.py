@@ -30,6 +30,13 @@ def test_library_exports_every_declared_symbol(lib):
     for n in sorted(names):
         assert hasattr(lib, n), f"librs_engine.so does not export {n}"
     assert lib.rs_abi_version() == 1
+    # the polygoniser's crop form is an additive entry: declared, exported, bound with its 16 arguments, and it refuses a call
+    # without buffers before it touches a device
+    assert {"rs_op_polygonize", "rs_op_polygonize_crops", "rs_polygonize_caps"} <= names
+    assert len(lib.rs_op_polygonize_crops.argtypes) == 16 and len(lib.rs_op_polygonize.argtypes) == 13
+    assert lib.rs_op_polygonize_crops(None, 3, 5, None, None, 24, 40, 0.75, 0, 0, None, None, None, None, None, None) != 0
+    assert b"rs_op_polygonize_crops" in lib.rs_last_error()
+    assert lib.rs_op_polygonize_crops(None, 0, 5, None, None, 24, 40, 0.75, 0, 0, None, None, None, None, None, None) != 0
 
 
 def test_rs_spec_layout_matches_header(lib):

@@ -76,6 +76,85 @@ def test_integer_argmax_rdp_equals_the_oracle_on_rings():
     assert n > 3000
 
 
+# ------------------------------------------------------------------------------------------------ masks at the kernel's capacities
+@pytest.mark.parametrize("name", list(R.CAPACITY_MASKS))
+def test_capacity_masks_have_the_stated_counts(name):
+    """(E, R, V) of every mask the GPU tests hold the kernel's caps with, from the Python formulation: the GPU tests predict the
+    kernel's flag from these numbers, never from the kernel."""
+    build, want = R.CAPACITY_MASKS[name]
+    m = build()
+    assert max(m.shape) <= R.MAX_SIDE
+    assert R.counts(m) == want
+    e = R.edges_of(m)
+    assert len(e) == R.edge_count(m) and sorted(R.successor(e)) == list(range(len(e)))
+
+
+def test_capacity_masks_sit_on_both_sides_of_every_cap():
+    c = {k: v[1] for k, v in R.CAPACITY_MASKS.items()}
+    flagged = {k for k, v in c.items() if R.over_a_cap(v)}
+    assert flagged == {"stripes_plus_pixel", "dots_plus_pixel", "vertices_300", "full_canvas_cleared_pixel"}
+    assert c["stripes"][0] == R.EDGE_CAP and c["full_canvas"][0] == R.EDGE_CAP and c["dots"][1] == R.RING_CAP and c["vertices_299"][2] == R.VERTEX_CAP
+    # each over-the-cap mask exceeds ONE cap only
+    assert [sum(a > b for a, b in zip(c[k], (R.EDGE_CAP, R.RING_CAP, R.VERTEX_CAP))) for k in sorted(flagged)] == [1, 1, 1, 1]
+    assert c["stripes_plus_pixel"][0] > R.EDGE_CAP and c["dots_plus_pixel"][1] > R.RING_CAP and c["vertices_300"][2] > R.VERTEX_CAP
+    lib = load_library()
+    caps = [C.c_int32() for _ in range(4)]
+    lib.rs_polygonize_caps(*[C.byref(x) for x in caps])
+    assert tuple(x.value for x in caps) == (R.EDGE_CAP, R.VERTEX_CAP, R.RING_CAP, R.MAX_SIDE)
+
+
+@pytest.mark.parametrize("which", list(R.RANDOM_POPULATIONS))
+def test_random_populations_straddle_one_cap(which):
+    k = R.RANDOM_POPULATIONS[which][2]
+    caps = (R.EDGE_CAP, R.RING_CAP, R.VERTEX_CAP)
+    cs = [R.counts(m) for m in R.random_population(which)]
+    assert any(c[k] > caps[k] for c in cs) and any(c[k] <= caps[k] for c in cs), [c[k] for c in cs]
+    for c in cs:
+        assert all(c[j] <= caps[j] for j in range(3) if j != k), c
+
+
+def test_capacity_masks_equal_the_oracle():
+    """The formulation at its limits against the oracle: a ring of 403 vertices around the corner distance, 512 rings, long chords."""
+    s = 0.7071067811865476
+    for name in ("stripes", "dots", "vertices_299", "staircase_200", "far_corner_hole"):
+        m = R.CAPACITY_MASKS[name][0]()
+        for eps in (0.0, 0.75, float(np.nextafter(s, 0.0)), s, float(np.nextafter(s, 1.0))):
+            assert _as_float(R.polygons(m, eps)) == _oracle(m, eps), (name, eps)
+
+
+@pytest.mark.parametrize("hw", [(24, 40), (45, 45)], ids=["40x24", "45x45"])
+def test_host_crops_equal_host_canvases_where_the_rect_holds_the_mask(hw):
+    """The reference of the GPU crop tests: rs_vectorize_mask_crops on bytes cut with numpy gives rs_vectorize_masks' arrays when the
+    rect contains the mask, and the arrays of the rect's own pixels when it cuts through."""
+    h, w = hw
+    lib = load_library()
+    cases = R.crop_cases(h, w)
+    for name, (canvas, rect, whole) in cases.items():
+        x0b, oy, wb, rows = rect
+        assert x0b > 0 and oy > 0 and oy + rows <= h and x0b + wb <= (w + 7) // 8, name
+        bits = R.crop_bits(canvas, rect)
+        assert whole == (int(bits.sum()) == int(canvas.sum())), name
+        if name == "cut_on_four_sides":
+            assert bits[0].any() and bits[-1].any() and bits[:, 0].any() and bits[:, -1].any()
+        if name == "last_byte_partial":
+            assert bits.shape[1] == 21 and bits[:, -1].any()
+        packed = R.pack(canvas[None])
+        data = np.ascontiguousarray(packed[0, oy:oy + rows, x0b:x0b + wb]).reshape(-1)
+        rects = np.array([rect], np.int32); offs = np.zeros(1, np.uint32)
+        for eps in (0.0, 0.75):
+            r = lib.rs_vectorize_mask_crops(data.ctypes.data_as(C.c_void_p), rects.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), 1, h, w, eps, 1)
+            assert r
+            got = _vec_arrays(lib, r)
+            lib.rs_vec_free(r)
+            other = R.pack(R.pad_to(bits, h, w, oy, 8 * x0b)[None])          # the rect's pixels alone on the canvas
+            for ref in ([other] + ([packed] if whole else [])):
+                q = lib.rs_vectorize_masks(ref.ctypes.data_as(C.c_void_p), 1, h, w, eps, 1)
+                want = _vec_arrays(lib, q)
+                lib.rs_vec_free(q)
+                for a, b in zip(got, want):
+                    assert a.dtype == b.dtype and np.array_equal(a, b), (name, eps)
+
+
 # ------------------------------------------------------------------------------------------------ rs_vec_from_tables
 def _vec_arrays(lib, r):
     c = [C.c_int64() for _ in range(4)]
