@@ -6,15 +6,8 @@
 #include <string.h>
 
 #include <cmath>
-#include <functional>
-#include <map>
-#include <set>
-#include <string>
-#include <vector>
 
-#include "../../include/rs_engine.h"
-#include "detect.h"
-#include "polygonize.h"
+#include "engine_internal.h"
 #include "train.h"
 
 // ------------------------------------------------------------------------------------- errors
@@ -47,47 +40,6 @@ void rs_set_error(const char* fmt, ...) {
   vsnprintf(g_err, sizeof g_err, fmt, a);
   va_end(a);
 }
-
-namespace {
-
-// DT_SPLIT16: an activation of the split-operand mode -- two fp16 planes of the registered shape back to back (hi, then lo); value = hi + lo
-enum { DT_F16 = 1, DT_F32 = 2, DT_I32 = 3, DT_U8 = 4, DT_SPLIT16 = 5 };
-static size_t dt_size(int dt) { return (dt == DT_F16 || dt == DT_SPLIT16) ? 2 : (dt == DT_U8 ? 1 : 4); }
-
-struct TensorInfo {
-  std::string name;
-  void* p = nullptr;
-  int dtype = 0, ndim = 0, halo = 0;
-  int64_t dims[5] = {1, 1, 1, 1, 1};
-  size_t bytes = 0;
-};
-
-struct Act {   // NHWC fp16 activation with halo
-  half_t* p = nullptr;
-  long long lo = 0;   // split-operand mode: element offset of the lo plane behind p (0 = single plane)
-  int N = 0, H = 0, W = 0, C = 0, pad = 0;
-  int Hp() const { return H + 2 * pad; }
-  int Wp() const { return W + 2 * pad; }
-};
-
-struct Stage {
-  std::string name;
-  std::function<int(int, hipStream_t)> fn;
-  double flops_per_image = 0, bytes_per_image = 0;   // algorithmic, per tile (0 = n/a)
-  double ms_total = 0;
-  int calls = 0;
-  double last_flops = 0, last_bytes = 0;
-  int variant = -2;      // conv tile variant of the last call (-2 = not a conv stage)
-  bool narrow = false;   // latency-bound detection glue (few workgroups): runs on the engine's side stream
-  bool grad_side = false;   // trainer: weight / bias gradient, off the input-gradient chain (may run on the trainer's side stream)
-  int bucket = -1;          // trainer: gradient bucket this stage writes into (rs_trainer::buckets), -1 = none
-  int phase = 0;         // 0 = preprocess..RPN proposals, 1 = box head..detections, 2 = mask head + paste
-  hipEvent_t handoff = nullptr;   // recorded on the previous stage's stream when this stage switches streams
-};
-
-struct BlobEntry { const void* host; void* dev; int dtype; int ndim; int64_t dims[4]; size_t nbytes; };
-
-}  // namespace
 
 // host-only helpers -------------------------------------------------------------------------
 extern "C" void rs_resize_shape(int h, int w, int short_edge, int max_size, int* new_h, int* new_w) {
@@ -143,215 +95,6 @@ extern "C" int rs_resize_coeffs(int in_size, int out_size, int32_t* bounds, int3
 }
 
 // =================================================================================== engine
-struct rs_engine {
-  rs_spec spec;
-  int device = 0;
-  hipStream_t stream = nullptr;         // "wide" stream: every kernel that fills the chip (may be shared between engines)
-  bool own_stream = false;
-  hipStream_t copy_stream = nullptr;    // device-to-host result copies (rs_engine_fetch_async), overlapping the next batch
-  hipEvent_t ev_results = nullptr;      // recorded on `stream` when a forward's results are complete
-  hipEvent_t ev_copied = nullptr;       // recorded on `copy_stream` after the last result copy; the next forward's box head waits for it
-  bool copy_pending = false;
-  hipStream_t narrow = nullptr;         // side stream for the latency-bound glue kernels (null = everything on `stream`)
-  bool on_narrow = false;               // which stream the most recently enqueued stage went to
-  hipEvent_t ev_join = nullptr;         // narrow -> wide join at the end of a forward that ends on the side stream
-  bool cur_record = false;              // profiling decision of the forward in flight (taken at phase 0)
-  int max_batch = 0, tile_h = 0, tile_w = 0, tile_c = 0;
-  int net_h = 0, net_w = 0, pad_h = 0, pad_w = 0;
-  int use_glds = 1;    // -1 = fp32 validation path (launch_conv forwards to launch_conv_f32)
-  bool f32 = false;    // rs_spec.precision == 1: activations and weights are float
-  bool split = false;  // rs_spec.precision == 2: split-operand mode -- activations and weights as hi + lo fp16 planes, three MFMA passes (common.h ConvParams::split)
-  int profiling = 0;   // 0 off, 1 = events + host sync per stage, 2 = events only (resolved later)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;   // mode 2
-  std::vector<int> ev_stage;
-  std::vector<int> ev_batch;
-  size_t ev_used = 0;
-  int resolve_profile();
-
-  void* blob_dev = nullptr;
-  std::map<std::string, BlobEntry> blob;
-  std::vector<void*> allocs;
-  std::vector<TensorInfo> tensors;
-  std::vector<Stage> stages;
-
-  uint8_t* tiles_dev = nullptr;
-  // per-image resized sizes inside the net_h x net_w canvas (training: INPUT.MIN_SIZE_TRAIN drawn per image, the batch padded to the
-  // largest -- [EXT d2: data/dataset_mapper.py, structures/image_list.py]); empty = every image fills the canvas
-  struct ResizeTab { int* b = nullptr; int* k = nullptr; int ks = 0; };
-  std::map<int, ResizeTab> tab_h, tab_v;   // by output size
-  std::vector<int> img_new_h, img_new_w;
-  float* img_hw_dev = nullptr;             // [max_batch][2] clip size of the proposals per image (h, w)
-  int resize_tab(int in_size, int out_size, std::map<int, ResizeTab>& cache, ResizeTab* out);
-  int set_image_sizes(const int32_t* new_h, const int32_t* new_w, int n);
-  // results (device)
-  int* det_count = nullptr;
-  float* det_boxes = nullptr;
-  float* det_boxes_net = nullptr;
-  float* det_scores = nullptr;
-  int* det_classes = nullptr;
-  uint8_t* masks = nullptr;
-  float* mask_probs = nullptr;
-  int D = 0;
-  // mask crops for the host (rs_engine_fetch_crops_*): table + compacted data on the device, byte count read back pinned
-  int* crop_rects = nullptr;
-  unsigned int* crop_offsets = nullptr;
-  unsigned long long* crop_total = nullptr;
-  uint8_t* crop_data = nullptr;
-  unsigned long long* h_crop_total = nullptr;   // pinned
-  hipEvent_t ev_crop_hdr = nullptr;
-  // polygons for the host (rs_engine_fetch_polygons_*): allocated on the first call, an engine that never asks keeps none of it
-  PolyParams poly;                              // scratch + compacted tables on the device
-  bool poly_ready = false;
-  int* h_poly_totals = nullptr;                 // pinned [4]
-  hipEvent_t ev_poly_hdr = nullptr;
-
-  // the precision of the activations, as the launchers take it (PreprocParams::out_f32, RoiAlignParams::f32, MaskPredictParams::f32)
-  int prec_code() const { return f32 ? 1 : (split ? 2 : 0); }
-  int planes() const { return split ? 2 : 1; }        // fp16 planes per activation / weight
-  size_t esize() const { return f32 ? 4 : 2; }        // bytes per element of one plane
-
-  int alloc(void** p, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    bytes = (bytes + 255) & ~(size_t)255;
-    RS_HIP(hipMalloc(p, bytes));
-    allocs.push_back(*p);
-    RS_HIP(hipMemsetAsync(*p, 0, bytes, stream));
-    return RS_OK;
-  }
-  // A zeroed device buffer of the given shape, entered in the tensor table (rs_engine_tensor); buffers nobody inspects take plain alloc
-  template <class T>
-  int new_tensor(T** p, const std::string& name, int dtype, std::vector<int64_t> dims, int halo = 0) {
-    TensorInfo t;
-    t.name = name; t.dtype = dtype; t.ndim = (int)dims.size(); t.halo = halo;
-    size_t nb = dt_size(dtype);
-    for (size_t i = 0; i < dims.size(); ++i) { t.dims[i] = dims[i]; nb *= (size_t)dims[i]; }
-    t.bytes = dtype == DT_SPLIT16 ? 2 * nb : nb;
-    int rc = alloc((void**)p, t.bytes);
-    if (rc) return rc;
-    t.p = *p;
-    tensors.push_back(t);
-    return RS_OK;
-  }
-  int new_act(Act* a, const std::string& name, int N, int H, int W, int C, int pad) {
-    a->N = N; a->H = H; a->W = W; a->C = C; a->pad = pad;
-    a->lo = split ? (long long)N * a->Hp() * a->Wp() * C : 0;
-    return new_tensor(&a->p, name, f32 ? DT_F32 : (split ? DT_SPLIT16 : DT_F16), {N, a->Hp(), a->Wp(), C}, pad);
-  }
-  // Appends a stage and returns it for its `fn`.  A stage that counts saturated values passes the address of its launch parameters'
-  // `sat` field and gets the counter of its own position in `stages` (null in a trainer's forward engine).  Call it in a statement of
-  // its own, before the lambda that copies the parameters: in `add_stage(..).fn = [p]..` the right-hand side is evaluated first.
-  Stage& add_stage(const std::string& name, double flops_per_image, double bytes_per_image, unsigned long long** sat = nullptr) {
-    if (sat) *sat = sat_dev ? sat_dev + stages.size() : nullptr;
-    stages.emplace_back();
-    Stage& st = stages.back();
-    st.name = name; st.flops_per_image = flops_per_image; st.bytes_per_image = bytes_per_image;
-    return st;
-  }
-  const BlobEntry* find(const std::string& n) {
-    auto it = blob.find(n);
-    return it == blob.end() ? nullptr : &it->second;
-  }
-  // GEMM weights of a layer: "<layer>.w" (fp16) or "<layer>.w32" in the fp32 validation mode
-  // split-operand mode: "<layer>.ws" = fp16 [2][rows][Kpad] (hi rows, then lo rows, of the row-scaled weight) + "<layer>.wsi" fp32 [rows] (inverse scales)
-  const BlobEntry* findw(const std::string& layer) { return find(layer + (f32 ? ".w32" : (split ? ".ws" : ".w"))); }
-  int wrows(const BlobEntry* w) const { return (int)(split ? w->dims[0] / 2 : w->dims[0]); }
-  // fills the split-operand fields of a conv whose weight entry is w (no-op in the other modes)
-  int set_split(ConvParams* p, const std::string& wname, const BlobEntry* w, const Act* in, const Act* out, const Act* res, const Act* up, const Act* in2) {
-    if (!split) return RS_OK;
-    const BlobEntry* si = find(wname + ".wsi");
-    RS_CHECK(si && si->dtype == DT_F32 && si->dims[0] >= w->dims[0] / 2 && (w->dims[0] & 1) == 0, RS_ERR_BLOB, "row scales of %s missing from blob (split-operand mode)", wname.c_str());
-    p->split = 1;
-    p->wscale = (const float*)si->dev;
-    p->w_lo = (long long)(w->dims[0] / 2) * w->dims[1];
-    if (in) p->in_lo = in->lo;
-    if (out) p->out_lo = out->lo;
-    if (res) p->res_lo = res->lo;
-    if (up) p->up_lo = up->lo;
-    if (in2) p->in2_lo = in2->lo;
-    return RS_OK;
-  }
-  int parse_blob(const void* data, size_t nbytes);
-  struct DeferredConv { ConvParams p; int m_per_image = 0; double flops = 0, bytes = 0; };
-  struct ConvDesc {                  // one conv / linear stage (add_conv): ConvDesc{k, stride, pad, relu}, the rest by name
-    int k = 1, stride = 1, pad = 0;
-    bool relu = false;
-    const Act* res = nullptr;        // residual added before the ReLU
-    const Act* up = nullptr;         // coarser map added 2x-upsampled (FPN top-down path)
-    int cin_real = 0;                // input channels in the FLOP count (stem: 3 of 8 padded channels); 0 = in.C
-    int units_per_tile = 1;          // images of the conv per input tile (1 for feature maps, D for per-RoI maps)
-    const int* m_count = nullptr;    // device-side count of units actually present
-    const Act* in2 = nullptr;        // second K source: 1x1 taps at stride2 (projection shortcut folded into conv3)
-    int stride2 = 1;
-    DeferredConv* defer = nullptr;   // filled instead of a stage: the caller merges it into a multi-map launch (add_merged_convs)
-  };
-  int add_conv(const std::string& name, const std::string& wname, const Act& in, const Act& out, const ConvDesc& d);
-  int add_merged_convs(const std::string& name, const std::vector<DeferredConv>& d);
-  // ---- the graph builder: build() runs the sections below in order; `Graph` is what one section hands to the next
-  // (the detections a forward returns are the det_* members above)
-  struct Graph {
-    Act x0, c1, res_out[4], P[5];
-    Act rpn_t[RS_MAX_LEVELS];          // 3x3 RPN conv outputs (written only where the heads are not fused into it)
-    float* rpn_ho[RS_MAX_LEVELS];      // RPN head outputs (objectness + deltas)
-    float* prop_boxes = nullptr;
-    int *prop_count = nullptr, *prop_level = nullptr, *prop_order = nullptr;
-    float* pred = nullptr;             // box predictor output
-    int *slot_list = nullptr, *det_total = nullptr;   // compacted detection slots of the batch, for the mask head
-  };
-  struct ResCursor {                   // running state of the residual stages, block to block
-    Act cur;
-    Act t1_pre;                        // conv1 output of the NEXT block when the previous block's fused tail already produced it
-    bool have_t1 = false;
-    int bott = 64, cout = 0;
-  };
-  int build();
-  int build_input(Graph& g);
-  int build_stem(Graph& g);
-  int build_res_stages(Graph& g);
-  int build_bottleneck(ResCursor& r, int si, int bi);
-  int add_fused_tail(const std::string& nm, const std::string& next, const Act& t1, const Act& x, const Act& out, const Act* t1n, bool proj);
-  int build_fpn(Graph& g);
-  int build_rpn(Graph& g);
-  int build_box_head(Graph& g);
-  int build_mask_head(Graph& g);
-  // FPN output convs / RPN 3x3 of all levels as one multi-map launch each
-  bool merge_maps() const { return merge_levels && !f32 && rs_debug().conv_deep && use_glds > 0; }
-  int add_nms_rule(const char* head, NmsParams* np, int group);
-  RoiAlignParams roi_align_levels(const Graph& g) const;
-  int run(const uint8_t* tiles, int n, int phase = -1);
-  int run_stages(int n, bool record, int phase = -1, bool all_wide = false);
-  int assign_phases();
-  int use_graph = 0;
-  int fuse_shortcut = 1;
-  int fuse_bneck = 1;
-  int fuse_stem = 1;      // stem conv + ReLU + max-pool as one launch (inference engines, fp16 path)
-  bool frozen_fusions_only = false;   // a trainer's forward engine: layer fusions only where nothing is differentiated (stem + res2 at FREEZE_AT 2)
-  int merge_levels = 1;   // FPN output convs / RPN 3x3 of all levels as one multi-map launch each (inference engines, fp16 path)
-  long long forward_index = 0;
-  // Saturation counts: one u64 per stage, indexed like `stages`; inference engines only (a trainer's forward engine: null).
-  // Every forward zeroes the live array at its start and copies it to the snapshot at the end of its last phase; the fetches copy the
-  // snapshot only, so a next forward that is already counting never races a result copy.
-  static constexpr int kSatCap = 512;
-  unsigned long long* sat_dev = nullptr;     // live counters of the forward in flight
-  unsigned long long* sat_snap = nullptr;    // the last finished forward's
-  unsigned long long* h_sat_copy = nullptr;  // pinned target of the fetch copies
-  bool sat_copy_pending = false;
-  std::vector<int64_t> h_sat;                // the most recent fetched forward's
-  int sat_copy(hipStream_t s) {
-    if (!sat_dev) return RS_OK;
-    RS_HIP(hipMemcpyAsync(h_sat_copy, sat_snap, stages.size() * 8, hipMemcpyDeviceToHost, s));
-    sat_copy_pending = true;
-    return RS_OK;
-  }
-  void sat_publish() {
-    if (!sat_copy_pending) return;
-    h_sat.assign(h_sat_copy, h_sat_copy + stages.size());
-    sat_copy_pending = false;
-  }
-  std::set<int> warmed;
-  std::map<int, hipGraphExec_t> graphs;
-};
-
 int rs_engine::parse_blob(const void* data, size_t nbytes) {
   const uint8_t* b = (const uint8_t*)data;
   RS_CHECK(nbytes >= 16, RS_ERR_BLOB, "weight blob too small");
@@ -1330,32 +1073,104 @@ int rs_engine::resolve_profile() {
   return RS_OK;
 }
 
+// ---- the steps of a result fetch (rs_engine_fetch and the rs_engine_fetch_*_async / _wait entries)
+int rs_engine::ensure_crop_header() {
+  if (ev_crop_hdr) return RS_OK;
+  RS_HIP(hipEventCreateWithFlags(&ev_crop_hdr, hipEventDisableTiming));
+  RS_HIP(hipHostMalloc((void**)&h_crop_total, 16, hipHostMallocDefault));
+  return RS_OK;
+}
+
+int rs_engine::ensure_polygon_buffers() {
+  if (poly_ready) return RS_OK;
+  const int inst = max_batch * D;
+  size_t b_hdr, b_prc, b_rlen, b_xy;
+  polygonize_scratch_bytes(inst, &b_hdr, &b_prc, &b_rlen, &b_xy);
+  PolyParams& q = poly;
+  memset(&q, 0, sizeof q);
+  int rc;
+  if ((rc = alloc((void**)&q.s_hdr, b_hdr))) return rc;
+  if ((rc = alloc((void**)&q.s_prc, b_prc))) return rc;
+  if ((rc = alloc((void**)&q.s_rlen, b_rlen))) return rc;
+  if ((rc = alloc((void**)&q.s_xy, b_xy))) return rc;
+  if ((rc = alloc((void**)&q.header, (size_t)inst * PG_HDR * 4))) return rc;
+  if ((rc = alloc((void**)&q.poly_ring_count, (size_t)inst * PG_RING_CAP * 4))) return rc;
+  if ((rc = alloc((void**)&q.ring_len, (size_t)inst * PG_RING_CAP * 4))) return rc;
+  if ((rc = alloc((void**)&q.xy, (size_t)inst * PG_VERTEX_CAP * 4))) return rc;
+  if ((rc = alloc((void**)&q.totals, 16))) return rc;
+  RS_HIP(hipEventCreateWithFlags(&ev_poly_hdr, hipEventDisableTiming));
+  RS_HIP(hipHostMalloc((void**)&h_poly_totals, 16, hipHostMallocDefault));
+  poly_ready = true;
+  return RS_OK;
+}
+
+int rs_engine::begin_fetch(hipStream_t* s) {
+  if (!copy_stream) {
+    RS_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+    RS_HIP(hipEventCreateWithFlags(&ev_results, hipEventDisableTiming));
+    RS_HIP(hipEventCreateWithFlags(&ev_copied, hipEventDisableTiming));
+  }
+  RS_HIP(hipEventRecord(ev_results, stream));          // everything enqueued so far for this engine (its last phase included)
+  RS_HIP(hipStreamWaitEvent(copy_stream, ev_results, 0));
+  *s = copy_stream;
+  return RS_OK;
+}
+
+int rs_engine::end_fetch(hipStream_t s, hipEvent_t header) {
+  { int rc = sat_copy(s); if (rc) return rc; }
+  RS_HIP(hipEventRecord(ev_copied, s));
+  if (header) RS_HIP(hipEventRecord(header, s));
+  copy_pending = true;
+  return RS_OK;
+}
+
+int rs_engine::enqueue_dets(const rs_dets* o, int n, hipStream_t s, bool want_masks) {
+  RS_HIP(hipMemcpyAsync(o->count, det_count, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  if (o->boxes) RS_HIP(hipMemcpyAsync(o->boxes, det_boxes, (size_t)n * D * 16, hipMemcpyDeviceToHost, s));
+  if (o->scores) RS_HIP(hipMemcpyAsync(o->scores, det_scores, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
+  if (o->classes) RS_HIP(hipMemcpyAsync(o->classes, det_classes, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
+  if (want_masks && o->masks && masks) RS_HIP(hipMemcpyAsync(o->masks, masks, (size_t)n * D * tile_h * ((tile_w + 7) / 8), hipMemcpyDeviceToHost, s));
+  return RS_OK;
+}
+
+int rs_engine::launch_crops(int n, hipStream_t s) {
+  CropParams cp;
+  memset(&cp, 0, sizeof cp);
+  cp.det_boxes = det_boxes; cp.det_count = det_count; cp.masks = masks; cp.n = n; cp.D = D; cp.h = tile_h; cp.w = tile_w;
+  cp.Wb = (tile_w + 7) / 8; cp.rects = crop_rects; cp.offsets = crop_offsets; cp.total = crop_total; cp.data = crop_data;
+  return launch_mask_crops(cp, s);
+}
+
+int rs_engine::launch_polygons(int n, double rdp_epsilon, hipStream_t s) {
+  PolyParams pp = poly;
+  pp.masks = masks; pp.rects = crop_rects; pp.det_count = det_count; pp.instances = n * D; pp.D = D; pp.h = tile_h; pp.w = tile_w;
+  pp.Wb = (tile_w + 7) / 8; pp.eps = rdp_epsilon;
+  pp.edge_cap = rs_debug().poly_edge_cap ? rs_debug().poly_edge_cap : PG_EDGE_CAP;
+  pp.vertex_cap = rs_debug().poly_vertex_cap ? rs_debug().poly_vertex_cap : PG_VERTEX_CAP;
+  return launch_polygonize(pp, s);
+}
+
+int rs_engine::enqueue_crop_table(rs_mask_crops* c, int n, hipStream_t s) {
+  RS_HIP(hipMemcpyAsync(c->rects, crop_rects, (size_t)n * D * 16, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(c->offsets, crop_offsets, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(h_crop_total, crop_total, 8, hipMemcpyDeviceToHost, s));
+  return RS_OK;
+}
+
+// after the header event: the byte count has landed, copy exactly the bytes in use
+int rs_engine::enqueue_crop_bytes(rs_mask_crops* c, hipStream_t s) {
+  const unsigned long long used = *h_crop_total;
+  RS_CHECK(used <= c->capacity, RS_ERR_ARG, "mask crops need %llu bytes, the caller's buffer holds %llu", used, (unsigned long long)c->capacity);
+  c->used = used;
+  if (used) RS_HIP(hipMemcpyAsync(c->data, crop_data, (size_t)used, hipMemcpyDeviceToHost, s));
+  return RS_OK;
+}
+
 // ===================================================================================== C ABI
 extern "C" {
 
 const char* rs_last_error(void) { return g_err; }
 int rs_abi_version(void) { return RS_ABI_VERSION; }
-
-// rs_fdiv (common.h) as an operator, for its test: out[i] = a[i] / b[i] through the device code's division
-__global__ void fdiv_kernel(const float* a, const float* b, float* out, long long n) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = rs_fdiv(a[i], b[i]);
-}
-int rs_op_fdiv(const float* a, const float* b, float* out, int64_t n, void* stream) {
-  RS_CHECK(a && b && out && n > 0, RS_ERR_ARG, "bad argument");
-  hipLaunchKernelGGL(fdiv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, b, out, (long long)n);
-  RS_HIP(hipGetLastError());
-  return RS_OK;
-}
-
-int rs_memcpy_d2h(void* dst, const void* src, size_t n) {
-  RS_HIP(hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));
-  return RS_OK;
-}
-int rs_memcpy_h2d(void* dst, const void* src, size_t n) {
-  RS_HIP(hipMemcpy(dst, src, n, hipMemcpyHostToDevice));
-  return RS_OK;
-}
 
 int rs_spec_batched_nms(const rs_spec* spec) {
   RS_CHECK(spec, RS_ERR_ARG, "null argument");
@@ -1369,8 +1184,8 @@ int rs_spec_batched_nms(const rs_spec* spec) {
 }  // extern "C"
 
 // rs_engine_create, or with `for_trainer` the forward engine of an rs_trainer (rs_engine::frozen_fusions_only)
-static int engine_create(const rs_spec* spec, const void* weights, size_t nbytes, int device_ordinal, int max_batch,
-                         int tile_h, int tile_w, int tile_c, void* stream, bool for_trainer, rs_engine** out) {
+int engine_create(const rs_spec* spec, const void* weights, size_t nbytes, int device_ordinal, int max_batch,
+                  int tile_h, int tile_w, int tile_c, void* stream, bool for_trainer, rs_engine** out) {
   RS_CHECK(spec && weights && out, RS_ERR_ARG, "null argument");
   const int nms_mode = rs_spec_batched_nms(spec);     // checks struct_size: the current struct, or the one that ends before batched_nms (mode 0)
   if (nms_mode < 0) return nms_mode;
@@ -1490,21 +1305,13 @@ int rs_engine_sync(rs_engine* e) {
 int rs_engine_fetch(rs_engine* e, int n, rs_dets* o) {
   RS_CHECK(e && o && o->count, RS_ERR_ARG, "null argument");
   RS_CHECK(n >= 1 && n <= e->max_batch, RS_ERR_ARG, "batch %d", n);
-  const int D = e->D;
+  RS_CHECK(!o->masks || e->masks, RS_ERR_ARG, "masks requested but MASK_ON is false");
+  RS_CHECK(!o->mask_probs || e->mask_probs, RS_ERR_ARG, "mask_probs requested but MASK_ON is false");
   hipStream_t s = e->stream;
-  RS_HIP(hipMemcpyAsync(o->count, e->det_count, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-  if (o->boxes) RS_HIP(hipMemcpyAsync(o->boxes, e->det_boxes, (size_t)n * D * 16, hipMemcpyDeviceToHost, s));
-  if (o->scores) RS_HIP(hipMemcpyAsync(o->scores, e->det_scores, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
-  if (o->classes) RS_HIP(hipMemcpyAsync(o->classes, e->det_classes, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
-  if (o->masks) {
-    RS_CHECK(e->masks, RS_ERR_ARG, "masks requested but MASK_ON is false");
-    RS_HIP(hipMemcpyAsync(o->masks, e->masks, (size_t)n * D * e->tile_h * ((e->tile_w + 7) / 8), hipMemcpyDeviceToHost, s));
-  }
-  if (o->mask_probs) {
-    RS_CHECK(e->mask_probs, RS_ERR_ARG, "mask_probs requested but MASK_ON is false");
-    RS_HIP(hipMemcpyAsync(o->mask_probs, e->mask_probs, (size_t)n * D * RS_MASK_SIDE * RS_MASK_SIDE * 4, hipMemcpyDeviceToHost, s));
-  }
-  { int rc = e->sat_copy(s); if (rc) return rc; }
+  int rc;
+  if ((rc = e->enqueue_dets(o, n, s, true))) return rc;
+  if (o->mask_probs) RS_HIP(hipMemcpyAsync(o->mask_probs, e->mask_probs, (size_t)n * e->D * RS_MASK_SIDE * RS_MASK_SIDE * 4, hipMemcpyDeviceToHost, s));
+  if ((rc = e->sat_copy(s))) return rc;
   RS_HIP(hipStreamSynchronize(s));
   e->sat_publish();
   return RS_OK;
@@ -1537,70 +1344,34 @@ int rs_engine_upload_async(rs_engine* e, const uint8_t* tiles_host, int n) {
   return RS_OK;
 }
 
+// The three asynchronous fetches are sequences of the rs_engine fetch steps above (engine_internal.h).  On the copy stream, in this order:
+// crop kernel, polygon kernel, detection copies, crop table, polygon headers, saturation snapshot, ev_copied, the header event.
 int rs_engine_fetch_async(rs_engine* e, int n, rs_dets* o) {
   RS_CHECK(e && o && o->count && n >= 1 && n <= e->max_batch, RS_ERR_ARG, "bad argument");
-  if (!e->copy_stream) {
-    RS_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
-    RS_HIP(hipEventCreateWithFlags(&e->ev_results, hipEventDisableTiming));
-    RS_HIP(hipEventCreateWithFlags(&e->ev_copied, hipEventDisableTiming));
-  }
-  const int D = e->D;
-  hipStream_t s = e->copy_stream;
-  RS_HIP(hipEventRecord(e->ev_results, e->stream));          // everything enqueued so far for this engine (its last phase included)
-  RS_HIP(hipStreamWaitEvent(s, e->ev_results, 0));
-  RS_HIP(hipMemcpyAsync(o->count, e->det_count, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-  if (o->boxes) RS_HIP(hipMemcpyAsync(o->boxes, e->det_boxes, (size_t)n * D * 16, hipMemcpyDeviceToHost, s));
-  if (o->scores) RS_HIP(hipMemcpyAsync(o->scores, e->det_scores, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
-  if (o->classes) RS_HIP(hipMemcpyAsync(o->classes, e->det_classes, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
-  if (o->masks && e->masks) RS_HIP(hipMemcpyAsync(o->masks, e->masks, (size_t)n * D * e->tile_h * ((e->tile_w + 7) / 8), hipMemcpyDeviceToHost, s));
-  { int rc = e->sat_copy(s); if (rc) return rc; }
-  RS_HIP(hipEventRecord(e->ev_copied, s));
-  e->copy_pending = true;
-  return RS_OK;
+  hipStream_t s = nullptr;
+  int rc;
+  if ((rc = e->begin_fetch(&s))) return rc;
+  if ((rc = e->enqueue_dets(o, n, s, true))) return rc;
+  return e->end_fetch(s, nullptr);
 }
 
 int rs_engine_fetch_crops_async(rs_engine* e, int n, rs_dets* o, rs_mask_crops* c) {
   RS_CHECK(e && o && o->count && c && c->rects && c->offsets && c->data && n >= 1 && n <= e->max_batch, RS_ERR_ARG, "bad argument");
   RS_CHECK(e->masks && e->crop_data, RS_ERR_ARG, "mask crops requested but MASK_ON is false");
-  if (!e->copy_stream) {
-    RS_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
-    RS_HIP(hipEventCreateWithFlags(&e->ev_results, hipEventDisableTiming));
-    RS_HIP(hipEventCreateWithFlags(&e->ev_copied, hipEventDisableTiming));
-  }
-  if (!e->ev_crop_hdr) {
-    RS_HIP(hipEventCreateWithFlags(&e->ev_crop_hdr, hipEventDisableTiming));
-    RS_HIP(hipHostMalloc((void**)&e->h_crop_total, 16, hipHostMallocDefault));
-  }
-  const int D = e->D;
-  hipStream_t s = e->copy_stream;
-  RS_HIP(hipEventRecord(e->ev_results, e->stream));
-  RS_HIP(hipStreamWaitEvent(s, e->ev_results, 0));
-  CropParams cp;
-  memset(&cp, 0, sizeof cp);
-  cp.det_boxes = e->det_boxes; cp.det_count = e->det_count; cp.masks = e->masks; cp.n = n; cp.D = D; cp.h = e->tile_h; cp.w = e->tile_w;
-  cp.Wb = (e->tile_w + 7) / 8; cp.rects = e->crop_rects; cp.offsets = e->crop_offsets; cp.total = e->crop_total; cp.data = e->crop_data;
-  { int rc = launch_mask_crops(cp, s); if (rc) return rc; }
-  RS_HIP(hipMemcpyAsync(o->count, e->det_count, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-  if (o->boxes) RS_HIP(hipMemcpyAsync(o->boxes, e->det_boxes, (size_t)n * D * 16, hipMemcpyDeviceToHost, s));
-  if (o->scores) RS_HIP(hipMemcpyAsync(o->scores, e->det_scores, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
-  if (o->classes) RS_HIP(hipMemcpyAsync(o->classes, e->det_classes, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
-  RS_HIP(hipMemcpyAsync(c->rects, e->crop_rects, (size_t)n * D * 16, hipMemcpyDeviceToHost, s));
-  RS_HIP(hipMemcpyAsync(c->offsets, e->crop_offsets, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
-  RS_HIP(hipMemcpyAsync(e->h_crop_total, e->crop_total, 8, hipMemcpyDeviceToHost, s));
-  { int rc = e->sat_copy(s); if (rc) return rc; }
-  RS_HIP(hipEventRecord(e->ev_copied, s));       // detections and canvases are free for the next forward: the crops live in their own buffer
-  RS_HIP(hipEventRecord(e->ev_crop_hdr, s));
-  e->copy_pending = true;
-  return RS_OK;
+  hipStream_t s = nullptr;
+  int rc;
+  if ((rc = e->ensure_crop_header())) return rc;
+  if ((rc = e->begin_fetch(&s))) return rc;
+  if ((rc = e->launch_crops(n, s))) return rc;
+  if ((rc = e->enqueue_dets(o, n, s, false))) return rc;
+  if ((rc = e->enqueue_crop_table(c, n, s))) return rc;
+  return e->end_fetch(s, e->ev_crop_hdr);     // detections and canvases are free for the next forward: the crops live in their own buffer
 }
 
 int rs_engine_fetch_crops_wait(rs_engine* e, rs_mask_crops* c) {
   RS_CHECK(e && c && c->data && e->ev_crop_hdr, RS_ERR_ARG, "rs_engine_fetch_crops_wait without rs_engine_fetch_crops_async");
   RS_HIP(hipEventSynchronize(e->ev_crop_hdr));
-  const unsigned long long used = *e->h_crop_total;
-  RS_CHECK(used <= c->capacity, RS_ERR_ARG, "mask crops need %llu bytes, the caller's buffer holds %llu", used, (unsigned long long)c->capacity);
-  c->used = used;
-  if (used) RS_HIP(hipMemcpyAsync(c->data, e->crop_data, (size_t)used, hipMemcpyDeviceToHost, e->copy_stream));
+  { int rc = e->enqueue_crop_bytes(c, e->copy_stream); if (rc) return rc; }
   RS_HIP(hipStreamSynchronize(e->copy_stream));
   e->sat_publish();
   return RS_OK;
@@ -1612,64 +1383,18 @@ int rs_engine_fetch_polygons_async(rs_engine* e, int n, rs_dets* o, rs_polygons*
   RS_CHECK(c && c->rects && c->offsets && c->data, RS_ERR_ARG, "rs_polygons.crops is incomplete");
   RS_CHECK(e->masks && e->crop_data, RS_ERR_ARG, "polygons requested but MASK_ON is false");
   RS_CHECK(e->tile_h <= PG_MAX_SIDE && e->tile_w <= PG_MAX_SIDE, RS_ERR_UNSUPPORTED, "polygons on the device need tiles up to %d x %d", PG_MAX_SIDE, PG_MAX_SIDE);
-  const int D = e->D;
-  if (!e->copy_stream) {
-    RS_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
-    RS_HIP(hipEventCreateWithFlags(&e->ev_results, hipEventDisableTiming));
-    RS_HIP(hipEventCreateWithFlags(&e->ev_copied, hipEventDisableTiming));
-  }
-  if (!e->ev_crop_hdr) {
-    RS_HIP(hipEventCreateWithFlags(&e->ev_crop_hdr, hipEventDisableTiming));
-    RS_HIP(hipHostMalloc((void**)&e->h_crop_total, 16, hipHostMallocDefault));
-  }
-  if (!e->poly_ready) {
-    const int inst = e->max_batch * D;
-    size_t b_hdr, b_prc, b_rlen, b_xy;
-    polygonize_scratch_bytes(inst, &b_hdr, &b_prc, &b_rlen, &b_xy);
-    PolyParams& q = e->poly;
-    memset(&q, 0, sizeof q);
-    int rc;
-    if ((rc = e->alloc((void**)&q.s_hdr, b_hdr))) return rc;
-    if ((rc = e->alloc((void**)&q.s_prc, b_prc))) return rc;
-    if ((rc = e->alloc((void**)&q.s_rlen, b_rlen))) return rc;
-    if ((rc = e->alloc((void**)&q.s_xy, b_xy))) return rc;
-    if ((rc = e->alloc((void**)&q.header, (size_t)inst * PG_HDR * 4))) return rc;
-    if ((rc = e->alloc((void**)&q.poly_ring_count, (size_t)inst * PG_RING_CAP * 4))) return rc;
-    if ((rc = e->alloc((void**)&q.ring_len, (size_t)inst * PG_RING_CAP * 4))) return rc;
-    if ((rc = e->alloc((void**)&q.xy, (size_t)inst * PG_VERTEX_CAP * 4))) return rc;
-    if ((rc = e->alloc((void**)&q.totals, 16))) return rc;
-    RS_HIP(hipEventCreateWithFlags(&e->ev_poly_hdr, hipEventDisableTiming));
-    RS_HIP(hipHostMalloc((void**)&e->h_poly_totals, 16, hipHostMallocDefault));
-    e->poly_ready = true;
-  }
-  hipStream_t s = e->copy_stream;
-  RS_HIP(hipEventRecord(e->ev_results, e->stream));
-  RS_HIP(hipStreamWaitEvent(s, e->ev_results, 0));
-  CropParams cp;
-  memset(&cp, 0, sizeof cp);
-  cp.det_boxes = e->det_boxes; cp.det_count = e->det_count; cp.masks = e->masks; cp.n = n; cp.D = D; cp.h = e->tile_h; cp.w = e->tile_w;
-  cp.Wb = (e->tile_w + 7) / 8; cp.rects = e->crop_rects; cp.offsets = e->crop_offsets; cp.total = e->crop_total; cp.data = e->crop_data;
-  { int rc = launch_mask_crops(cp, s); if (rc) return rc; }
-  PolyParams pp = e->poly;
-  pp.masks = e->masks; pp.rects = e->crop_rects; pp.det_count = e->det_count; pp.instances = n * D; pp.D = D; pp.h = e->tile_h; pp.w = e->tile_w;
-  pp.Wb = cp.Wb; pp.eps = rdp_epsilon;
-  pp.edge_cap = rs_debug().poly_edge_cap ? rs_debug().poly_edge_cap : PG_EDGE_CAP;
-  pp.vertex_cap = rs_debug().poly_vertex_cap ? rs_debug().poly_vertex_cap : PG_VERTEX_CAP;
-  { int rc = launch_polygonize(pp, s); if (rc) return rc; }
-  RS_HIP(hipMemcpyAsync(o->count, e->det_count, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-  if (o->boxes) RS_HIP(hipMemcpyAsync(o->boxes, e->det_boxes, (size_t)n * D * 16, hipMemcpyDeviceToHost, s));
-  if (o->scores) RS_HIP(hipMemcpyAsync(o->scores, e->det_scores, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
-  if (o->classes) RS_HIP(hipMemcpyAsync(o->classes, e->det_classes, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
-  RS_HIP(hipMemcpyAsync(c->rects, e->crop_rects, (size_t)n * D * 16, hipMemcpyDeviceToHost, s));
-  RS_HIP(hipMemcpyAsync(c->offsets, e->crop_offsets, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
-  RS_HIP(hipMemcpyAsync(e->h_crop_total, e->crop_total, 8, hipMemcpyDeviceToHost, s));
-  RS_HIP(hipMemcpyAsync(g->header, pp.header, (size_t)n * D * PG_HDR * 4, hipMemcpyDeviceToHost, s));
-  RS_HIP(hipMemcpyAsync(e->h_poly_totals, pp.totals, 16, hipMemcpyDeviceToHost, s));
-  { int rc = e->sat_copy(s); if (rc) return rc; }
-  RS_HIP(hipEventRecord(e->ev_copied, s));       // detections and canvases are free for the next forward: crops and polygons live in their own buffers
-  RS_HIP(hipEventRecord(e->ev_poly_hdr, s));
-  e->copy_pending = true;
-  return RS_OK;
+  hipStream_t s = nullptr;
+  int rc;
+  if ((rc = e->ensure_crop_header())) return rc;
+  if ((rc = e->ensure_polygon_buffers())) return rc;
+  if ((rc = e->begin_fetch(&s))) return rc;
+  if ((rc = e->launch_crops(n, s))) return rc;
+  if ((rc = e->launch_polygons(n, rdp_epsilon, s))) return rc;
+  if ((rc = e->enqueue_dets(o, n, s, false))) return rc;
+  if ((rc = e->enqueue_crop_table(c, n, s))) return rc;
+  RS_HIP(hipMemcpyAsync(g->header, e->poly.header, (size_t)n * e->D * PG_HDR * 4, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(e->h_poly_totals, e->poly.totals, 16, hipMemcpyDeviceToHost, s));
+  return e->end_fetch(s, e->ev_poly_hdr);     // ... and so are they here: crops and polygons live in their own buffers
 }
 
 int rs_engine_fetch_polygons_wait(rs_engine* e, rs_polygons* g) {
@@ -1684,14 +1409,11 @@ int rs_engine_fetch_polygons_wait(rs_engine* e, rs_polygons* g) {
   if (t[0]) RS_HIP(hipMemcpyAsync(g->poly_ring_count, e->poly.poly_ring_count, (size_t)t[0] * 4, hipMemcpyDeviceToHost, s));
   if (t[1]) RS_HIP(hipMemcpyAsync(g->ring_len, e->poly.ring_len, (size_t)t[1] * 4, hipMemcpyDeviceToHost, s));
   if (t[2]) RS_HIP(hipMemcpyAsync(g->xy, e->poly.xy, (size_t)t[2] * 4, hipMemcpyDeviceToHost, s));
-  rs_mask_crops* c = g->crops;
   g->masks_copied = 0;
-  c->used = 0;
+  g->crops->used = 0;
   if (t[3] > 0 || g->want_masks) {
-    const unsigned long long used = *e->h_crop_total;
-    RS_CHECK(used <= c->capacity, RS_ERR_ARG, "mask crops need %llu bytes, the caller's buffer holds %llu", used, (unsigned long long)c->capacity);
-    c->used = used;
-    if (used) RS_HIP(hipMemcpyAsync(c->data, e->crop_data, (size_t)used, hipMemcpyDeviceToHost, s));
+    int rc = e->enqueue_crop_bytes(g->crops, s);
+    if (rc) return rc;
     g->masks_copied = 1;
   }
   RS_HIP(hipStreamSynchronize(s));
@@ -1788,20 +1510,6 @@ int rs_engine_stage_variant(rs_engine* e, int i) {
   return e->stages[i].variant;
 }
 
-int rs_op_conv_variant(int m, int cin, int k, int cout, int cin2, int deconv2x, int out_f32, int* stages_out) {
-  ConvParams p;
-  memset(&p, 0, sizeof p);
-  p.M = m; p.Cin = cin; p.KH = p.KW = k; p.Cout = cout; p.mode = deconv2x ? 1 : 0; p.out_f32 = out_f32;
-  p.stride = 1; p.in_Cs = cin; p.out_Cs = cout;
-  p.Kpad = (k * k * (cin < 64 ? 8 : cin) + cin2 + 63) / 64 * 64;
-  if (cin < 64 && k == 7) p.Kpad = 256;       // the stem's padded tap rows (weights.py STEM_KW_PAD)
-  static const half_t dummy = (half_t)0;
-  if (cin2 > 0) { p.in2 = &dummy; p.Cin2 = cin2; }
-  const int v = conv_choose_variant(p, -1, 1);
-  if (stages_out) *stages_out = p.stages;
-  return cin < 64 ? 5 : v;
-}
-
 int rs_engine_tensor(rs_engine* e, const char* name, void** dev_ptr, int* dtype, int* ndim, int64_t dims[5], int* halo) {
   RS_CHECK(e && name, RS_ERR_ARG, "null argument");
   for (const TensorInfo& t : e->tensors) {
@@ -1834,387 +1542,12 @@ int rs_engine_net_shape(rs_engine* e, int* rh, int* rw, int* ph, int* pw) {
   return RS_OK;
 }
 
-// ------------------------------------------------------------------------- stand-alone operators
-static long long* g_conv_probe = nullptr;   // -DRS_CLOCK_PROBE diagnostic builds: see rs_debug_set_conv_probe
-static thread_local unsigned long long* g_op_sat = nullptr;   // rs_op_set_saturation_counter
-struct SplitArgs { long long in_lo, w_lo, out_lo, res_lo, up_lo; const float* wscale; };
-static int op_conv2d(const void* in, const void* w, const float* bias, void* out, const void* residual, const void* upsample_add,
-                     int n, int hi, int wi, int cin, int in_halo, int kh, int kw, int stride, int pad, int cout, int kpad,
-                     int out_halo, int relu, int out_f32, int deconv2x, int variant, int use_glds, void* stream,
-                     const void* in2, int h2, int w2, int cin2, int in2_halo, int stride2, const SplitArgs* sa = nullptr) {
-  RS_CHECK(in && w && bias && out, RS_ERR_ARG, "null argument");
-  RS_CHECK(in_halo >= pad, RS_ERR_ARG, "input halo %d < pad %d", in_halo, pad);
-  const int ho = (hi + 2 * pad - kh) / stride + 1, wo = (wi + 2 * pad - kw) / stride + 1;
-  ConvParams p;
-  memset(&p, 0, sizeof p);
-  p.in = (const half_t*)in; p.w = (const half_t*)w; p.bias = bias; p.out = out;
-  p.res = (const half_t*)residual; p.up = (const half_t*)upsample_add;
-  p.M = n * ho * wo; p.Ho = ho; p.Wo = wo;
-  p.in_Hp = hi + 2 * in_halo; p.in_Wp = wi + 2 * in_halo; p.in_Cs = cin; p.in_off = in_halo - pad;
-  p.stride = stride; p.KH = kh; p.KW = kw; p.Cin = cin; p.Kpad = kpad; p.Cout = cout;
-  const int oh = deconv2x ? 2 * ho : ho, ow = deconv2x ? 2 * wo : wo;
-  p.out_Hp = oh + 2 * out_halo; p.out_Wp = ow + 2 * out_halo; p.out_Cs = cout; p.out_pad = out_halo;
-  if (upsample_add) { p.up_Hp = ho / 2 + 2 * out_halo; p.up_Wp = wo / 2 + 2 * out_halo; p.up_Cs = cout; p.up_pad = out_halo; }
-  p.relu = relu; p.mode = deconv2x ? 1 : 0; p.out_f32 = out_f32;
-  p.probe = g_conv_probe;
-  p.sat = g_op_sat;
-  if (sa) {
-    RS_CHECK(sa->wscale && !in2, RS_ERR_ARG, "split-operand conv: row scales missing (or a second K source, which the operator does not take)");
-    p.split = 1; p.in_lo = sa->in_lo; p.w_lo = sa->w_lo; p.out_lo = sa->out_lo; p.res_lo = sa->res_lo; p.up_lo = sa->up_lo; p.wscale = sa->wscale;
-  }
-  if (in2) {
-    RS_CHECK(stride2 >= 1 && (ho - 1) * stride2 < h2 && (wo - 1) * stride2 < w2, RS_ERR_ARG, "second source geometry");
-    p.in2 = (const half_t*)in2; p.in2_Hp = h2 + 2 * in2_halo; p.in2_Wp = w2 + 2 * in2_halo; p.in2_Cs = cin2;
-    p.in2_off = in2_halo; p.stride2 = stride2; p.Cin2 = cin2;
-  }
-  int* koff_dev = nullptr;
-  if (cin < 64 && use_glds >= 0) {
-    RS_CHECK(cin == 8, RS_ERR_UNSUPPORTED, "small-Cin path needs cin == 8");
-    std::vector<int> koff(kpad / 8, 0);
-    for (int t = 0; t < kh * kw && t < (int)koff.size(); ++t) koff[t] = ((t / kw) * p.in_Wp + (t % kw)) * cin;
-    RS_HIP(hipMalloc((void**)&koff_dev, koff.size() * 4));
-    RS_HIP(hipMemcpy(koff_dev, koff.data(), koff.size() * 4, hipMemcpyHostToDevice));
-    p.koff = koff_dev;
-  }
-  int rc = launch_conv(p, (hipStream_t)stream, variant, use_glds);
-  if (koff_dev) {
-    (void)hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(koff_dev);
-  }
-  return rc;
-}
-
-int rs_debug_set_conv_probe(void* buffer) { g_conv_probe = (long long*)buffer; return RS_OK; }
-int rs_op_set_saturation_counter(void* dev_u64) { g_op_sat = (unsigned long long*)dev_u64; return RS_OK; }
-
-int rs_op_conv2d(const void* in, const void* w, const float* bias, void* out, const void* residual, const void* upsample_add,
-                 int n, int hi, int wi, int cin, int in_halo, int kh, int kw, int stride, int pad, int cout, int kpad,
-                 int out_halo, int relu, int out_f32, int deconv2x, int variant, int use_glds, void* stream) {
-  return op_conv2d(in, w, bias, out, residual, upsample_add, n, hi, wi, cin, in_halo, kh, kw, stride, pad, cout, kpad, out_halo,
-                   relu, out_f32, deconv2x, variant, use_glds, stream, nullptr, 0, 0, 0, 0, 1);
-}
-
-// The same convolution in the split-operand precision mode (rs_spec.precision == 2): every fp16 tensor is a hi plane with its lo plane `*_lo`
-// ELEMENTS behind it (value = hi + lo), the weight rows are scaled by a power of two per row and `wscale` holds the inverses.
-int rs_op_conv2d_split(const void* in, int64_t in_lo, const void* w, int64_t w_lo, const float* wscale, const float* bias, void* out, int64_t out_lo,
-                       const void* residual, int64_t res_lo, const void* upsample_add, int64_t up_lo,
-                       int n, int hi, int wi, int cin, int in_halo, int kh, int kw, int stride, int pad, int cout, int kpad,
-                       int out_halo, int relu, int out_f32, int deconv2x, int variant, void* stream) {
-  SplitArgs sa = {in_lo, w_lo, out_lo, res_lo, up_lo, wscale};
-  return op_conv2d(in, w, bias, out, residual, upsample_add, n, hi, wi, cin, in_halo, kh, kw, stride, pad, cout, kpad, out_halo,
-                   relu, out_f32, deconv2x, variant, 1, stream, nullptr, 0, 0, 0, 0, 1, &sa);
-}
-
-int rs_op_conv2d_dual(const void* in, const void* in2, const void* w, const float* bias, void* out,
-                      int n, int hi, int wi, int cin, int in_halo, int kh, int kw, int stride, int pad,
-                      int h2, int w2, int cin2, int in2_halo, int stride2,
-                      int cout, int kpad, int out_halo, int relu, int variant, void* stream) {
-  RS_CHECK(in2, RS_ERR_ARG, "null argument");
-  return op_conv2d(in, w, bias, out, nullptr, nullptr, n, hi, wi, cin, in_halo, kh, kw, stride, pad, cout, kpad, out_halo,
-                   relu, 0, 0, variant, 1, stream, in2, h2, w2, cin2, in2_halo, stride2);
-}
-
-int rs_op_bneck_tail(const void* t1, const void* w2, const float* b2, const void* w3p, const float* b3, const void* x, void* out,
-                     const void* w1p, const float* b1, void* t1n, const void* x0, const void* wsc, int n, int h, int w, int width, void* stream) {
-  RS_CHECK(t1 && w2 && b2 && w3p && b3 && out && n > 0 && h > 0 && w > 0, RS_ERR_ARG, "bad argument");
-  RS_CHECK(width == 64 || width == 128, RS_ERR_UNSUPPORTED, "bneck_tail: bottleneck width %d (64 or 128)", width);
-  BneckParams p;
-  memset(&p, 0, sizeof p);
-  p.t1 = (const half_t*)t1; p.w2 = (const half_t*)w2; p.b2 = b2; p.w3p = (const half_t*)w3p; p.b3 = b3; p.x = (const half_t*)x; p.out = (half_t*)out;
-  p.w1p = (const half_t*)w1p; p.b1 = b1; p.t1n = (half_t*)t1n; p.x0 = (const half_t*)x0; p.wsc = (const half_t*)wsc;
-  p.M = n * h * w; p.H = h; p.W = w; p.Hp = h + 2; p.Wp = w + 2; p.CB = width / 64;
-  p.sat = g_op_sat;
-  return launch_bneck_tail(p, (hipStream_t)stream);
-}
-
-int rs_op_bneck_tail_split(const void* t1, int64_t t1_lo, const void* w2, const float* s2, const float* b2, const void* w3p, const float* s3, const float* b3,
-                           const void* x, int64_t x_lo, void* out, int64_t out_lo, const void* w1p, const float* s1, const float* b1, void* t1n, int64_t t1n_lo,
-                           const void* x0, int64_t x0_lo, int n, int h, int w, int width, void* stream) {
-  RS_CHECK(t1 && w2 && s2 && b2 && w3p && s3 && b3 && (x || x0) && out && n > 0 && h > 0 && w > 0, RS_ERR_ARG, "bad argument");
-  RS_CHECK(width == 64 || width == 128, RS_ERR_UNSUPPORTED, "bneck_tail_split: bottleneck width %d (64 or 128)", width);
-  BneckSplitParams p;
-  memset(&p, 0, sizeof p);
-  p.t1 = (const half_t*)t1; p.t1_lo = t1_lo;
-  p.w2 = (const half_t*)w2; p.w2_lo = (long long)width * 9 * width; p.s2 = s2; p.b2 = b2;
-  p.w3p = (const half_t*)w3p; p.w3_lo = 4ll * width * (width + (x0 ? 64 : 0)); p.s3 = s3; p.b3 = b3;
-  p.x = (const half_t*)x; p.x_lo = x_lo; p.x0 = (const half_t*)x0; p.x0_lo = x0_lo; p.out = (half_t*)out; p.out_lo = out_lo;
-  p.w1p = (const half_t*)w1p; p.w1_lo = 4ll * width * width; p.s1 = s1; p.b1 = b1; p.t1n = (half_t*)t1n; p.t1n_lo = t1n_lo;
-  p.M = n * h * w; p.H = h; p.W = w; p.Hp = h + 2; p.Wp = w + 2; p.CB = width / 64;
-  p.sat = g_op_sat;
-  return launch_bneck_tail_split(p, (hipStream_t)stream);
-}
-
-int rs_op_mask_overlap(const uint8_t* det_masks, int n_det, const uint8_t* label_masks, int n_labels, int h, int w, int32_t* inter,
-                       int32_t* label_area, void* stream) {
-  return launch_mask_overlap(det_masks, n_det, label_masks, n_labels, h, w, inter, label_area, (hipStream_t)stream);
-}
-
-// the same on the detection masks of tile `tile` of the engine's last forward (all D slots; slots >= count hold stale canvases,
-// the caller reads the first count[tile] columns)
+// rs_op_mask_overlap on the detection masks of tile `tile` of the engine's last forward (all D slots; slots >= count hold stale
+// canvases, the caller reads the first count[tile] columns)
 int rs_engine_label_overlap(rs_engine* e, int tile, const uint8_t* label_masks_dev, int n_labels, int32_t* inter_dev, int32_t* label_area_dev) {
   RS_CHECK(e && e->masks && tile >= 0 && tile < e->max_batch && label_masks_dev && inter_dev && label_area_dev, RS_ERR_ARG, "bad argument");
   const size_t per = (size_t)e->tile_h * ((e->tile_w + 7) / 8);
   return launch_mask_overlap(e->masks + (size_t)tile * e->D * per, e->D, label_masks_dev, n_labels, e->tile_h, e->tile_w, inter_dev, label_area_dev, e->stream);
 }
 
-int rs_op_conv2d_dgrad(const void* dy, const void* w_t, void* dx, const void* res, const float* res32, const void* mask,
-                       const void* down, int n, int hi, int wi, int cin, int ho, int wo, int cout, int kh, int kw, int stride,
-                       int pad, int kpad, int halo, int variant, void* stream) {
-  RS_CHECK(dy && w_t && dx, RS_ERR_ARG, "null argument");
-  RS_CHECK(stride == 1 || (kh == 1 && kw == 1), RS_ERR_UNSUPPORTED, "dgrad: stride %d needs a 1x1 kernel (STRIDE_IN_1X1)", stride);
-  RS_CHECK(halo >= kh - 1 - pad && halo >= 0 && kh == kw, RS_ERR_ARG, "dgrad: halo %d too small", halo);
-  // the input gradient of conv(x, W, stride 1, pad) is conv(dy, W^T flipped, stride 1, pad' = k-1-pad); of a stride-s 1x1
-  // convolution it is the 1x1 convolution of dy stored at every s-th pixel of dx
-  ConvParams p;
-  memset(&p, 0, sizeof p);
-  const int pad_t = kh - 1 - pad;
-  const int oh = stride == 1 ? ho + 2 * pad_t - kh + 1 : ho, ow = stride == 1 ? wo + 2 * pad_t - kw + 1 : wo;
-  RS_CHECK(stride == 1 ? (oh == hi && ow == wi) : ((ho - 1) * stride < hi && (wo - 1) * stride < wi), RS_ERR_ARG, "dgrad: geometry");
-  void* zero_bias = nullptr;
-  RS_HIP(hipMalloc(&zero_bias, (size_t)cin * 4 + 256));
-  RS_HIP(hipMemsetAsync(zero_bias, 0, (size_t)cin * 4 + 256, (hipStream_t)stream));
-  p.in = (const half_t*)dy; p.w = (const half_t*)w_t; p.bias = (const float*)zero_bias; p.out = dx;
-  p.res = (const half_t*)res; p.res32 = res32; p.mask = (const half_t*)mask; p.down = (const half_t*)down;
-  p.M = n * oh * ow; p.Ho = oh; p.Wo = ow;
-  p.in_Hp = ho + 2 * halo; p.in_Wp = wo + 2 * halo; p.in_Cs = cout; p.in_off = halo - pad_t;
-  p.stride = 1; p.KH = kh; p.KW = kw; p.Cin = cout; p.Kpad = kpad; p.Cout = cin;
-  p.out_Hp = hi + 2 * halo; p.out_Wp = wi + 2 * halo; p.out_Cs = cin; p.out_pad = halo;
-  p.out_stride = stride;
-  if (down) { p.down_Hp = 2 * hi + 2 * halo; p.down_Wp = 2 * wi + 2 * halo; p.down_Cs = cin; p.down_pad = halo; }
-  int rc = launch_conv(p, (hipStream_t)stream, variant, 1);
-  (void)hipStreamSynchronize((hipStream_t)stream);
-  (void)hipFree(zero_bias);
-  return rc;
-}
-
-static int op_conv2d_wgrad(const void* dy, const void* x, float* grad, const float* scale, int n, int hi, int wi, int cin, int in_halo,
-                           int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits, void* stream, int f32);
-int rs_op_conv2d_wgrad(const void* dy, const void* x, float* grad, const float* scale, int n, int hi, int wi, int cin, int in_halo,
-                       int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits, void* stream) {
-  return op_conv2d_wgrad(dy, x, grad, scale, n, hi, wi, cin, in_halo, kh, kw, stride, pad, cout, kpad, dy_halo, splits, stream, 0);
-}
-// the same weight gradient from fp32 operands (reference-precision trainer: conv_wgrad_f32_kernel)
-int rs_op_conv2d_wgrad_f32(const void* dy, const void* x, float* grad, const float* scale, int n, int hi, int wi, int cin, int in_halo,
-                           int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits, void* stream) {
-  return op_conv2d_wgrad(dy, x, grad, scale, n, hi, wi, cin, in_halo, kh, kw, stride, pad, cout, kpad, dy_halo, splits, stream, 1);
-}
-static int op_conv2d_wgrad(const void* dy, const void* x, float* grad, const float* scale, int n, int hi, int wi, int cin, int in_halo,
-                           int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits, void* stream, int f32) {
-  RS_CHECK(dy && x && grad, RS_ERR_ARG, "null argument");
-  RS_CHECK(in_halo >= pad, RS_ERR_ARG, "input halo %d < pad %d", in_halo, pad);
-  const int ho = (hi + 2 * pad - kh) / stride + 1, wo = (wi + 2 * pad - kw) / stride + 1;
-  WgradParams p;
-  memset(&p, 0, sizeof p);
-  p.dy = (const half_t*)dy; p.x = (const half_t*)x; p.grad = grad; p.scale = scale;
-  p.M = n * ho * wo; p.Ho = ho; p.Wo = wo;
-  p.dy_Hp = ho + 2 * dy_halo; p.dy_Wp = wo + 2 * dy_halo; p.dy_Cs = cout; p.dy_pad = dy_halo;
-  p.in_Hp = hi + 2 * in_halo; p.in_Wp = wi + 2 * in_halo; p.in_Cs = cin; p.in_off = in_halo - pad;
-  p.stride = stride; p.KH = kh; p.KW = kw; p.Cin = cin; p.Cout = cout; p.Kpad = kpad;
-  p.f32 = f32;
-  p.splits = splits > 0 ? splits : wgrad_splits(p);
-  hipStream_t s = (hipStream_t)stream;
-  void *partial = nullptr, *zeros = nullptr;
-  RS_HIP(hipMalloc(&partial, (size_t)p.splits * cout * kpad * 4));
-  RS_HIP(hipMalloc(&zeros, (size_t)cout * 2 + 256));
-  RS_HIP(hipMemsetAsync(zeros, 0, (size_t)cout * 2 + 256, s));
-  RS_HIP(hipMemsetAsync(partial, 0, (size_t)p.splits * cout * kpad * 4, s));   // K padding columns stay zero
-  p.partial = (float*)partial; p.zeros = (const half_t*)zeros;
-  int rc = launch_conv_wgrad(p, s);
-  (void)hipStreamSynchronize(s);
-  (void)hipFree(partial);
-  (void)hipFree(zeros);
-  return rc;
-}
-
-int rs_op_nms(const float* boxes, const int32_t* counts, const uint8_t* valid, uint8_t* keep, int segments, int cap,
-              float thresh, void* stream) {
-  RS_CHECK(boxes && counts && keep && segments > 0, RS_ERR_ARG, "bad argument");
-  RS_CHECK(cap >= 1 && cap <= 2048, RS_ERR_ARG, "cap %d outside [1,2048]", cap);
-  NmsParams p = {};
-  p.boxes = boxes; p.count = counts; p.valid = valid; p.keep = keep; p.cap = cap; p.thresh = thresh;
-  void* scratch = nullptr;
-  // the engine's dispatch: training capacity always keeps the suppression mask in global memory; at cap <= 1024 the engine passes
-  // scratch too, and launch_nms takes the global-memory form for <= 32 segments, the LDS form above that
-  if (cap > 1024) {
-    RS_HIP(hipMalloc(&scratch, (size_t)segments * 2048 * 32 * 8));
-    p.scratch = (unsigned long long*)scratch;
-  } else if (segments <= 32) {
-    RS_HIP(hipMalloc(&scratch, (size_t)segments * 1024 * 16 * 8));
-    p.scratch = (unsigned long long*)scratch;
-  }
-  int rc = launch_nms(p, segments, (hipStream_t)stream);
-  if (scratch) { (void)hipStreamSynchronize((hipStream_t)stream); (void)hipFree(scratch); }
-  return rc;
-}
-
-int rs_op_batched_nms(const float* boxes, const int32_t* counts, const uint8_t* valid, uint8_t* keep, int images, int segments_per_image,
-                      int cap, float thresh, int rule, void* stream) {
-  return rs_op_batched_nms_decision(boxes, counts, valid, keep, images, segments_per_image, cap, thresh, rule, nullptr, nullptr, stream);
-}
-
-int rs_op_batched_nms_decision(const float* boxes, const int32_t* counts, const uint8_t* valid, uint8_t* keep, int images, int segments_per_image,
-                               int cap, float thresh, int rule, int32_t* rule_out, float* unit_out, void* stream) {
-  RS_CHECK(boxes && counts && keep && images > 0 && segments_per_image > 0, RS_ERR_ARG, "bad argument");
-  RS_CHECK(cap >= 1 && cap <= 2048, RS_ERR_ARG, "cap %d outside [1,2048]", cap);
-  RS_CHECK(rule == 0 || rule == 1, RS_ERR_ARG, "rule %d (0 = per category, 1 = torchvision's size rule)", rule);
-  const int segments = images * segments_per_image;
-  RS_CHECK(rule || (!rule_out && !unit_out), RS_ERR_ARG, "rule 0 takes no decision");
-  if (!rule) return rs_op_nms(boxes, counts, valid, keep, segments, cap, thresh, stream);
-  RS_CHECK(cap > 1000, RS_ERR_ARG, "cap %d: the size rule needs a capacity above 1000 boxes per segment", cap);
-  hipStream_t s = (hipStream_t)stream;
-  NmsParams p = {};
-  p.boxes = boxes; p.count = counts; p.valid = valid; p.keep = keep; p.cap = cap; p.thresh = thresh;
-  void *scratch = nullptr, *dec = nullptr;
-  RS_HIP(hipMalloc(&dec, (size_t)images * 12));
-  // the suppression mask as in rs_op_nms (= the engine's dispatch)
-  const size_t sbytes = cap > 1024 ? (size_t)segments * 2048 * 32 * 8 : (segments <= 32 ? (size_t)segments * 1024 * 16 * 8 : 0);
-  if (sbytes && hipMalloc(&scratch, sbytes) != hipSuccess) { (void)hipFree(dec); rs_set_error("hipMalloc(%zu)", sbytes); return RS_ERR_HIP; }
-  p.scratch = (unsigned long long*)scratch;
-  p.rule = (int*)dec; p.unit = (float*)((char*)dec + (size_t)images * 8); p.group = segments_per_image;
-  int rc = launch_nms(p, segments, s);
-  // the decision as nms_kernel's prologue left it (the engine's rpn_nms_rule / rpn_nms_unit tensors)
-  if (!rc && rule_out && hipMemcpyAsync(rule_out, p.rule, (size_t)images * 8, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = RS_ERR_HIP;
-  if (!rc && unit_out && hipMemcpyAsync(unit_out, p.unit, (size_t)images * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = RS_ERR_HIP;
-  (void)hipStreamSynchronize(s);
-  (void)hipFree(dec);
-  if (scratch) (void)hipFree(scratch);
-  return rc;
-}
-
-int rs_op_det_merge(const float* dec_boxes, const float* dec_scores, const int32_t* seg_roi, const int32_t* seg_count, const uint8_t* keep,
-                    int images, int num_classes, int cap, int dets_per_image, float scale_x, float scale_y, float out_w, float out_h,
-                    float* det_boxes_net, float* det_boxes, float* det_scores, int32_t* det_classes, int32_t* det_roi, int32_t* det_count,
-                    void* stream) {
-  RS_CHECK(dec_boxes && dec_scores && seg_roi && seg_count && keep && det_boxes_net && det_boxes && det_scores && det_classes && det_count &&
-               images > 0, RS_ERR_ARG, "bad argument");
-  RS_CHECK(num_classes >= 1 && num_classes <= RS_MAX_CLASSES, RS_ERR_UNSUPPORTED, "NUM_CLASSES %d outside [1,%d]", num_classes, RS_MAX_CLASSES);
-  RS_CHECK(cap >= 1 && cap <= 1024, RS_ERR_ARG, "cap %d outside [1,1024]", cap);
-  { const int rc0 = det_merge_check(num_classes, dets_per_image); if (rc0) return rc0; }
-  hipStream_t s = (hipStream_t)stream;
-  DetMergeParams p;
-  memset(&p, 0, sizeof p);
-  p.dec_boxes = dec_boxes; p.dec_scores = dec_scores; p.seg_roi = seg_roi; p.seg_count = seg_count; p.keep = keep;
-  p.K = num_classes; p.cap = cap; p.dets_per_image = dets_per_image;
-  p.scale_x = scale_x; p.scale_y = scale_y; p.out_w = out_w; p.out_h = out_h;
-  p.det_boxes_net = det_boxes_net; p.det_boxes = det_boxes; p.det_scores = det_scores; p.det_classes = det_classes; p.det_roi = det_roi;
-  p.det_count = det_count;
-  void* ws = nullptr;
-  if (num_classes > RS_DET_GROUP) {    // the partial winners between the two launches, for the time of this call (the engine owns its own)
-    const size_t G = (size_t)det_merge_groups(num_classes);
-    const size_t kb = (size_t)images * G * dets_per_image * 8;
-    RS_HIP(hipMalloc(&ws, kb + (size_t)images * G * 4));
-    p.part_keys = (unsigned long long*)ws; p.part_count = (int*)((char*)ws + kb);
-  }
-  int rc = launch_det_merge(p, images, s);
-  if (ws) { (void)hipStreamSynchronize(s); (void)hipFree(ws); }
-  return rc;
-}
-
-int rs_op_roi_align(const void* const feats[4], const int32_t heights[4], const int32_t widths[4], const float scales[4],
-                    int nlevels, const float* rois, int n_rois, int rois_per_image, int P, int out_halo, void* out,
-                    int32_t* levels_out, void* stream) {
-  RS_CHECK(feats && rois && out && nlevels >= 1 && nlevels <= 4 && n_rois > 0 && rois_per_image > 0, RS_ERR_ARG, "bad argument");
-  RoiAlignParams p;
-  memset(&p, 0, sizeof p);
-  for (int l = 0; l < nlevels; ++l) { p.feat[l] = (const half_t*)feats[l]; p.H[l] = heights[l]; p.W[l] = widths[l]; p.scale[l] = scales[l]; }
-  p.nlevels = nlevels; p.C = 256; p.rois = rois; p.S = n_rois; p.slots_per_image = rois_per_image;
-  p.out = (half_t*)out; p.P = P; p.out_pad = out_halo; p.out_level = levels_out;
-  rs_debug_reload();                                         // RS_ROI_WINDOW: the operator tests switch between the two forward forms
-  return launch_roi_align(p, (hipStream_t)stream);
-}
-
-int rs_op_roi_align_bwd(float* const dfeats[4], const int32_t heights[4], const int32_t widths[4], const float scales[4],
-                        int nlevels, const float* rois, int n_rois, int rois_per_image, int P, int out_halo, const void* dout,
-                        void* stream) {
-  RS_CHECK(dfeats && rois && dout && nlevels >= 1 && nlevels <= 4 && n_rois > 0 && rois_per_image > 0, RS_ERR_ARG, "bad argument");
-  RoiAlignParams p;
-  memset(&p, 0, sizeof p);
-  for (int l = 0; l < nlevels; ++l) { p.dfeat[l] = dfeats[l]; p.H[l] = heights[l]; p.W[l] = widths[l]; p.scale[l] = scales[l]; }
-  p.nlevels = nlevels; p.C = 256; p.rois = rois; p.S = n_rois; p.slots_per_image = rois_per_image;
-  p.out = (half_t*)dout; p.P = P; p.out_pad = out_halo;
-  rs_debug_reload();                                         // RS_ROI_BWD_ATOMIC: the operator tests switch between the two forms
-  // workspace of the owner-computes form (the trainer owns its own): per-entry tables + the overflow counter, for the time of this call
-  p.n_images = (n_rois + rois_per_image - 1) / rois_per_image;
-  void* ws = nullptr;
-  RS_HIP(hipMalloc(&ws, (size_t)n_rois * RS_ROI_BWD_TABLE_BYTES + 64));
-  p.bwd_overflow = (int*)ws;
-  p.bwd_tables = (char*)ws + 64;
-  const int rc = launch_roi_align_bwd(p, (hipStream_t)stream);
-  hipError_t he = hipStreamSynchronize((hipStream_t)stream);
-  hipFree(ws);
-  RS_HIP(he);
-  return rc;
-}
-
-int rs_op_rpn_loss(const float* head, void* dhead, const int32_t* labels, const float* anchors, const float* matched_gt,
-                   float* loss_out, int n, int hw, int num_anchors, int cs, int level_off, int total_anchors, float normalizer,
-                   float loss_scale, void* stream) {
-  RpnLossParams p;
-  memset(&p, 0, sizeof p);
-  p.head = head; p.dhead = (half_t*)dhead; p.labels = labels; p.anchors = anchors; p.matched_gt = matched_gt; p.loss_out = loss_out;
-  p.A = num_anchors; p.cs = cs; p.HW = hw; p.n_anchors = hw * num_anchors; p.level_off = level_off; p.total_anchors = total_anchors;
-  p.normalizer = normalizer; p.loss_scale = loss_scale;
-  return launch_rpn_loss(p, n, (hipStream_t)stream);
-}
-
-int rs_op_box_loss(const float* pred, void* dpred, const int32_t* gt_classes, const float* proposals, const float* gt_boxes,
-                   float* loss_out, int n_rois, int num_classes, int cs, float n_valid, const float reg_weights[4], float loss_scale,
-                   void* stream) {
-  RS_CHECK(reg_weights, RS_ERR_ARG, "null argument");
-  BoxLossParams p;
-  memset(&p, 0, sizeof p);
-  p.pred = pred; p.dpred = (half_t*)dpred; p.gt_classes = gt_classes; p.proposals = proposals; p.gt_boxes = gt_boxes; p.loss_out = loss_out;
-  p.n_rois = n_rois; p.K = num_classes; p.cs = cs; p.n_valid = n_valid;
-  p.wx = reg_weights[0]; p.wy = reg_weights[1]; p.ww = reg_weights[2]; p.wh = reg_weights[3]; p.loss_scale = loss_scale;
-  return launch_box_loss(p, (hipStream_t)stream);
-}
-
-int rs_op_mask_loss(const float* logits, void* dlogits, const uint8_t* targets, const int32_t* gt_classes, float* loss_out, int n_masks,
-                    int side, int cs, float loss_scale, void* stream) {
-  MaskLossParams p;
-  memset(&p, 0, sizeof p);
-  p.logits = logits; p.dlogits = (half_t*)dlogits; p.targets = targets; p.gt_classes = gt_classes; p.loss_out = loss_out;
-  p.n_masks = n_masks; p.S = side; p.cs = cs; p.loss_scale = loss_scale;
-  return launch_mask_loss(p, (hipStream_t)stream);
-}
-
-int rs_op_match(const float* boxes, int per_image_boxes, const int32_t* box_count, const float* gt, const int32_t* gt_count,
-                int32_t* matched, int32_t* labels, float* best_iou, int n_images, int n_boxes, int gt_cap, float t_lo, float t_hi,
-                int lbl_lo, int lbl_mid, int lbl_hi, int allow_low_quality, void* stream) {
-  MatchParams p;
-  memset(&p, 0, sizeof p);
-  p.boxes = boxes; p.per_image_boxes = per_image_boxes; p.box_count = box_count; p.gt = gt; p.gt_count = gt_count;
-  p.matched = matched; p.labels = labels; p.best_iou = best_iou; p.n_boxes = n_boxes; p.gt_cap = gt_cap;
-  p.t_lo = t_lo; p.t_hi = t_hi; p.lbl_lo = lbl_lo; p.lbl_mid = lbl_mid; p.lbl_hi = lbl_hi;
-  void* scratch = nullptr;
-  if (allow_low_quality) {
-    RS_HIP(hipMalloc(&scratch, (size_t)n_images * gt_cap * 4));
-    p.gt_best = (unsigned int*)scratch;
-  }
-  int rc = launch_match(p, n_images, (hipStream_t)stream);
-  if (scratch) { (void)hipStreamSynchronize((hipStream_t)stream); (void)hipFree(scratch); }
-  return rc;
-}
-
-int rs_op_subsample(int32_t* labels, int32_t* sampled, int32_t* sampled_count, int n_images, int n, int num_samples,
-                    float positive_fraction, int bg_label, int rpn_mode, uint32_t seed, void* stream) {
-  SubsampleParams p;
-  memset(&p, 0, sizeof p);
-  p.labels = labels; p.sampled = sampled; p.sampled_count = sampled_count; p.n = n; p.num_samples = num_samples;
-  p.positive_fraction = positive_fraction; p.bg_label = bg_label; p.rpn_mode = rpn_mode; p.seed = seed;
-  return launch_subsample(p, n_images, (hipStream_t)stream);
-}
-
-int rs_op_sgd_momentum(float* w, float* momentum_buf, const float* grad, int64_t n, float lr, float momentum, float weight_decay,
-                       float inv_loss_scale, int first_step, void* stream) {
-  return launch_sgd_momentum(w, momentum_buf, grad, n, lr, momentum, weight_decay, inv_loss_scale, first_step, (hipStream_t)stream);
-}
-
-int rs_op_fold_weights(const float* w32, const float* scale, void* w_fwd, void* w_bwd, int cout, int cin, int kh, int kw, int kpad,
-                       int kpad_t, void* stream) {
-  return launch_fold_weights(w32, scale, (half_t*)w_fwd, (half_t*)w_bwd, cout, cin, kh, kw, kpad, cout, kpad_t, (hipStream_t)stream);
-}
-
 }  // extern "C"
-
-#include "train_engine.inc"

@@ -1,0 +1,429 @@
+// librs_engine.so host side: the stand-alone operators rs_op_* of include/rs_engine.h -- one kernel launcher each on caller-owned device
+// buffers, for the operator tests and the tools.  Nothing here touches an engine.
+#include <string.h>
+
+#include <vector>
+
+#include "../../include/rs_engine.h"
+#include "detect.h"
+#include "train.h"
+
+namespace {
+
+// Device scratch that lives for one operator call (the engine and the trainer own theirs for good).  Leaving the scope waits for the
+// stream the launch went to, if anything was allocated, and frees it -- on the error returns too.
+struct OpScratch {
+  hipStream_t stream;
+  void* held[2] = {nullptr, nullptr};
+  int n = 0;
+  explicit OpScratch(void* s) : stream((hipStream_t)s) {}
+  OpScratch(const OpScratch&) = delete;
+  OpScratch& operator=(const OpScratch&) = delete;
+  int alloc(void** p, size_t bytes) {
+    RS_CHECK(n < 2, RS_ERR_ARG, "OpScratch: more than two buffers");
+    RS_HIP(hipMalloc(p, bytes));
+    held[n++] = *p;
+    return RS_OK;
+  }
+  hipError_t sync() const { return n ? hipStreamSynchronize(stream) : hipSuccess; }
+  ~OpScratch() {
+    (void)sync();
+    for (int i = 0; i < n; ++i) (void)hipFree(held[i]);
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+// rs_fdiv (common.h) as an operator, for its test: out[i] = a[i] / b[i] through the device code's division
+__global__ void fdiv_kernel(const float* a, const float* b, float* out, long long n) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = rs_fdiv(a[i], b[i]);
+}
+int rs_op_fdiv(const float* a, const float* b, float* out, int64_t n, void* stream) {
+  RS_CHECK(a && b && out && n > 0, RS_ERR_ARG, "bad argument");
+  hipLaunchKernelGGL(fdiv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, b, out, (long long)n);
+  RS_HIP(hipGetLastError());
+  return RS_OK;
+}
+
+int rs_memcpy_d2h(void* dst, const void* src, size_t n) {
+  RS_HIP(hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));
+  return RS_OK;
+}
+int rs_memcpy_h2d(void* dst, const void* src, size_t n) {
+  RS_HIP(hipMemcpy(dst, src, n, hipMemcpyHostToDevice));
+  return RS_OK;
+}
+
+int rs_op_conv_variant(int m, int cin, int k, int cout, int cin2, int deconv2x, int out_f32, int* stages_out) {
+  ConvParams p;
+  memset(&p, 0, sizeof p);
+  p.M = m; p.Cin = cin; p.KH = p.KW = k; p.Cout = cout; p.mode = deconv2x ? 1 : 0; p.out_f32 = out_f32;
+  p.stride = 1; p.in_Cs = cin; p.out_Cs = cout;
+  p.Kpad = (k * k * (cin < 64 ? 8 : cin) + cin2 + 63) / 64 * 64;
+  if (cin < 64 && k == 7) p.Kpad = 256;       // the stem's padded tap rows (weights.py STEM_KW_PAD)
+  static const half_t dummy = (half_t)0;
+  if (cin2 > 0) { p.in2 = &dummy; p.Cin2 = cin2; }
+  const int v = conv_choose_variant(p, -1, 1);
+  if (stages_out) *stages_out = p.stages;
+  return cin < 64 ? 5 : v;
+}
+
+static long long* g_conv_probe = nullptr;   // -DRS_CLOCK_PROBE diagnostic builds: see rs_debug_set_conv_probe
+static thread_local unsigned long long* g_op_sat = nullptr;   // rs_op_set_saturation_counter
+struct SplitArgs { long long in_lo, w_lo, out_lo, res_lo, up_lo; const float* wscale; };
+static int op_conv2d(const void* in, const void* w, const float* bias, void* out, const void* residual, const void* upsample_add,
+                     int n, int hi, int wi, int cin, int in_halo, int kh, int kw, int stride, int pad, int cout, int kpad,
+                     int out_halo, int relu, int out_f32, int deconv2x, int variant, int use_glds, void* stream,
+                     const void* in2, int h2, int w2, int cin2, int in2_halo, int stride2, const SplitArgs* sa = nullptr) {
+  RS_CHECK(in && w && bias && out, RS_ERR_ARG, "null argument");
+  RS_CHECK(in_halo >= pad, RS_ERR_ARG, "input halo %d < pad %d", in_halo, pad);
+  const int ho = (hi + 2 * pad - kh) / stride + 1, wo = (wi + 2 * pad - kw) / stride + 1;
+  ConvParams p;
+  memset(&p, 0, sizeof p);
+  p.in = (const half_t*)in; p.w = (const half_t*)w; p.bias = bias; p.out = out;
+  p.res = (const half_t*)residual; p.up = (const half_t*)upsample_add;
+  p.M = n * ho * wo; p.Ho = ho; p.Wo = wo;
+  p.in_Hp = hi + 2 * in_halo; p.in_Wp = wi + 2 * in_halo; p.in_Cs = cin; p.in_off = in_halo - pad;
+  p.stride = stride; p.KH = kh; p.KW = kw; p.Cin = cin; p.Kpad = kpad; p.Cout = cout;
+  const int oh = deconv2x ? 2 * ho : ho, ow = deconv2x ? 2 * wo : wo;
+  p.out_Hp = oh + 2 * out_halo; p.out_Wp = ow + 2 * out_halo; p.out_Cs = cout; p.out_pad = out_halo;
+  if (upsample_add) { p.up_Hp = ho / 2 + 2 * out_halo; p.up_Wp = wo / 2 + 2 * out_halo; p.up_Cs = cout; p.up_pad = out_halo; }
+  p.relu = relu; p.mode = deconv2x ? 1 : 0; p.out_f32 = out_f32;
+  p.probe = g_conv_probe;
+  p.sat = g_op_sat;
+  if (sa) {
+    RS_CHECK(sa->wscale && !in2, RS_ERR_ARG, "split-operand conv: row scales missing (or a second K source, which the operator does not take)");
+    p.split = 1; p.in_lo = sa->in_lo; p.w_lo = sa->w_lo; p.out_lo = sa->out_lo; p.res_lo = sa->res_lo; p.up_lo = sa->up_lo; p.wscale = sa->wscale;
+  }
+  if (in2) {
+    RS_CHECK(stride2 >= 1 && (ho - 1) * stride2 < h2 && (wo - 1) * stride2 < w2, RS_ERR_ARG, "second source geometry");
+    p.in2 = (const half_t*)in2; p.in2_Hp = h2 + 2 * in2_halo; p.in2_Wp = w2 + 2 * in2_halo; p.in2_Cs = cin2;
+    p.in2_off = in2_halo; p.stride2 = stride2; p.Cin2 = cin2;
+  }
+  OpScratch scratch(stream);
+  if (cin < 64 && use_glds >= 0) {
+    RS_CHECK(cin == 8, RS_ERR_UNSUPPORTED, "small-Cin path needs cin == 8");
+    std::vector<int> koff(kpad / 8, 0);
+    for (int t = 0; t < kh * kw && t < (int)koff.size(); ++t) koff[t] = ((t / kw) * p.in_Wp + (t % kw)) * cin;
+    int* koff_dev = nullptr;
+    { int rc = scratch.alloc((void**)&koff_dev, koff.size() * 4); if (rc) return rc; }
+    RS_HIP(hipMemcpy(koff_dev, koff.data(), koff.size() * 4, hipMemcpyHostToDevice));
+    p.koff = koff_dev;
+  }
+  return launch_conv(p, (hipStream_t)stream, variant, use_glds);
+}
+
+int rs_debug_set_conv_probe(void* buffer) { g_conv_probe = (long long*)buffer; return RS_OK; }
+int rs_op_set_saturation_counter(void* dev_u64) { g_op_sat = (unsigned long long*)dev_u64; return RS_OK; }
+
+int rs_op_conv2d(const void* in, const void* w, const float* bias, void* out, const void* residual, const void* upsample_add,
+                 int n, int hi, int wi, int cin, int in_halo, int kh, int kw, int stride, int pad, int cout, int kpad,
+                 int out_halo, int relu, int out_f32, int deconv2x, int variant, int use_glds, void* stream) {
+  return op_conv2d(in, w, bias, out, residual, upsample_add, n, hi, wi, cin, in_halo, kh, kw, stride, pad, cout, kpad, out_halo,
+                   relu, out_f32, deconv2x, variant, use_glds, stream, nullptr, 0, 0, 0, 0, 1);
+}
+
+// The same convolution in the split-operand precision mode (rs_spec.precision == 2): every fp16 tensor is a hi plane with its lo plane `*_lo`
+// ELEMENTS behind it (value = hi + lo), the weight rows are scaled by a power of two per row and `wscale` holds the inverses.
+int rs_op_conv2d_split(const void* in, int64_t in_lo, const void* w, int64_t w_lo, const float* wscale, const float* bias, void* out, int64_t out_lo,
+                       const void* residual, int64_t res_lo, const void* upsample_add, int64_t up_lo,
+                       int n, int hi, int wi, int cin, int in_halo, int kh, int kw, int stride, int pad, int cout, int kpad,
+                       int out_halo, int relu, int out_f32, int deconv2x, int variant, void* stream) {
+  SplitArgs sa = {in_lo, w_lo, out_lo, res_lo, up_lo, wscale};
+  return op_conv2d(in, w, bias, out, residual, upsample_add, n, hi, wi, cin, in_halo, kh, kw, stride, pad, cout, kpad, out_halo,
+                   relu, out_f32, deconv2x, variant, 1, stream, nullptr, 0, 0, 0, 0, 1, &sa);
+}
+
+int rs_op_conv2d_dual(const void* in, const void* in2, const void* w, const float* bias, void* out,
+                      int n, int hi, int wi, int cin, int in_halo, int kh, int kw, int stride, int pad,
+                      int h2, int w2, int cin2, int in2_halo, int stride2,
+                      int cout, int kpad, int out_halo, int relu, int variant, void* stream) {
+  RS_CHECK(in2, RS_ERR_ARG, "null argument");
+  return op_conv2d(in, w, bias, out, nullptr, nullptr, n, hi, wi, cin, in_halo, kh, kw, stride, pad, cout, kpad, out_halo,
+                   relu, 0, 0, variant, 1, stream, in2, h2, w2, cin2, in2_halo, stride2);
+}
+
+int rs_op_bneck_tail(const void* t1, const void* w2, const float* b2, const void* w3p, const float* b3, const void* x, void* out,
+                     const void* w1p, const float* b1, void* t1n, const void* x0, const void* wsc, int n, int h, int w, int width, void* stream) {
+  RS_CHECK(t1 && w2 && b2 && w3p && b3 && out && n > 0 && h > 0 && w > 0, RS_ERR_ARG, "bad argument");
+  RS_CHECK(width == 64 || width == 128, RS_ERR_UNSUPPORTED, "bneck_tail: bottleneck width %d (64 or 128)", width);
+  BneckParams p;
+  memset(&p, 0, sizeof p);
+  p.t1 = (const half_t*)t1; p.w2 = (const half_t*)w2; p.b2 = b2; p.w3p = (const half_t*)w3p; p.b3 = b3; p.x = (const half_t*)x; p.out = (half_t*)out;
+  p.w1p = (const half_t*)w1p; p.b1 = b1; p.t1n = (half_t*)t1n; p.x0 = (const half_t*)x0; p.wsc = (const half_t*)wsc;
+  p.M = n * h * w; p.H = h; p.W = w; p.Hp = h + 2; p.Wp = w + 2; p.CB = width / 64;
+  p.sat = g_op_sat;
+  return launch_bneck_tail(p, (hipStream_t)stream);
+}
+
+int rs_op_bneck_tail_split(const void* t1, int64_t t1_lo, const void* w2, const float* s2, const float* b2, const void* w3p, const float* s3, const float* b3,
+                           const void* x, int64_t x_lo, void* out, int64_t out_lo, const void* w1p, const float* s1, const float* b1, void* t1n, int64_t t1n_lo,
+                           const void* x0, int64_t x0_lo, int n, int h, int w, int width, void* stream) {
+  RS_CHECK(t1 && w2 && s2 && b2 && w3p && s3 && b3 && (x || x0) && out && n > 0 && h > 0 && w > 0, RS_ERR_ARG, "bad argument");
+  RS_CHECK(width == 64 || width == 128, RS_ERR_UNSUPPORTED, "bneck_tail_split: bottleneck width %d (64 or 128)", width);
+  BneckSplitParams p;
+  memset(&p, 0, sizeof p);
+  p.t1 = (const half_t*)t1; p.t1_lo = t1_lo;
+  p.w2 = (const half_t*)w2; p.w2_lo = (long long)width * 9 * width; p.s2 = s2; p.b2 = b2;
+  p.w3p = (const half_t*)w3p; p.w3_lo = 4ll * width * (width + (x0 ? 64 : 0)); p.s3 = s3; p.b3 = b3;
+  p.x = (const half_t*)x; p.x_lo = x_lo; p.x0 = (const half_t*)x0; p.x0_lo = x0_lo; p.out = (half_t*)out; p.out_lo = out_lo;
+  p.w1p = (const half_t*)w1p; p.w1_lo = 4ll * width * width; p.s1 = s1; p.b1 = b1; p.t1n = (half_t*)t1n; p.t1n_lo = t1n_lo;
+  p.M = n * h * w; p.H = h; p.W = w; p.Hp = h + 2; p.Wp = w + 2; p.CB = width / 64;
+  p.sat = g_op_sat;
+  return launch_bneck_tail_split(p, (hipStream_t)stream);
+}
+
+int rs_op_mask_overlap(const uint8_t* det_masks, int n_det, const uint8_t* label_masks, int n_labels, int h, int w, int32_t* inter,
+                       int32_t* label_area, void* stream) {
+  return launch_mask_overlap(det_masks, n_det, label_masks, n_labels, h, w, inter, label_area, (hipStream_t)stream);
+}
+
+
+int rs_op_conv2d_dgrad(const void* dy, const void* w_t, void* dx, const void* res, const float* res32, const void* mask,
+                       const void* down, int n, int hi, int wi, int cin, int ho, int wo, int cout, int kh, int kw, int stride,
+                       int pad, int kpad, int halo, int variant, void* stream) {
+  RS_CHECK(dy && w_t && dx, RS_ERR_ARG, "null argument");
+  RS_CHECK(stride == 1 || (kh == 1 && kw == 1), RS_ERR_UNSUPPORTED, "dgrad: stride %d needs a 1x1 kernel (STRIDE_IN_1X1)", stride);
+  RS_CHECK(halo >= kh - 1 - pad && halo >= 0 && kh == kw, RS_ERR_ARG, "dgrad: halo %d too small", halo);
+  // the input gradient of conv(x, W, stride 1, pad) is conv(dy, W^T flipped, stride 1, pad' = k-1-pad); of a stride-s 1x1
+  // convolution it is the 1x1 convolution of dy stored at every s-th pixel of dx
+  ConvParams p;
+  memset(&p, 0, sizeof p);
+  const int pad_t = kh - 1 - pad;
+  const int oh = stride == 1 ? ho + 2 * pad_t - kh + 1 : ho, ow = stride == 1 ? wo + 2 * pad_t - kw + 1 : wo;
+  RS_CHECK(stride == 1 ? (oh == hi && ow == wi) : ((ho - 1) * stride < hi && (wo - 1) * stride < wi), RS_ERR_ARG, "dgrad: geometry");
+  OpScratch scratch(stream);
+  void* zero_bias = nullptr;
+  { int rc = scratch.alloc(&zero_bias, (size_t)cin * 4 + 256); if (rc) return rc; }
+  RS_HIP(hipMemsetAsync(zero_bias, 0, (size_t)cin * 4 + 256, (hipStream_t)stream));
+  p.in = (const half_t*)dy; p.w = (const half_t*)w_t; p.bias = (const float*)zero_bias; p.out = dx;
+  p.res = (const half_t*)res; p.res32 = res32; p.mask = (const half_t*)mask; p.down = (const half_t*)down;
+  p.M = n * oh * ow; p.Ho = oh; p.Wo = ow;
+  p.in_Hp = ho + 2 * halo; p.in_Wp = wo + 2 * halo; p.in_Cs = cout; p.in_off = halo - pad_t;
+  p.stride = 1; p.KH = kh; p.KW = kw; p.Cin = cout; p.Kpad = kpad; p.Cout = cin;
+  p.out_Hp = hi + 2 * halo; p.out_Wp = wi + 2 * halo; p.out_Cs = cin; p.out_pad = halo;
+  p.out_stride = stride;
+  if (down) { p.down_Hp = 2 * hi + 2 * halo; p.down_Wp = 2 * wi + 2 * halo; p.down_Cs = cin; p.down_pad = halo; }
+  return launch_conv(p, (hipStream_t)stream, variant, 1);
+}
+
+static int op_conv2d_wgrad(const void* dy, const void* x, float* grad, const float* scale, int n, int hi, int wi, int cin, int in_halo,
+                           int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits, void* stream, int f32);
+int rs_op_conv2d_wgrad(const void* dy, const void* x, float* grad, const float* scale, int n, int hi, int wi, int cin, int in_halo,
+                       int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits, void* stream) {
+  return op_conv2d_wgrad(dy, x, grad, scale, n, hi, wi, cin, in_halo, kh, kw, stride, pad, cout, kpad, dy_halo, splits, stream, 0);
+}
+// the same weight gradient from fp32 operands (reference-precision trainer: conv_wgrad_f32_kernel)
+int rs_op_conv2d_wgrad_f32(const void* dy, const void* x, float* grad, const float* scale, int n, int hi, int wi, int cin, int in_halo,
+                           int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits, void* stream) {
+  return op_conv2d_wgrad(dy, x, grad, scale, n, hi, wi, cin, in_halo, kh, kw, stride, pad, cout, kpad, dy_halo, splits, stream, 1);
+}
+static int op_conv2d_wgrad(const void* dy, const void* x, float* grad, const float* scale, int n, int hi, int wi, int cin, int in_halo,
+                           int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits, void* stream, int f32) {
+  RS_CHECK(dy && x && grad, RS_ERR_ARG, "null argument");
+  RS_CHECK(in_halo >= pad, RS_ERR_ARG, "input halo %d < pad %d", in_halo, pad);
+  const int ho = (hi + 2 * pad - kh) / stride + 1, wo = (wi + 2 * pad - kw) / stride + 1;
+  WgradParams p;
+  memset(&p, 0, sizeof p);
+  p.dy = (const half_t*)dy; p.x = (const half_t*)x; p.grad = grad; p.scale = scale;
+  p.M = n * ho * wo; p.Ho = ho; p.Wo = wo;
+  p.dy_Hp = ho + 2 * dy_halo; p.dy_Wp = wo + 2 * dy_halo; p.dy_Cs = cout; p.dy_pad = dy_halo;
+  p.in_Hp = hi + 2 * in_halo; p.in_Wp = wi + 2 * in_halo; p.in_Cs = cin; p.in_off = in_halo - pad;
+  p.stride = stride; p.KH = kh; p.KW = kw; p.Cin = cin; p.Cout = cout; p.Kpad = kpad;
+  p.f32 = f32;
+  p.splits = splits > 0 ? splits : wgrad_splits(p);
+  hipStream_t s = (hipStream_t)stream;
+  OpScratch scratch(stream);
+  void *partial = nullptr, *zeros = nullptr;
+  { int rc = scratch.alloc(&partial, (size_t)p.splits * cout * kpad * 4); if (rc) return rc; }
+  { int rc = scratch.alloc(&zeros, (size_t)cout * 2 + 256); if (rc) return rc; }
+  RS_HIP(hipMemsetAsync(zeros, 0, (size_t)cout * 2 + 256, s));
+  RS_HIP(hipMemsetAsync(partial, 0, (size_t)p.splits * cout * kpad * 4, s));   // K padding columns stay zero
+  p.partial = (float*)partial; p.zeros = (const half_t*)zeros;
+  return launch_conv_wgrad(p, s);
+}
+
+int rs_op_nms(const float* boxes, const int32_t* counts, const uint8_t* valid, uint8_t* keep, int segments, int cap,
+              float thresh, void* stream) {
+  RS_CHECK(boxes && counts && keep && segments > 0, RS_ERR_ARG, "bad argument");
+  RS_CHECK(cap >= 1 && cap <= 2048, RS_ERR_ARG, "cap %d outside [1,2048]", cap);
+  NmsParams p = {};
+  p.boxes = boxes; p.count = counts; p.valid = valid; p.keep = keep; p.cap = cap; p.thresh = thresh;
+  OpScratch scratch(stream);
+  // the engine's dispatch: training capacity always keeps the suppression mask in global memory; at cap <= 1024 the engine passes
+  // scratch too, and launch_nms takes the global-memory form for <= 32 segments, the LDS form above that
+  if (cap > 1024) {
+    int rc = scratch.alloc((void**)&p.scratch, (size_t)segments * 2048 * 32 * 8);
+    if (rc) return rc;
+  } else if (segments <= 32) {
+    int rc = scratch.alloc((void**)&p.scratch, (size_t)segments * 1024 * 16 * 8);
+    if (rc) return rc;
+  }
+  return launch_nms(p, segments, (hipStream_t)stream);
+}
+
+int rs_op_batched_nms(const float* boxes, const int32_t* counts, const uint8_t* valid, uint8_t* keep, int images, int segments_per_image,
+                      int cap, float thresh, int rule, void* stream) {
+  return rs_op_batched_nms_decision(boxes, counts, valid, keep, images, segments_per_image, cap, thresh, rule, nullptr, nullptr, stream);
+}
+
+int rs_op_batched_nms_decision(const float* boxes, const int32_t* counts, const uint8_t* valid, uint8_t* keep, int images, int segments_per_image,
+                               int cap, float thresh, int rule, int32_t* rule_out, float* unit_out, void* stream) {
+  RS_CHECK(boxes && counts && keep && images > 0 && segments_per_image > 0, RS_ERR_ARG, "bad argument");
+  RS_CHECK(cap >= 1 && cap <= 2048, RS_ERR_ARG, "cap %d outside [1,2048]", cap);
+  RS_CHECK(rule == 0 || rule == 1, RS_ERR_ARG, "rule %d (0 = per category, 1 = torchvision's size rule)", rule);
+  const int segments = images * segments_per_image;
+  RS_CHECK(rule || (!rule_out && !unit_out), RS_ERR_ARG, "rule 0 takes no decision");
+  if (!rule) return rs_op_nms(boxes, counts, valid, keep, segments, cap, thresh, stream);
+  RS_CHECK(cap > 1000, RS_ERR_ARG, "cap %d: the size rule needs a capacity above 1000 boxes per segment", cap);
+  hipStream_t s = (hipStream_t)stream;
+  NmsParams p = {};
+  p.boxes = boxes; p.count = counts; p.valid = valid; p.keep = keep; p.cap = cap; p.thresh = thresh;
+  OpScratch scratch(stream);
+  void* dec = nullptr;
+  { int rc = scratch.alloc(&dec, (size_t)images * 12); if (rc) return rc; }
+  // the suppression mask as in rs_op_nms (= the engine's dispatch)
+  const size_t sbytes = cap > 1024 ? (size_t)segments * 2048 * 32 * 8 : (segments <= 32 ? (size_t)segments * 1024 * 16 * 8 : 0);
+  if (sbytes) { int rc = scratch.alloc((void**)&p.scratch, sbytes); if (rc) return rc; }
+  p.rule = (int*)dec; p.unit = (float*)((char*)dec + (size_t)images * 8); p.group = segments_per_image;
+  int rc = launch_nms(p, segments, s);
+  // the decision as nms_kernel's prologue left it (the engine's rpn_nms_rule / rpn_nms_unit tensors)
+  if (!rc && rule_out && hipMemcpyAsync(rule_out, p.rule, (size_t)images * 8, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = RS_ERR_HIP;
+  if (!rc && unit_out && hipMemcpyAsync(unit_out, p.unit, (size_t)images * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = RS_ERR_HIP;
+  return rc;
+}
+
+int rs_op_det_merge(const float* dec_boxes, const float* dec_scores, const int32_t* seg_roi, const int32_t* seg_count, const uint8_t* keep,
+                    int images, int num_classes, int cap, int dets_per_image, float scale_x, float scale_y, float out_w, float out_h,
+                    float* det_boxes_net, float* det_boxes, float* det_scores, int32_t* det_classes, int32_t* det_roi, int32_t* det_count,
+                    void* stream) {
+  RS_CHECK(dec_boxes && dec_scores && seg_roi && seg_count && keep && det_boxes_net && det_boxes && det_scores && det_classes && det_count &&
+               images > 0, RS_ERR_ARG, "bad argument");
+  RS_CHECK(num_classes >= 1 && num_classes <= RS_MAX_CLASSES, RS_ERR_UNSUPPORTED, "NUM_CLASSES %d outside [1,%d]", num_classes, RS_MAX_CLASSES);
+  RS_CHECK(cap >= 1 && cap <= 1024, RS_ERR_ARG, "cap %d outside [1,1024]", cap);
+  { const int rc0 = det_merge_check(num_classes, dets_per_image); if (rc0) return rc0; }
+  hipStream_t s = (hipStream_t)stream;
+  DetMergeParams p;
+  memset(&p, 0, sizeof p);
+  p.dec_boxes = dec_boxes; p.dec_scores = dec_scores; p.seg_roi = seg_roi; p.seg_count = seg_count; p.keep = keep;
+  p.K = num_classes; p.cap = cap; p.dets_per_image = dets_per_image;
+  p.scale_x = scale_x; p.scale_y = scale_y; p.out_w = out_w; p.out_h = out_h;
+  p.det_boxes_net = det_boxes_net; p.det_boxes = det_boxes; p.det_scores = det_scores; p.det_classes = det_classes; p.det_roi = det_roi;
+  p.det_count = det_count;
+  OpScratch scratch(stream);
+  if (num_classes > RS_DET_GROUP) {    // the partial winners between the two launches, for the time of this call (the engine owns its own)
+    const size_t G = (size_t)det_merge_groups(num_classes);
+    const size_t kb = (size_t)images * G * dets_per_image * 8;
+    void* ws = nullptr;
+    { int rc = scratch.alloc(&ws, kb + (size_t)images * G * 4); if (rc) return rc; }
+    p.part_keys = (unsigned long long*)ws; p.part_count = (int*)((char*)ws + kb);
+  }
+  return launch_det_merge(p, images, s);
+}
+
+int rs_op_roi_align(const void* const feats[4], const int32_t heights[4], const int32_t widths[4], const float scales[4],
+                    int nlevels, const float* rois, int n_rois, int rois_per_image, int P, int out_halo, void* out,
+                    int32_t* levels_out, void* stream) {
+  RS_CHECK(feats && rois && out && nlevels >= 1 && nlevels <= 4 && n_rois > 0 && rois_per_image > 0, RS_ERR_ARG, "bad argument");
+  RoiAlignParams p;
+  memset(&p, 0, sizeof p);
+  for (int l = 0; l < nlevels; ++l) { p.feat[l] = (const half_t*)feats[l]; p.H[l] = heights[l]; p.W[l] = widths[l]; p.scale[l] = scales[l]; }
+  p.nlevels = nlevels; p.C = 256; p.rois = rois; p.S = n_rois; p.slots_per_image = rois_per_image;
+  p.out = (half_t*)out; p.P = P; p.out_pad = out_halo; p.out_level = levels_out;
+  rs_debug_reload();                                         // RS_ROI_WINDOW: the operator tests switch between the two forward forms
+  return launch_roi_align(p, (hipStream_t)stream);
+}
+
+int rs_op_roi_align_bwd(float* const dfeats[4], const int32_t heights[4], const int32_t widths[4], const float scales[4],
+                        int nlevels, const float* rois, int n_rois, int rois_per_image, int P, int out_halo, const void* dout,
+                        void* stream) {
+  RS_CHECK(dfeats && rois && dout && nlevels >= 1 && nlevels <= 4 && n_rois > 0 && rois_per_image > 0, RS_ERR_ARG, "bad argument");
+  RoiAlignParams p;
+  memset(&p, 0, sizeof p);
+  for (int l = 0; l < nlevels; ++l) { p.dfeat[l] = dfeats[l]; p.H[l] = heights[l]; p.W[l] = widths[l]; p.scale[l] = scales[l]; }
+  p.nlevels = nlevels; p.C = 256; p.rois = rois; p.S = n_rois; p.slots_per_image = rois_per_image;
+  p.out = (half_t*)dout; p.P = P; p.out_pad = out_halo;
+  rs_debug_reload();                                         // RS_ROI_BWD_ATOMIC: the operator tests switch between the two forms
+  // workspace of the owner-computes form (the trainer owns its own): per-entry tables + the overflow counter, for the time of this call
+  p.n_images = (n_rois + rois_per_image - 1) / rois_per_image;
+  OpScratch scratch(stream);
+  void* ws = nullptr;
+  { int rc = scratch.alloc(&ws, (size_t)n_rois * RS_ROI_BWD_TABLE_BYTES + 64); if (rc) return rc; }
+  p.bwd_overflow = (int*)ws;
+  p.bwd_tables = (char*)ws + 64;
+  const int rc = launch_roi_align_bwd(p, (hipStream_t)stream);
+  RS_HIP(scratch.sync());
+  return rc;
+}
+
+int rs_op_rpn_loss(const float* head, void* dhead, const int32_t* labels, const float* anchors, const float* matched_gt,
+                   float* loss_out, int n, int hw, int num_anchors, int cs, int level_off, int total_anchors, float normalizer,
+                   float loss_scale, void* stream) {
+  RpnLossParams p;
+  memset(&p, 0, sizeof p);
+  p.head = head; p.dhead = (half_t*)dhead; p.labels = labels; p.anchors = anchors; p.matched_gt = matched_gt; p.loss_out = loss_out;
+  p.A = num_anchors; p.cs = cs; p.HW = hw; p.n_anchors = hw * num_anchors; p.level_off = level_off; p.total_anchors = total_anchors;
+  p.normalizer = normalizer; p.loss_scale = loss_scale;
+  return launch_rpn_loss(p, n, (hipStream_t)stream);
+}
+
+int rs_op_box_loss(const float* pred, void* dpred, const int32_t* gt_classes, const float* proposals, const float* gt_boxes,
+                   float* loss_out, int n_rois, int num_classes, int cs, float n_valid, const float reg_weights[4], float loss_scale,
+                   void* stream) {
+  RS_CHECK(reg_weights, RS_ERR_ARG, "null argument");
+  BoxLossParams p;
+  memset(&p, 0, sizeof p);
+  p.pred = pred; p.dpred = (half_t*)dpred; p.gt_classes = gt_classes; p.proposals = proposals; p.gt_boxes = gt_boxes; p.loss_out = loss_out;
+  p.n_rois = n_rois; p.K = num_classes; p.cs = cs; p.n_valid = n_valid;
+  p.wx = reg_weights[0]; p.wy = reg_weights[1]; p.ww = reg_weights[2]; p.wh = reg_weights[3]; p.loss_scale = loss_scale;
+  return launch_box_loss(p, (hipStream_t)stream);
+}
+
+int rs_op_mask_loss(const float* logits, void* dlogits, const uint8_t* targets, const int32_t* gt_classes, float* loss_out, int n_masks,
+                    int side, int cs, float loss_scale, void* stream) {
+  MaskLossParams p;
+  memset(&p, 0, sizeof p);
+  p.logits = logits; p.dlogits = (half_t*)dlogits; p.targets = targets; p.gt_classes = gt_classes; p.loss_out = loss_out;
+  p.n_masks = n_masks; p.S = side; p.cs = cs; p.loss_scale = loss_scale;
+  return launch_mask_loss(p, (hipStream_t)stream);
+}
+
+int rs_op_match(const float* boxes, int per_image_boxes, const int32_t* box_count, const float* gt, const int32_t* gt_count,
+                int32_t* matched, int32_t* labels, float* best_iou, int n_images, int n_boxes, int gt_cap, float t_lo, float t_hi,
+                int lbl_lo, int lbl_mid, int lbl_hi, int allow_low_quality, void* stream) {
+  MatchParams p;
+  memset(&p, 0, sizeof p);
+  p.boxes = boxes; p.per_image_boxes = per_image_boxes; p.box_count = box_count; p.gt = gt; p.gt_count = gt_count;
+  p.matched = matched; p.labels = labels; p.best_iou = best_iou; p.n_boxes = n_boxes; p.gt_cap = gt_cap;
+  p.t_lo = t_lo; p.t_hi = t_hi; p.lbl_lo = lbl_lo; p.lbl_mid = lbl_mid; p.lbl_hi = lbl_hi;
+  OpScratch scratch(stream);
+  if (allow_low_quality) {
+    int rc = scratch.alloc((void**)&p.gt_best, (size_t)n_images * gt_cap * 4);
+    if (rc) return rc;
+  }
+  return launch_match(p, n_images, (hipStream_t)stream);
+}
+
+int rs_op_subsample(int32_t* labels, int32_t* sampled, int32_t* sampled_count, int n_images, int n, int num_samples,
+                    float positive_fraction, int bg_label, int rpn_mode, uint32_t seed, void* stream) {
+  SubsampleParams p;
+  memset(&p, 0, sizeof p);
+  p.labels = labels; p.sampled = sampled; p.sampled_count = sampled_count; p.n = n; p.num_samples = num_samples;
+  p.positive_fraction = positive_fraction; p.bg_label = bg_label; p.rpn_mode = rpn_mode; p.seed = seed;
+  return launch_subsample(p, n_images, (hipStream_t)stream);
+}
+
+int rs_op_sgd_momentum(float* w, float* momentum_buf, const float* grad, int64_t n, float lr, float momentum, float weight_decay,
+                       float inv_loss_scale, int first_step, void* stream) {
+  return launch_sgd_momentum(w, momentum_buf, grad, n, lr, momentum, weight_decay, inv_loss_scale, first_step, (hipStream_t)stream);
+}
+
+int rs_op_fold_weights(const float* w32, const float* scale, void* w_fwd, void* w_bwd, int cout, int cin, int kh, int kw, int kpad,
+                       int kpad_t, void* stream) {
+  return launch_fold_weights(w32, scale, (half_t*)w_fwd, (half_t*)w_bwd, cout, cin, kh, kw, kpad, cout, kpad_t, (hipStream_t)stream);
+}
+
+}  // extern "C"

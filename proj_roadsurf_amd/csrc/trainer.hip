@@ -1,5 +1,5 @@
-// Training engine -- included by engine.hip (same translation unit: it drives rs_engine's
-// stages, activations and weight blob directly).
+// librs_engine.so host side: the training engine, the rs_trainer_* entries of include/rs_engine.h.  It drives
+// the stages, activations and weight blob of its forward engine directly (engine_internal.h).
 //
 // What detectron2's SimpleTrainer.run_step does with autograd ([EXT d2: engine/train_loop.py; modeling/meta_arch/rcnn.py
 // GeneralizedRCNN.forward]) is laid out here as an explicit backward stage list over the forward engine's buffers:
@@ -13,6 +13,12 @@
 //   * one SGD-momentum launch updates the whole flat buffer, one fold launch per layer regenerates the two fp16 operands.
 // Stage A (this file, round 1): trunk backward (FPN + res5..res3) from given gradients of p2..p6, checked against the
 // training oracle's autograd.  The loss/label kernels (train_kernels.hip) and the RoI-head backward are wired in next.
+#include <string.h>
+
+#include <cmath>
+
+#include "engine_internal.h"
+#include "train.h"
 
 namespace {
 

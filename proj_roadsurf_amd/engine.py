@@ -462,12 +462,12 @@ class Engine:
         self._crop_offsets = self._pinned((n, D), np.uint32) if self.spec.mask_on else None
         self._crop_data: Optional[np.ndarray] = None
         self._crops_struct: Optional[RsMaskCrops] = None
-        self._crops_pending = False
         # polygons (rs_engine_fetch_polygons_*): pinned tables, allocated on the first polygon fetch
         self._poly_struct: Optional[RsPolygons] = None
-        self._poly_pending = False
-        self._poly_landed = False
         self._poly_eps = 0.0
+        # the kind of fetch_async that is in flight, and of the one wait_results waited for last: None, "canvas", "crops" or "polygons"
+        self._fetch_pending: Optional[str] = None
+        self._fetch_landed: Optional[str] = None
 
     def _dets_struct(self, want_probs: bool) -> RsDets:
         d = RsDets()
@@ -481,46 +481,44 @@ class Engine:
                 d.mask_probs = self._probs.ctypes.data_as(C.POINTER(C.c_float))
         return d
 
-    def _collect(self, n: int, want_probs: bool, crops: bool = False, polygons: bool = False) -> List[Instances]:
+    # The mask payload of tile i (c detections) as Instances takes it, one function per kind of fetch
+    def _tile_canvas(self, i: int, c: int, want_probs: bool = False) -> Dict[str, Any]:
+        return dict(packed_masks=self._masks[i, :c].copy() if self._masks is not None else None,
+                    mask_probs=self._probs[i, :c].copy() if (self._probs is not None and want_probs) else None)
+
+    def _tile_crops(self, i: int, c: int, want_probs: bool = False) -> Dict[str, Any]:
+        rects = self._crop_rects[i, :c].copy()
+        offs = self._crop_offsets[i, :c].astype(np.int64)
+        if c:
+            lo = int(offs[0])
+            hi = int(offs[c - 1]) + int(rects[c - 1, 2]) * int(rects[c - 1, 3])
+            data = self._crop_data[lo:hi].copy()          # the tile's crops are contiguous, in slot order
+            offs = (offs - lo).astype(np.uint32)
+        else:
+            data, offs = np.zeros(0, np.uint8), np.zeros(0, np.uint32)
+        return dict(packed_masks=None, mask_probs=None, crops=(rects, offs, data))
+
+    def _tile_polygons(self, i: int, c: int, want_probs: bool = False) -> Dict[str, Any]:
+        hdr = self._poly_header[i, :c].copy()
+        if c:
+            lo = hdr[0, 4:7].copy()
+            hi = hdr[c - 1, 4:7] + hdr[c - 1, 1:4]
+            hdr[:, 4:7] -= lo
+        else:
+            lo = hi = np.zeros(3, np.int32)
+        tables = PolygonTables(hdr, self._poly_prc[lo[0]:hi[0]].copy(), self._poly_rlen[lo[1]:hi[1]].copy(),
+                               self._poly_xy[lo[2]:hi[2]].copy(), self._poly_eps)
+        masks = self._tile_crops(i, c) if self._poly_struct.masks_copied else dict(packed_masks=None, mask_probs=None)
+        return dict(masks, polygons=tables)
+
+    def _collect(self, n: int, want_probs: bool, kind: str = "canvas") -> List[Instances]:
+        """``Instances`` of tiles 0..n-1 out of the pinned buffers; ``kind``: what the fetch left there for the masks."""
+        masks_of = {"canvas": self._tile_canvas, "crops": self._tile_crops, "polygons": self._tile_polygons}[kind]
         out = []
-        if polygons:
-            crops = bool(self._poly_struct.masks_copied)
-        if crops or polygons:
-            for i in range(n):
-                c = int(self._count[i])
-                tables = None
-                if polygons:
-                    hdr = self._poly_header[i, :c].copy()
-                    if c:
-                        lo = hdr[0, 4:7].copy()
-                        hi = hdr[c - 1, 4:7] + hdr[c - 1, 1:4]
-                        hdr[:, 4:7] -= lo
-                    else:
-                        lo = hi = np.zeros(3, np.int32)
-                    tables = PolygonTables(hdr, self._poly_prc[lo[0]:hi[0]].copy(), self._poly_rlen[lo[1]:hi[1]].copy(),
-                                           self._poly_xy[lo[2]:hi[2]].copy(), self._poly_eps)
-                if not crops:
-                    out.append(Instances((self.tile_h, self.tile_w), self._boxes[i, :c].copy(), self._scores[i, :c].copy(),
-                                         self._classes[i, :c].astype(np.int64), None, None, polygons=tables))
-                    continue
-                rects = self._crop_rects[i, :c].copy()
-                offs = self._crop_offsets[i, :c].astype(np.int64)
-                if c:
-                    lo = int(offs[0])
-                    hi = int(offs[c - 1]) + int(rects[c - 1, 2]) * int(rects[c - 1, 3])
-                    data = self._crop_data[lo:hi].copy()          # the tile's crops are contiguous, in slot order
-                    offs = (offs - lo).astype(np.uint32)
-                else:
-                    data, offs = np.zeros(0, np.uint8), np.zeros(0, np.uint32)
-                out.append(Instances((self.tile_h, self.tile_w), self._boxes[i, :c].copy(), self._scores[i, :c].copy(),
-                                     self._classes[i, :c].astype(np.int64), None, None, crops=(rects, offs, data), polygons=tables))
-            return out
         for i in range(n):
             c = int(self._count[i])
             out.append(Instances((self.tile_h, self.tile_w), self._boxes[i, :c].copy(), self._scores[i, :c].copy(),
-                                 self._classes[i, :c].astype(np.int64),
-                                 self._masks[i, :c].copy() if self._masks is not None else None,
-                                 self._probs[i, :c].copy() if (self._probs is not None and want_probs) else None))
+                                 self._classes[i, :c].astype(np.int64), **masks_of(i, c, want_probs)))
         return out
 
     # ------------------------------------------------------------------ inference
@@ -595,32 +593,30 @@ class Engine:
             d.masks = None
             _check(self.lib, self.lib.rs_engine_fetch_polygons_async(self._h, n, C.byref(d), C.byref(self._poly_struct), float(rdp_epsilon)),
                    "rs_engine_fetch_polygons_async")
-            self._poly_pending = True
-            return
-        if crops and self._masks is not None:
+            self._fetch_pending = "polygons"
+        elif crops and self._masks is not None:
             d.masks = None
             _check(self.lib, self.lib.rs_engine_fetch_crops_async(self._h, n, C.byref(d), C.byref(self._crops_buffers())), "rs_engine_fetch_crops_async")
-            self._crops_pending = True
-            return
-        _check(self.lib, self.lib.rs_engine_fetch_async(self._h, n, C.byref(d)), "rs_engine_fetch_async")
+            self._fetch_pending = "crops"
+        else:
+            _check(self.lib, self.lib.rs_engine_fetch_async(self._h, n, C.byref(d)), "rs_engine_fetch_async")
+            self._fetch_pending = "canvas"
 
     def wait_results(self) -> None:
         """Block until the copies of the last ``fetch_async`` have landed (for crops: wait for the crop table, copy exactly the
         bytes in use, wait for them; for polygons the same with the polygon headers and rows)."""
-        self._poly_landed = False
-        if self._poly_pending:
+        kind, self._fetch_pending = self._fetch_pending or "canvas", None
+        if kind == "polygons":
             _check(self.lib, self.lib.rs_engine_fetch_polygons_wait(self._h, C.byref(self._poly_struct)), "rs_engine_fetch_polygons_wait")
-            self._poly_pending, self._poly_landed, self._crops_landed = False, True, False
-        elif self._crops_pending:
+        elif kind == "crops":
             _check(self.lib, self.lib.rs_engine_fetch_crops_wait(self._h, C.byref(self._crops_struct)), "rs_engine_fetch_crops_wait")
-            self._crops_pending, self._crops_landed = False, True
         else:
             _check(self.lib, self.lib.rs_engine_fetch_wait(self._h), "rs_engine_fetch_wait")
-            self._crops_landed = False
+        self._fetch_landed = kind
 
     def collect_results(self, n: int) -> List[Instances]:
         """``Instances`` of the results ``wait_results`` waited for (copies out of the pinned buffers)."""
-        return self._collect(n, False, crops=getattr(self, "_crops_landed", False), polygons=self._poly_landed)
+        return self._collect(n, False, self._fetch_landed or "canvas")
 
     def fetch_wait(self, n: int) -> List[Instances]:
         self.wait_results()

@@ -75,7 +75,7 @@ def load_solver(d2_yaml: str) -> Dict[str, Any]:
     }
 
 
-# capacities of the training engine (csrc/train_engine.inc): ground-truth boxes per image, mask-head entries per image,
+# capacities of the training engine (csrc/trainer.hip): ground-truth boxes per image, mask-head entries per image,
 # RoI slots per image, RPN candidates per level
 GT_CAP, MASK_ENTRIES_CAP, ROI_CAP, RPN_PRE_TOPK_CAP, RPN_POST_TOPK_CAP = 128, 256, 1024, 2048, 1024
 

@@ -1,4 +1,4 @@
-"""What the engine graph builder (csrc/engine.hip rs_engine::build and its build_* sections) builds under every structural switch,
+"""What the engine graph builder (csrc/engine.hip: rs_engine::build and its build_* sections, declared in csrc/engine_internal.h) builds under every structural switch,
 precision and spec variant: ordered stage names, tensor count and the ordered tensor table (name | dtype | dims | halo) against
 tests/golden/engine_structure.json.  The engine or trainer is created and inspected, no forward runs.  The configurations and the
 fixture come from tools/parity/engine_manifest.py; on a deliberate change of the graph, rewrite the fixture with its --fixture."""

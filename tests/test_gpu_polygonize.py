@@ -202,6 +202,41 @@ def test_engine_polygons_equal_crops_plus_host_vectoriser(small, n):
         assert g.has("pred_masks") and np.array_equal(g._packed, r._packed)
 
 
+FETCH_ORDER = ("canvas", "canvas", "crops", "crops", "polygons", "polygons", "canvas", "polygons+masks", "crops", "canvas", "polygons", "crops")
+FETCH_ARGS = {"canvas": dict(crops=False), "crops": dict(crops=True), "polygons": dict(polygons=True, rdp_epsilon=0.75),
+              "polygons+masks": dict(polygons=True, rdp_epsilon=0.75, masks=True)}
+
+
+def test_fetch_kinds_in_every_order(small):
+    """One engine, a forward on the same tiles before every fetch, the three kinds of fetch in an order that holds every ordered pair of
+    distinct kinds and each kind twice in a row: whatever was fetched before, a fetch gives the synchronous fetch's detections, the
+    canvas and crops fetches its mask bits, the polygon fetch the polygons of the crops."""
+    spec, W, tiles, eng = small
+    kinds = [k.split("+")[0] for k in FETCH_ORDER]
+    pairs = set(zip(kinds, kinds[1:]))
+    assert pairs >= {(a, b) for a in ("canvas", "crops", "polygons") for b in ("canvas", "crops", "polygons")}
+    for n in (3, 2):
+        crops_lists = [_lists(r, 0.75) for r in _run(eng, tiles[:n], crops=True)]
+        for step, what in enumerate(FETCH_ORDER):
+            got = _run(eng, tiles[:n], **FETCH_ARGS[what])
+            ref = eng.fetch(n)                                    # the same forward, copied on the forward's own stream
+            assert len(got) == len(ref) == n and sum(len(r) for r in ref) > 0
+            flagged = any(len(g._polygons.flagged) for g in got) if what.startswith("polygons") else False
+            for i, (g, r) in enumerate(zip(got, ref)):
+                where = f"n {n} step {step} ({what}) tile {i}"
+                assert _same_dets(g, r), f"{where}: detections differ"
+                if what.startswith("polygons"):
+                    assert g._polygons is not None and g._polygons.rdp_epsilon == 0.75, where
+                    assert _lists(g, 0.75) == crops_lists[i], f"{where}: polygons differ"
+                    assert g.has("pred_masks") == (what == "polygons+masks" or flagged), where
+                    if g.has("pred_masks"):
+                        assert np.array_equal(g.pred_masks, r.pred_masks), f"{where}: mask bits differ"
+                else:
+                    assert g._polygons is None and (g._crops is not None) == (what == "crops"), where
+                    assert g.pred_masks.dtype == r.pred_masks.dtype and np.array_equal(g.pred_masks, r.pred_masks), f"{where}: mask bits differ"
+                    assert _lists(g, 0.75) == crops_lists[i], f"{where}: polygons differ"
+
+
 def _crop_edge_counts(inst):
     """E of every instance of a tile from its crop bytes, the crop taken as a mask of its own (what the kernel counts)."""
     rects, offs, data = inst._crops

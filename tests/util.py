@@ -10,7 +10,7 @@ from proj_roadsurf_amd.matching import box_iou, match_detections, wilson_lower  
 
 def conv_stage_shapes(spec, net_h=800, net_w=800):
     """(stage name, output pixels per tile, cin, k, cout, cin2, forced variant or None) of every GEMM stage of the fp16
-    inference engine, in execution order -- the host-side mirror of csrc/engine.hip's builder sections (rs_engine::build_stem,
+    inference engine, in execution order -- the host-side mirror of csrc/engine.hip's builder sections (declared in csrc/engine_internal.h: rs_engine::build_stem,
     build_bottleneck / add_fused_tail, build_fpn, build_rpn, build_box_head, build_mask_head) that the tile-dispatch tests enumerate.  Output pixels per tile times the batch size is the GEMM's M."""
     out = []
     h2, w2, h4, w4 = net_h // 2, net_w // 2, net_h // 4, net_w // 4

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the engine graph builder (csrc/engine.hip) builds, one JSON record per configuration: structure (net shape, ordered stage
+"""What the engine graph builder (csrc/engine.hip, over struct rs_engine of csrc/engine_internal.h; for a trainer, reached from csrc/trainer.hip) builds, one JSON record per configuration: structure (net shape, ordered stage
 names, ordered tensor table), accounting and dispatch (flops / bytes / kernel per stage, conv variants) and output bits (sha256 of
 every registered tensor's device buffer and of the returned detections).  Two manifests of the same machine are compared field for
 field with ``--compare``: a change of the builder that is meant to keep behaviour must leave the manifest as it was.
