@@ -635,6 +635,48 @@ int rs_rasterize_entries(const double* polys, const int64_t* poly_off, const int
 int rs_op_mask_targets(const double* polys, const int64_t* poly_off, const int32_t* poly_len, const int32_t* inst_first, int n_inst,
                        const int32_t* entry_inst, const float* boxes, int n_entries, int mask_size, uint8_t* out);
 
+/* ------------------------------------------------------------------ validation AP on the device (csrc/val_ap.hip)
+ * The segm side of COCO AP needs, per (detection, ground truth) pair, the pixel count of the intersection and the two areas: integers
+ * that decide the float64 IoU completely (proj_roadsurf_amd/coco_eval.py mask_iou_from_counts).
+ *
+ * rs_op_rasterize_canvas: the polygon tables of rs_op_mask_targets (host pointers), one instance per ground truth, rasterised onto
+ * whole side x side canvases in the rs_dets.masks layout -- out [n_inst][side][(side+7)/8] bytes (host), bit x % 8 of byte x / 8 =
+ * pixel x, padding bits zero -- bit for bit rs_rasterize_polygons_within_box(instance's polygons, box (0, 0, side, side), side).
+ * side in [1, 1024]; an instance without polygons gives an all-zero mask.  Null tables, a side outside the range and an odd poly_len
+ * are refused (RS_ERR_ARG) before a device is touched.
+ *
+ * rs_op_mask_pair_counts: caller-owned device memory.  det_masks [n_tiles][slots][side][(side+7)/8], det_count [n_tiles]; gt_masks
+ * [instances][side][(side+7)/8] (as rs_op_rasterize_canvas writes them), tile t owning instances tile_first[t] .. tile_first[t+1]-1
+ * (at most gt_cap of them are read).  Out, int32: inter [n_tiles][slots][gt_cap] = popcount(detection AND ground truth), det_area
+ * [n_tiles][slots], gt_area [n_tiles][gt_cap]; slots at or past det_count[t] and ground truths past the tile's own are zero.
+ * side * ((side+7)/8) must be a multiple of 4 (RS_ERR_UNSUPPORTED otherwise).  Enqueues on `stream`, does not wait. */
+int rs_op_rasterize_canvas(const double* polys, const int64_t* poly_off, const int32_t* poly_len, const int32_t* inst_first, int n_inst,
+                           int side, uint8_t* out);
+int rs_op_mask_pair_counts(const uint8_t* det_masks, const int32_t* det_count, int n_tiles, int slots, const uint8_t* gt_masks,
+                           const int32_t* tile_first, int gt_cap, int side, int32_t* inter, int32_t* det_area, int32_t* gt_area, void* stream);
+
+/* The same on the detections of the engine's last forward, the counterpart of rs_engine_fetch_crops_*: rs_engine_fetch_eval_async
+ * packs the ground-truth polygons of the batch's n tiles (tables as above; tile_first [n + 1], the first instance of every tile; tile
+ * pixels) into pinned staging and enqueues, on the copy stream behind the forward, their upload, the rasteriser, the pair counts and
+ * the copies of count / boxes / scores / classes (dets->masks and ->mask_probs are ignored: no mask travels) and of the three tables
+ * into caller-allocated (rs_host_alloc) buffers inter [n][D][RS_EVAL_GT_CAP], det_area [n][D], gt_area [n][RS_EVAL_GT_CAP].
+ * rs_engine_fetch_eval_wait waits for them.  The device pool holds, for an engine of max_batch N, N * RS_EVAL_GT_CAP instances with
+ * at most RS_EVAL_GT_CAP per tile, N * 512 polygons and N * 65536 doubles; it is allocated on the first call.  A batch beyond it, a
+ * non-square tile, a side above 1024 or one whose packed masks are no whole 32-bit words, and an engine with MASK_ON false return
+ * RS_EVAL_DOES_NOT_FIT (positive, not an error: nothing was enqueued, evaluate this batch from rs_engine_fetch's masks).
+ * rs_engine_eval_fits is that check alone (host only), for a caller that wants to know before the forward. */
+#define RS_EVAL_DOES_NOT_FIT 2
+#define RS_EVAL_GT_CAP 128
+typedef struct rs_eval_counts {
+  int32_t* inter;     /* [n][D][RS_EVAL_GT_CAP] */
+  int32_t* det_area;  /* [n][D] */
+  int32_t* gt_area;   /* [n][RS_EVAL_GT_CAP] */
+} rs_eval_counts;
+int rs_engine_eval_fits(rs_engine* e, int n, const int64_t* poly_off, const int32_t* poly_len, const int32_t* inst_first, const int32_t* tile_first);
+int rs_engine_fetch_eval_async(rs_engine* e, int n, rs_dets* dets_host, const double* polys, const int64_t* poly_off, const int32_t* poly_len,
+                               const int32_t* inst_first, const int32_t* tile_first, rs_eval_counts* counts_host);
+int rs_engine_fetch_eval_wait(rs_engine* e);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,9 @@ known precision/recall staircase, score ordering, area ranges, crowd handling) a
 ground-truth sets (crowd regions, empty images, tied scores, max_dets caps, annotated areas; bbox and segm) against an independent
 brute-force statement of the definitions (oracle/coco_ap_oracle.py: declarative matching, interpolated precision by its definition;
 test infrastructure, never imported here) to 1e-9.  Masks are numpy bool arrays here (the engine's
-``Instances.pred_masks`` / rasterised ground-truth polygons), boxes XYXY."""
+``Instances.pred_masks`` / rasterised ground-truth polygons), boxes XYXY.  For ``segm`` an image may carry integer pixel counts
+instead of masks (``mask_inter`` / ``mask_area``, counted on the device: ``Engine.eval_counts``); the IoUs, and so the match records,
+are the same bits (``mask_iou_from_counts``)."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -48,6 +50,18 @@ def mask_iou(d: np.ndarray, g: np.ndarray, crowd: np.ndarray) -> np.ndarray:
     gf = g.reshape(g.shape[0], int(np.prod(g.shape[1:]))).astype(np.float64)
     inter = df @ gf.T
     ad, ag = df.sum(1), gf.sum(1)
+    union = np.where(crowd[None, :], ad[:, None], ad[:, None] + ag[None, :] - inter)
+    return np.where(union > 0, inter / np.maximum(union, 1e-300), 0.0)
+
+
+def mask_iou_from_counts(inter: np.ndarray, d_area: np.ndarray, g_area: np.ndarray, crowd: np.ndarray) -> np.ndarray:
+    """``mask_iou`` from pixel counts: inter (D,G) = |detection AND ground truth|, d_area (D,), g_area (G,) = the masks' own pixel
+    counts (integers).  The same float64 arithmetic on the same values -- 0/1 products and their sums are exact in float64 -- so the
+    result equals ``mask_iou`` on the masks the counts were taken from, bit for bit."""
+    inter = np.asarray(inter, np.float64).reshape(len(d_area), len(g_area))
+    if inter.shape[0] == 0 or inter.shape[1] == 0:
+        return np.zeros(inter.shape)
+    ad, ag = np.asarray(d_area, np.float64), np.asarray(g_area, np.float64)
     union = np.where(crowd[None, :], ad[:, None], ad[:, None] + ag[None, :] - inter)
     return np.where(union > 0, inter / np.maximum(union, 1e-300), 0.0)
 
@@ -101,7 +115,13 @@ def match_images(gts: Sequence[Dict], dets: Sequence[Dict], num_classes: int, io
             gb, db = np.asarray(g["boxes"], np.float64).reshape(-1, 4)[gm], np.asarray(d["boxes"], np.float64).reshape(-1, 4)[dm]
             crowd = np.asarray(g.get("crowd", np.zeros(len(g["classes"]), bool)), bool)[gm]
             sc = np.asarray(d["scores"], np.float64)[dm]
-            if iou_type == "segm":
+            if iou_type == "segm" and "mask_inter" in d:
+                # integer counts in place of masks (Engine.eval_counts): d["mask_inter"] (D,G) over ALL of the image's detections and
+                # ground truths, d["mask_area"] (D,), g["mask_area"] (G,)
+                g_area = np.asarray(g["mask_area"], np.float64).reshape(-1)[gm]
+                d_area = np.asarray(d["mask_area"], np.float64).reshape(-1)[dm]
+                ious = mask_iou_from_counts(np.asarray(d["mask_inter"]).reshape(len(dm), len(gm))[dm][:, gm], d_area, g_area, crowd)
+            elif iou_type == "segm":
                 gmk, dmk = np.asarray(g["masks"], bool)[gm], np.asarray(d["masks"], bool)[dm]
                 ious = mask_iou(dmk, gmk, crowd)
                 g_area = gmk.sum(axis=(1, 2)).astype(np.float64) if gmk.ndim == 3 else np.zeros(gmk.shape[0])
@@ -166,5 +186,6 @@ def accumulate(per_image: Sequence[Dict], num_classes: int) -> Dict[str, float]:
 
 def evaluate(gts: Sequence[Dict], dets: Sequence[Dict], num_classes: int, iou_type: str = "bbox", max_dets: int = 100) -> Dict[str, float]:
     """gts[i] / dets[i] describe image i: {"boxes" (k,4) XYXY, "classes" (k,), ["masks" (k,H,W) bool], ["crowd" (k,) bool]} and
-    {"boxes", "classes", "scores", ["masks"]}.  ``accumulate(match_images(...))``."""
+    {"boxes", "classes", "scores", ["masks"]}; for segm, in place of the two "masks": dets[i]["mask_inter"] (k_det, k_gt) int,
+    dets[i]["mask_area"] (k_det,) and gts[i]["mask_area"] (k_gt,) pixel counts.  ``accumulate(match_images(...))``."""
     return accumulate(match_images(gts, dets, num_classes, iou_type, max_dets), num_classes)

@@ -8,7 +8,9 @@
 #include <cmath>
 
 #include "engine_internal.h"
+#include "polygon_pool.h"
 #include "train.h"
+#include "val_ap.h"
 
 // ------------------------------------------------------------------------------------- errors
 static thread_local char g_err[1024] = "";
@@ -1104,6 +1106,41 @@ int rs_engine::ensure_polygon_buffers() {
   return RS_OK;
 }
 
+int rs_engine::ensure_eval_buffers() {
+  if (eval_pool) return RS_OK;
+  MtLayout L;
+  mt_layout(max_batch, max_batch * RS_EVAL_GT_CAP, max_batch * 512, (size_t)max_batch * 65536, &L);
+  const size_t mask_bytes = (size_t)tile_h * ((tile_w + 7) / 8);
+  int rc;
+  if ((rc = alloc((void**)&eval_gt_masks, (size_t)max_batch * RS_EVAL_GT_CAP * mask_bytes))) return rc;
+  if ((rc = alloc((void**)&eval_inter, (size_t)max_batch * D * RS_EVAL_GT_CAP * 4))) return rc;
+  if ((rc = alloc((void**)&eval_det_area, (size_t)max_batch * D * 4))) return rc;
+  if ((rc = alloc((void**)&eval_gt_area, (size_t)max_batch * RS_EVAL_GT_CAP * 4))) return rc;
+  RS_HIP(hipEventCreateWithFlags(&ev_eval_upload, hipEventDisableTiming));
+  RS_HIP(hipHostMalloc((void**)&eval_pinned, L.bytes, hipHostMallocDefault));
+  eval_pool_bytes = L.bytes;
+  return alloc((void**)&eval_pool, L.bytes);      // last: its presence says that all of the above exists
+}
+
+// upload of the packed pool, rasteriser, pair counts: on the copy stream, behind the forward and in front of the result copies
+int rs_engine::launch_eval_counts(int n, const void* layout, hipStream_t s) {
+  const MtLayout& L = *(const MtLayout*)layout;
+  RS_HIP(hipMemcpyAsync(eval_pool, eval_pinned, L.bytes, hipMemcpyHostToDevice, s));
+  RS_HIP(hipEventRecord(ev_eval_upload, s));
+  eval_upload_pending = true;
+  CanvasRasterParams q;
+  memset(&q, 0, sizeof q);
+  q.inst_first = (const int*)(eval_pool + L.o_inst); q.poly_off = (const int*)(eval_pool + L.o_off); q.poly_len = (const int*)(eval_pool + L.o_len);
+  q.polys = (const double*)(eval_pool + L.o_xy); q.out = eval_gt_masks; q.n_inst = L.n_inst; q.side = tile_h;
+  { int rc = launch_canvas_raster(q, s); if (rc) return rc; }
+  PairCountParams c;
+  memset(&c, 0, sizeof c);
+  c.det_masks = masks; c.det_count = det_count; c.gt_masks = eval_gt_masks; c.tile_first = (const int*)eval_pool;
+  c.inter = eval_inter; c.det_area = eval_det_area; c.gt_area = eval_gt_area; c.n = n; c.D = D; c.g_cap = RS_EVAL_GT_CAP;
+  c.bytes = (long long)tile_h * ((tile_w + 7) / 8);
+  return launch_mask_pair_counts(c, s);
+}
+
 int rs_engine::begin_fetch(hipStream_t* s) {
   if (!copy_stream) {
     RS_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
@@ -1254,6 +1291,8 @@ void rs_engine_destroy(rs_engine* e) {
   if (e->h_crop_total) (void)hipHostFree(e->h_crop_total);
   if (e->ev_poly_hdr) (void)hipEventDestroy(e->ev_poly_hdr);
   if (e->h_poly_totals) (void)hipHostFree(e->h_poly_totals);
+  if (e->ev_eval_upload) (void)hipEventDestroy(e->ev_eval_upload);
+  if (e->eval_pinned) (void)hipHostFree(e->eval_pinned);
   if (e->h_sat_copy) (void)hipHostFree(e->h_sat_copy);
   if (e->ev_results) (void)hipEventDestroy(e->ev_results);
   if (e->ev_copied) (void)hipEventDestroy(e->ev_copied);
@@ -1344,7 +1383,7 @@ int rs_engine_upload_async(rs_engine* e, const uint8_t* tiles_host, int n) {
   return RS_OK;
 }
 
-// The three asynchronous fetches are sequences of the rs_engine fetch steps above (engine_internal.h).  On the copy stream, in this order:
+// The asynchronous fetches are sequences of the rs_engine fetch steps above (engine_internal.h).  On the copy stream, in this order:
 // crop kernel, polygon kernel, detection copies, crop table, polygon headers, saturation snapshot, ev_copied, the header event.
 int rs_engine_fetch_async(rs_engine* e, int n, rs_dets* o) {
   RS_CHECK(e && o && o->count && n >= 1 && n <= e->max_batch, RS_ERR_ARG, "bad argument");
@@ -1420,6 +1459,51 @@ int rs_engine_fetch_polygons_wait(rs_engine* e, rs_polygons* g) {
   e->sat_publish();
   return RS_OK;
 }
+
+// Does the batch fit the device pool of the validation counts?  RS_OK, RS_EVAL_DOES_NOT_FIT, or an error for tables that are malformed.
+int rs_engine_eval_fits(rs_engine* e, int n, const int64_t* poly_off, const int32_t* poly_len, const int32_t* inst_first, const int32_t* tile_first) {
+  RS_CHECK(e && inst_first && tile_first && n >= 1 && n <= e->max_batch, RS_ERR_ARG, "bad argument");
+  RS_CHECK(tile_first[0] == 0, RS_ERR_ARG, "tile_first must start at 0");
+  for (int i = 0; i < n; ++i) RS_CHECK(tile_first[i + 1] >= tile_first[i], RS_ERR_ARG, "tile_first decreases at tile %d", i);
+  if (!e->masks || e->tile_h != e->tile_w || e->tile_h > CR_MAX_SIDE || ((long long)e->tile_h * ((e->tile_w + 7) / 8)) % 4) return RS_EVAL_DOES_NOT_FIT;
+  for (int i = 0; i < n; ++i) if (tile_first[i + 1] - tile_first[i] > RS_EVAL_GT_CAP) return RS_EVAL_DOES_NOT_FIT;
+  const int n_inst = tile_first[n];
+  RS_CHECK(inst_first[0] == 0, RS_ERR_ARG, "polygons: inst_first must start at 0");
+  for (int g = 0; g < n_inst; ++g) RS_CHECK(inst_first[g + 1] >= inst_first[g], RS_ERR_ARG, "polygons: inst_first decreases at instance %d", g);
+  const int n_poly = inst_first[n_inst];
+  if (n_poly > e->max_batch * 512) return RS_EVAL_DOES_NOT_FIT;
+  RS_CHECK(n_poly == 0 || poly_len, RS_ERR_ARG, "polygons: null table");
+  size_t doubles = 0;
+  for (int q = 0; q < n_poly; ++q) {
+    RS_CHECK(poly_len[q] >= 2 && !(poly_len[q] & 1), RS_ERR_ARG, "polygon %d: %d doubles", q, poly_len[q]);
+    doubles += (size_t)poly_len[q];
+  }
+  (void)poly_off;
+  return doubles > (size_t)e->max_batch * 65536 ? RS_EVAL_DOES_NOT_FIT : RS_OK;
+}
+
+int rs_engine_fetch_eval_async(rs_engine* e, int n, rs_dets* o, const double* polys, const int64_t* poly_off, const int32_t* poly_len,
+                               const int32_t* inst_first, const int32_t* tile_first, rs_eval_counts* c) {
+  RS_CHECK(e && o && o->count && c && c->inter && c->det_area && c->gt_area && n >= 1 && n <= e->max_batch, RS_ERR_ARG, "bad argument");
+  { int rc = rs_engine_eval_fits(e, n, poly_off, poly_len, inst_first, tile_first); if (rc) return rc; }
+  MtLayout L;
+  { int rc = mt_measure(polys, poly_off, poly_len, inst_first, tile_first[n], n, &L); if (rc) return rc; }
+  hipStream_t s = nullptr;
+  int rc;
+  if ((rc = e->ensure_eval_buffers())) return rc;
+  RS_CHECK(L.bytes <= e->eval_pool_bytes, RS_ERR_ARG, "validation polygons: %zu bytes packed, the pool holds %zu", L.bytes, e->eval_pool_bytes);
+  if (e->eval_upload_pending) { RS_HIP(hipEventSynchronize(e->ev_eval_upload)); e->eval_upload_pending = false; }
+  mt_pack(e->eval_pinned, L, polys, poly_off, poly_len, inst_first, tile_first);
+  if ((rc = e->begin_fetch(&s))) return rc;
+  if ((rc = e->launch_eval_counts(n, &L, s))) return rc;
+  if ((rc = e->enqueue_dets(o, n, s, false))) return rc;
+  RS_HIP(hipMemcpyAsync(c->inter, e->eval_inter, (size_t)n * e->D * RS_EVAL_GT_CAP * 4, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(c->det_area, e->eval_det_area, (size_t)n * e->D * 4, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(c->gt_area, e->eval_gt_area, (size_t)n * RS_EVAL_GT_CAP * 4, hipMemcpyDeviceToHost, s));
+  return e->end_fetch(s, nullptr);            // the counts live in their own buffers: detections and canvases are free for the next forward
+}
+
+int rs_engine_fetch_eval_wait(rs_engine* e) { return rs_engine_fetch_wait(e); }
 
 int rs_engine_fetch_wait(rs_engine* e) {
   RS_CHECK(e, RS_ERR_ARG, "null engine");

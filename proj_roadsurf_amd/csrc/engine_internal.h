@@ -112,9 +112,20 @@ struct rs_engine {
   int* h_poly_totals = nullptr;                 // pinned [4]
   hipEvent_t ev_poly_hdr = nullptr;
 
+  // validation counts for the host (rs_engine_fetch_eval_*): allocated on the first call, like the polygons' buffers
+  uint8_t* eval_pool = nullptr;                 // device: the batch's ground-truth polygons (polygon_pool.h)
+  uint8_t* eval_pinned = nullptr;               // pinned staging of the pool
+  size_t eval_pool_bytes = 0;
+  uint8_t* eval_gt_masks = nullptr;             // [max_batch * RS_EVAL_GT_CAP][tile_h][ceil(tile_w / 8)]
+  int *eval_inter = nullptr, *eval_det_area = nullptr, *eval_gt_area = nullptr;
+  hipEvent_t ev_eval_upload = nullptr;          // recorded behind the pool's upload: the staging may be packed again after it
+  bool eval_upload_pending = false;
+
   // the steps of a result fetch, in the order the fetch entries enqueue them (engine.hip)
   int ensure_crop_header();
   int ensure_polygon_buffers();
+  int ensure_eval_buffers();
+  int launch_eval_counts(int n, const void* layout, hipStream_t s);   // layout: the MtLayout of what eval_pinned holds
   int begin_fetch(hipStream_t* s);                       // creates the copy stream on first use; it waits for the work enqueued on `stream` so far
   int launch_crops(int n, hipStream_t s);
   int launch_polygons(int n, double rdp_epsilon, hipStream_t s);

@@ -6,7 +6,9 @@
 
 #include "../../include/rs_engine.h"
 #include "detect.h"
+#include "polygon_pool.h"
 #include "train.h"
+#include "val_ap.h"
 
 namespace {
 
@@ -181,6 +183,48 @@ int rs_op_mask_overlap(const uint8_t* det_masks, int n_det, const uint8_t* label
   return launch_mask_overlap(det_masks, n_det, label_masks, n_labels, h, w, inter, label_area, (hipStream_t)stream);
 }
 
+
+// canvas_raster_kernel as an operator, the counterpart of rs_op_mask_targets: host pointers in, packs and uploads the polygons,
+// rasterises one canvas per instance and copies the bit-packed masks back.  Arguments are refused before a device is touched.
+int rs_op_rasterize_canvas(const double* polys, const int64_t* poly_off, const int32_t* poly_len, const int32_t* inst_first, int n_inst,
+                           int side, uint8_t* out) {
+  RS_CHECK(inst_first && n_inst >= 0 && (out || n_inst == 0), RS_ERR_ARG, "rasterize_canvas: null table");
+  RS_CHECK(side >= 1 && side <= CR_MAX_SIDE, RS_ERR_ARG, "rasterize_canvas: side %d outside [1, %d]", side, CR_MAX_SIDE);
+  MtLayout L;
+  { int rc = mt_measure(polys, poly_off, poly_len, inst_first, n_inst, 0, &L); if (rc) return rc; }
+  RS_CHECK(L.n_doubles <= (size_t)MT_MAX_DOUBLES, RS_ERR_UNSUPPORTED, "rasterize_canvas: more than %d doubles of polygons", MT_MAX_DOUBLES);
+  if (n_inst == 0) return RS_OK;
+  std::vector<uint8_t> host(L.bytes);
+  const int32_t zero = 0;
+  mt_pack(host.data(), L, polys, poly_off, poly_len, inst_first, &zero);
+  const size_t bytes = (size_t)n_inst * side * ((side + 7) / 8);
+  OpScratch scratch(nullptr);
+  uint8_t *pool = nullptr, *m = nullptr;
+  { int rc = scratch.alloc((void**)&pool, L.bytes); if (rc) return rc; }
+  { int rc = scratch.alloc((void**)&m, bytes); if (rc) return rc; }
+  RS_HIP(hipMemcpy(pool, host.data(), L.bytes, hipMemcpyHostToDevice));
+  CanvasRasterParams q;
+  memset(&q, 0, sizeof q);
+  q.inst_first = (const int*)(pool + L.o_inst); q.poly_off = (const int*)(pool + L.o_off); q.poly_len = (const int*)(pool + L.o_len);
+  q.polys = (const double*)(pool + L.o_xy); q.out = m; q.n_inst = n_inst; q.side = side;
+  { int rc = launch_canvas_raster(q, nullptr); if (rc) return rc; }
+  RS_HIP(hipMemcpy(out, m, bytes, hipMemcpyDeviceToHost));
+  return RS_OK;
+}
+
+// mask_pair_counts_kernel on caller-owned device memory (see include/rs_engine.h)
+int rs_op_mask_pair_counts(const uint8_t* det_masks, const int32_t* det_count, int n_tiles, int slots, const uint8_t* gt_masks,
+                           const int32_t* tile_first, int gt_cap, int side, int32_t* inter, int32_t* det_area, int32_t* gt_area, void* stream) {
+  RS_CHECK(det_masks && det_count && tile_first && inter && det_area && gt_area, RS_ERR_ARG, "mask_pair_counts: null buffer");
+  RS_CHECK(side >= 1 && side <= CR_MAX_SIDE, RS_ERR_ARG, "mask_pair_counts: side %d outside [1, %d]", side, CR_MAX_SIDE);
+  RS_CHECK(n_tiles >= 1 && slots >= 1 && gt_cap >= 1, RS_ERR_ARG, "mask_pair_counts: %d tiles, %d slots, %d ground truths per tile", n_tiles, slots, gt_cap);
+  PairCountParams q;
+  memset(&q, 0, sizeof q);
+  q.det_masks = det_masks; q.det_count = det_count; q.gt_masks = gt_masks; q.tile_first = tile_first;
+  q.inter = inter; q.det_area = det_area; q.gt_area = gt_area; q.n = n_tiles; q.D = slots; q.g_cap = gt_cap;
+  q.bytes = (long long)side * ((side + 7) / 8);
+  return launch_mask_pair_counts(q, (hipStream_t)stream);
+}
 
 int rs_op_conv2d_dgrad(const void* dy, const void* w_t, void* dx, const void* res, const float* res32, const void* mask,
                        const void* down, int n, int hi, int wi, int cin, int ho, int wo, int cout, int kh, int kw, int stride,

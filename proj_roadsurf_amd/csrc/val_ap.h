@@ -1,0 +1,35 @@
+// Validation AP on the device (val_ap.hip): ground-truth polygons rasterised onto whole canvases in the rs_dets.masks layout, and the
+// pixel counts of every (detection, ground truth) pair of a batch of tiles.  DESIGN.md section 8 ("Validation AP on the device").
+#pragma once
+#include "common.h"
+// after common.h: the HIP runtime header defines what MT_HD expands to
+#include "canvas_raster.h"
+
+// One mask per instance, [n_inst][side][(side + 7) / 8] bytes, bit x % 8 of byte x / 8 = pixel x, padding bits zero: bit for bit
+// rs_rasterize_polygons_within_box(polygons of the instance, box (0, 0, side, side), mask_size side).  Tables as MaskTargetsParams
+// (polygon_pool.h).  Every byte of `out` is written, an instance without polygons gives zeros.
+struct CanvasRasterParams {
+  const int* inst_first;    // [n_inst + 1]
+  const int* poly_off;      // [n_poly] doubles into polys
+  const int* poly_len;      // [n_poly] doubles
+  const double* polys;
+  uint8_t* out;
+  int n_inst, side;
+};
+int launch_canvas_raster(const CanvasRasterParams& p, hipStream_t s);
+
+// inter [n][D][g_cap], det_area [n][D], gt_area [n][g_cap] (int32) over the detection slots < count[tile] and the ground truths
+// tile_first[tile] .. tile_first[tile + 1] - 1 of gt_masks; everything else in the three tables is zero.  Masks of `bytes` bytes each
+// (a multiple of 4): det_masks [n][D][bytes], gt_masks [instances][bytes].
+struct PairCountParams {
+  const uint8_t* det_masks;
+  const int* det_count;     // [n]
+  const uint8_t* gt_masks;
+  const int* tile_first;    // [n + 1]
+  int* inter;
+  int* det_area;
+  int* gt_area;
+  int n, D, g_cap;
+  long long bytes;
+};
+int launch_mask_pair_counts(const PairCountParams& p, hipStream_t s);

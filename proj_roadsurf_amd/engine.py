@@ -95,6 +95,10 @@ class RsPolygons(C.Structure):
 POLY_HDR = 8       # RS_POLY_HDR: flagged, polygons, rings, vertices, first polygon, first ring, first vertex, 0
 
 
+class RsEvalCounts(C.Structure):
+    _fields_ = [("inter", C.POINTER(C.c_int32)), ("det_area", C.POINTER(C.c_int32)), ("gt_area", C.POINTER(C.c_int32))]
+
+
 class PolygonTables:
     """Polygons of the instances of one tile as the device polygoniser leaves them (include/rs_engine.h, ``rs_op_polygonize``):
     ``header`` (n, 8) int32 per instance [flagged, polygons, rings, vertices, first polygon, first ring, first vertex, 0] with the
@@ -214,6 +218,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.rs_polygonize_caps.restype = None
     lib.rs_op_polygonize.argtypes = [vp, i32, i32, i32, C.c_double, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.rs_op_polygonize_crops.argtypes = [vp, i32, i32, vp, vp, i32, i32, C.c_double, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.rs_op_rasterize_canvas.argtypes = [vp] * 4 + [i32, i32, vp]
+    lib.rs_op_mask_pair_counts.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp]
+    lib.rs_engine_eval_fits.argtypes = [vp, i32, vp, vp, vp, vp]
+    lib.rs_engine_fetch_eval_async.argtypes = [vp, i32, C.POINTER(RsDets), vp, vp, vp, vp, vp, C.POINTER(RsEvalCounts)]
+    lib.rs_engine_fetch_eval_wait.argtypes = [vp]
     lib.rs_rasterize_polygons_within_box.argtypes = [f64p, i32p, i32, f64p, i32, u8p]
     lib.rs_memcpy_d2h.argtypes = [vp, vp, C.c_size_t]
     lib.rs_op_fdiv.argtypes = [vp, vp, vp, C.c_int64, vp]
@@ -468,6 +477,9 @@ class Engine:
         # the kind of fetch_async that is in flight, and of the one wait_results waited for last: None, "canvas", "crops" or "polygons"
         self._fetch_pending: Optional[str] = None
         self._fetch_landed: Optional[str] = None
+        # validation counts (rs_engine_fetch_eval_*): pinned tables, allocated on the first eval_counts; batches that did not fit
+        self._eval_struct: Optional[RsEvalCounts] = None
+        self.eval_fallbacks = 0
 
     def _dets_struct(self, want_probs: bool) -> RsDets:
         d = RsDets()
@@ -621,6 +633,59 @@ class Engine:
     def fetch_wait(self, n: int) -> List[Instances]:
         self.wait_results()
         return self.collect_results(n)
+
+    def eval_counts(self, tiles_or_n, gt_polygons: Sequence[Sequence[Sequence[np.ndarray]]]):
+        """What COCO's segm matching needs of a validation batch, counted on the device: ``tiles_or_n`` = (n, h, w, c) uint8 tiles (a
+        forward is run on them) or n, the batch size of the forward already enqueued; gt_polygons[tile][gt index] = list of polygons
+        ([x0, y0, ...], tile pixels).  The ground truths are rasterised onto full canvases on the GPU (bit for bit
+        ``rasterize_polygons_within_box(polygons, (0, 0, w, h), h)``) and no mask travels to the host.  Returns per tile
+        ``(Instances without masks, inter (D_t, G_t) int32, det_area (D_t,), gt_area (G_t,))`` -- pixel counts of detection AND ground
+        truth and of either alone, for ``coco_eval.match_images`` (keys mask_inter / mask_area) -- or ``None`` when the batch does
+        not fit the device pool (more than 128 ground truths in a tile, max_batch * 512 polygons or max_batch * 65536 coordinates; a
+        non-square tile or one above 1024 px; MASK_ON false): then nothing was run or enqueued, ``eval_fallbacks`` counts it, and the
+        caller evaluates this batch from ``infer``'s masks."""
+        n = int(tiles_or_n) if np.isscalar(tiles_or_n) else int(tiles_or_n.shape[0])
+        if len(gt_polygons) != n or not 1 <= n <= self.max_batch:
+            raise ValueError(f"{len(gt_polygons)} ground-truth lists for a batch of {n} (1..{self.max_batch})")
+        arrs = [np.asarray(p, np.float64).reshape(-1) for img in gt_polygons for polys in img for p in polys]
+        lens = np.array([a.size for a in arrs] or [0], np.int32)
+        off = np.zeros(max(len(arrs), 1), np.int64)
+        if len(arrs) > 1:
+            off[1:] = np.cumsum(lens[:-1], dtype=np.int64)
+        flat = np.ascontiguousarray(np.concatenate(arrs)) if arrs else np.zeros(1)
+        inst_first = np.zeros(sum(len(img) for img in gt_polygons) + 1, np.int32)
+        inst_first[1:] = np.cumsum([len(polys) for img in gt_polygons for polys in img])
+        tile_first = np.zeros(n + 1, np.int32)
+        tile_first[1:] = np.cumsum([len(img) for img in gt_polygons])
+        rc = self.lib.rs_engine_eval_fits(self._h, n, off.ctypes.data, lens.ctypes.data, inst_first.ctypes.data, tile_first.ctypes.data)
+        if rc == RS_EVAL_DOES_NOT_FIT:
+            self.eval_fallbacks += 1
+            return None
+        _check(self.lib, rc, "rs_engine_eval_fits")
+        if not np.isscalar(tiles_or_n):
+            self.infer_device(self.upload_async(np.ascontiguousarray(tiles_or_n)), n)
+        if self._eval_struct is None:
+            self._eval_inter = self._pinned((self.max_batch, self.D, EVAL_GT_CAP), np.int32)
+            self._eval_det_area = self._pinned((self.max_batch, self.D), np.int32)
+            self._eval_gt_area = self._pinned((self.max_batch, EVAL_GT_CAP), np.int32)
+            c = RsEvalCounts()
+            c.inter = self._eval_inter.ctypes.data_as(C.POINTER(C.c_int32))
+            c.det_area = self._eval_det_area.ctypes.data_as(C.POINTER(C.c_int32))
+            c.gt_area = self._eval_gt_area.ctypes.data_as(C.POINTER(C.c_int32))
+            self._eval_struct = c
+        d = self._dets_struct(False)
+        d.masks = None
+        rc = self.lib.rs_engine_fetch_eval_async(self._h, n, C.byref(d), flat.ctypes.data, off.ctypes.data, lens.ctypes.data, inst_first.ctypes.data,
+                                                 tile_first.ctypes.data, C.byref(self._eval_struct))
+        _check(self.lib, rc, "rs_engine_fetch_eval_async")       # the fit was checked above: any other code here is an error
+        _check(self.lib, self.lib.rs_engine_fetch_eval_wait(self._h), "rs_engine_fetch_eval_wait")
+        out = []
+        for i in range(n):
+            c, g = int(self._count[i]), int(tile_first[i + 1] - tile_first[i])
+            inst = Instances((self.tile_h, self.tile_w), self._boxes[i, :c].copy(), self._scores[i, :c].copy(), self._classes[i, :c].astype(np.int64),
+                             None, None)
+            out.append((inst, self._eval_inter[i, :c, :g].copy(), self._eval_det_area[i, :c].copy(), self._eval_gt_area[i, :g].copy()))
+        return out
 
     def infer_device(self, tiles_dev_ptr: int, n: int) -> None:
         """Enqueue a forward on tiles already in device memory (no wait)."""
@@ -1058,6 +1123,8 @@ class Predictor:
 
 
 MASK_TARGET_MODES = ("host", "device")
+RS_EVAL_DOES_NOT_FIT = 2       # include/rs_engine.h: rs_engine_fetch_eval_async, the batch's ground truth exceeds the device pool
+EVAL_GT_CAP = 128              # RS_EVAL_GT_CAP: ground truths per tile, and the row length of the count tables
 RS_POLYGONS_DO_NOT_FIT = 1     # include/rs_engine.h: rs_trainer_set_polygons, the batch's polygons exceed the device pool
 
 

@@ -51,6 +51,31 @@ def overlap_counts_device(lib, det_dev_ptr: int, n_det: int, lab_packed: np.ndar
     return inter.cpu().numpy(), area.cpu().numpy()
 
 
+def pair_counts_device(det_packed: np.ndarray, det_count: np.ndarray, gt_packed: np.ndarray, tile_first: np.ndarray, side: int,
+                       gt_cap: int = 128, prefill: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``rs_op_mask_pair_counts`` on host arrays (uploaded through torch): det_packed (tiles, slots, side, ceil(side / 8)) and gt_packed
+    (instances, side, ceil(side / 8)) bit-packed masks, det_count (tiles,), tile_first (tiles + 1,) -> inter (tiles, slots, gt_cap),
+    det_area (tiles, slots), gt_area (tiles, gt_cap) int32; everything outside the counted slots and the tiles' own ground truths is
+    zero.  ``prefill``: what the output buffers hold before the call (the operator clears them itself)."""
+    import torch
+    from .engine import _check, load_library
+    lib = load_library()
+    n, slots = int(det_packed.shape[0]), int(det_packed.shape[1])
+    dev = torch.device("cuda")
+    det = torch.from_numpy(np.ascontiguousarray(det_packed)).to(dev)
+    gt = torch.from_numpy(np.ascontiguousarray(gt_packed)).to(dev) if gt_packed.size else None
+    cnt = torch.from_numpy(np.ascontiguousarray(det_count, np.int32)).to(dev)
+    first = torch.from_numpy(np.ascontiguousarray(tile_first, np.int32)).to(dev)
+    inter = torch.full((n, slots, gt_cap), prefill, dtype=torch.int32, device=dev)
+    d_area = torch.full((n, slots), prefill, dtype=torch.int32, device=dev)
+    g_area = torch.full((n, gt_cap), prefill, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    _check(lib, lib.rs_op_mask_pair_counts(det.data_ptr(), cnt.data_ptr(), n, slots, gt.data_ptr() if gt is not None else None, first.data_ptr(),
+                                           gt_cap, side, inter.data_ptr(), d_area.data_ptr(), g_area.data_ptr(), None), "rs_op_mask_pair_counts")
+    torch.cuda.synchronize()
+    return inter.cpu().numpy(), d_area.cpu().numpy(), g_area.cpu().numpy()
+
+
 def weighted_scores(inter: np.ndarray, label_area: np.ndarray, scores: np.ndarray, classes: np.ndarray, road_ids: Sequence) -> List[Dict]:
     """``get_weighted_scores`` (R:determine_class.py:97-120) from pixel counts: one row per (label, detection) pair with
     ``area_pred_in_label = round(intersection / label area, 2) > 0.05``; ``weighted_score = area_pred_in_label * score``."""

@@ -212,6 +212,34 @@ def training_sampler(n: int, seed: int, rank: int, world: int):
             k += 1
 
 
+def validation_chunk(eng, spec, chunk: Sequence[Dict[str, Any]], tiles: np.ndarray, val_ap: str = "host"):
+    """Inference on one chunk of validation records and what ``coco_eval.match_images`` needs of it: (gts, dets, fell_back), one
+    dict each per image.  ``val_ap`` "host": the detection masks are copied back and unpacked, every ground-truth polygon is
+    rasterised at tile size on the host, and the images carry "masks".  "device": ``Engine.eval_counts`` rasterises the ground
+    truth and counts the mask overlaps on the GPU, and the images carry the integer tables ("mask_inter" / "mask_area") -- the same
+    match records; a chunk that does not fit the device pool takes the host path (fell_back)."""
+    from .train_targets import rasterize_polygons_within_box
+    gts, dts = [], []
+    fell_back = False
+    if val_ap == "device" and spec.mask_on:
+        counted = eng.eval_counts(tiles, [r["polygons"] for r in chunk])
+        if counted is not None:
+            for r, (inst, inter, d_area, g_area) in zip(chunk, counted):
+                gts.append({"boxes": r["boxes"], "classes": r["classes"], "mask_area": g_area})
+                dts.append({"boxes": inst.pred_boxes, "classes": inst.pred_classes, "scores": inst.scores, "mask_inter": inter, "mask_area": d_area})
+            return gts, dts, False
+        fell_back = True
+    for r, inst in zip(chunk, eng.infer(tiles)):
+        h, w = tiles.shape[1:3]
+        g = {"boxes": r["boxes"], "classes": r["classes"]}
+        d = {"boxes": inst.pred_boxes, "classes": inst.pred_classes, "scores": inst.scores}
+        if spec.mask_on and h == w:
+            g["masks"] = np.stack([rasterize_polygons_within_box(p, np.array([0.0, 0.0, w, h]), h) for p in r["polygons"]])
+            d["masks"] = inst.pred_masks
+        gts.append(g); dts.append(d)
+    return gts, dts, fell_back
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("config_file", help="YAML with a 'train_model.py' section (R:config/config_obj_detec.yaml)")
@@ -234,6 +262,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "back, rasterised on host threads and uploaded.  device: the batch's polygons are uploaded with the targets and "
                          "rasterised on the GPU, the same bytes without a host wait inside the step; a batch whose polygons do not fit the "
                          "device pool runs the host path for that step")
+    ap.add_argument("--val-ap", choices=("host", "device"), default="host",
+                    help="where the validation AP's mask overlaps are counted.  host (default): every detection mask is copied back, every "
+                         "ground-truth polygon rasterised on the host and the IoUs taken from the masks.  device: the ground truth is "
+                         "rasterised and the pixel counts of every (detection, ground truth) pair are taken on the GPU; only integers "
+                         "travel and the match records are the same.  A chunk that does not fit the device pool is evaluated on the host")
     return ap
 
 
@@ -388,6 +421,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             tot, cnt = float(t[0]), int(t[1])
         return tot / max(cnt, 1)
 
+    val_ap_fallbacks = [0]                # chunks of a --val-ap device run that were evaluated on the host
+    if args.val_ap == "device":
+        log.info("val_ap: device (ground truth rasterised and mask pair counts taken on the GPU; only integers travel)")
+
     def validation_ap() -> Dict[str, float]:
         """COCOEvaluator on the val set (bbox + segm AP; coco_eval.py) with the CURRENT weights.  As detectron2's
         ``inference_on_dataset`` + ``COCOEvaluator`` do, the images are sharded over the ranks (rank r takes val_recs[r::world]):
@@ -398,7 +435,6 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         if not val_recs:
             return {}
         from .coco_eval import accumulate, match_images
-        from .train_targets import rasterize_polygons_within_box
         vt = ms.select(sizes[-1])
         eng = vt.inference_engine()
         mine = list(range(rank, len(val_recs), world))
@@ -406,15 +442,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         for k in range(0, len(mine), per_rank):
             chunk = [val_recs[i] for i in mine[k:k + per_rank]]
             tiles = np.stack([read_tile(r["file_name"]) for r in chunk])
-            for r, inst in zip(chunk, eng.infer(tiles)):
-                h, w = tiles.shape[1:3]
-                g = {"boxes": r["boxes"], "classes": r["classes"]}
-                d = {"boxes": inst.pred_boxes, "classes": inst.pred_classes, "scores": inst.scores}
-                if spec.mask_on and h == w:
-                    g["masks"] = np.stack([rasterize_polygons_within_box(p, np.array([0.0, 0.0, w, h]), h) for p in r["polygons"]])
-                    d["masks"] = inst.pred_masks
-                gts.append(g); dts.append(d)
-        segm = spec.mask_on and all("masks" in g for g in gts)
+            g, d, fell_back = validation_chunk(eng, spec, chunk, tiles, args.val_ap)
+            gts += g; dts += d
+            val_ap_fallbacks[0] += int(fell_back)            # that chunk alone took the host path; nothing is truncated
+        segm = spec.mask_on and all("masks" in g or "mask_area" in g for g in gts)
         local = {"idx": mine, "bbox": match_images(gts, dts, spec.num_classes, "bbox", spec.detections_per_image),
                  "segm": match_images(gts, dts, spec.num_classes, "segm", spec.detections_per_image) if segm else None}
         parts = [local]
@@ -526,6 +557,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     loader.shutdown(wait=True)
     if ms.mask_target_fallbacks:
         log.info("mask_targets: %d steps rasterised on the host (their polygons did not fit the device pool)", ms.mask_target_fallbacks)
+    if args.val_ap == "device":
+        log.info("val_ap: %d chunks evaluated on the host (they did not fit the device pool)", val_ap_fallbacks[0])
     ms.close()
     if metrics:
         metrics.close()

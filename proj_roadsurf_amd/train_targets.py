@@ -78,3 +78,26 @@ def rasterize_polygons_within_box(polygons: Sequence[np.ndarray], box: np.ndarra
     if rc != 0:
         raise RsError(f"rs_rasterize_polygons_within_box failed ({rc})")
     return out.astype(bool)
+
+
+def rasterize_canvases_device(instances: Sequence[Sequence[np.ndarray]], side: int, packed: bool = False) -> np.ndarray:
+    """Every instance's polygons on a whole ``side`` x ``side`` canvas, on the GPU (``rs_op_rasterize_canvas``): bit for bit
+    ``rasterize_polygons_within_box(polygons, (0, 0, side, side), side)`` per instance.  Returns (n, side, side) bool, or with
+    ``packed`` the bytes as they leave the device, (n, side, ceil(side / 8)) in the ``rs_dets.masks`` layout.  Needs a HIP device."""
+    from .engine import load_library, _check
+    lib = load_library()
+    n = len(instances)
+    arrs = [np.asarray(p, np.float64).reshape(-1) for polys in instances for p in polys]
+    lens = np.array([a.size for a in arrs] or [0], np.int32)
+    off = np.zeros(max(len(arrs), 1), np.int64)
+    if len(arrs) > 1:
+        off[1:] = np.cumsum(lens[:-1], dtype=np.int64)
+    flat = np.ascontiguousarray(np.concatenate(arrs)) if arrs else np.zeros(1)
+    first = np.zeros(n + 1, np.int32)
+    first[1:] = np.cumsum([len(polys) for polys in instances])
+    out = np.zeros((n, side, (side + 7) // 8), np.uint8)
+    _check(lib, lib.rs_op_rasterize_canvas(flat.ctypes.data, off.ctypes.data, lens.ctypes.data, first.ctypes.data, n, side, out.ctypes.data),
+           "rs_op_rasterize_canvas")
+    if packed:
+        return out
+    return np.unpackbits(out, axis=-1, bitorder="little")[:, :, :side].astype(bool)
