@@ -306,6 +306,18 @@ int rs_op_conv2d_wgrad(const void* dy, const void* in, float* grad, const float*
 int rs_op_conv2d_wgrad_f32(const void* dy, const void* in, float* grad, const float* scale, int n, int hi, int wi, int cin,
                        int in_halo, int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits,
                        void* stream);
+/* the same fp32 operands and fp32 result with the product on the fp16 matrix cores ("weight gradients on split operands"):
+ * each operand is scaled by one power of two per call (abs-max pass on the device, no read-back) and split into hi + lo fp16 planes,
+ * three v_mfma_f32_16x16x32_f16 products (hi.lo, hi.hi, lo.hi) go into one fp32 accumulator, the scale is undone exactly and the fixed-order
+ * reduction of the other two operators follows: two calls give the same bits.  Per element
+ *   |result - exact| <= 2^-20 sum|dy||in| + 2^-36 M max|dy| max|in| + (the accumulation-order error of rs_op_conv2d_wgrad_f32).
+ * Allocates its plane scratch for the call; null operands and bad geometry are refused (RS_ERR_ARG) before a device is touched.
+ * rs_op_conv2d_wgrad_split_serves: 1 when a layer of these channel counts runs on the fp16 matrix cores, 0 when the call (and the
+ * trainer's split mode) falls through to the fp32 kernel for it -- channel counts that are no multiple of 8.  Host only. */
+int rs_op_conv2d_wgrad_split(const void* dy, const void* in, float* grad, const float* scale, int n, int hi, int wi, int cin,
+                       int in_halo, int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits,
+                       void* stream);
+int rs_op_conv2d_wgrad_split_serves(int cin, int cout);
 
 /* Greedy NMS over `segments` independent lists of up to `cap` (<= 2048) boxes in priority order
  * (torchvision.ops.nms: suppress when the fp32 IoU > thresh). keep: [segments][cap] 0/1.
@@ -477,6 +489,14 @@ int rs_trainer_mask_backward_device(rs_trainer* t, int n);
 int rs_trainer_set_rpn_topk(rs_trainer* t, int pre_nms_topk_train, int post_nms_topk_train);
 /* Sampler sizes (defaults = the reference YAML: 256 @ 0.5 anchors, 1024 @ 0.25 RoIs per image). */
 int rs_trainer_set_sampling(rs_trainer* t, int rpn_batch, float rpn_positive_fraction, int roi_batch, float roi_positive_fraction);
+/* Weight-gradient product of the reference-precision (fp32) trainer: 0 = fp32 matrix cores (default), 1 = split operands on the fp16
+ * matrix cores (rs_op_conv2d_wgrad_split; storage, forward and input gradients stay fp32).  Read when a stage launches, so it may be
+ * switched between steps; the plane scratch (largest fp32 dY + largest fp32 X of one layer) is allocated when mode 1 is first set.  The
+ * abs-max and split passes run inside the `*.w` stages, so rs_trainer_stage_info includes their time.  Call it between steps from the
+ * thread that drives the trainer, with the trainer's device current: the first switch to mode 1 allocates on the current device and
+ * waits for the trainer's stream; a failed allocation leaves the mode as it was.  RS_ERR_UNSUPPORTED on an fp16 trainer, RS_ERR_ARG on a
+ * null handle or another mode. */
+int rs_trainer_set_wgrad_mode(rs_trainer* t, int mode);
 /* SGD with momentum on the flat buffers + refold.  The gradient is first checked for inf / nan (fp16 loss scale too large for
  * this batch): then the step is skipped on the device -- weights and momentum unchanged -- and the tensor "grad_overflow" [1]
  * reads 1; lower the scale with rs_trainer_set_loss_scale before the next forward (GradScaler semantics, no host sync here). */

@@ -300,7 +300,18 @@ struct WgradParams {
   int splits;           // pixel-range splits (gridDim.z); wgrad_splits() proposes one
   int accumulate;       // 1: grad += result
   int f32;              // 1: dy and x point to fp32 data (reference-precision trainer): conv_wgrad_f32_kernel
+  // f32 = 1 only.  split_ops = 1: the product runs on the fp16 matrix cores from hi + lo fp16 planes of the power-of-two scaled
+  // operands (conv_wgrad_split_kernel).  split_scratch: WGS_HEAD_BYTES of header, then [2][split_dy_cap] and [2][split_x_cap] halfs
+  // (hi plane, lo plane); the caps are the elements of the largest dY / X the scratch serves.  Shapes wgrad_split_serves() refuses
+  // run conv_wgrad_f32_kernel.
+  int split_ops;
+  void* split_scratch;
+  long long split_dy_cap, split_x_cap;
 };
+constexpr size_t WGS_ZERO_OFFSET = 128;            // header: amax / non-finite words, then a zero row of 64 halfs (one channel chunk row)
+constexpr size_t WGS_HEAD_BYTES = 256;
+static inline size_t wgrad_split_scratch_bytes(long long dy_cap, long long x_cap) { return WGS_HEAD_BYTES + (size_t)(dy_cap + x_cap) * 4; }
+bool wgrad_split_serves(const WgradParams& p);
 int wgrad_splits(const WgradParams& p);
 int launch_conv_wgrad(const WgradParams& p, hipStream_t stream);
 

@@ -375,6 +375,276 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32_kernel(const WgradParams p
     }
 }
 
+// ------------------------------------------------------------------------------------------------ fp32 operands on the fp16 matrix cores
+// Opt-in form of the reference-precision weight gradient (WgradParams::split_ops): the fp32 operands become hi + lo fp16
+// planes and the product runs as three v_mfma_f32_16x16x32_f16 blocks into one fp32 accumulator, dY_hi.X_lo, dY_hi.X_hi, dY_lo.X_hi
+// (lo.lo dropped), the order of the split-operand forward loop.
+//   1. wgrad_split_amax_kernel: abs-max of each operand over the elements the GEMM reads (rows bounded by m_count * m_mul), as an
+//      integer atomicMax on the bits of |v| (deterministic), non-finite values left out and flagged.
+//   2. wgrad_split_planes_kernel: t = v * 2^e with e = 14 - floor(log2(amax)) (the scaled maximum lies in [2^14, 2^15); e = 0 for a
+//      zero or non-finite tensor), hi = fp16(t), lo = fp16(t - hi), written in the geometry of the source (zero halo kept).
+//   3. conv_wgrad_split_kernel: the CB = 2 structure of conv_wgrad_kernel (LDS-DMA rows, row_key swizzle, transposed reads) with a
+//      32-pixel K step, so that a stage holds hi and lo sub-tiles of both operands in the fp16 kernel's 32 KB; the accumulator is
+//      multiplied by 2^-(e_dy + e_x) (exact) before the fp32 partial tile is stored, and wgrad_reduce_kernel runs unchanged.
+// Everything is ordered by the stream; the amax words are read from device memory by the kernels behind them.
+constexpr int SBK = 32;
+constexpr int SSUB = SBK * 128;               // one [32 px][64 ch] fp16 sub-tile: 4 KB
+constexpr int S_STAGE = 8 * SSUB;             // dY hi 0, hi 1, lo 0, lo 1, X hi half 0, hi half 1, lo half 0, lo half 1
+constexpr int S_LDS_BYTES = 2 * S_STAGE;      // 64 KB: two workgroups per CU
+
+__device__ __forceinline__ int wgs_rows(const WgradParams& p) {
+  int M = p.M;
+  if (p.m_count) {
+    const long long mc = (long long)(*p.m_count) * p.m_mul;
+    if (mc < M) M = (int)mc;
+  }
+  return M;
+}
+// elements (from the tensor's first) that hold every dY / X element the GEMM reads for rows m < M: whole padded rows up to the last one
+__host__ __device__ __forceinline__ void wgs_range(const WgradParams& p, int M, long long* dy_el, long long* x_el) {
+  if (M <= 0) { *dy_el = 0; *x_el = 0; return; }
+  const int row = (M - 1) / p.Wo, n = row / p.Ho, y = row - n * p.Ho;
+  *dy_el = ((long long)n * p.dy_Hp + y + p.dy_pad + 1) * p.dy_Wp * p.dy_Cs;
+  *x_el = ((long long)n * p.in_Hp + y * p.stride + p.KH + p.in_off) * p.in_Wp * p.in_Cs;
+}
+__device__ __forceinline__ unsigned* wgs_words(const WgradParams& p) { return (unsigned*)p.split_scratch; }   // amax dY, flag dY, amax X, flag X
+__device__ __forceinline__ int wgs_exp(unsigned amax_bits, unsigned nonfinite) {
+  if (nonfinite || amax_bits == 0) return 0;
+  const int be = (int)(amax_bits >> 23);
+  const int E = be ? be - 127 : (31 - __clz((int)amax_bits)) - 149;     // floor(log2(amax)), subnormal fp32 included
+  return 14 - E;
+}
+
+__global__ __launch_bounds__(256) void wgrad_split_amax_kernel(const WgradParams p) {
+  long long dy_el, x_el;
+  wgs_range(p, wgs_rows(p), &dy_el, &x_el);
+  const int isx = blockIdx.y;
+  const float* src = isx ? (const float*)p.x : (const float*)p.dy;
+  const unsigned n4 = (unsigned)((isx ? x_el : dy_el) >> 2);
+  const unsigned q4 = (unsigned)(isx ? p.in_Cs : p.dy_Cs) >> 2;
+  const int used = isx ? p.Cin : p.Cout;                          // channels past these are not operands of the product
+  const bool filter = used < (int)(q4 << 2);
+  unsigned mx = 0, nf = 0;
+  for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+    const f32x4 v = *(const f32x4*)(src + 4ll * i);
+    const int c = filter ? (int)((i % q4) << 2) : 0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const unsigned b = __float_as_uint(v[t]) & 0x7fffffffu;
+      if (filter && c + t >= used) continue;
+      if (b >= 0x7f800000u) nf = 1;
+      else mx = b > mx ? b : mx;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const unsigned o = (unsigned)__shfl_xor((int)mx, off), f = (unsigned)__shfl_xor((int)nf, off);
+    mx = o > mx ? o : mx;
+    nf |= f;
+  }
+  // one atomic per workgroup, not per wave: atomics on one word serialise in L2, and the grid is capped at 512 workgroups per operand
+  __shared__ unsigned part[2][4];
+  if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = mx; part[1][threadIdx.x >> 6] = nf; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 1; k < 4; ++k) { mx = part[0][k] > mx ? part[0][k] : mx; nf |= part[1][k]; }
+    unsigned* w = wgs_words(p) + 2 * isx;
+    if (mx) atomicMax(w, mx);
+    if (nf) atomicOr(w + 1, 1u);
+  }
+}
+
+__global__ __launch_bounds__(256) void wgrad_split_planes_kernel(const WgradParams p) {
+  long long dy_el, x_el;
+  wgs_range(p, wgs_rows(p), &dy_el, &x_el);
+  const int isx = blockIdx.y;
+  const float* src = isx ? (const float*)p.x : (const float*)p.dy;
+  const unsigned n4 = (unsigned)((isx ? x_el : dy_el) >> 2);
+  const unsigned* w = wgs_words(p) + 2 * isx;
+  const int e = wgs_exp(w[0], w[1]);
+  half_t* hi = (half_t*)((char*)p.split_scratch + WGS_HEAD_BYTES) + (isx ? 2 * p.split_dy_cap : 0);
+  half_t* lo = hi + (isx ? p.split_x_cap : p.split_dy_cap);
+  for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+    const f32x4 v = *(const f32x4*)(src + 4ll * i);
+    half4 h, l;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const float s = ldexpf(v[t], e);            // exact: |s| < 2^15
+      h[t] = (half_t)s;                           // round to nearest even
+      l[t] = (half_t)(s - (float)h[t]);
+    }
+    *(half4*)(hi + 4ll * i) = h;
+    *(half4*)(lo + 4ll * i) = l;
+  }
+}
+
+__global__ __launch_bounds__(256) void conv_wgrad_split_kernel(const WgradParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wr = wave >> 1, wc = wave & 1;      // wave tile: channels wr*64.., K columns wc*64..
+  const int co0 = blockIdx.x * 128;
+  const int M = wgs_rows(p);
+  const half_t* zeros = (const half_t*)((const char*)p.split_scratch + WGS_ZERO_OFFSET);   // one 64-channel chunk row of zeros
+  const half_t* dyh = (const half_t*)((const char*)p.split_scratch + WGS_HEAD_BYTES);
+  const half_t* xh = dyh + 2 * p.split_dy_cap;
+  const long long dy_lo = p.split_dy_cap, x_lo = p.split_x_cap;
+
+  const int slices = p.Cin >> 6;
+  const int units = p.KH * p.KW * slices;
+  int x_off[2], k_col[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    int u = blockIdx.y * 2 + h;
+    if (u >= units) u = units - 1;              // odd unit count: the second half repeats the last unit (not stored)
+    const int tap = u / slices, sl = u - tap * slices;
+    const int kh = tap / p.KW, kw = tap - kh * p.KW;
+    x_off[h] = (kh * p.in_Wp + kw) * p.in_Cs + sl * 64;
+    k_col[h] = tap * p.Cin + sl * 64;
+  }
+  const bool second_valid = (blockIdx.y * 2 + 1) < units;
+
+  const int steps_total = (M + SBK - 1) / SBK;
+  const int per = (steps_total + gridDim.z - 1) / gridDim.z;
+  const int s0 = blockIdx.z * per;
+  int s1 = s0 + per;
+  if (s1 > steps_total) s1 = steps_total;
+
+  // ---- staging: a sub-tile is 4 pieces of 8 rows; wave w stages piece w of each of the 8 sub-tiles
+  const int lrow = lane >> 3, lchk = lane & 7;
+  auto stage = [&](int buf, int step) {
+    char* dst = smem + buf * S_STAGE + wave * 1024;
+    const int r = wave * 8 + lrow;                             // row inside the 32-pixel K step
+    const int m = step * SBK + r;
+    const int src_chunk = (lchk ^ row_key(r)) * 8;
+    const bool live = m < M;
+    long long oy = 0, ox = 0;                                  // rows past M read the zero row on both sides
+    if (live) {
+      const int x = m % p.Wo;
+      const int t = m / p.Wo;
+      const int y = t % p.Ho;
+      const int n = t / p.Ho;
+      oy = ((long long)(n * p.dy_Hp + y + p.dy_pad) * p.dy_Wp + x + p.dy_pad) * p.dy_Cs;
+      ox = ((long long)(n * p.in_Hp + y * p.stride + p.in_off) * p.in_Wp + x * p.stride + p.in_off) * p.in_Cs;
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      // channel chunks past the gradient buffer's row (narrow heads) read the zero row
+      const bool in_row = live && co0 + h * 64 + src_chunk < p.dy_Cs;
+      const half_t* g = in_row ? dyh + oy + co0 + h * 64 + src_chunk : zeros + src_chunk;
+      glds16(g, dst + h * SSUB);
+      glds16(in_row ? g + dy_lo : g, dst + (2 + h) * SSUB);
+      const half_t* gx = live ? xh + ox + x_off[h] + src_chunk : zeros + src_chunk;
+      glds16(gx, dst + (4 + h) * SSUB);
+      glds16(live ? gx + x_lo : gx, dst + (6 + h) * SSUB);
+    }
+  };
+
+  // ---- transposed fragment reads, as conv_wgrad_kernel with one 32-pixel MFMA step per stage
+  const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  auto tr_addr = [&](int cb, int hh) {
+    const int r = g * 8 + hh * 4 + q;
+    const int c = 2 * cb + (pp >> 1);
+    return (unsigned)(r * 128 + ((c ^ row_key(r)) << 4) + 8 * (pp & 1));
+  };
+  unsigned t_addr[4][2];                          // [block][hh], inside a sub-tile
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) t_addr[i][hh] = lds0 + tr_addr(i, hh);
+  const unsigned ah_sub = wr * SSUB, al_sub = (2 + wr) * SSUB, bh_sub = (4 + wc) * SSUB, bl_sub = (6 + wc) * SSUB;
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+#define RS_TR(dst, addr) asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(dst) : "v"(addr))
+  if (s0 < s1) {
+    stage(0, s0);
+    int buf = 0;
+    for (int s = s0; s < s1; ++s) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // step s has landed
+      __syncthreads();                                         // ... for every wave; and everyone is done reading step s-1
+      if (s + 1 < s1) stage(buf ^ 1, s + 1);
+      const unsigned bo = (unsigned)(buf * S_STAGE);
+      // 32 reads in the order dY hi, X lo, X hi, dY lo (the order the product blocks need them).  lgkmcnt is a 4-bit counter: never more
+      // than 15 in flight, so the last read of a group goes out behind the wait for the group before it, together with the first seven
+      // of the next group, which land under the 16 MFMAs of the block in between.
+      half4v ah[4][2], al[4][2], bh[4][2], bl[4][2];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) RS_TR(ah[i][hh], t_addr[i][hh] + ah_sub + bo);
+#pragma unroll
+      for (int k = 0; k < 7; ++k) RS_TR(bl[k >> 1][k & 1], t_addr[k >> 1][k & 1] + bl_sub + bo);        // 15 in flight
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("s_waitcnt lgkmcnt(7)" ::: "memory");                                                // dY hi is here
+      RS_TR(bl[3][1], t_addr[3][1] + bl_sub + bo);
+#pragma unroll
+      for (int k = 0; k < 7; ++k) RS_TR(bh[k >> 1][k & 1], t_addr[k >> 1][k & 1] + bh_sub + bo);        // <= 15 in flight
+      asm volatile("s_waitcnt lgkmcnt(7)" ::: "memory");                                                // X lo is here
+      RS_TR(bh[3][1], t_addr[3][1] + bh_sub + bo);
+#pragma unroll
+      for (int k = 0; k < 7; ++k) RS_TR(al[k >> 1][k & 1], t_addr[k >> 1][k & 1] + al_sub + bo);        // <= 15 in flight
+      __builtin_amdgcn_sched_barrier(0);
+      half8 af[4], bf[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        af[i] = __builtin_shufflevector(ah[i][0], ah[i][1], 0, 1, 2, 3, 4, 5, 6, 7);
+        bf[i] = __builtin_shufflevector(bl[i][0], bl[i][1], 0, 1, 2, 3, 4, 5, 6, 7);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], bf[j], acc[i][j], 0, 0, 0);   // hi . lo
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("s_waitcnt lgkmcnt(7)" ::: "memory");                                                // X hi is here
+      RS_TR(al[3][1], t_addr[3][1] + al_sub + bo);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) bf[i] = __builtin_shufflevector(bh[i][0], bh[i][1], 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], bf[j], acc[i][j], 0, 0, 0);   // hi . hi
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) af[i] = __builtin_shufflevector(al[i][0], al[i][1], 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], bf[j], acc[i][j], 0, 0, 0);   // lo . hi
+      buf ^= 1;
+    }
+  }
+#undef RS_TR
+
+  // ---- undo the operand scales (a power of two: exact) and store the partial tile: D[row = 4*(lane>>4) + e][col = lane&15] of block (i, j)
+  if (wc == 1 && !second_valid) return;
+  const unsigned* w = wgs_words(p);
+  const int unscale = -(wgs_exp(w[0], w[1]) + wgs_exp(w[2], w[3]));
+  float* out = p.partial + (long long)blockIdx.z * p.Cout * p.Kpad;
+  const int kc = k_col[wc];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int co = co0 + wr * 64 + i * 16 + (lane >> 4) * 4 + e;
+      if (co >= p.Cout) continue;
+      float* row = out + (long long)co * p.Kpad + kc + (lane & 15);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) row[j * 16] = ldexpf(acc[i][j][e], unscale);
+    }
+  }
+}
+
 }  // namespace
 
 // 256-wide tile (CB 4) where it pays: more than 128 output channels, at least 4 K-column tiles, and a pixel range per
@@ -392,7 +662,24 @@ static inline int wgrad_cb(const WgradParams& p) {
   return steps / s >= 8 ? 4 : 2;
 }
 
+// Shapes conv_wgrad_split_kernel takes; the others run conv_wgrad_f32_kernel in split mode too (rs_op_conv2d_wgrad_split_serves).
+bool wgrad_split_serves(const WgradParams& p) {
+  return p.f32 && p.dy_Cs % 8 == 0 && p.in_Cs % 8 == 0 && p.Cin % 64 == 0;
+}
+
 int wgrad_splits(const WgradParams& p) {
+  if (p.f32 && p.split_ops && wgrad_split_serves(p)) {
+    // conv_wgrad_split_kernel: 128 channels x 128 K columns per workgroup, two workgroups per CU, at least four 32-pixel steps per
+    // split.  Never more than the fp32 kernel's choice allows for (that one has at most twice as many output tiles and aims at 1280
+    // workgroups), so the trainer's partial-tile scratch serves both.
+    const long long out_tiles = (long long)cdiv(p.Cout, 128) * cdiv(p.KH * p.KW * (p.Cin >> 6), 2);
+    const int steps = cdiv(p.M, SBK);
+    long long s = cdiv(512, out_tiles);
+    if (s > steps / 4) s = steps / 4;
+    if (s < 1) s = 1;
+    if (s > 64) s = 64;
+    return (int)s;
+  }
   if (p.f32) {
     // conv_wgrad_f32_kernel: a workgroup is 64 channels x 4 K-column tiles of 64, its waves are independent and hide their own load
     // latency only through the waves beside them -- aim at ~5 waves per SIMD (1280 workgroups), at least 8 four-pixel steps per split
@@ -418,7 +705,39 @@ int wgrad_splits(const WgradParams& p) {
   return (int)s;
 }
 
+static int launch_conv_wgrad_split(const WgradParams& p, hipStream_t stream) {
+  RS_CHECK(p.dy && p.x && p.partial && p.grad && p.split_scratch, RS_ERR_ARG, "wgrad (split operands): null pointer");
+  const int units = p.KH * p.KW * (p.Cin >> 6);
+  RS_CHECK(p.M > 0 && p.Cout >= 1 && p.Cout <= p.dy_Cs && units * 64 == p.Kpad && p.splits >= 1 && p.Ho >= 1 && p.Wo >= 1, RS_ERR_ARG,
+           "wgrad (split operands): Cin %d must be a multiple of 64 and K = %d unpadded", p.Cin, p.Kpad);
+  long long dy_el, x_el;
+  wgs_range(p, p.M, &dy_el, &x_el);
+  RS_CHECK(dy_el <= p.split_dy_cap && x_el <= p.split_x_cap && dy_el < (1ll << 32) && x_el < (1ll << 32), RS_ERR_ARG,
+           "wgrad (split operands): operands of %lld and %lld elements exceed the plane scratch (%lld, %lld)", dy_el, x_el, p.split_dy_cap, p.split_x_cap);
+  static bool done = false;
+  if (!done) {
+    RS_HIP(hipFuncSetAttribute((const void*)conv_wgrad_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS_BYTES));
+    done = true;
+  }
+  RS_HIP(hipMemsetAsync(p.split_scratch, 0, 16, stream));
+  const long long big = dy_el > x_el ? dy_el : x_el;
+  int blocks = cdiv(big, 4 * 256 * 4);
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(wgrad_split_amax_kernel, dim3(blocks > 512 ? 512 : blocks, 2), dim3(256), 0, stream, p);
+  RS_HIP(hipGetLastError());
+  hipLaunchKernelGGL(wgrad_split_planes_kernel, dim3(blocks, 2), dim3(256), 0, stream, p);
+  RS_HIP(hipGetLastError());
+  hipLaunchKernelGGL(conv_wgrad_split_kernel, dim3(cdiv(p.Cout, 128), cdiv(units, 2), p.splits), dim3(256), S_LDS_BYTES, stream, p);
+  RS_HIP(hipGetLastError());
+  const long long n_el = (long long)p.Cout * p.Kpad;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)cdiv(n_el, 64)), dim3(256), 0, stream, p.partial, p.splits, n_el, p.Kpad,
+                     p.scale, p.grad, p.accumulate);
+  RS_HIP(hipGetLastError());
+  return RS_OK;
+}
+
 int launch_conv_wgrad(const WgradParams& p, hipStream_t stream) {
+  if (p.f32 && p.split_ops && wgrad_split_serves(p)) return launch_conv_wgrad_split(p, stream);
   if (p.f32) {
     RS_CHECK(p.dy && p.x && p.partial && p.grad, RS_ERR_ARG, "wgrad: null pointer");
     const int units = p.KH * p.KW * (p.Cin >> 6);

@@ -255,7 +255,7 @@ int rs_op_conv2d_dgrad(const void* dy, const void* w_t, void* dx, const void* re
 }
 
 static int op_conv2d_wgrad(const void* dy, const void* x, float* grad, const float* scale, int n, int hi, int wi, int cin, int in_halo,
-                           int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits, void* stream, int f32);
+                           int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits, void* stream, int f32);   // f32 = 2: split operands
 int rs_op_conv2d_wgrad(const void* dy, const void* x, float* grad, const float* scale, int n, int hi, int wi, int cin, int in_halo,
                        int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits, void* stream) {
   return op_conv2d_wgrad(dy, x, grad, scale, n, hi, wi, cin, in_halo, kh, kw, stride, pad, cout, kpad, dy_halo, splits, stream, 0);
@@ -264,6 +264,26 @@ int rs_op_conv2d_wgrad(const void* dy, const void* x, float* grad, const float* 
 int rs_op_conv2d_wgrad_f32(const void* dy, const void* x, float* grad, const float* scale, int n, int hi, int wi, int cin, int in_halo,
                            int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits, void* stream) {
   return op_conv2d_wgrad(dy, x, grad, scale, n, hi, wi, cin, in_halo, kh, kw, stride, pad, cout, kpad, dy_halo, splits, stream, 1);
+}
+// the fp32 weight gradient with the product on the fp16 matrix cores (hi + lo planes of the scaled operands: conv_wgrad_split_kernel);
+// the plane scratch lives for the call.  Arguments are refused before a device is touched.
+int rs_op_conv2d_wgrad_split(const void* dy, const void* x, float* grad, const float* scale, int n, int hi, int wi, int cin, int in_halo,
+                             int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits, void* stream) {
+  RS_CHECK(dy && x && grad, RS_ERR_ARG, "rs_op_conv2d_wgrad_split: null operand");
+  RS_CHECK(n >= 1 && hi >= 1 && wi >= 1 && kh >= 1 && kw >= 1 && stride >= 1 && pad >= 0 && in_halo >= pad && dy_halo >= 0 && hi + 2 * pad >= kh &&
+           wi + 2 * pad >= kw, RS_ERR_ARG, "rs_op_conv2d_wgrad_split: geometry (%d x %d x %d input, %dx%d kernel, stride %d, pad %d, halos %d / %d)",
+           n, hi, wi, kh, kw, stride, pad, in_halo, dy_halo);
+  RS_CHECK(cin >= 64 && cin % 64 == 0 && cout >= 1 && cout % 4 == 0 && kpad == kh * kw * cin, RS_ERR_ARG,
+           "rs_op_conv2d_wgrad_split: cin %d must be a multiple of 64, cout %d of 4, and kpad %d = kh * kw * cin", cin, cout, kpad);
+  return op_conv2d_wgrad(dy, x, grad, scale, n, hi, wi, cin, in_halo, kh, kw, stride, pad, cout, kpad, dy_halo, splits, stream, 2);
+}
+// 1 when rs_op_conv2d_wgrad_split (and the trainer's split mode) runs this layer on the fp16 matrix cores, 0 when it falls through to the
+// fp32 kernel (gradient rows or inputs whose channel count is no multiple of 8).  Host only.
+int rs_op_conv2d_wgrad_split_serves(int cin, int cout) {
+  WgradParams p;
+  memset(&p, 0, sizeof p);
+  p.f32 = 1; p.Cin = cin; p.in_Cs = cin; p.Cout = cout; p.dy_Cs = cout;
+  return cin >= 64 && cout >= 1 && wgrad_split_serves(p) ? 1 : 0;
 }
 static int op_conv2d_wgrad(const void* dy, const void* x, float* grad, const float* scale, int n, int hi, int wi, int cin, int in_halo,
                            int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits, void* stream, int f32) {
@@ -277,13 +297,26 @@ static int op_conv2d_wgrad(const void* dy, const void* x, float* grad, const flo
   p.dy_Hp = ho + 2 * dy_halo; p.dy_Wp = wo + 2 * dy_halo; p.dy_Cs = cout; p.dy_pad = dy_halo;
   p.in_Hp = hi + 2 * in_halo; p.in_Wp = wi + 2 * in_halo; p.in_Cs = cin; p.in_off = in_halo - pad;
   p.stride = stride; p.KH = kh; p.KW = kw; p.Cin = cin; p.Cout = cout; p.Kpad = kpad;
-  p.f32 = f32;
+  p.f32 = f32 ? 1 : 0;
+  p.split_ops = f32 == 2;
   p.splits = splits > 0 ? splits : wgrad_splits(p);
   hipStream_t s = (hipStream_t)stream;
   OpScratch scratch(stream);
   void *partial = nullptr, *zeros = nullptr;
   { int rc = scratch.alloc(&partial, (size_t)p.splits * cout * kpad * 4); if (rc) return rc; }
-  { int rc = scratch.alloc(&zeros, (size_t)cout * 2 + 256); if (rc) return rc; }
+  // split operands: the header (with its zero row) and the planes come before the fp16 kernel's zero row in the same allocation
+  size_t planes = 0;
+  if (p.split_ops) {
+    p.split_dy_cap = (long long)n * p.dy_Hp * p.dy_Wp * p.dy_Cs;
+    p.split_x_cap = (long long)n * p.in_Hp * p.in_Wp * p.in_Cs;
+    planes = (wgrad_split_scratch_bytes(p.split_dy_cap, p.split_x_cap) + 255) & ~(size_t)255;
+  }
+  { int rc = scratch.alloc(&zeros, planes + (size_t)cout * 2 + 256); if (rc) return rc; }
+  if (p.split_ops) {
+    p.split_scratch = zeros;
+    RS_HIP(hipMemsetAsync(zeros, 0, WGS_HEAD_BYTES, s));
+    zeros = (char*)zeros + planes;
+  }
   RS_HIP(hipMemsetAsync(zeros, 0, (size_t)cout * 2 + 256, s));
   RS_HIP(hipMemsetAsync(partial, 0, (size_t)p.splits * cout * kpad * 4, s));   // K padding columns stay zero
   p.partial = (float*)partial; p.zeros = (const half_t*)zeros;

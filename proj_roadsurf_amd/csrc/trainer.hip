@@ -72,6 +72,16 @@ struct rs_trainer {
   unsigned fold_blocks = 0;
   size_t partial_floats = 0;
   half_t* zeros = nullptr;       // zero fp16 row (wgrad tail rows)
+  // weight gradients on split operands (rs_trainer_set_wgrad_mode; fp32 trainer only): hi + lo fp16 planes of the dY and X of the stage
+  // that is running -- the `*.w` stages follow one another on one stream, so one scratch serves them all
+  int wgrad_mode = 0;
+  void* wgs_scratch = nullptr;
+  long long wgs_dy_cap = 0, wgs_x_cap = 0;   // elements of the largest dY / X of any weight-gradient stage
+  void wgs_note(long long dy_el, long long x_el) { if (dy_el > wgs_dy_cap) wgs_dy_cap = dy_el; if (x_el > wgs_x_cap) wgs_x_cap = x_el; }
+  void wgs_apply(WgradParams& p) const {
+    p.split_ops = f32 && wgrad_mode == 1;
+    p.split_scratch = wgs_scratch; p.split_dy_cap = wgs_dy_cap; p.split_x_cap = wgs_x_cap;
+  }
   float* zero_bias = nullptr;    // zero fp32 bias for input-gradient convolutions
   std::vector<void*> allocs;
   std::vector<TensorInfo> tensors;
@@ -331,9 +341,11 @@ int rs_trainer::add_wgrad(const std::string& stage, const std::string& layer, co
     p.partial = self->partial;
     p.grad = self->grad + w_off;
     p.accumulate = accumulate ? 1 : 0;
+    self->wgs_apply(p);
     p.splits = wgrad_splits(p);
     return launch_conv_wgrad(p, s);
   };
+  wgs_note((long long)dy.N * dy.Hp() * dy.Wp() * dy.C, (long long)x.N * x.Hp() * x.Wp() * x.C);
   st.grad_side = true;
   st.bucket = bucket_of(layer);
   (cur ? cur : &bwd)->push_back(st);
@@ -1086,9 +1098,12 @@ int rs_trainer::build_mask_training() {
       Stage sw;
       sw.name = "bwd.mask.deconv.w";
       sw.fn = [p, per14, self, w_off](int n, hipStream_t s) mutable {
-        p.M = n * per14; p.partial = self->partial; p.grad = self->grad + w_off; p.accumulate = 0; p.splits = wgrad_splits(p);
+        p.M = n * per14; p.partial = self->partial; p.grad = self->grad + w_off; p.accumulate = 0;
+        self->wgs_apply(p);
+        p.splits = wgrad_splits(p);
         return launch_conv_wgrad(p, s);
       };
+      wgs_note((long long)curm.N * curm.Hp() * curm.Wp() * curm.C, (long long)dDec.N * dDec.Hp() * dDec.Wp() * dDec.C);
       sw.grad_side = true;
       mask_bwd.push_back(sw);
       const half_t* ddp = dDec.p;
@@ -1494,6 +1509,19 @@ int rs_trainer_set_rpn_topk(rs_trainer* t, int pre_nms_topk_train, int post_nms_
 int rs_trainer_set_sampling(rs_trainer* t, int rpn_batch, float rpn_positive_fraction, int roi_batch, float roi_positive_fraction) {
   RS_CHECK(t && rpn_batch >= 1 && roi_batch >= 1 && roi_batch <= rs_trainer::PC, RS_ERR_ARG, "bad sampling sizes (RoI batch at most %d)", rs_trainer::PC);
   t->rpn_batch = rpn_batch; t->rpn_pos_frac = rpn_positive_fraction; t->roi_batch = roi_batch; t->roi_pos_frac = roi_positive_fraction;
+  return RS_OK;
+}
+
+int rs_trainer_set_wgrad_mode(rs_trainer* t, int mode) {
+  RS_CHECK(t, RS_ERR_ARG, "rs_trainer_set_wgrad_mode: null trainer");
+  RS_CHECK(mode == 0 || mode == 1, RS_ERR_ARG, "rs_trainer_set_wgrad_mode: mode %d (0 = fp32 matrix cores, 1 = split operands)", mode);
+  RS_CHECK(t->f32 || mode == 0, RS_ERR_UNSUPPORTED, "rs_trainer_set_wgrad_mode: split operands serve the fp32 trainer; this one is fp16 and already on the fp16 matrix cores");
+  if (mode == 1 && !t->wgs_scratch) {
+    int rc = t->alloc(&t->wgs_scratch, wgrad_split_scratch_bytes(t->wgs_dy_cap, t->wgs_x_cap));   // zero-filled on the chain stream
+    if (rc) return rc;
+    RS_HIP(hipStreamSynchronize(t->stream));     // ... before a side-stream stage reads its zero row
+  }
+  t->wgrad_mode = mode;
   return RS_OK;
 }
 

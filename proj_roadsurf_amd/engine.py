@@ -184,6 +184,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.rs_op_bneck_tail_split.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp]
     lib.rs_op_conv2d_dgrad.argtypes = [vp] * 7 + [i32] * 14 + [vp]
     lib.rs_op_conv2d_wgrad.argtypes = [vp, vp, vp, vp] + [i32] * 13 + [vp]
+    lib.rs_op_conv2d_wgrad_split.argtypes = lib.rs_op_conv2d_wgrad.argtypes
+    lib.rs_op_conv2d_wgrad_split_serves.argtypes = [i32, i32]
     lib.rs_op_nms.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, vp]
     lib.rs_op_batched_nms.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_float, i32, vp]
     lib.rs_op_batched_nms_decision.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_float, i32, vp, vp, vp]
@@ -1123,9 +1125,17 @@ class Predictor:
 
 
 MASK_TARGET_MODES = ("host", "device")
+WGRAD_MODES = ("f32", "split")   # rs_trainer_set_wgrad_mode 0 / 1
 RS_EVAL_DOES_NOT_FIT = 2       # include/rs_engine.h: rs_engine_fetch_eval_async, the batch's ground truth exceeds the device pool
 EVAL_GT_CAP = 128              # RS_EVAL_GT_CAP: ground truths per tile, and the row length of the count tables
 RS_POLYGONS_DO_NOT_FIT = 1     # include/rs_engine.h: rs_trainer_set_polygons, the batch's polygons exceed the device pool
+
+
+def _check_wgrad(wgrad: str, spec: "EngineSpec") -> None:
+    if wgrad not in WGRAD_MODES:
+        raise ValueError(f"wgrad must be one of {WGRAD_MODES}, got {wgrad!r}")
+    if wgrad == "split" and spec.precision == "fp16":
+        raise ValueError("wgrad='split' serves the fp32 trainer (precision='fp32'); the fp16 trainer already runs on the fp16 matrix cores")
 
 
 class Trainer:
@@ -1135,14 +1145,19 @@ class Trainer:
     ``apply_sgd`` = the optimiser step; ``allreduce_gradients`` = DDP's gradient averaging over RCCL."""
 
     def __init__(self, spec: EngineSpec, weights: Dict[str, np.ndarray], tile_shape: Tuple[int, int, int], batch: int = 2,
-                 device: int = 0, loss_scale: float = 1.0, lib_path: Optional[str] = None, mask_targets: str = "host"):
-        """``mask_targets``: where ``train_step`` rasterises the mask head's ground-truth crops.  "host" (default): read the sampled
+                 device: int = 0, loss_scale: float = 1.0, lib_path: Optional[str] = None, mask_targets: str = "host", wgrad: str = "f32"):
+        """``wgrad``: the weight-gradient product of the fp32 trainer.  "f32" (default): fp32 matrix cores.  "split": the fp32 operands
+        become hi + lo fp16 planes and the product runs on the fp16 matrix cores; storage, forward and input gradients
+        stay fp32.  ``set_wgrad_mode`` switches between steps.
+
+        ``mask_targets``: where ``train_step`` rasterises the mask head's ground-truth crops.  "host" (default): read the sampled
         RoIs back, rasterise on host threads, upload (``mask_entries`` + ``mask_backward``).  "device": upload the batch's polygons
         with the targets and rasterise on the GPU (``set_polygons`` + ``mask_backward_device``) -- the same bytes, no host wait
         inside the step; a batch whose polygons do not fit the device pool runs the host path for that step
         (``mask_target_fallbacks`` counts them)."""
         if mask_targets not in MASK_TARGET_MODES:
             raise ValueError(f"mask_targets must be one of {MASK_TARGET_MODES}, got {mask_targets!r}")
+        _check_wgrad(wgrad, spec)
         self.mask_targets = mask_targets
         self.mask_target_fallbacks = 0
         self.lib = lib = load_library(lib_path)
@@ -1163,6 +1178,7 @@ class Trainer:
         lib.rs_trainer_roi_step.argtypes = [vp, i32, C.c_uint32]
         lib.rs_trainer_set_sampling.argtypes = [vp, i32, C.c_float, i32, C.c_float]
         lib.rs_trainer_set_rpn_topk.argtypes = [vp, i32, i32]
+        lib.rs_trainer_set_wgrad_mode.argtypes = [vp, i32]
         lib.rs_trainer_set_grad_divisor.argtypes = [vp, C.c_float]
         lib.rs_trainer_copy_state.argtypes = [vp, vp]
         lib.rs_trainer_grad_buffer.argtypes = [vp]
@@ -1200,6 +1216,9 @@ class Trainer:
                                           float(loss_scale), C.byref(h)), "rs_trainer_create")
         self._h = h
         self._eng = C.c_void_p(lib.rs_trainer_engine(h))
+        self.wgrad = "f32"
+        if wgrad != "f32":
+            self.set_wgrad_mode(wgrad)
 
     def _tensor_ptr(self, name: str, engine: bool = False):
         p, dt, nd, halo = C.c_void_p(), C.c_int32(), C.c_int32(), C.c_int32()
@@ -1483,6 +1502,13 @@ class Trainer:
         from .weights import master_to_d2
         return master_to_d2(self.spec, base, lambda name: self.tensor(name))
 
+    def set_wgrad_mode(self, mode: str) -> None:
+        """Weight-gradient product of the following steps: one of ``WGRAD_MODES``.  An fp16 trainer refuses "split" (``RsError``)."""
+        if mode not in WGRAD_MODES:
+            raise ValueError(f"wgrad must be one of {WGRAD_MODES}, got {mode!r}")
+        _check(self.lib, self.lib.rs_trainer_set_wgrad_mode(self._h, WGRAD_MODES.index(mode)), "rs_trainer_set_wgrad_mode")
+        self.wgrad = mode
+
     def set_sampling(self, rpn_batch: int = 256, rpn_positive_fraction: float = 0.5, roi_batch: int = 1024, roi_positive_fraction: float = 0.25) -> None:
         _check(self.lib, self.lib.rs_trainer_set_sampling(self._h, rpn_batch, rpn_positive_fraction, roi_batch, roi_positive_fraction), "rs_trainer_set_sampling")
 
@@ -1543,10 +1569,12 @@ class MultiScaleTrainer:
     (``rs_trainer_copy_state``)."""
 
     def __init__(self, spec: EngineSpec, weights: Dict[str, np.ndarray], tile_shape: Tuple[int, int, int], sizes: Sequence[int], batch: int = 1,
-                 device: int = 0, loss_scale: float = 1024.0, mask_targets: str = "host"):
+                 device: int = 0, loss_scale: float = 1024.0, mask_targets: str = "host", wgrad: str = "f32"):
         if mask_targets not in MASK_TARGET_MODES:
             raise ValueError(f"mask_targets must be one of {MASK_TARGET_MODES}, got {mask_targets!r}")
+        _check_wgrad(wgrad, spec)
         self.mask_targets = mask_targets
+        self.wgrad = wgrad
         self.spec, self.weights, self.tile_shape, self.batch, self.device, self.loss_scale = spec, weights, tile_shape, batch, device, loss_scale
         self.sizes = [int(s) for s in sizes]
         self._t: Dict[int, Trainer] = {}
@@ -1557,6 +1585,12 @@ class MultiScaleTrainer:
         self._sampling = tuple(a)
         for t in self._t.values():
             t.set_sampling(*a)
+
+    def set_wgrad_mode(self, mode: str) -> None:
+        _check_wgrad(mode, self.spec)
+        self.wgrad = mode
+        for t in self._t.values():
+            t.set_wgrad_mode(mode)
 
     def set_loss_scale(self, loss_scale: float) -> None:
         self.loss_scale = float(loss_scale)
@@ -1573,7 +1607,7 @@ class MultiScaleTrainer:
         """The trainer for shortest-edge ``size``, holding the up-to-date optimiser state."""
         if size not in self._t:
             t = Trainer(self.spec.replace(min_size_test=int(size)), self.weights, self.tile_shape, self.batch, self.device, self.loss_scale,
-                        mask_targets=self.mask_targets)
+                        mask_targets=self.mask_targets, wgrad=self.wgrad)
             if self._sampling:
                 t.set_sampling(*self._sampling)
             if getattr(self, "_rpn_topk", None):

@@ -262,6 +262,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "back, rasterised on host threads and uploaded.  device: the batch's polygons are uploaded with the targets and "
                          "rasterised on the GPU, the same bytes without a host wait inside the step; a batch whose polygons do not fit the "
                          "device pool runs the host path for that step")
+    ap.add_argument("--wgrad", choices=("f32", "split"), default="f32",
+                    help="the weight-gradient product of the fp32 trainer.  f32 (default): fp32 operands on the fp32 matrix cores.  split: "
+                         "the fp32 operands are scaled by a power of two per tensor and split into hi + lo fp16 planes, and the product runs "
+                         "on the fp16 matrix cores with an fp32 accumulator; storage, forward and input gradients stay fp32.  Refused when "
+                         "the run resolves to the fp16 trainer")
     ap.add_argument("--val-ap", choices=("host", "device"), default="host",
                     help="where the validation AP's mask overlaps are counted.  host (default): every detection mask is copied back, every "
                          "ground-truth polygon rasterised on the host and the IoUs taken from the masks.  device: the ground truth is "
@@ -356,6 +361,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     log.info("batched_nms: %s", {"per_category": "per-category (one NMS per FPN level)",
                                  "torchvision": "torchvision (size rule: shifted coordinates at <= 1000 boxes per image)"}[spec.batched_nms])
     log.info("precision: %s (%s)", precision, "--precision" if args.precision != "auto" else f"SOLVER.AMP.ENABLED {sv['amp']}")
+    if args.wgrad == "split" and precision != "fp32":
+        raise SystemExit("--wgrad split serves the fp32 trainer, and this run resolves to the fp16 trainer "
+                         f"({'--precision fp16' if args.precision != 'auto' else 'SOLVER.AMP.ENABLED true'}), which already runs on the fp16 "
+                         "matrix cores; drop --wgrad split or give --precision fp32")
+    log.info("wgrad: %s", {"f32": "f32 (weight gradients on the fp32 matrix cores)",
+                           "split": "split (fp32 operands as hi + lo fp16 planes, weight gradients on the fp16 matrix cores)"}[args.wgrad])
     from .engine import MultiScaleTrainer      # fails loudly without librs_engine.so / a HIP device
     from .make_detections import read_tile
     first = read_tile(recs[0]["file_name"])
@@ -366,7 +377,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     if sv["min_size_sampling"] == "range" and len(sizes) == 2:
         sizes = list(range(sizes[0], sizes[1] + 1, 32))
     ms = MultiScaleTrainer(spec, W, first.shape, sizes, batch=per_rank, device=local_rank, loss_scale=args.loss_scale,
-                           mask_targets=args.mask_targets)
+                           mask_targets=args.mask_targets, wgrad=args.wgrad)
     log.info("mask_targets: %s", {"host": "host (sampled RoIs read back, rasterised on host threads)",
                                   "device": "device (polygons uploaded with the targets, rasterised on the GPU)"}[args.mask_targets])
     ms.set_sampling(sv["rpn_batch"], sv["rpn_pos"], sv["roi_batch"], sv["roi_pos"])
