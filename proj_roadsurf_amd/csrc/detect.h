@@ -1,4 +1,4 @@
-// Parameter blocks of the proposal / detection kernels (detect_kernels.hip).
+// Parameter blocks of the proposal / detection kernels (detect_kernels.hip; RoiAlignParams: roi_align.hip).
 #pragma once
 #include "common.h"
 

@@ -889,7 +889,7 @@ int rs_trainer::build_box_training() {
     }
     q.nlevels = 4; q.C = 256; q.rois = prop_boxes; q.per_image_count = prop_count; q.slots_per_image = PC; q.out = dPool.p; q.P = PR; q.out_pad = 0;
     q.f32 = f32 ? 1 : 0;
-    // owner-computes backward (detect_kernels.hip roi_bwd_gather_kernel): per-entry tables + the counter of entries left to the atomic kernel
+    // owner-computes backward (roi_align.hip roi_bwd_gather_kernel): per-entry tables + the counter of entries left to the atomic kernel
     if ((rc = alloc(&q.bwd_tables, (size_t)N * PC * RS_ROI_BWD_TABLE_BYTES))) return rc;
     if ((rc = alloc((void**)&q.bwd_overflow, 64))) return rc;
     Stage st;

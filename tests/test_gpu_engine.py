@@ -32,7 +32,7 @@ import torch.nn.functional as F
 from proj_roadsurf_amd.engine import Engine
 from proj_roadsurf_amd.spec import EngineSpec
 from proj_roadsurf_amd.weights import synthetic_weights
-from tests.util import match_detections, synthetic_tiles
+from tests.util import match_detections, roi_grid as _roi_grid, synthetic_tiles
 
 pytestmark = pytest.mark.gpu
 
@@ -184,19 +184,6 @@ def check_levels(eng, n):
     for i in range(n):
         m = int(pc[i])
         assert np.array_equal(lv[i, :m], O.assign_levels(torch.from_numpy(pb[i, :m]), 2, 5).numpy()), f"image {i}: FPN level assignment must be exact"
-
-
-def _roi_grid(box, P, sc, H, W):
-    """(gh, gw) of torchvision's adaptive sampling and the feature-cell window [y0, y1) x [x0, x1) the RoI's samples can touch."""
-    f32 = np.float32
-    x1, y1, x2, y2 = (f32(v) for v in box)
-    sw, sh = f32(x1 * f32(sc) - f32(0.5)), f32(y1 * f32(sc) - f32(0.5))
-    ew, eh = f32(x2 * f32(sc) - f32(0.5)), f32(y2 * f32(sc) - f32(0.5))
-    gh = max(int(np.ceil(float(f32(f32(eh - sh) / f32(P))))), 0)
-    gw = max(int(np.ceil(float(f32(f32(ew - sw) / f32(P))))), 0)
-    y0, x0 = int(np.clip(np.floor(sh), 0, H - 1)), int(np.clip(np.floor(sw), 0, W - 1))
-    yb, xb = int(np.clip(np.floor(eh) + 2, 1, H)), int(np.clip(np.floor(ew) + 2, 1, W))
-    return gh, gw, (y0, max(yb, y0 + 1)), (x0, max(xb, x0 + 1))
 
 
 def _check_pooled(O, feats_i, box, lvl, P, got, precision, ratios):
@@ -920,7 +907,7 @@ def test_fused_stem_changes_no_bit(gpu_required, monkeypatch, precision):
 
 def test_roi_visiting_order_is_a_permutation_and_changes_no_bit(gpu_required, monkeypatch):
     """box.roi_align visits the proposals sorted by (pooler level, top row, left column) instead of in score order, so that
-    neighbouring workgroups read neighbouring rows of one feature map (L2 hits; csrc/detect_kernels.hip rpn_merge_kernel /
+    neighbouring workgroups read neighbouring rows of one feature map (L2 hits; csrc/detect_kernels.hip rpn_merge_kernel, csrc/roi_align.hip /
     RoiAlignParams::order).  Pure scheduling: the order is a permutation of every image's slots, sorted as stated over the valid
     ones, and the pooled features, levels and detections are BIT-identical to the engine without it (RS_ROI_ORDER=0)."""
     spec = EngineSpec(num_classes=2, min_size_test=512, max_size_test=853)

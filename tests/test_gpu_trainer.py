@@ -1093,7 +1093,7 @@ def test_batch_with_an_image_without_ground_truth(gpu_required):
 
 
 def test_two_training_runs_give_the_same_bits(gpu_required):
-    """Gradients never pass through float atomics any more (round 3: the RoIAlign backward is owner-computes, csrc/detect_kernels.hip
+    """Gradients never pass through float atomics any more (round 3: the RoIAlign backward is owner-computes, csrc/roi_align.hip
     roi_bwd_gather_kernel; weight gradients, bias gradients and the split-K reductions always summed in a fixed order): two runs of the
     same 12 SGD steps (batch 2, 256 x 256 scenes, box + mask heads, both trainer precisions) end in BIT-identical weights.  Only the
     logged loss values still go through a float atomic (one per wave), so the loss curves agree to rounding, not bit for bit."""

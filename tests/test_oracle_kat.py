@@ -79,7 +79,7 @@ def test_fpn_level_oracle_at_the_cut_points():
     point of the GPU test's sweep (v one float at a time across 0.5, 1, 2; degenerate, very large and random boxes): this pins
     the oracle's level assignment on whatever CPU runs the suite.  Then the cut points are re-derived from the formula -- the
     smallest v of each level, among every float v in the 33-float window around each cut -- and must equal the constants of
-    fpn_level() in csrc/detect_kernels.hip; the old `v >= 2^k` rule must differ at each cut."""
+    fpn_level() in csrc/roi_geom.h; the old `v >= 2^k` rule must differ at each cut."""
     from tests import util as U
 
     boxes = U.fpn_level_edge_boxes(seed=0)
@@ -89,9 +89,9 @@ def test_fpn_level_oracle_at_the_cut_points():
     assert len(bad) == 0, [(boxes[i].tolist(), int(got[i]), int(ref[i])) for i in bad[:8]]
     # the issue's example: a 224 x 223.99998 box is p4 (index 2), not p3
     assert int(O.assign_levels(torch.tensor([[0.0, 0.0, 224.0, 223.99998]]), 2, 5)[0]) == 2
-    src = open(os.path.join(os.path.dirname(__file__), "..", "proj_roadsurf_amd", "csrc", "detect_kernels.hip")).read()
+    src = open(os.path.join(os.path.dirname(__file__), "..", "proj_roadsurf_amd", "csrc", "roi_geom.h")).read()
     body = src[src.index("int fpn_level(float v)"):]
-    consts = [int(h, 16) for h in re.findall(r"__uint_as_float\((0x[0-9a-fA-F]+)u\)", body[:body.index("\n}")])]
+    consts = [int(h, 16) for h in re.findall(r"rg_f32\((0x[0-9a-fA-F]+)u\)", body[:body.index("\n}")])]
     assert len(consts) == 3
     derived = []
     for k, cut in enumerate(U.FPN_CUTS):

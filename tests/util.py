@@ -217,3 +217,16 @@ def fpn_level_boundary_boxes(per_cut=2):
         idx = np.nonzero(differ & (np.abs(v - cut) < 1e-5))[0]
         out += [b[i] for i in idx[:: max(1, len(idx) // per_cut)][:per_cut]]
     return np.array(out, np.float32)
+
+
+def roi_grid(box, P, sc, H, W):
+    """(gh, gw) of torchvision's adaptive sampling and the feature-cell window [y0, y1) x [x0, x1) the RoI's samples can touch."""
+    f32 = np.float32
+    x1, y1, x2, y2 = (f32(v) for v in box)
+    sw, sh = f32(x1 * f32(sc) - f32(0.5)), f32(y1 * f32(sc) - f32(0.5))
+    ew, eh = f32(x2 * f32(sc) - f32(0.5)), f32(y2 * f32(sc) - f32(0.5))
+    gh = max(int(np.ceil(float(f32(f32(eh - sh) / f32(P))))), 0)
+    gw = max(int(np.ceil(float(f32(f32(ew - sw) / f32(P))))), 0)
+    y0, x0 = int(np.clip(np.floor(sh), 0, H - 1)), int(np.clip(np.floor(sw), 0, W - 1))
+    yb, xb = int(np.clip(np.floor(eh) + 2, 1, H)), int(np.clip(np.floor(ew) + 2, 1, W))
+    return gh, gw, (y0, max(yb, y0 + 1)), (x0, max(xb, x0 + 1))
