@@ -99,7 +99,7 @@ typedef struct rs_dets {
   int32_t* classes;   /* [n][D]     0-based contiguous class id  (Instances.pred_classes) */
   uint8_t* masks;     /* [n][D][h][ceil(w/8)] bit-packed rows, bit b of a byte = pixel 8*byte+b
                          (Instances.pred_masks, >= mask_threshold) */
-  float* mask_probs;  /* [n][D][28][28] sigmoid probabilities before pasting */
+  float* mask_probs;  /* [n][D][28][28] sigmoid probabilities before pasting; rows at or past count[i] are unspecified (zero or an earlier batch's values) */
 } rs_dets;
 
 /* Detection masks cropped to their boxes (a pasted mask is zero outside its box): what the streaming host interface copies
@@ -254,6 +254,10 @@ int rs_engine_label_overlap(rs_engine* e, int tile, const uint8_t* label_masks_d
  * (tests/test_host_cpu.py::test_conv_variant_table).  Also returns the number of LDS K-step buffers in *stages_out. */
 int rs_op_conv_variant(int m, int cin, int k, int cout, int cin2, int deconv2x, int out_f32, int* stages_out);
 
+/* The same rule in the split-operand precision mode, which also depends on the stride; deconv_predict = 1: the mask head's fused deconv 2x2 s2 +
+ * predictor over m input pixels (4 * cout rows), as the engine launches it. */
+int rs_op_conv_variant_split(int m, int cin, int k, int stride, int cout, int cin2, int deconv_predict, int* stages_out);
+
 /* Diagnostic builds only (csrc compiled with -DRS_CLOCK_PROBE, tools/ubench/clock_probe.py): device buffer of 2 int64 per
  * workgroup that rs_op_conv2d's 256x256 deep-prefetch kernel fills with {shader clocks, 100 MHz ticks} spent in its K loop.
  * No effect in the production build. */
@@ -271,6 +275,12 @@ int rs_op_conv2d_split(const void* in, int64_t in_lo, const void* w, int64_t w_l
                        const void* residual, int64_t res_lo, const void* upsample_add, int64_t up_lo,
                        int n, int hi, int wi, int cin, int in_halo, int kh, int kw, int stride, int pad, int cout, int kpad,
                        int out_halo, int relu, int out_f32, int deconv2x, int variant, void* stream);
+
+/* The mask head's fused deconv 2x2 s2 + ReLU + predictor in the split-operand mode on caller tensors: in [entries][side + 2][side + 2][256] (halo 1), w [1024][256]
+ * (rows (dy, dx, cout), scaled; wscale / bias [1024]), dot_w [classes][256] fp32, slot[entry] the row of logits [slots][2 side][2 side] an entry writes, cls[slot] its
+ * class; only min(entries, *count_dev) entries run.  variant 14 / 10 / 0 ADD into logits (zero them first); 28 (29 / 30 / 31: 64 / 128 / 256-pixel tiles) store them. */
+int rs_op_deconv_predict_split(const void* in, int64_t in_lo, const void* w, int64_t w_lo, const float* wscale, const float* bias, const float* dot_w, int classes,
+                               const int32_t* cls, const int32_t* slot, const int32_t* count_dev, float* logits, int entries, int side, int variant, void* stream);
 
 /* Bottleneck output with a projection shortcut as ONE GEMM over two activation sources:
  *   out = act( conv_khxkw(in; W[:, :kh*kw*cin]) + conv_1x1_stride2(in2; W[:, kh*kw*cin:]) + bias )

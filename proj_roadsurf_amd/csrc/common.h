@@ -83,6 +83,7 @@ struct RsDebug {
   int wreg_dbg = 0;               // RS_WREG_DBG              conv_wreg timing ablations (bit 0: no epilogue / stores, bit 2: no operand loads; results wrong)
   int wreg_waves = 2;             // RS_WREG_WAVES            conv_wreg form: 2 = 32-pixel tiles, two workgroups of four waves per CU (ships); 4 / 8 = 64-pixel tiles, one workgroup of four / eight waves
   int conv_wreg = 1;              // RS_CONV_WREG             0: never the persistent register-weight kernel (variant 22, conv_wreg.hip)
+  int conv_wide1x1 = 1;           // RS_CONV_WIDE1X1          0: the split engine never takes conv_wide1x1_split.hip (variant 28) for the fused mask deconv + predictor
   int stem_small_tile = 1;        // RS_STEM_SMALL_TILE       0: 256x64 stem tile
   int deep_dbg = 0;               // RS_DEEP_DBG              -DRS_DEEP_CEILING builds only
   int deconv_variant = 22;        // RS_DECONV_VARIANT        kernel of the fused deconv + predictor: conv_wreg (22), or conv_igemm's 128x256 (14), 64x256 (10), 128x128 (0) tile
@@ -347,4 +348,8 @@ int launch_conv_deep(const ConvParams& p, hipStream_t stream, int tile_px = 256)
 int rs_device_cu_count();                                        // CUs of the current device (256 without one), conv_deep.hip
 bool conv_wreg_ok(const ConvParams& p);                          // conv_wreg.hip: persistent 1x1 (Cin 256) with register-resident weights, variant 22
 int launch_conv_wreg(const ConvParams& p, hipStream_t stream, int waves = 0);   // waves: 4 / 8 per workgroup, 0 = RS_WREG_WAVES
+bool conv_wide1x1_split_ok(const ConvParams& p);                // conv_wide1x1_split.hip: split mode, 1x1 / stride 1 / Cin 256, all rows per pixel tile, variant 28
+int launch_conv_wide1x1_split(const ConvParams& p, hipStream_t stream, int tile_px);   // tile_px: 64 / 128 (four waves) or 256 (eight waves)
+constexpr int WIDE1X1_TILE_PX = 128;                            // the tile height variant 28 ships with
+constexpr int WIDE1X1_MIN_M = 4 * 100 * 196;                    // input pixels of the mask head from which conv_choose_variant takes variant 28 (four tiles of 100 entries)
 int launch_conv_deep_multi(const ConvParams& common, const ConvSeg* segs, const int* m_per_image, int nseg, int images, hipStream_t stream);

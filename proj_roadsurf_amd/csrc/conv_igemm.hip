@@ -437,6 +437,8 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
         // fused mask predictor: partial dot product of this lane's 4*MI channels with the predicted class' weights
         const int slot = p.dot_slot[n];
         const float* wv = p.dot_w + (long long)p.dot_cls[slot] * p.Cout + cb;
+        // (split mode, 128x256 tile: the compiler fuses the first four terms of this sum and adds the other twelve as rounded products; conv_wide1x1_split.hip's
+        //  dot_term() mirrors that compiled form to give the same bits, and tests/test_gpu_split_wide1x1.py fails if an edit here or a compiler changes it)
         float sdot = 0.f;
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
@@ -588,7 +590,8 @@ int launch_variant(const ConvParams& p, hipStream_t stream, int use_glds) {
 thread_local int g_last_conv_variant = -2;
 
 // Tile variants: 0 = 128x128, 1 = 256x64, 2 = 256x16 fp32-out (small heads), 3 = 256x128, 4 = 256x256 (conv_igemm),
-// 5 = small-Cin stem (reported only), 7 = 64x128, 8 = 128x64, 9 = 32x128, 10 = 64x256, 12 = conv_deep 256x256, 14 = 128x256.
+// 5 = small-Cin stem (reported only), 7 = 64x128, 8 = 128x64, 9 = 32x128, 10 = 64x256, 12 = conv_deep 256x256, 14 = 128x256,
+// 28 = conv_wide1x1_split (split mode only).
 //
 // conv_choose_variant() is the WHOLE dispatch rule -- a pure function of the layer shape (M = batch * Ho * Wo, so of the
 // batch size too) and of the debug switches; launch_conv() only validates and launches what it returns.  It is exported as
@@ -618,6 +621,13 @@ int conv_choose_variant(ConvParams& p, int force_variant, int use_glds) {
   const int nkd = smallc ? 0 : nk;
   const long long tiles0 = (long long)cdiv(p.M, 128) * (rows / 128 > 0 ? rows / 128 : 1);
   const long long tiles4 = (long long)cdiv(p.M, 256) * (rows / 256 > 0 ? rows / 256 : 1);
+  // Split-operand mode, the mask head's fused deconv + predictor (1x1, K = 256, 1024 rows): all rows per pixel tile with the pixels held in registers
+  // (conv_wide1x1_split.hip), from the pixel count where it was measured ahead of the 128x256 tile -- four tiles of 100 entries, 206 against 293 us at eight,
+  // 410 against 611 at sixteen; level at one and two.  The plain layer of that shape (res4.x.conv3, residual + ReLU) keeps conv_deep: its 40 000 pixels make 313
+  // workgroups, 144 against 122 us (profiles/split_wide1x1/README.md); variants 28 - 31 still run it when asked by number.
+  // Below that count, and with RS_CONV_WIDE1X1=0, the split engine's fused predictor keeps the 128x256 tile (one workgroup holds a (dy, dx) group).
+  if (p.split && p.mode == 2 && rows % 256 == 0)
+    return (D.conv_wide1x1 && use_glds > 0 && p.M >= WIDE1X1_MIN_M && conv_wide1x1_split_ok(p)) ? 28 : 14;
   if (rows <= 16) return 2;
   if (!D.conv_tuned || p.mode != 0 || smallc) return rows % 128 == 0 ? 0 : 1;
   if (rows % 128 != 0) return 8;                                          // Cout = 64: 128x64 beats 256x64 everywhere
@@ -692,6 +702,11 @@ int launch_conv(const ConvParams& p_in, hipStream_t stream, int force_variant, i
     RS_CHECK(conv_wreg_ok(p) && !train_opts, RS_ERR_UNSUPPORTED, "conv: variant %d takes 1x1 / Cin 256 / Cout %% 256 == 0 inference layers only", v);
     g_last_conv_variant = v;
     return launch_conv_wreg(p, stream, v == 23 ? 8 : (v == 25 ? 2 : (v == 26 ? 4 : 0)));
+  }
+  if (v >= 28 && v <= 31) {      // split mode: all rows per pixel tile (conv_wide1x1_split.hip); 28 = the height that ships, 29 / 30 / 31 = 64 / 128 / 256 pixels by name (sweep tool, tests)
+    RS_CHECK(use_glds > 0 && !train_opts, RS_ERR_UNSUPPORTED, "conv: variant %d needs LDS-DMA staging and no training epilogue", v);
+    g_last_conv_variant = v;
+    return launch_conv_wide1x1_split(p, stream, v == 28 ? WIDE1X1_TILE_PX : 64 << (v - 29));
   }
   if (v == 12 || (v >= 15 && v <= 20)) {     // 256x256 with 3 activation stages / 2 weight stages (conv_deep.hip); 15 / 16 / 17: 160 / 192 / 224 pixels, 18 / 19 / 20: 64 / 96 / 128
     RS_CHECK(!p.in2, RS_ERR_UNSUPPORTED, "conv: variant %d has no second K source", v);

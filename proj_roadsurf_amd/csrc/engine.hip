@@ -22,7 +22,7 @@ void rs_debug_reload() {
   RsDebug d;
   auto rd = [](const char* name, int* v) { const char* e = getenv(name); if (e && *e) *v = atoi(e); };
   rd("RS_CONV_SINGLE_STAGE_NK", &d.conv_single_stage_nk); rd("RS_CONV_PERSIST", &d.conv_persist); rd("RS_CONV_TUNED", &d.conv_tuned);
-  rd("RS_CONV_DEEP", &d.conv_deep); rd("RS_CONV_WIDE_PX", &d.conv_wide_px); rd("RS_CONV_WREG", &d.conv_wreg); rd("RS_WREG_DBG", &d.wreg_dbg); rd("RS_ROI_BWD_ATOMIC", &d.roi_bwd_atomic); rd("RS_WREG_WAVES", &d.wreg_waves); rd("RS_STEM_SMALL_TILE", &d.stem_small_tile); rd("RS_DEEP_DBG", &d.deep_dbg);
+  rd("RS_CONV_DEEP", &d.conv_deep); rd("RS_CONV_WIDE_PX", &d.conv_wide_px); rd("RS_CONV_WREG", &d.conv_wreg); rd("RS_CONV_WIDE1X1", &d.conv_wide1x1); rd("RS_WREG_DBG", &d.wreg_dbg); rd("RS_ROI_BWD_ATOMIC", &d.roi_bwd_atomic); rd("RS_WREG_WAVES", &d.wreg_waves); rd("RS_STEM_SMALL_TILE", &d.stem_small_tile); rd("RS_DEEP_DBG", &d.deep_dbg);
   rd("RS_DECONV_VARIANT", &d.deconv_variant); rd("RS_FUSE_MASK_PREDICTOR", &d.fuse_mask_predictor); rd("RS_SIDE_STREAM", &d.side_stream);
   rd("RS_NARROW_ROIALIGN", &d.narrow_roialign); rd("RS_USE_GLDS", &d.use_glds); rd("RS_FUSE_SHORTCUT", &d.fuse_shortcut); rd("RS_MERGE_LEVELS", &d.merge_levels); rd("RS_FUSE_RPN_HEADS", &d.fuse_rpn_heads); rd("RS_DEEP_TAIL", &d.deep_tail); rd("RS_DEEP_TILE_PX", &d.deep_tile_px); rd("RS_FUSE_BNECK", &d.fuse_bneck); rd("RS_FUSE_STEM", &d.fuse_stem);
   rd("RS_USE_GRAPH", &d.use_graph); rd("RS_GRAPH_SMALL", &d.graph_small); rd("RS_TRAIN_ROI_SIDE", &d.train_roi_side);
@@ -894,12 +894,18 @@ int rs_engine::build_mask_head(Graph& g) {
     add_stage("mask.deconv_predict", 2.0 * D * per_roi * 256 * 1024 + 2.0 * D * RS_MASK_SIDE * RS_MASK_SIDE * 256,
               (double)D * per_roi * 256 * 2 * planes() + (double)D * RS_MASK_SIDE * RS_MASK_SIDE * 4).fn =
         [dp, per_roi, Dc, glds, probs, zero_per_tile, sp](int n, hipStream_t s) mutable {
-      RS_HIP(hipMemsetAsync(probs, 0, zero_per_tile * n, s));
       dp.M = n * Dc * per_roi;
       // conv_wreg.hip (22: persistent, a (dy, dx) group's weights in registers) or conv_igemm's tile where one workgroup holds all 256
-      // channels of a group (14 / 10); the two give the same bits
+      // channels of a group (14 / 10); the two give the same bits.  Split mode: conv_wide1x1_split.hip (28) from the rule's pixel count on, which
+      // STORES every logit that mask.bias_sigmoid and mask.paste read (the entries below the device-side count) -- no zeroing, no atomics; same bits again
       const int dv = rs_debug().deconv_variant;
-      return launch_conv(dp, s, (dv == 22 && (sp || !(rs_debug().conv_wreg && glds > 0))) ? 14 : dv, glds);
+      int force = (dv == 22 && (sp || !(rs_debug().conv_wreg && glds > 0))) ? 14 : dv;
+      if (dv == 22 && sp) {      // the rule's answer for the split mode: 28 or 14 (conv_choose_variant)
+        ConvParams probe = dp;
+        force = conv_choose_variant(probe, -1, glds);
+      }
+      if (!(force >= 28 && force <= 31)) RS_HIP(hipMemsetAsync(probs, 0, zero_per_tile * n, s));
+      return launch_conv(dp, s, force, glds);
     };
     mp.f32 = 0;
     mp.in = nullptr; mp.w = nullptr;
@@ -1579,8 +1585,8 @@ int rs_engine_stage_kernel(rs_engine* e, int i, char* name_out) {
                                 "conv1x1_wreg_kernel 32 px x 256 ch (persistent, weights in registers, operand tiles by LDS-DMA, two workgroups per CU)",
                                 "bneck_tail_split_kernel 128 px (conv2 + conv3 + next conv1 chained through registers)"};
   const int v = e->stages[i].variant;
-  const char* s = v == -1 ? "conv_f32_mfma_kernel" : (v >= 0 && v <= 23 ? names[v] : "");
-  if (e->split && v >= 0 && v <= 23) {
+  const char* s = v == -1 ? "conv_f32_mfma_kernel" : (v >= 0 && v <= 23 ? names[v] : (v >= 28 && v <= 31 ? "conv_wide1x1_split_kernel (all rows per pixel tile, pixels in registers)" : ""));
+  if (e->split && ((v >= 0 && v <= 23) || (v >= 28 && v <= 31))) {
     snprintf(name_out, 96, "%.62s [split: hi+lo planes, 3 MFMA blocks]", s);
     return RS_OK;
   }

@@ -73,6 +73,21 @@ int rs_op_conv_variant(int m, int cin, int k, int cout, int cin2, int deconv2x, 
   return cin < 64 ? 5 : v;
 }
 
+// The same rule for the split-operand mode (ConvParams::split), with the stride and the fused mask predictor (deconv 2x2 s2 + predictor: 4 * cout rows) it depends on
+int rs_op_conv_variant_split(int m, int cin, int k, int stride, int cout, int cin2, int deconv_predict, int* stages_out) {
+  ConvParams p;
+  memset(&p, 0, sizeof p);
+  p.M = m; p.Cin = cin; p.KH = p.KW = k; p.Cout = cout; p.mode = deconv_predict ? 2 : 0;
+  p.stride = stride; p.in_Cs = cin; p.out_Cs = cout; p.split = 1;
+  p.Kpad = (k * k * (cin < 64 ? 8 : cin) + cin2 + 63) / 64 * 64;
+  if (cin < 64 && k == 7) p.Kpad = 256;
+  static const half_t dummy = (half_t)0;
+  if (cin2 > 0) { p.in2 = &dummy; p.Cin2 = cin2; }
+  const int v = conv_choose_variant(p, -1, 1);
+  if (stages_out) *stages_out = p.stages;
+  return cin < 64 ? 5 : v;
+}
+
 static long long* g_conv_probe = nullptr;   // -DRS_CLOCK_PROBE diagnostic builds: see rs_debug_set_conv_probe
 static thread_local unsigned long long* g_op_sat = nullptr;   // rs_op_set_saturation_counter
 struct SplitArgs { long long in_lo, w_lo, out_lo, res_lo, up_lo; const float* wscale; };
@@ -137,6 +152,25 @@ int rs_op_conv2d_split(const void* in, int64_t in_lo, const void* w, int64_t w_l
   SplitArgs sa = {in_lo, w_lo, out_lo, res_lo, up_lo, wscale};
   return op_conv2d(in, w, bias, out, residual, upsample_add, n, hi, wi, cin, in_halo, kh, kw, stride, pad, cout, kpad, out_halo,
                    relu, out_f32, deconv2x, variant, 1, stream, nullptr, 0, 0, 0, 0, 1, &sa);
+}
+
+// The mask head's fused deconv 2x2 s2 + ReLU + predictor (ConvParams::mode 2) in the split-operand mode on caller tensors: `in` [entries][side + 2][side + 2][256]
+// (halo 1) as hi / lo planes, w [4 * 256][256] scaled rows (+ lo plane), bias / wscale [1024], dot_w [classes][256] fp32, slot[entry] -> row of `logits`
+// [slots][2 side][2 side] (bias-free logits), cls[slot] the class.  Rows = min(entries, *count_dev) * side^2.  Variants 14 / 10 / 0 accumulate into `logits` (the
+// caller zeroes it), 28 - 31 store.
+int rs_op_deconv_predict_split(const void* in, int64_t in_lo, const void* w, int64_t w_lo, const float* wscale, const float* bias, const float* dot_w, int classes,
+                               const int32_t* cls, const int32_t* slot, const int32_t* count_dev, float* logits, int entries, int side, int variant, void* stream) {
+  RS_CHECK(in && w && wscale && bias && dot_w && cls && slot && logits && entries > 0 && side > 0 && classes > 0, RS_ERR_ARG, "deconv_predict_split: bad argument");
+  ConvParams p;
+  memset(&p, 0, sizeof p);
+  p.in = (const half_t*)in; p.w = (const half_t*)w; p.bias = bias; p.wscale = wscale;
+  p.split = 1; p.in_lo = in_lo; p.w_lo = w_lo;
+  p.M = entries * side * side; p.Ho = side; p.Wo = side;
+  p.in_Hp = side + 2; p.in_Wp = side + 2; p.in_Cs = 256; p.in_off = 1; p.stride = 1; p.KH = p.KW = 1; p.Cin = 256; p.Kpad = 256; p.Cout = 256;
+  p.out_Hp = 2 * side; p.out_Wp = 2 * side; p.out_Cs = 256; p.relu = 1; p.mode = 2;
+  p.m_count = count_dev; p.m_mul = side * side;
+  p.dot_w = dot_w; p.dot_cls = cls; p.dot_slot = slot; p.dot_out = logits; p.dot_k = classes;
+  return launch_conv(p, (hipStream_t)stream, variant, 1);
 }
 
 int rs_op_conv2d_dual(const void* in, const void* in2, const void* w, const float* bias, void* out,

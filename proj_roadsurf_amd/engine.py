@@ -172,6 +172,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.rs_engine_stage_kernel.argtypes = [vp, i32, C.c_char_p]
     lib.rs_engine_stage_variant.argtypes = [vp, i32]
     lib.rs_op_conv_variant.argtypes = [i32] * 7 + [i32p]
+    if hasattr(lib, "rs_op_conv_variant_split"):      # RS_ENGINE_LIB may name an older build (A/B measurements against a parent commit)
+        lib.rs_op_conv_variant_split.argtypes = [i32] * 7 + [i32p]
     lib.rs_engine_tensor.argtypes = [vp, C.c_char_p, C.POINTER(vp), i32p, i32p, C.POINTER(C.c_int64), i32p]
     lib.rs_engine_tensor_count.argtypes = [vp]
     lib.rs_engine_tensor_name.argtypes = [vp, i32, C.c_char_p]
@@ -182,6 +184,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     i64 = C.c_int64
     lib.rs_op_conv2d_split.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64] + [i32] * 16 + [vp]
     lib.rs_op_bneck_tail_split.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp]
+    if hasattr(lib, "rs_op_deconv_predict_split"):
+        lib.rs_op_deconv_predict_split.argtypes = [vp, i64, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.rs_op_conv2d_dgrad.argtypes = [vp] * 7 + [i32] * 14 + [vp]
     lib.rs_op_conv2d_wgrad.argtypes = [vp, vp, vp, vp] + [i32] * 13 + [vp]
     lib.rs_op_conv2d_wgrad_split.argtypes = lib.rs_op_conv2d_wgrad.argtypes
