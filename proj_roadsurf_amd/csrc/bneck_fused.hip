@@ -29,7 +29,7 @@
 // does and feeds it to the t1n accumulators.  The block input (residual) of a pass is loaded one pass ahead into registers.
 #include <type_traits>
 
-#include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
@@ -56,11 +56,6 @@ struct Cfg {
   static constexpr int LDS_BYTES = RING * STAGE + NBIAS * 4;   // CB 1: 73.5 KB, CB 2: 67 KB -- two workgroups per CU
 };
 
-__device__ __forceinline__ void glds16(const half_t* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 // A 16-byte global load the COMPILER does not track (hipcc waits vmcnt(0) at the first use of any ordinary load while LDS-DMA
 // pieces are in flight, cdna_hip_programming.md "Projection GEMM" item 4b): the caller owns the wait -- a counted s_waitcnt that
 // names the destination registers as operands, so no use can move above it.
@@ -74,7 +69,6 @@ __device__ __forceinline__ half8 pack8(const f32x4& a, const f32x4& b) {
   h[4] = (half_t)b[0]; h[5] = (half_t)b[1]; h[6] = (half_t)b[2]; h[7] = (half_t)b[3];
   return h;
 }
-__device__ __forceinline__ float clamp_h(float f) { return f > 65504.f ? 65504.f : f; }     // after ReLU: only the upper bound matters
 
 // DBG (diagnostic builds through RS_BNECK_DBG, results wrong by construction): 1 = no residual loads, 2 = no `out` stores,
 // 4 = no conv2 activation staging
@@ -93,11 +87,7 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_kernel(const BneckParams p) 
   const int ntiles = (M + BM - 1) / BM;
   const int q = blockIdx.x;
   if (q >= ntiles) return;
-  int m0;
-  {
-    const int qn = ntiles >> 3, r = ntiles & 7, x = q & 7;      // XCD-aware order (conv_igemm.hip): neighbouring tiles share an L2
-    m0 = ((x < r ? x * (qn + 1) : r * (qn + 1) + (x - r) * qn) + (q >> 3)) * BM;
-  }
+  const int m0 = xcd_tile(q, ntiles) * BM;      // neighbouring tiles share an L2
   const int lrow = lane >> 3, lchk = lane & 7;
   // ---- conv2 staging pointers: BM/32 passes of 32 activation rows, CBW/32 passes of weight rows (this wave: rows ps*32 + wave*8 + lrow)
   const half_t* aptr[BM / 32];
@@ -105,15 +95,14 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_kernel(const BneckParams p) 
   for (int ps = 0; ps < BM / 32; ++ps) {
     int m = m0 + ps * 32 + wave * 8 + lrow;
     if (m >= M) m = M - 1;
-    const int x = m % p.W, t = m / p.W, y = t % p.H, n = t / p.H;
-    aptr[ps] = p.t1 + ((long long)(n * p.Hp + y) * p.Wp + x) * CBW + (lchk ^ lrow) * 8;     // tap (0,0) of the zero-haloed map
+    const Pix px = pix_of(m, p.W, p.H);
+    aptr[ps] = p.t1 + ((long long)(px.n * p.Hp + px.y) * p.Wp + px.x) * CBW + chunk_f16(src_chunk(lchk, act_key(lrow)));     // tap (0,0) of the zero-haloed map
   }
   const half_t* wptr[CBW / 32];
 #pragma unroll
   for (int ps = 0; ps < CBW / 32; ++ps) {
     const int row = ps * 32 + wave * 8 + lrow;
-    const int key = (row & 3) | (((row / (4 * MIB)) & 1) << 2);
-    wptr[ps] = p.w2 + (long long)row * (9 * CBW) + (lchk ^ key) * 8;
+    wptr[ps] = p.w2 + (long long)row * (9 * CBW) + chunk_f16(src_chunk(lchk, w_key(row, 4 * MIB)));
   }
   auto stage_tap = [&](int buf, int step) {                     // K step = (64-channel slice, tap)
     char* abase = smem + buf * STAGE;
@@ -133,17 +122,17 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_kernel(const BneckParams p) 
 #pragma unroll
     for (int ps = 0; ps < 2; ++ps) {
       const int row = ps * 32 + wave * 8 + lrow;
-      const int key = (row & 3) | (((row >> 4) & 1) << 2);
+      const int dch = chunk_f16(src_chunk(lchk, w_key(row, 16)));
 #pragma unroll
       for (int c = 0; c < CB; ++c)
-        glds16(p.w3p + (long long)(pass * 64 + row) * CBW + c * 64 + (lchk ^ key) * 8, base + c * 8192 + (ps * 32 + wave * 8) * 128);
-      if (SC) glds16(p.wsc + (long long)(pass * 64 + row) * 64 + (lchk ^ key) * 8, base + G::SC_OFF + (ps * 32 + wave * 8) * 128);
+        glds16(p.w3p + (long long)(pass * 64 + row) * CBW + c * 64 + dch, base + c * 8192 + (ps * 32 + wave * 8) * 128);
+      if (SC) glds16(p.wsc + (long long)(pass * 64 + row) * 64 + dch, base + G::SC_OFF + (ps * 32 + wave * 8) * 128);
     }
     if (NEXT) {
 #pragma unroll
       for (int ps = 0; ps < CBW / 32; ++ps) {
         const int row = ps * 32 + wave * 8 + lrow;
-        const int key = (row & 3) | (((row / (4 * MIB)) & 1) << 2);
+        const int key = (row & 3) | (((row / (4 * MIB)) & 1) << 2);      // w_key(row, 4 * MIB) of conv_tile.h, by hand: through the helper this kernel spills more
         glds16(p.w1p + (long long)row * C4 + pass * 64 + (lchk ^ key) * 8, base + G::W1_OFF + (ps * 32 + wave * 8) * 128);
       }
     }
@@ -152,12 +141,12 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_kernel(const BneckParams p) 
   const int fi = lane & 15, fq = lane >> 4, fkey = lane & 7;
   int w_off[4], wB_off[MIB], x_off[NJ];          // rows of a 64-row slice / of a CBW-row matrix this lane reads as MFMA A rows
 #pragma unroll
-  for (int i = 0; i < 4; ++i) w_off[i] = ((fi >> 2) * 16 + i * 4 + (fi & 3)) * 128;
+  for (int i = 0; i < 4; ++i) w_off[i] = frag_row(fi, i, 16) * 128;
 #pragma unroll
-  for (int i = 0; i < MIB; ++i) wB_off[i] = ((fi >> 2) * 4 * MIB + i * 4 + (fi & 3)) * 128;
+  for (int i = 0; i < MIB; ++i) wB_off[i] = frag_row(fi, i, 4 * MIB) * 128;
 #pragma unroll
   for (int j = 0; j < NJ; ++j) x_off[j] = (wave * PXW + j * 16 + fi) * 128;
-  const int c_off[2] = {(fq ^ fkey) * 16, ((4 + fq) ^ fkey) * 16};
+  const int c_off[2] = {frag_off(fq, fkey, 0), frag_off(fq, fkey, 1)};
 
   // ---- pixel geometry of this lane's 4 pixels (pixel block j, column fi)
   long long opix[NJ];
@@ -171,8 +160,8 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_kernel(const BneckParams p) 
     const int m = m0 + wave * PXW + j * 16 + fi;
     valid[j] = m < M;
     const int mm = valid[j] ? m : M - 1;
-    const int x = mm % p.W, t = mm / p.W, y = t % p.H, n = t / p.H;
-    opix[j] = (long long)(n * p.Hp + y + 1) * p.Wp + x + 1;
+    const Pix px = pix_of(mm, p.W, p.H);
+    opix[j] = (long long)(px.n * p.Hp + px.y + 1) * p.Wp + px.x + 1;
   }
   // Residual (block input) of one pass: 32 bytes per pixel and lane, loaded ONE PASS AHEAD into registers -- issued right after
   // the wait that opens pass q, consumed in pass q+1 behind that pass's wait, so the HBM latency of the 328 MB residual stream
@@ -255,7 +244,7 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_kernel(const BneckParams p) 
         for (int r = 0; r < 4; ++r) {
           const float v = acc[i][j][r] + b2v[i][r];
           satc += __builtin_popcountll(__builtin_amdgcn_ballot_w64(valid[j] && v > 65504.f));      // after ReLU a NaN is 0: only v > 65504 counts
-          acc[i][j][r] = clamp_h(v > 0.f ? v : 0.f);
+          acc[i][j][r] = clamp_h16_pos(v > 0.f ? v : 0.f);
         }
 #pragma unroll
       for (int s2 = 0; s2 < 2 * CB; ++s2) tf[s2][j] = pack8(acc[2 * s2][j], acc[2 * s2 + 1][j]);
@@ -319,7 +308,7 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_kernel(const BneckParams p) 
           const float res = SC ? 0.f : (float)rb[pass & 1][j][i >> 1][(i & 1) * 4 + r];     // loaded one pass ago (gload16_untracked), covered by the wait above
           const float v = a2[i][r] + b3q[i][r] + res;
           satc += __builtin_popcountll(__builtin_amdgcn_ballot_w64(valid[j] && v > 65504.f));
-          a2[i][r] = clamp_h(v > 0.f ? v : 0.f);
+          a2[i][r] = clamp_h16_pos(v > 0.f ? v : 0.f);
         }
       const half8 o0 = pack8(a2[0], a2[1]), o1 = pack8(a2[2], a2[3]);
       if (valid[j] && !(DBG & 2)) {
@@ -355,7 +344,7 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_kernel(const BneckParams p) 
         for (int r = 0; r < 4; ++r) {
           const float v = acc3[i][j][r] + b1v[i][r];
           satn += v > 65504.f ? 1u : 0u;
-          acc3[i][j][r] = clamp_h(v > 0.f ? v : 0.f);
+          acc3[i][j][r] = clamp_h16_pos(v > 0.f ? v : 0.f);
         }
       rs_sat_flush(p.sat, satn);
       half_t* op = p.t1n + opix[j] * CBW + fq * 4 * MIB;

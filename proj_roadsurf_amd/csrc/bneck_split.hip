@@ -25,7 +25,7 @@
 //
 // What bounds it (profiles/r04/tail_split_ablation.txt): every workgroup alternates a matrix-bound conv2 phase with an HBM-bound conv3 phase and the two
 // overlap badly across workgroups; a deeper-pipelined variant (three-stage ring, double-buffered pass slices, residual one pass ahead) measured the same.
-#include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
@@ -47,29 +47,20 @@ struct SCfg {
   static constexpr int LDS_BYTES = 2 * STAGE > PASS_BYTES ? 2 * STAGE : PASS_BYTES;     // CB 1: 48 KB, CB 2: 64 KB
 };
 
-__device__ __forceinline__ void glds16s(const half_t* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 // fp32 values of two accumulators (8 consecutive channels) -> hi / lo fragments
 __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, half8& h, half8& l) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    h[r] = (half_t)a[r]; l[r] = (half_t)(a[r] - (float)h[r]);
-    h[4 + r] = (half_t)b[r]; l[4 + r] = (half_t)(b[r] - (float)h[4 + r]);
+    const HiLo sa = split_round(a[r]), sb = split_round(b[r]);
+    h[r] = sa.h; l[r] = sa.l;
+    h[4 + r] = sb.h; l[4 + r] = sb.l;
   }
 }
 __device__ __forceinline__ float relu_clamp(float v, unsigned& satc, bool count) {    // count: add a saturated value to satc (common.h rs_sat_flush)
   v = v > 0.f ? v : 0.f;
   satc += count ? rs_sat_bad(v) : 0u;
-  return v > 65504.f ? 65504.f : v;
+  return clamp_h16_pos(v);
 }
-
-#define RS_MFMA3(acc, wh, wl, xh, xl)                                      \
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl, acc, 0, 0, 0);      \
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh, acc, 0, 0, 0);      \
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh, acc, 0, 0, 0);
 
 template <int CB, bool NEXT, bool PROJ>
 __global__ __launch_bounds__(NT, 2) void bneck_tail_split_kernel(const BneckSplitParams p) {
@@ -83,11 +74,7 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_split_kernel(const BneckSpli
   const int ntiles = (M + BM - 1) / BM;
   const int q = blockIdx.x;
   if (q >= ntiles) return;
-  int m0;
-  {
-    const int qn = ntiles >> 3, r = ntiles & 7, x = q & 7;      // XCD-aware order (conv_igemm.hip): neighbouring tiles share an L2
-    m0 = ((x < r ? x * (qn + 1) : r * (qn + 1) + (x - r) * qn) + (q >> 3)) * BM;
-  }
+  const int m0 = xcd_tile(q, ntiles) * BM;      // neighbouring tiles share an L2
   const int lrow = lane >> 3, lchk = lane & 7;
   // ---- conv2 staging: data chunk d of a 128-byte row = hi halfs 8 d .. 8 d + 7 of the step's 32 channels (d < 4) or their lo halfs (d >= 4)
   const half_t* aptr[BM / 32];
@@ -95,47 +82,42 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_split_kernel(const BneckSpli
   for (int ps = 0; ps < BM / 32; ++ps) {
     int m = m0 + ps * 32 + wave * 8 + lrow;
     if (m >= M) m = M - 1;
-    const int x = m % p.W, t = m / p.W, y = t % p.H, n = t / p.H;
-    const int d = lchk ^ lrow;
-    aptr[ps] = p.t1 + ((long long)(n * p.Hp + y) * p.Wp + x) * CBW + (d & 3) * 8 + (d >> 2) * p.t1_lo;     // tap (0,0) of the zero-haloed map
+    const Pix px = pix_of(m, p.W, p.H);
+    aptr[ps] = p.t1 + ((long long)(px.n * p.Hp + px.y) * p.Wp + px.x) * CBW + chunk_split(src_chunk(lchk, act_key(lrow)), p.t1_lo);     // tap (0,0) of the zero-haloed map
   }
   const half_t* wptr[CBW / 32];
 #pragma unroll
   for (int ps = 0; ps < CBW / 32; ++ps) {
     const int row = ps * 32 + wave * 8 + lrow;
-    const int key = (row & 3) | (((row / (4 * MIB)) & 1) << 2);
-    const int d = lchk ^ key;
-    wptr[ps] = p.w2 + (long long)row * (9 * CBW) + (d & 3) * 8 + (d >> 2) * p.w2_lo;
+    wptr[ps] = p.w2 + (long long)row * (9 * CBW) + chunk_split(src_chunk(lchk, w_key(row, 4 * MIB)), p.w2_lo);
   }
   auto stage_tap = [&](int buf, int step) {                     // K step = (32-channel slice, tap)
     char* abase = smem + buf * STAGE;
     const int slice = step / 9, tap = step - slice * 9;
     const int a_off = ((tap / 3) * p.Wp + (tap % 3)) * CBW + slice * 32;
 #pragma unroll
-    for (int ps = 0; ps < BM / 32; ++ps) glds16s(aptr[ps] + a_off, abase + (ps * 32 + wave * 8) * 128);
+    for (int ps = 0; ps < BM / 32; ++ps) glds16(aptr[ps] + a_off, abase + (ps * 32 + wave * 8) * 128);
 #pragma unroll
-    for (int ps = 0; ps < CBW / 32; ++ps) glds16s(wptr[ps] + tap * CBW + slice * 32, abase + BM * 128 + (ps * 32 + wave * 8) * 128);
+    for (int ps = 0; ps < CBW / 32; ++ps) glds16(wptr[ps] + tap * CBW + slice * 32, abase + BM * 128 + (ps * 32 + wave * 8) * 128);
   };
   // pass slices: W3p rows 64 pass .. +63 as 2 CB K steps of 32 (its K = CBW columns), W1p columns 64 pass .. +63 (2 K steps) of its CBW rows
   auto stage_pass = [&](int pass) {
 #pragma unroll
     for (int ps = 0; ps < 2; ++ps) {
       const int row = ps * 32 + wave * 8 + lrow;
-      const int key = (row & 3) | (((row >> 4) & 1) << 2);
-      const int d = lchk ^ key;
+      const long long dch = chunk_split(src_chunk(lchk, w_key(row, 16)), p.w3_lo);
 #pragma unroll
       for (int s = 0; s < G::S3; ++s)
-        glds16s(p.w3p + (long long)(pass * 64 + row) * G::W3K + s * 32 + (d & 3) * 8 + (d >> 2) * p.w3_lo, smem + s * 8192 + (ps * 32 + wave * 8) * 128);
+        glds16(p.w3p + (long long)(pass * 64 + row) * G::W3K + s * 32 + dch, smem + s * 8192 + (ps * 32 + wave * 8) * 128);
     }
     if (NEXT) {
 #pragma unroll
       for (int ps = 0; ps < CBW / 32; ++ps) {
         const int row = ps * 32 + wave * 8 + lrow;
-        const int key = (row & 3) | (((row / (4 * MIB)) & 1) << 2);
-        const int d = lchk ^ key;
+        const long long dch = chunk_split(src_chunk(lchk, w_key(row, 4 * MIB)), p.w1_lo);
 #pragma unroll
         for (int s = 0; s < 2; ++s)
-          glds16s(p.w1p + (long long)row * C4 + pass * 64 + s * 32 + (d & 3) * 8 + (d >> 2) * p.w1_lo, smem + G::W3_BYTES + s * CBW * 128 + (ps * 32 + wave * 8) * 128);
+          glds16(p.w1p + (long long)row * C4 + pass * 64 + s * 32 + dch, smem + G::W3_BYTES + s * CBW * 128 + (ps * 32 + wave * 8) * 128);
       }
     }
   };
@@ -143,12 +125,12 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_split_kernel(const BneckSpli
   const int fi = lane & 15, fq = lane >> 4, fkey = lane & 7;
   int w_off[4], wB_off[MIB], x_off[NJ];          // rows of a 64-row slice / of a CBW-row matrix this lane reads as MFMA A rows
 #pragma unroll
-  for (int i = 0; i < 4; ++i) w_off[i] = ((fi >> 2) * 16 + i * 4 + (fi & 3)) * 128;
+  for (int i = 0; i < 4; ++i) w_off[i] = frag_row(fi, i, 16) * 128;
 #pragma unroll
-  for (int i = 0; i < MIB; ++i) wB_off[i] = ((fi >> 2) * 4 * MIB + i * 4 + (fi & 3)) * 128;
+  for (int i = 0; i < MIB; ++i) wB_off[i] = frag_row(fi, i, 4 * MIB) * 128;
 #pragma unroll
   for (int j = 0; j < NJ; ++j) x_off[j] = (wave * PXW + j * 16 + fi) * 128;
-  const int ch_off = (fq ^ fkey) * 16, cl_off = ((4 + fq) ^ fkey) * 16;        // this lane's hi / lo fragment inside a row
+  const int ch_off = frag_off(fq, fkey, 0), cl_off = frag_off(fq, fkey, 1);    // this lane's hi / lo fragment inside a row
 
   long long opix[NJ];
   bool valid[NJ];
@@ -158,8 +140,8 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_split_kernel(const BneckSpli
     const int m = m0 + wave * PXW + j * 16 + fi;
     valid[j] = m < M;
     const int mm = valid[j] ? m : M - 1;
-    const int x = mm % p.W, t = mm / p.W, y = t % p.H, n = t / p.H;
-    opix[j] = (long long)(n * p.Hp + y + 1) * p.Wp + x + 1;
+    const Pix px = pix_of(mm, p.W, p.H);
+    opix[j] = (long long)(px.n * p.Hp + px.y + 1) * p.Wp + px.x + 1;
   }
 
   // ================================================================ conv2
@@ -174,11 +156,10 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_split_kernel(const BneckSpli
     for (int ps = 0; ps < BM / 32; ++ps) {
       int m = m0 + ps * 32 + wave * 8 + lrow;
       if (m >= M) m = M - 1;
-      const int x = m % p.W, t = m / p.W, y = t % p.H, n = t / p.H;
-      const int d = lchk ^ lrow;
-      const half_t* xp = p.x0 + ((long long)(n * p.Hp + y + 1) * p.Wp + x + 1) * 64 + (d & 3) * 8 + (d >> 2) * p.x0_lo;
+      const Pix px = pix_of(m, p.W, p.H);
+      const half_t* xp = p.x0 + ((long long)(px.n * p.Hp + px.y + 1) * p.Wp + px.x + 1) * 64 + chunk_split(src_chunk(lchk, act_key(lrow)), p.x0_lo);
 #pragma unroll
-      for (int s = 0; s < 2; ++s) glds16s(xp + s * 32, base + s * BM * 128 + (ps * 32 + wave * 8) * 128);
+      for (int s = 0; s < 2; ++s) glds16(xp + s * 32, base + s * BM * 128 + (ps * 32 + wave * 8) * 128);
     }
   };
   for (int t = 0; t < KS2; ++t) {
@@ -193,7 +174,7 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_split_kernel(const BneckSpli
     for (int i = 0; i < MIB; ++i) {       // weight fragments of one 16-row block at a time: 2 CB x 16 registers less than all of them up front
       const half8 wh = *(const half8*)(sb + BM * 128 + wB_off[i] + ch_off), wl = *(const half8*)(sb + BM * 128 + wB_off[i] + cl_off);
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) { RS_MFMA3(acc[i][j], wh, wl, xh[j], xl[j]) }
+      for (int j = 0; j < NJ; ++j) mfma_split3(acc[i][j], wh, wl, xh[j], xl[j]);
     }
   }
   // ---- t2 = relu(acc * s2 + b2) as hi / lo fragments: K step s of conv3 takes accumulators 2s, 2s+1 = channels 16 CB fq + 8 s + j
@@ -260,13 +241,13 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_split_kernel(const BneckSpli
 #pragma unroll
         for (int s = 0; s < 2 * CB; ++s) {
           const half8 wh = *(const half8*)(smem + s * 8192 + w_off[i] + ch_off), wl = *(const half8*)(smem + s * 8192 + w_off[i] + cl_off);
-          RS_MFMA3(a2[i], wh, wl, th[s][j], tl[s][j])
+          mfma_split3(a2[i], wh, wl, th[s][j], tl[s][j]);
         }
         if (PROJ) {
 #pragma unroll
           for (int s = 0; s < 2; ++s) {
             const half8 wh = *(const half8*)(smem + (2 * CB + s) * 8192 + w_off[i] + ch_off), wl = *(const half8*)(smem + (2 * CB + s) * 8192 + w_off[i] + cl_off);
-            RS_MFMA3(a2[i], wh, wl, x0h[s][j], x0l[s][j])
+            mfma_split3(a2[i], wh, wl, x0h[s][j], x0l[s][j]);
           }
         }
       }
@@ -293,8 +274,8 @@ __global__ __launch_bounds__(NT, 2) void bneck_tail_split_kernel(const BneckSpli
           const char* wb = smem + G::W3_BYTES + wB_off[i];
           const half8 w0h = *(const half8*)(wb + ch_off), w0l = *(const half8*)(wb + cl_off);
           const half8 w1h = *(const half8*)(wb + CBW * 128 + ch_off), w1l = *(const half8*)(wb + CBW * 128 + cl_off);
-          RS_MFMA3(acc3[i][j], w0h, w0l, o0h, o0l)
-          RS_MFMA3(acc3[i][j], w1h, w1l, o1h, o1l)
+          mfma_split3(acc3[i][j], w0h, w0l, o0h, o0l);
+          mfma_split3(acc3[i][j], w1h, w1l, o1h, o1l);
         }
       }
     }

@@ -14,7 +14,7 @@
 // Issue order is always weights then activations, so the wait that publishes a step is `s_waitcnt vmcnt(4)`:
 // everything but the 4 youngest LDS-DMA pieces (the activations two steps ahead) has landed; raw s_barrier.
 // The fragment reads are software-pipelined over half K steps against the MFMAs (see the main loop).
-#include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
@@ -23,17 +23,12 @@ constexpr int ASTAGE = 256 * 128, WSTAGE = BN * 128;      // 32 KB each
 constexpr int W_BASE = 3 * ASTAGE;
 constexpr int LDS_BYTES = 3 * ASTAGE + 2 * WSTAGE;        // 160 KB
 
-__device__ __forceinline__ void glds16(const half_t* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 // One tile: NJ * 32 pixels x 256 channels.  TRAIN: instantiation with the backward-epilogue options down / res32 / mask (conv_igemm.hip),
 // compiled out of the inference kernel
 // SPLIT: the split-operand precision mode (ConvParams::split, common.h).  A K step covers 32 channels and its 128-byte LDS rows are [32 hi halfs | 32 lo
 // halfs] (data chunks 0-3 from the hi plane, 4-7 from the lo plane: a per-lane constant in the LDS-DMA source pointers), so the stages, the LDS-DMA pieces
 // and the fragment reads of a step are those of the fp16 kernel -- the "first half" fragments are the hi ones, the "second half" the lo ones -- while the
-// step runs THREE MFMA blocks, W_hi.X_lo, W_hi.X_hi, W_lo.X_hi (the order conv_igemm.hip uses), with the reads of the other fragment sets in flight under
+// step runs THREE MFMA blocks, W_hi.X_lo, W_hi.X_hi, W_lo.X_hi (the order mfma_split3 of conv_tile.h owns; placed by hand here), with the reads of the other fragment sets in flight under
 // them (own main loop below): 96 MFMAs per 24 fragment reads and 8 LDS-DMA pieces instead of 64, so the LDS port that co-bounds the fp16 kernel has slack.
 // The epilogue descales by the row's power of two and writes hi / lo planes.
 template <int DBG, bool TRAIN, int NJ, bool SPLIT>
@@ -62,21 +57,19 @@ __device__ __forceinline__ void conv_deep_tile(const ConvParams& p, char* smem, 
   for (int ps = 0; ps < APS; ++ps) {
     int m = m0 + ps * 64 + wave * 8 + lrow;
     if (m >= M) m = M - 1;
-    const int x = m % Wo;
-    const int t = m / Wo;
-    const int y = t % Ho;
-    const int n = t / Ho;
+    const Pix px = pix_of(m, Wo, Ho);
     const long long base =
-        ((long long)(n * in_Hp + y * p.stride + p.in_off) * in_Wp + x * p.stride + p.in_off) * p.in_Cs;
-    if constexpr (SPLIT) aoffb[ps] = (unsigned)((base + ((lchk ^ lrow) & 3) * 8 + ((lchk ^ lrow) >> 2) * in_lo) * 2);
-    else aptr[ps] = g_in + base + (lchk ^ lrow) * 8;
+        ((long long)(px.n * in_Hp + px.y * p.stride + p.in_off) * in_Wp + px.x * p.stride + p.in_off) * p.in_Cs;
+    const int dch = src_chunk(lchk, act_key(lrow));
+    if constexpr (SPLIT) aoffb[ps] = (unsigned)((base + chunk_split(dch, in_lo)) * 2);
+    else aptr[ps] = g_in + base + chunk_f16(dch);
   }
 #pragma unroll
   for (int ps = 0; ps < 4; ++ps) {
     const int row = ps * 64 + wave * 8 + lrow;
-    const int key = (row & 3) | (((row >> 4) & 1) << 2);
-    if constexpr (SPLIT) woffb[ps] = (unsigned)(((long long)(n0 + row) * p.Kpad + ((lchk ^ key) & 3) * 8 + ((lchk ^ key) >> 2) * p.w_lo) * 2);
-    else wptr[ps] = g_w + (long long)(n0 + row) * p.Kpad + (lchk ^ key) * 8;
+    const int dch = src_chunk(lchk, w_key(row, 4 * MI));
+    if constexpr (SPLIT) woffb[ps] = (unsigned)(((long long)(n0 + row) * p.Kpad + chunk_split(dch, p.w_lo)) * 2);
+    else wptr[ps] = g_w + (long long)(n0 + row) * p.Kpad + chunk_f16(dch);
   }
   constexpr int KST = SPLIT ? 32 : 64;      // channels a K step covers
   const int nk = p.KH * p.KW * (p.Cin / KST);
@@ -119,10 +112,10 @@ __device__ __forceinline__ void conv_deep_tile(const ConvParams& p, char* smem, 
   const int fi = lane & 15, fq = lane >> 4, fkey = lane & 7;
   int w_off[MI], x_off[NJ];
 #pragma unroll
-  for (int i = 0; i < MI; ++i) w_off[i] = W_BASE + (wch * 64 + (fi >> 2) * 16 + i * 4 + (fi & 3)) * 128;
+  for (int i = 0; i < MI; ++i) w_off[i] = W_BASE + (wch * 64 + frag_row(fi, i, 4 * MI)) * 128;
 #pragma unroll
   for (int j = 0; j < NJ; ++j) x_off[j] = (wpx * WPX + j * 16 + fi) * 128;
-  const int c0_off = (fq ^ fkey) * 16, c1_off = ((4 + fq) ^ fkey) * 16;
+  const int c0_off = frag_off(fq, fkey, 0), c1_off = frag_off(fq, fkey, 1);
 
   f32x4 acc[MI][NJ];
 #pragma unroll
@@ -144,7 +137,7 @@ __device__ __forceinline__ void conv_deep_tile(const ConvParams& p, char* smem, 
   // ones, fenced with sched_barrier on both sides (MFMAs are register-only and would otherwise move across them).
   half8 wf0[MI], xf0[NJ], wf1[MI], xf1[NJ];
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  const unsigned wrow = (unsigned)(W_BASE + (wch * 64 + (fi >> 2) * 16 + (fi & 3)) * 128);
+  const unsigned wrow = (unsigned)(W_BASE + (wch * 64 + frag_row(fi, 0, 4 * MI)) * 128);
   const unsigned xrow = (unsigned)((wpx * WPX + fi) * 128);
   const unsigned wa0 = lds0 + wrow + c0_off, wa1 = lds0 + wrow + c1_off;
   const unsigned xa0 = lds0 + xrow + c0_off, xa1 = lds0 + xrow + c1_off;
@@ -376,30 +369,23 @@ __device__ __forceinline__ void conv_deep_tile(const ConvParams& p, char* smem, 
     p.probe[2 * q + 1] = (long long)(__builtin_amdgcn_s_memrealtime() - pr_r0);
   }
 #endif
-  // ---- epilogue (as conv_igemm.hip, mode 0): lane holds channels crow .. crow+15 of pixel (j, fi)
+  // ---- epilogue (conv_tile.h, as conv_igemm.hip's mode 0): lane holds channels crow .. crow+15 of pixel (j, fi)
   const int crow = n0 + wch * 64 + fq * 16;
-  float bias[16];
-#pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    const f32x4 b4 = *(const f32x4*)(g_bias + crow + i * 4);
-    bias[i * 4 + 0] = b4[0]; bias[i * 4 + 1] = b4[1]; bias[i * 4 + 2] = b4[2]; bias[i * 4 + 3] = b4[3];
-  }
-  float wsc[SPLIT ? 16 : 1];
-  if constexpr (SPLIT) {
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      const f32x4 s4 = *(const f32x4*)(g_wscale + crow + i * 4);
-      wsc[i * 4 + 0] = s4[0]; wsc[i * 4 + 1] = s4[1]; wsc[i * 4 + 2] = s4[2]; wsc[i * 4 + 3] = s4[3];
-    }
-  }
+  const EpiRows<MI, SPLIT> rw = epi_rows<MI, SPLIT>(g_bias, g_wscale, crow);
   unsigned satc = 0;                               // elements clamped to the fp16 range (common.h rs_sat_flush)
-  if (!TRAIN && SPLIT && p.head_w) {
-    // The fused 16-row head in the split-operand mode: relu(acc * scale + bias) is split into hi + lo exactly as the store would split it, and
-    // the head is three MFMA products per 32-deep step (H_hi.B_hi, H_hi.B_lo, H_lo.B_hi) on the head's own hi / lo planes (row-scaled; the
-    // inverse scale is applied when the four channel waves' partial sums are added).
+  if (!TRAIN && p.head_w) {
+    // Fused 16-row 1x1 head on top of this convolution (RPN: objectness + anchor deltas): the 256-channel output tile never leaves
+    // the CU.  relu(acc + bias), rounded to fp16 exactly as the store would round it, is per lane 16 consecutive channels of a
+    // pixel = the B operand of two 32-deep MFMA steps when the head's K columns are stored in the chaining order (weights.py
+    // _perm_k64, see bneck_fused.hip).  Each wave reduces its 64 channels; the four channel waves are summed through LDS in a
+    // fixed order, so the result is bitwise reproducible.
+    // SPLIT: relu(acc * scale + bias) is split into hi + lo exactly as the store would split it, and the head is three MFMA products per
+    // 32-deep step (H_hi.B_hi, H_hi.B_lo, H_lo.B_hi) on the head's own hi / lo planes (row-scaled; the inverse scale is applied when the
+    // four channel waves' partial sums are added).
     const half_t* hw = p.head_w + (long long)fi * 256 + wch * 64 + fq * 8;
     const half8 ha0 = *(const half8*)hw, ha1 = *(const half8*)(hw + 32);
-    const half8 hl0 = *(const half8*)(hw + p.head_w_lo), hl1 = *(const half8*)(hw + p.head_w_lo + 32);
+    half8 hl0, hl1;
+    if constexpr (SPLIT) { hl0 = *(const half8*)(hw + p.head_w_lo); hl1 = *(const half8*)(hw + p.head_w_lo + 32); }
     f32x4 hacc[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -411,76 +397,24 @@ __device__ __forceinline__ void conv_deep_tile(const ConvParams& p, char* smem, 
       for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float f = acc[i][j][r] * wsc[i * 4 + r] + bias[i * 4 + r];
+          float f;
+          if constexpr (SPLIT) f = acc[i][j][r] * rw.wsc[i * 4 + r] + rw.bias[i * 4 + r];
+          else f = acc[i][j][r] + rw.bias[i * 4 + r];
           if (p.relu) f = f > 0.f ? f : 0.f;
           sath += mv ? rs_sat_bad(f) : 0u;
-          f = f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f);
-          const half_t h = (half_t)f;
-          const half_t l = (half_t)(f - (float)h);
-          if (i < 2) { b0[i * 4 + r] = h; l0[i * 4 + r] = l; } else { b1[(i - 2) * 4 + r] = h; l1[(i - 2) * 4 + r] = l; }
+          const HiLo s = split_round(clamp_h16(f));
+          if (i < 2) { b0[i * 4 + r] = s.h; l0[i * 4 + r] = s.l; } else { b1[(i - 2) * 4 + r] = s.h; l1[(i - 2) * 4 + r] = s.l; }
         }
       rs_sat_flush(p.sat, sath);
       f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
       a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ha0, b0, a, 0, 0, 0);
       a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ha1, b1, a, 0, 0, 0);
-      a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ha0, l0, a, 0, 0, 0);
-      a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ha1, l1, a, 0, 0, 0);
-      a = __builtin_amdgcn_mfma_f32_16x16x32_f16(hl0, b0, a, 0, 0, 0);
-      a = __builtin_amdgcn_mfma_f32_16x16x32_f16(hl1, b1, a, 0, 0, 0);
-      hacc[j] = a;
-    }
-    asm volatile("s_barrier" ::: "memory");          // every wave is past its last fragment reads: the stage buffers are free
-    float* part = (float*)smem;                      // [4 channel waves][2 WPX pixels][16] partial sums
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) *(f32x4*)(part + ((wch * 2 * WPX + wpx * WPX + j * 16 + fi) * 16 + fq * 4)) = hacc[j];
-    __syncthreads();
-    const int px = tid >> 1, oh = (tid & 1) * 8;
-    const int m = m0 + px;
-    if (px < 2 * WPX && m < M) {
-      f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        s0 += *(const f32x4*)(part + ((w * 2 * WPX + px) * 16 + oh));
-        s1 += *(const f32x4*)(part + ((w * 2 * WPX + px) * 16 + oh + 4));
+      if constexpr (SPLIT) {
+        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ha0, l0, a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ha1, l1, a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(hl0, b0, a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(hl1, b1, a, 0, 0, 0);
       }
-      s0 = s0 * *(const f32x4*)(p.head_scale + oh) + *(const f32x4*)(p.head_b + oh);
-      s1 = s1 * *(const f32x4*)(p.head_scale + oh + 4) + *(const f32x4*)(p.head_b + oh + 4);
-      const int x = m % Wo, t = m / Wo, y = t % Ho, n = t / Ho;
-      float* op = g_head_out + ((long long)(n * Ho + y) * Wo + x) * 16 + oh;
-      *(f32x4*)op = s0;
-      *(f32x4*)(op + 4) = s1;
-    }
-    return;
-  }
-  if (!TRAIN && !SPLIT && p.head_w) {
-    // Fused 16-row 1x1 head on top of this convolution (RPN: objectness + anchor deltas): the 256-channel output tile never leaves
-    // the CU.  relu(acc + bias), rounded to fp16 exactly as the store would round it, is per lane 16 consecutive channels of a
-    // pixel = the B operand of two 32-deep MFMA steps when the head's K columns are stored in the chaining order (weights.py
-    // _perm_k64, see bneck_fused.hip).  Each wave reduces its 64 channels; the four channel waves are summed through LDS in a
-    // fixed order, so the result is bitwise reproducible.
-    const half_t* hw = p.head_w + (long long)fi * 256 + wch * 64 + fq * 8;
-    const half8 ha0 = *(const half8*)hw, ha1 = *(const half8*)(hw + 32);
-    f32x4 hacc[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      half8 b0, b1;
-      // the head's input counts too, flushed per 16-pixel block: a counter carried across the blocks beside hacc[] costs the split head scratch
-      const bool mv = m0 + wpx * WPX + j * 16 + fi < M;
-      unsigned sath = 0;
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float f = acc[i][j][r] + bias[i * 4 + r];
-          if (p.relu) f = f > 0.f ? f : 0.f;
-          sath += mv ? rs_sat_bad(f) : 0u;
-          f = f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f);
-          if (i < 2) b0[i * 4 + r] = (half_t)f; else b1[(i - 2) * 4 + r] = (half_t)f;
-        }
-      rs_sat_flush(p.sat, sath);
-      f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
-      a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ha0, b0, a, 0, 0, 0);
-      a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ha1, b1, a, 0, 0, 0);
       hacc[j] = a;
     }
     asm volatile("s_barrier" ::: "memory");          // every wave is past its last fragment reads (lgkmcnt(0) in the last K step): the stage buffers are free
@@ -491,14 +425,20 @@ __device__ __forceinline__ void conv_deep_tile(const ConvParams& p, char* smem, 
     const int px = tid >> 1, oh = (tid & 1) * 8;
     const int m = m0 + px;
     if (px < 2 * WPX && m < M) {
-      f32x4 s0 = *(const f32x4*)(p.head_b + oh), s1 = *(const f32x4*)(p.head_b + oh + 4);
+      // fp16: the bias first, then the four partial sums; split: the partial sums from zero, then * inverse scale + bias
+      f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (!SPLIT) { s0 = *(const f32x4*)(p.head_b + oh); s1 = *(const f32x4*)(p.head_b + oh + 4); }
 #pragma unroll
       for (int w = 0; w < 4; ++w) {
         s0 += *(const f32x4*)(part + ((w * 2 * WPX + px) * 16 + oh));
         s1 += *(const f32x4*)(part + ((w * 2 * WPX + px) * 16 + oh + 4));
       }
-      const int x = m % Wo, t = m / Wo, y = t % Ho, n = t / Ho;
-      float* op = g_head_out + ((long long)(n * Ho + y) * Wo + x) * 16 + oh;
+      if constexpr (SPLIT) {
+        s0 = s0 * *(const f32x4*)(p.head_scale + oh) + *(const f32x4*)(p.head_b + oh);
+        s1 = s1 * *(const f32x4*)(p.head_scale + oh + 4) + *(const f32x4*)(p.head_b + oh + 4);
+      }
+      const Pix hp = pix_of(m, Wo, Ho);
+      float* op = g_head_out + ((long long)(hp.n * Ho + hp.y) * Wo + hp.x) * 16 + oh;
       *(f32x4*)op = s0;
       *(f32x4*)(op + 4) = s1;
     }
@@ -508,106 +448,12 @@ __device__ __forceinline__ void conv_deep_tile(const ConvParams& p, char* smem, 
   for (int j = 0; j < NJ; ++j) {
     const int m = m0 + wpx * WPX + j * 16 + fi;
     if (m >= M) continue;
-    const int x = m % Wo;
-    const int t = m / Wo;
-    const int y = t % Ho;
-    const int n = t / Ho;
-    const long long opix = (long long)(n * out_Hp + y + p.out_pad) * out_Wp + x + p.out_pad;
-    float v[16];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        if constexpr (SPLIT) v[i * 4 + r] = acc[i][j][r] * wsc[i * 4 + r] + bias[i * 4 + r];
-        else v[i * 4 + r] = acc[i][j][r] + bias[i * 4 + r];
-      }
-    if (p.res) {
-      const half_t* rp = p.res + opix * p.out_Cs + crow;
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const half4 h = *(const half4*)(rp + i * 4);
-        if constexpr (SPLIT) {
-          const half4 l = *(const half4*)(rp + p.res_lo + i * 4);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[i * 4 + r] += (float)h[r] + (float)l[r];
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[i * 4 + r] += (float)h[r];
-        }
-      }
-    }
-    if (p.up) {
-      const long long upix = (long long)(n * p.up_Hp + (y >> 1) + p.up_pad) * p.up_Wp + (x >> 1) + p.up_pad;
-      const half_t* up = p.up + upix * p.up_Cs + crow;
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const half4 h = *(const half4*)(up + i * 4);
-        if constexpr (SPLIT) {
-          const half4 l = *(const half4*)(up + p.up_lo + i * 4);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[i * 4 + r] += (float)h[r] + (float)l[r];
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[i * 4 + r] += (float)h[r];
-        }
-      }
-    }
-    if (TRAIN && p.down) {        // backward of the nearest 2x upsample: add the 2x2 block of the finer gradient map
-#pragma unroll
-      for (int dd = 0; dd < 4; ++dd) {
-        const long long dpix = (long long)(n * p.down_Hp + 2 * y + (dd >> 1) + p.down_pad) * p.down_Wp + 2 * x + (dd & 1) + p.down_pad;
-        const half_t* dp = p.down + dpix * p.down_Cs + crow;
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-          const half4 h = *(const half4*)(dp + i * 4);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[i * 4 + r] += (float)h[r];
-        }
-      }
-    }
-    if (TRAIN && p.res32) {
-      const float* rp = p.res32 + opix * p.out_Cs + crow;
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const f32x4 h = *(const f32x4*)(rp + i * 4);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[i * 4 + r] += h[r];
-      }
-    }
-    if (TRAIN && p.mask) {        // ReLU backward
-      const half_t* mp = p.mask + opix * p.out_Cs + crow;
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const half4 h = *(const half4*)(mp + i * 4);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[i * 4 + r] = (float)h[r] > 0.f ? v[i * 4 + r] : 0.f;
-      }
-    }
-    if (p.relu) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
-    }
-    if (p.out_f32) {
-      float* op = (float*)g_out + opix * p.out_Cs + crow;
-#pragma unroll
-      for (int i = 0; i < MI; ++i) *(f32x4*)(op + i * 4) = f32x4{v[i * 4], v[i * 4 + 1], v[i * 4 + 2], v[i * 4 + 3]};
-    } else {
-      half_t* op = (half_t*)g_out + opix * p.out_Cs + crow;
-#pragma unroll
-      for (int i = 0; i < MI; i += 2) {
-        half8 h, l;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-          float f = v[i * 4 + r];
-          satc += rs_sat_bad(f);
-          f = f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f);
-          h[r] = (half_t)f;
-          if constexpr (SPLIT) l[r] = (half_t)(f - (float)h[r]);
-        }
-        *(half8*)(op + i * 4) = h;
-        if constexpr (SPLIT) *(half8*)(op + out_lo + i * 4) = l;
-      }
-    }
+    const Pix px = pix_of(m, Wo, Ho);
+    const long long opix = (long long)(px.n * out_Hp + px.y + p.out_pad) * out_Wp + px.x + p.out_pad;
+    float v[4 * MI];
+    epi_values<MI, NJ, TRAIN, SPLIT>(v, p, acc, j, rw, opix, crow, px.x, px.y, px.n);
+    if (p.out_f32) epi_store_f32<MI>((float*)g_out + opix * p.out_Cs + crow, v);
+    else epi_store_h16<MI, SPLIT>((half_t*)g_out + opix * p.out_Cs + crow, out_lo, v, [&](float f, float) { satc += rs_sat_bad(f); });
   }
   rs_sat_flush(p.sat, satc);
 #ifdef RS_SPLIT_PHASES
@@ -634,11 +480,7 @@ template <int DBG, bool TRAIN = false, int NJF = 8, bool SPLIT = false>
 __global__ __launch_bounds__(NT) void conv_deep_kernel(const ConvParams p) {
   constexpr int BM = 32 * NJF;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  int M = p.M;
-  if (p.m_count) {
-    long long mc = (long long)(*p.m_count) * p.m_mul;
-    if (mc < M) M = (int)mc;
-  }
+  int M = conv_rows(p);
   const int tiles_n = p.Cout / BN;
   const int ntiles = p.nseg ? p.seg_tiles : tiles_n * ((M + BM - 1) / BM);
   const int nfull = ntiles - p.tail_tiles;
@@ -655,8 +497,7 @@ __global__ __launch_bounds__(NT) void conv_deep_kernel(const ConvParams p) {
   int Ho = p.Ho, Wo = p.Wo, in_Hp = p.in_Hp, in_Wp = p.in_Wp, out_Hp = p.out_Hp, out_Wp = p.out_Wp;
   int L, half = -1;
   if (q < nfull) {
-    const int qn = nfull >> 3, r = nfull & 7, x = q & 7;      // XCD-aware order, see conv_igemm.hip
-    L = (x < r ? x * (qn + 1) : r * (qn + 1) + (x - r) * qn) + (q >> 3);
+    L = xcd_tile(q, nfull);
   } else {
     L = nfull + ((q - nfull) >> 1);
     half = (q - nfull) & 1;

@@ -10,7 +10,7 @@
 //   * weights are the MFMA "A" operand, activations the "B" operand, so each lane ends up with
 //     4*MI CONSECUTIVE output channels of one pixel -> the epilogue stores 16-byte NHWC pieces
 //     straight from registers (bias + residual + FPN top-down add + ReLU fused, fp32 math).
-//   * both operands are staged global -> LDS with global_load_lds_dwordx4 (no VGPR round trip),
+//   * both operands are staged global -> LDS by LDS-DMA (glds16, conv_tile.h: no VGPR round trip),
 //     128-byte LDS rows, XOR swizzle applied on the per-lane SOURCE address and on the ds_read
 //     (LDS destination stays lane-linear), double buffered, one barrier per 64-deep K step.
 //   * activations carry a zero halo (common.h), so the gather has no bounds checks.
@@ -18,7 +18,7 @@
 //  measured 5-13 % SLOWER on the HBM-bound 1x1 layers than the present 32-bytes-per-lane layout.)
 // Tile variants (pixels x channels per workgroup): 128x128 (4 waves 2x2), 256x64 (4 waves 4x1),
 // 256x16 fp32-out (small heads).  Each wave owns NJ*16 pixels x MI*16 channels.
-#include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
@@ -32,18 +32,13 @@ struct Tile {
   static constexpr int LDS = 2 * STAGE + 1024;   // + K-chunk offset table (small-Cin path)
 };
 
-__device__ __forceinline__ void glds16(const half_t* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 // TRAIN: instantiation with the backward-epilogue options (down / res32 / mask / out_stride).  They are compiled out of the
 // inference instantiations: carrying them as run-time branches cost the small-tile, occupancy-sensitive layers 20-70 %
 // (measured: fused deconv 0.33 -> 0.58 ms, fpn_lateral2 0.24 -> 0.35 ms, 1760 -> 1530 tiles/s end to end).
 // SPLIT: the split-operand precision mode (ConvParams::split, common.h).  A K step covers 32 channels: the 128-byte LDS row of an operand is
 // [32 hi halfs | 32 lo halfs] of the same channels (data chunks 0-3 from the hi plane, 4-7 from the lo plane -- a per-lane constant added to the
-// LDS-DMA source address), so that both planes of both operands are staged ONCE and the three products W_hi.X_lo, W_hi.X_hi, W_lo.X_hi (in this
-// order, the same in conv_deep.hip: every tile accumulates an output in the same order) run on fragments of one stage.  K order: 32-channel slice
+// LDS-DMA source address), so that both planes of both operands are staged ONCE and the three products (mfma_split3, conv_tile.h: every tile
+// accumulates an output in the same order) run on fragments of one stage.  K order: 32-channel slice
 // outer, taps inner.  The stem (SMALLC: per-chunk tap table) keeps three passes over its padded K instead (hi.hi, hi.lo, lo.hi).  Per-row weight
 // descale in the epilogue, outputs written as hi / lo planes.  Compiled out of the fp16 instantiations.
 template <int WPX, int WCH, int MI, int NJ, bool SMALLC, bool GLDS, bool PERSIST, bool TRAIN = false, bool SPLIT = false>
@@ -59,11 +54,7 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wpx = wave / WCH, wch = wave % WCH;
 
-  int M = p.M;
-  if (p.m_count) {
-    long long mc = (long long)(*p.m_count) * p.m_mul;
-    if (mc < M) M = (int)mc;
-  }
+  const int M = conv_rows(p);
   // Tiles are walked in a grid-stride loop: launched with one workgroup per tile it runs once; launched
   // "persistent" (fewer workgroups than tiles) a workgroup streams through tiles q, q+G, q+2G ... and the
   // operands of the NEXT tile's first K step are already in flight while the current tile's epilogue
@@ -79,36 +70,29 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
   const half_t* aptr[PA];
   const half_t* wptr[PW];
   int m0 = 0, n0 = 0;
-  // XCD-aware tile order: positions q and q+8 share an XCD (L2); each XCD gets a contiguous run of logical
-  // tiles, channel tiles fastest, so tiles that re-read one activation panel hit the same L2.
   // per-lane source pointers of the activation rows this lane stages; `second` selects ConvParams::in2
   auto setup_acts = [&](bool second) {
 #pragma unroll
     for (int ps = 0; ps < PA; ++ps) {
       int m = m0 + ps * NW * 8 + wave * 8 + lrow;
       if (m >= M) m = M - 1;
-      const int x2 = m % p.Wo;
-      const int t = m / p.Wo;
-      const int y = t % p.Ho;
-      const int n = t / p.Ho;
-      // LDS slot lchk of row r holds data chunk (lchk ^ (r & 7)); r & 7 == lrow here.
-      const int dch = lchk ^ lrow;      // data chunk this lane stages
+      const Pix px = pix_of(m, p.Wo, p.Ho);
+      const int dch = src_chunk(lchk, act_key(lrow));      // data chunk this lane stages (the row's key: its index & 7 == lrow)
       if (second) {
         const long long base =
-            ((long long)(n * p.in2_Hp + y * p.stride2 + p.in2_off) * p.in2_Wp + x2 * p.stride2 + p.in2_off) * p.in2_Cs;
-        if constexpr (SPLIT) aptr[ps] = p.in2 + base + (dch & 3) * 8 + (dch >> 2) * p.in2_lo;
-        else aptr[ps] = p.in2 + base + dch * 8;
+            ((long long)(px.n * p.in2_Hp + px.y * p.stride2 + p.in2_off) * p.in2_Wp + px.x * p.stride2 + p.in2_off) * p.in2_Cs;
+        if constexpr (SPLIT) aptr[ps] = p.in2 + base + chunk_split(dch, p.in2_lo);
+        else aptr[ps] = p.in2 + base + chunk_f16(dch);
       } else {
         const long long base =
-            ((long long)(n * p.in_Hp + y * p.stride + p.in_off) * p.in_Wp + x2 * p.stride + p.in_off) * p.in_Cs;
-        if constexpr (SPLIT && !SMALLC) aptr[ps] = p.in + base + (dch & 3) * 8 + (dch >> 2) * p.in_lo;
-        else aptr[ps] = p.in + base + (SMALLC ? 0 : (dch * 8));
+            ((long long)(px.n * p.in_Hp + px.y * p.stride + p.in_off) * p.in_Wp + px.x * p.stride + p.in_off) * p.in_Cs;
+        if constexpr (SPLIT && !SMALLC) aptr[ps] = p.in + base + chunk_split(dch, p.in_lo);
+        else aptr[ps] = p.in + base + (SMALLC ? 0 : chunk_f16(dch));
       }
     }
   };
   auto setup_tile = [&](int qq) {
-    const int qn = ntiles >> 3, r = ntiles & 7, x = qq & 7;
-    const int L = (x < r ? x * (qn + 1) : r * (qn + 1) + (x - r) * qn) + (qq >> 3);
+    const int L = xcd_tile(qq, ntiles);      // channel tiles fastest: the tiles that re-read one activation panel share an L2
     const int tile_n = L % tiles_n;
     const int tile_m = L / tiles_n;
     m0 = tile_m * BM;
@@ -117,10 +101,10 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
 #pragma unroll
     for (int ps = 0; ps < PW; ++ps) {
       const int row = ps * NW * 8 + wave * 8 + lrow;
-      const int key = (row & 3) | (((row / (4 * MI)) & 1) << 2);
+      const int dch = src_chunk(lchk, w_key(row, 4 * MI));
       const int rr = row < BN ? row : BN - 1;
-      if constexpr (SPLIT && !SMALLC) wptr[ps] = p.w + (long long)(n0 + rr) * p.Kpad + ((lchk ^ key) & 3) * 8 + ((lchk ^ key) >> 2) * p.w_lo;
-      else wptr[ps] = p.w + (long long)(n0 + rr) * p.Kpad + (lchk ^ key) * 8;
+      if constexpr (SPLIT && !SMALLC) wptr[ps] = p.w + (long long)(n0 + rr) * p.Kpad + chunk_split(dch, p.w_lo);
+      else wptr[ps] = p.w + (long long)(n0 + rr) * p.Kpad + chunk_f16(dch);
     }
   };
 
@@ -150,7 +134,7 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
     for (int ps = 0; ps < PA; ++ps) {
       const half_t* g;
       if constexpr (SMALLC) {
-        g = aptr[ps] + koff_s[t * 8 + (lchk ^ lrow)];
+        g = aptr[ps] + koff_s[t * 8 + src_chunk(lchk, act_key(lrow))];
       } else {
         g = aptr[ps] + a_off;
       }
@@ -180,17 +164,13 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
   // ---- fragment read offsets (bytes inside a stage) ---------------------------------------
   const int fi = lane & 15;        // MFMA row (weights) / column (pixels) index of this lane
   const int fq = lane >> 4;        // k-slice of this lane
-  const int fkey = lane & 7;       // == key of every row this lane reads
+  const int fkey = lane & 7;       // == key of every row this lane reads (conv_tile.h)
   int w_off[MI], x_off[NJ];
 #pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    const int row = wch * MI * 16 + (fi >> 2) * 4 * MI + i * 4 + (fi & 3);
-    w_off[i] = BM * 128 + row * 128;
-  }
+  for (int i = 0; i < MI; ++i) w_off[i] = BM * 128 + (wch * MI * 16 + frag_row(fi, i, 4 * MI)) * 128;
 #pragma unroll
   for (int j = 0; j < NJ; ++j) x_off[j] = (wpx * NJ * 16 + j * 16 + fi) * 128;
-  const int c0_off = ((fq) ^ fkey) * 16;        // kk = 0
-  const int c1_off = ((4 + fq) ^ fkey) * 16;    // kk = 1
+  const int c0_off = frag_off(fq, fkey, 0), c1_off = frag_off(fq, fkey, 1);
 
   int kh = 0, kw = 0, c0 = 0;   // position of the NEXT K step to stage
   // K-step order: 64-channel slice OUTER, filter taps INNER.  All KH*KW taps of one channel slice touch the
@@ -267,18 +247,7 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
-          for (int j = 0; j < NJ; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[i], xl[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[i], xh[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[i], xh[j], acc[i][j], 0, 0, 0);
+          for (int j = 0; j < NJ; ++j) mfma_split3(acc[i][j], wh[i], wl[i], xh[j], xl[j]);
       } else if constexpr (NJ == 8) {
         // 8 waves in lockstep behind one barrier: all of them read fragments at the same time, so the second
         // half-step's fragments are requested before the first half-step's MFMAs instead of after them.
@@ -329,20 +298,7 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
     const int crow = n0c + ch_local;                 // row in the (possibly 4x grouped) weight matrix
     int g = 0, cb = crow;
     if (p.mode != 0) { g = crow / p.Cout; cb = crow % p.Cout; }
-    float bias[4 * MI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      const f32x4 b4 = *(const f32x4*)(p.bias + crow + i * 4);
-      bias[i * 4 + 0] = b4[0]; bias[i * 4 + 1] = b4[1]; bias[i * 4 + 2] = b4[2]; bias[i * 4 + 3] = b4[3];
-    }
-    float wsc[SPLIT ? 4 * MI : 1];
-    if constexpr (SPLIT) {
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const f32x4 s4 = *(const f32x4*)(p.wscale + crow + i * 4);
-        wsc[i * 4 + 0] = s4[0]; wsc[i * 4 + 1] = s4[1]; wsc[i * 4 + 2] = s4[2]; wsc[i * 4 + 3] = s4[3];
-      }
-    }
+    const EpiRows<MI, SPLIT> rw = epi_rows<MI, SPLIT>(p.bias, p.wscale, crow);
     float dotp[NJ];
     long long dot_idx[NJ];
 #pragma unroll
@@ -351,88 +307,14 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
     for (int j = 0; j < NJ; ++j) {
       const int m = m0c + wpx * NJ * 16 + j * 16 + fi;
       if (m >= M) continue;
-      const int x = m % p.Wo;
-      const int t = m / p.Wo;
-      const int y = t % p.Ho;
-      const int n = t / p.Ho;
+      const Pix px = pix_of(m, p.Wo, p.Ho);
+      const int x = px.x, y = px.y, n = px.n;
       int oy = y, ox = x;
       if (p.mode != 0) { oy = 2 * y + (g >> 1); ox = 2 * x + (g & 1); }
       else if (TRAIN && p.out_stride > 1) { oy = y * p.out_stride; ox = x * p.out_stride; }
       const long long opix = (long long)(n * p.out_Hp + oy + p.out_pad) * p.out_Wp + ox + p.out_pad;
       float v[4 * MI];
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if constexpr (SPLIT) v[i * 4 + r] = acc[i][j][r] * wsc[i * 4 + r] + bias[i * 4 + r];
-          else v[i * 4 + r] = acc[i][j][r] + bias[i * 4 + r];
-        }
-      if (p.res) {
-        const half_t* rp = p.res + opix * p.out_Cs + cb;
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-          const half4 h = *(const half4*)(rp + i * 4);
-          if constexpr (SPLIT) {
-            const half4 l = *(const half4*)(rp + p.res_lo + i * 4);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[i * 4 + r] += (float)h[r] + (float)l[r];
-          } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[i * 4 + r] += (float)h[r];
-          }
-        }
-      }
-      if (p.up) {
-        const long long upix = (long long)(n * p.up_Hp + (y >> 1) + p.up_pad) * p.up_Wp + (x >> 1) + p.up_pad;
-        const half_t* up = p.up + upix * p.up_Cs + cb;
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-          const half4 h = *(const half4*)(up + i * 4);
-          if constexpr (SPLIT) {
-            const half4 l = *(const half4*)(up + p.up_lo + i * 4);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[i * 4 + r] += (float)h[r] + (float)l[r];
-          } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[i * 4 + r] += (float)h[r];
-          }
-        }
-      }
-      if (TRAIN && p.down) {      // backward of the nearest 2x upsample: add the 2x2 block of the finer gradient map
-#pragma unroll
-        for (int dd = 0; dd < 4; ++dd) {
-          const long long dpix = (long long)(n * p.down_Hp + 2 * y + (dd >> 1) + p.down_pad) * p.down_Wp + 2 * x + (dd & 1) + p.down_pad;
-          const half_t* dp = p.down + dpix * p.down_Cs + cb;
-#pragma unroll
-          for (int i = 0; i < MI; ++i) {
-            const half4 h = *(const half4*)(dp + i * 4);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[i * 4 + r] += (float)h[r];
-          }
-        }
-      }
-      if (TRAIN && p.res32) {
-        const float* rp = p.res32 + opix * p.out_Cs + cb;
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-          const f32x4 h = *(const f32x4*)(rp + i * 4);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[i * 4 + r] += h[r];
-        }
-      }
-      if (TRAIN && p.mask) {      // ReLU backward
-        const half_t* mp = p.mask + opix * p.out_Cs + cb;
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-          const half4 h = *(const half4*)(mp + i * 4);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[i * 4 + r] = (float)h[r] > 0.f ? v[i * 4 + r] : 0.f;
-        }
-      }
-      if (p.relu) {
-#pragma unroll
-        for (int e = 0; e < 4 * MI; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
-      }
+      epi_values<MI, NJ, TRAIN, SPLIT>(v, p, acc, j, rw, opix, cb, x, y, n);
       if (p.mode == 2) {
         // fused mask predictor: partial dot product of this lane's 4*MI channels with the predicted class' weights
         const int slot = p.dot_slot[n];
@@ -449,44 +331,11 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
         dotp[j] = sdot;
         dot_idx[j] = (long long)slot * (4 * p.Ho * p.Wo) + (long long)oy * (2 * p.Wo) + ox;
       } else if (p.out_f32) {
-        float* op = (float*)p.out + opix * p.out_Cs + cb;
-#pragma unroll
-        for (int i = 0; i < MI; ++i) *(f32x4*)(op + i * 4) = f32x4{v[i * 4], v[i * 4 + 1], v[i * 4 + 2], v[i * 4 + 3]};
+        epi_store_f32<MI>((float*)p.out + opix * p.out_Cs + cb, v);
       } else {
-        half_t* op = (half_t*)p.out + opix * p.out_Cs + cb;
         // saturation screen (common.h rs_sat_bad): the sum of |clamped value| is NaN or >= 65504 whenever an element is NaN or out of range
         float scr = 0.f;
-        if constexpr (MI % 2 == 0) {
-#pragma unroll
-          for (int i = 0; i < MI; i += 2) {          // one 16-byte store per 8 channels (STORES_F16 per pixel)
-            half8 h, l;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-              float f = v[i * 4 + r];
-              f = f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f);
-              scr += __builtin_fabsf(f);
-              h[r] = (half_t)f;
-              if constexpr (SPLIT) l[r] = (half_t)(f - (float)h[r]);
-            }
-            *(half8*)(op + i * 4) = h;
-            if constexpr (SPLIT) *(half8*)(op + p.out_lo + i * 4) = l;
-          }
-        } else {
-#pragma unroll
-          for (int i = 0; i < MI; ++i) {
-            half4 h, l;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              float f = v[i * 4 + r];
-              f = f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f);
-              scr += __builtin_fabsf(f);
-              h[r] = (half_t)f;
-              if constexpr (SPLIT) l[r] = (half_t)(f - (float)h[r]);
-            }
-            *(half4*)(op + i * 4) = h;
-            if constexpr (SPLIT) *(half4*)(op + p.out_lo + i * 4) = l;
-          }
-        }
+        epi_store_h16<MI, SPLIT>((half_t*)p.out + opix * p.out_Cs + cb, p.out_lo, v, [&](float, float f) { scr += __builtin_fabsf(f); });      // STORES_F16 stores per pixel and plane
         if (!(scr < 65504.f)) {     // rare: count exactly
           unsigned c = 0;
 #pragma unroll

@@ -24,7 +24,7 @@
 //     adds the partials in a fixed order (bitwise reproducible; no float atomics), applies the per-output-channel
 //     FrozenBN scale (the trainable tensor is the UNFOLDED weight) and accumulates into the gradient.
 //   * rows of dY beyond M read a zero row (WgradParams::zeros), so the tail contributes nothing.
-#include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
@@ -42,10 +42,6 @@ template <int CB> struct WgCfg {
   static constexpr int LOADS = PCS * SUBS;                  // LDS-DMA pieces a lane issues per stage
 };
 
-__device__ __forceinline__ void glds16(const half_t* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 __device__ __forceinline__ int row_key(int r) { return (((r >> 1) & 1) << 1) | (((r >> 3) & 1) << 2); }
 
 template <int CB>
@@ -59,11 +55,7 @@ __global__ __launch_bounds__(WgCfg<CB>::NT) void conv_wgrad_kernel(const WgradPa
   const int wr = wave >> 1, wc = wave & 1;      // wave tile: channels wr*64.., K columns wc*64..
 
   const int co0 = blockIdx.x * BM;
-  int M = p.M;
-  if (p.m_count) {
-    const long long mc = (long long)(*p.m_count) * p.m_mul;
-    if (mc < M) M = (int)mc;
-  }
+  const int M = conv_rows(p);
   // K columns of this workgroup: two 64-wide halves, each one (tap, channel slice)
   const int slices = p.Cin >> 6;                // 64-channel slices per tap
   int x_off[2], k_col[2];
@@ -98,10 +90,8 @@ __global__ __launch_bounds__(WgCfg<CB>::NT) void conv_wgrad_kernel(const WgradPa
       const int src_chunk = (lchk ^ row_key(r)) * 8;
       const half_t *gy, *gx;
       if (m < M) {
-        const int x = m % p.Wo;
-        const int t = m / p.Wo;
-        const int y = t % p.Ho;
-        const int n = t / p.Ho;
+        const Pix px = pix_of(m, p.Wo, p.Ho);
+        const int x = px.x, y = px.y, n = px.n;
         gy = p.dy + ((long long)(n * p.dy_Hp + y + p.dy_pad) * p.dy_Wp + x + p.dy_pad) * p.dy_Cs + co0 + src_chunk;
         gx = p.x + ((long long)(n * p.in_Hp + y * p.stride + p.in_off) * p.in_Wp + x * p.stride + p.in_off) * p.in_Cs + src_chunk;
       } else {
@@ -281,11 +271,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32_kernel(const WgradParams p
   const int units = p.KH * p.KW * slices;
   const int unit = blockIdx.y * 4 + wave;
   if (unit >= units) return;
-  int M = p.M;
-  if (p.m_count) {
-    const long long mc = (long long)(*p.m_count) * p.m_mul;
-    if (mc < M) M = (int)mc;
-  }
+  const int M = conv_rows(p);
   const int co0 = blockIdx.x * 64;
   const int tap = unit / slices, ci0 = (unit - tap * slices) * 64, kh = tap / p.KW, kw = tap - kh * p.KW;
   const int steps = (M + 3) >> 2;
@@ -392,14 +378,6 @@ constexpr int SSUB = SBK * 128;               // one [32 px][64 ch] fp16 sub-til
 constexpr int S_STAGE = 8 * SSUB;             // dY hi 0, hi 1, lo 0, lo 1, X hi half 0, hi half 1, lo half 0, lo half 1
 constexpr int S_LDS_BYTES = 2 * S_STAGE;      // 64 KB: two workgroups per CU
 
-__device__ __forceinline__ int wgs_rows(const WgradParams& p) {
-  int M = p.M;
-  if (p.m_count) {
-    const long long mc = (long long)(*p.m_count) * p.m_mul;
-    if (mc < M) M = (int)mc;
-  }
-  return M;
-}
 // elements (from the tensor's first) that hold every dY / X element the GEMM reads for rows m < M: whole padded rows up to the last one
 __host__ __device__ __forceinline__ void wgs_range(const WgradParams& p, int M, long long* dy_el, long long* x_el) {
   if (M <= 0) { *dy_el = 0; *x_el = 0; return; }
@@ -417,7 +395,7 @@ __device__ __forceinline__ int wgs_exp(unsigned amax_bits, unsigned nonfinite) {
 
 __global__ __launch_bounds__(256) void wgrad_split_amax_kernel(const WgradParams p) {
   long long dy_el, x_el;
-  wgs_range(p, wgs_rows(p), &dy_el, &x_el);
+  wgs_range(p, conv_rows(p), &dy_el, &x_el);
   const int isx = blockIdx.y;
   const float* src = isx ? (const float*)p.x : (const float*)p.dy;
   const unsigned n4 = (unsigned)((isx ? x_el : dy_el) >> 2);
@@ -457,7 +435,7 @@ __global__ __launch_bounds__(256) void wgrad_split_amax_kernel(const WgradParams
 
 __global__ __launch_bounds__(256) void wgrad_split_planes_kernel(const WgradParams p) {
   long long dy_el, x_el;
-  wgs_range(p, wgs_rows(p), &dy_el, &x_el);
+  wgs_range(p, conv_rows(p), &dy_el, &x_el);
   const int isx = blockIdx.y;
   const float* src = isx ? (const float*)p.x : (const float*)p.dy;
   const unsigned n4 = (unsigned)((isx ? x_el : dy_el) >> 2);
@@ -471,8 +449,9 @@ __global__ __launch_bounds__(256) void wgrad_split_planes_kernel(const WgradPara
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const float s = ldexpf(v[t], e);            // exact: |s| < 2^15
-      h[t] = (half_t)s;                           // round to nearest even
-      l[t] = (half_t)(s - (float)h[t]);
+      const HiLo hl = split_round(s);             // round to nearest even
+      h[t] = hl.h;
+      l[t] = hl.l;
     }
     *(half4*)(hi + 4ll * i) = h;
     *(half4*)(lo + 4ll * i) = l;
@@ -486,7 +465,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_split_kernel(const WgradParams
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 1, wc = wave & 1;      // wave tile: channels wr*64.., K columns wc*64..
   const int co0 = blockIdx.x * 128;
-  const int M = wgs_rows(p);
+  const int M = conv_rows(p);
   const half_t* zeros = (const half_t*)((const char*)p.split_scratch + WGS_ZERO_OFFSET);   // one 64-channel chunk row of zeros
   const half_t* dyh = (const half_t*)((const char*)p.split_scratch + WGS_HEAD_BYTES);
   const half_t* xh = dyh + 2 * p.split_dy_cap;
@@ -522,10 +501,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_split_kernel(const WgradParams
     const bool live = m < M;
     long long oy = 0, ox = 0;                                  // rows past M read the zero row on both sides
     if (live) {
-      const int x = m % p.Wo;
-      const int t = m / p.Wo;
-      const int y = t % p.Ho;
-      const int n = t / p.Ho;
+      const Pix px = pix_of(m, p.Wo, p.Ho);
+      const int x = px.x, y = px.y, n = px.n;
       oy = ((long long)(n * p.dy_Hp + y + p.dy_pad) * p.dy_Wp + x + p.dy_pad) * p.dy_Cs;
       ox = ((long long)(n * p.in_Hp + y * p.stride + p.in_off) * p.in_Wp + x * p.stride + p.in_off) * p.in_Cs;
     }

@@ -23,7 +23,7 @@
 //           ascending order across its two passes, then __shfl_xor 16 and 32 -- one "channel wave" of the 128x256 tile; the four blocks of a (dy, dx)
 //           group are summed ((P0 + P1) + P2) + P3 as that tile sums its channel waves, in registers, and the logit is STORED: no LDS round trip, no atomic, and
 //           the logits need no zeroing (every word of an entry below the device-side count is written; the others are never read).
-#include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
@@ -31,11 +31,6 @@ constexpr int PR = 32;                    // weight rows per pass
 constexpr int KS = 8;                     // K steps of 32 channels
 constexpr int SLICE = KS * PR * 128;      // 32 KB
 constexpr int LDS_BYTES = 2 * SLICE;
-
-__device__ __forceinline__ void glds16w(const half_t* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 // One term of the predictor's dot, as the 128x256 tile's COMPILED code rounds it (the logits must carry its bits): the first four channels of a 64-row block are
 // fused multiply-adds, the other twelve are rounded products added one by one.  That is what hipcc makes of `sdot += v * w` in conv_igemm.hip's split
@@ -57,19 +52,11 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_wide1x1_split_k
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int M = p.M;
-  if (p.m_count) {
-    const long long mc = (long long)(*p.m_count) * p.m_mul;
-    if (mc < M) M = (int)mc;
-  }
+  const int M = conv_rows(p);
   const int ntiles = (M + BM - 1) / BM;
   const int q = blockIdx.x;
   if (q >= ntiles) return;                  // the grid comes from the capacity: nothing is touched past the device-side count
-  int m0;
-  {
-    const int qn = ntiles >> 3, r = ntiles & 7, x = q & 7;      // XCD-aware order (conv_igemm.hip): neighbouring tiles share an L2
-    m0 = ((x < r ? x * (qn + 1) : r * (qn + 1) + (x - r) * qn) + (q >> 3)) * BM;
-  }
+  const int m0 = xcd_tile(q, ntiles) * BM;      // neighbouring tiles share an L2
   const int rows = p.Cout * (MODE == 2 ? 4 : 1);
   const int npass = rows / PR;
 
@@ -79,20 +66,20 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_wide1x1_split_k
   const int rp = wave & 3, s0 = wave >> 2;
   const half_t* wsrc;
   {
-    const int d = lchk ^ ((lrow & 3) | ((rp & 1) << 2));        // data chunk of LDS slot lchk: 0-3 hi halfs, 4-7 lo halfs of the step's 32 channels
-    wsrc = p.w + (long long)(rp * 16 + lrow) * p.Kpad + s0 * 32 + (d & 3) * 8 + (d >> 2) * p.w_lo;
+    const int d = src_chunk(lchk, w_key(8 * rp + lrow, 8));     // data chunk of LDS slot lchk of slice row 8 rp + lrow (conv_tile.h: block height 8)
+    wsrc = p.w + (long long)(rp * 16 + lrow) * p.Kpad + s0 * 32 + chunk_split(d, p.w_lo);
   }
   auto stage_piece = [&](int pass, int k) {
     const half_t* g = wsrc + (long long)((pass >> 1) * 64 + (pass & 1) * 8) * p.Kpad;
     char* base = smem + (pass & 1) * SLICE + (s0 * PR + rp * 8) * 128;
-    glds16w(g + k * (NW / 4) * 32, base + k * (NW / 4) * PR * 128);
+    glds16(g + k * (NW / 4) * 32, base + k * (NW / 4) * PR * 128);
   };
 
   const int fi = lane & 15, fq = lane >> 4, fkey = lane & 7;
   int w_off[2];
 #pragma unroll
-  for (int ii = 0; ii < 2; ++ii) w_off[ii] = ((fi >> 2) * 8 + ii * 4 + (fi & 3)) * 128;
-  const int ch_off = (fq ^ fkey) * 16, cl_off = ((4 + fq) ^ fkey) * 16;        // this lane's hi / lo fragment inside a row
+  for (int ii = 0; ii < 2; ++ii) w_off[ii] = frag_row(fi, ii, 8) * 128;
+  const int ch_off = frag_off(fq, fkey, 0), cl_off = frag_off(fq, fkey, 1);    // this lane's hi / lo fragment inside a row
 
   // ---- this wave's pixels: B fragments of all eight K steps, both planes
   half8 xh[KS][NJ], xl[KS][NJ];
@@ -105,7 +92,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_wide1x1_split_k
     const int m = m0 + (wave * NJ + j) * 16 + fi;
     valid[j] = m < M;
     const int mm = valid[j] ? m : M - 1;
-    const int x = mm % p.Wo, t = mm / p.Wo, y = t % p.Ho, n = t / p.Ho;
+    const Pix px = pix_of(mm, p.Wo, p.Ho);
+    const int x = px.x, y = px.y, n = px.n;
     const half_t* xp = p.in + ((long long)(n * p.in_Hp + y + p.in_off) * p.in_Wp + x + p.in_off) * 256 + fq * 8;
 #pragma unroll
     for (int s = 0; s < KS; ++s) { xh[s][j] = *(const half8*)(xp + s * 32); xl[s][j] = *(const half8*)(xp + p.in_lo + s * 32); }
@@ -206,6 +194,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_wide1x1_split_k
       // last one has landed long before the wait in front of the epilogue
       if (more && 2 * s < NG) { stage_piece(pass + 1, 2 * s); stage_piece(pass + 1, 2 * s + 1); }
       __builtin_amdgcn_sched_barrier(0);
+      // the three products in mfma_split3's order (conv_tile.h owns it), placed by hand round the sched_barriers
 #pragma unroll
       for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
@@ -283,11 +272,11 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_wide1x1_split_k
         half8 h, l;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          float f = v[e];
-          f = f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f);
+          const float f = clamp_h16(v[e]);
           scr += __builtin_fabsf(f);
-          h[e] = (half_t)f;
-          l[e] = (half_t)(f - (float)h[e]);
+          const HiLo hl = split_round(f);
+          h[e] = hl.h;
+          l[e] = hl.l;
         }
         if (valid[j] && !(scr < 65504.f)) {     // rare: count exactly
           unsigned c = 0;

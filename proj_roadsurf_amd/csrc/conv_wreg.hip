@@ -37,30 +37,12 @@
 // an eight-wave form (variant 23: two waves per SIMD, 32 pixels of the tile each) measures the same 163-166 us because one barrier
 // pair per tile keeps all waves in the same phase.  Short walks lose to the prologue (128 KB of weights per workgroup): see the
 // dispatch rule in conv_choose_variant.
-#include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int MI = 4;
-
-__device__ __forceinline__ void glds16(const half_t* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-// Pixel m = m0 + r as (x, y, n) without a division: (x0, y0, n0) are the coordinates of m0 and (rx, ry, rn) those of the offset r
-// (rx < Wo, ry < Ho), so one carry per digit suffices.
-struct Pix { int x, y, n; };
-__device__ __forceinline__ Pix pix_add(int x0, int y0, int n0, int rx, int ry, int rn, int Wo, int Ho) {
-  int x = x0 + rx;
-  const int cx = x >= Wo;
-  x -= cx ? Wo : 0;
-  int y = y0 + ry + cx;
-  const int cy = y >= Ho;
-  y -= cy ? Ho : 0;
-  return Pix{x, y, n0 + rn + cy};
-}
 
 // EPI: 0 = bias (+ ReLU) only, 1 = residual (same geometry as the output), 2 = coarser map added at (y/2, x/2) (FPN top-down),
 //      3 = the mask head's 2x2 stride-2 transposed convolution + ReLU + predictor 1x1 of the predicted class (ConvParams::mode 2: the four
@@ -82,18 +64,11 @@ __global__ __launch_bounds__(256 * NWPX, BM == 32 ? 2 : 1) void conv1x1_wreg_ker
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wch = wave & 3, wpx = wave >> 2;      // wave = 64 channels x (64 / NWPX) pixels
-  int Mv = p.M;
-  if (p.m_count) { const long long mc = (long long)(*p.m_count) * p.m_mul; if (mc < Mv) Mv = (int)mc; }    // rows bounded by a device counter (mask head)
-  const int M = Mv, Wo = p.Wo, Ho = p.Ho;
+  const int M = conv_rows(p), Wo = p.Wo, Ho = p.Ho;      // rows bounded by a device counter (mask head)
   const int tiles_m = (M + BM - 1) / BM;
   const int groups = EPI == 3 ? 4 : p.Cout >> 8;
-  // XCD-aware order (conv_igemm.hip): workgroups b, b + 8, ... share an XCD; the `groups` workgroups that read one activation tile get
-  // consecutive logical ids, i.e. the same XCD's L2
-  int L;
-  {
-    const int G = gridDim.x, qn = G >> 3, r = G & 7, x = blockIdx.x & 7;
-    L = (x < r ? x * (qn + 1) : r * (qn + 1) + (x - r) * qn) + (blockIdx.x >> 3);
-  }
+  // the `groups` workgroups that read one activation tile get consecutive logical ids, i.e. the same XCD's L2
+  const int L = xcd_tile(blockIdx.x, gridDim.x);
   const int grp = L % groups, first = L / groups, step = gridDim.x / groups;
   const int ntl = first < tiles_m ? (tiles_m - 1 - first) / step + 1 : 0;     // this workgroup's tiles: first, first + step, ...
   if (ntl == 0) return;
@@ -102,27 +77,28 @@ __global__ __launch_bounds__(256 * NWPX, BM == 32 ? 2 : 1) void conv1x1_wreg_ker
   const int lrow = lane >> 3, lchk = lane & 7;
 
   // ---- pixel coordinates: the only divisions of the kernel (uniform ones for the tile walk, per-lane ones for the lane's fixed offsets)
-  const int HW = Ho * Wo;
   int tx, ty, tn;                                 // coordinates of the first pixel of the tile being ISSUED (uniform)
-  { const int m = first * BM; tn = m / HW; const int r = m - tn * HW; ty = r / Wo; tx = r - ty * Wo; }
+  { const Pix t = pix_of(first * BM, Wo, Ho); tx = t.x; ty = t.y; tn = t.n; }
   int dx, dy, dn;                                 // ... advance by `step` tiles
-  { const int m = step * BM; dn = m / HW; const int r = m - dn * HW; dy = r / Wo; dx = r - dy * Wo; }
+  { const Pix d = pix_of(step * BM, Wo, Ho); dx = d.x; dy = d.y; dn = d.n; }
   int ex = tx, ey = ty, en = tn;                  // the same walk for the tile being STORED
   int irx[PASSES], iry[PASSES], irn[PASSES];      // this lane's rows in the LDS-DMA passes
 #pragma unroll
   for (int ps = 0; ps < PASSES; ++ps) {
     const int r = ps * NWAVE * 8 + wave * 8 + lrow;
-    irn[ps] = r / HW; const int q = r - irn[ps] * HW; iry[ps] = q / Wo; irx[ps] = q - iry[ps] * Wo;
+    const Pix q = pix_of(r, Wo, Ho);
+    irx[ps] = q.x; iry[ps] = q.y; irn[ps] = q.n;
   }
   int orx[NJ], ory[NJ], orn[NJ];                  // ... and its pixels of the output fragment
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int r = (wpx * NJ + j) * 16 + fi;
-    orn[j] = r / HW; const int q = r - orn[j] * HW; ory[j] = q / Wo; orx[j] = q - ory[j] * Wo;
+    const Pix q = pix_of(r, Wo, Ho);
+    orx[j] = q.x; ory[j] = q.y; orn[j] = q.n;
   }
-  const int c0_off = (fq ^ fkey) * 16, c1_off = ((4 + fq) ^ fkey) * 16;
+  const int c0_off = frag_off(fq, fkey, 0), c1_off = frag_off(fq, fkey, 1);
   const int ec0 = ((2 * fq) ^ fkey) * 16, ec1 = ((2 * fq + 1) ^ fkey) * 16;
-  const int sw8 = (lchk ^ lrow) * 8;
+  const int sw8 = chunk_f16(src_chunk(lchk, act_key(lrow)));
   const int crow = n0 + wch * 64 + fq * 16;                       // lane holds channels crow .. crow + 15 of pixel (j, fi)
 
   // the LDS-DMA pieces of the tile at (tx, ty, tn), first pixel m0: activation rows, then the epilogue operand's rows
@@ -158,7 +134,7 @@ __global__ __launch_bounds__(256 * NWPX, BM == 32 ? 2 : 1) void conv1x1_wreg_ker
   half8 wreg[4][2][MI];
 #pragma unroll
   for (int i = 0; i < MI; ++i) {
-    const int row = n0 + wch * 64 + (fi >> 2) * 16 + i * 4 + (fi & 3);
+    const int row = n0 + wch * 64 + frag_row(fi, i, 4 * MI);
     const half_t* wr = p.w + (long long)row * p.Kpad + fq * 8;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {

@@ -12,7 +12,7 @@
 // pooled value, is BIT-identical to the two-kernel path.  What differs is where the B operand comes from: the 39x39 input pixels of the
 // patch are staged ONCE into LDS (8 bytes per pixel) and a lane's 8 k-values of a step -- two horizontally adjacent taps x 4 channels --
 // are 16 contiguous bytes of that image, read straight into the fragment; no im2col copy exists anywhere.
-#include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
@@ -44,8 +44,7 @@ __global__ __launch_bounds__(NT) void stem_pool_kernel(const StemPoolParams p) {
 #pragma unroll
     for (int i = 0; i < 7; ++i) {
       const int piece = i * NW + wave;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p.wf + (long long)piece * 512 + lane * 8),
-                                       (__attribute__((address_space(3))) void*)(wl + piece * 1024), 16, 0, 0);
+      glds16(p.wf + (long long)piece * 512 + lane * 8, wl + piece * 1024);
     }
   }
   // ---- input patch -> LDS: buffer rows 4 a0 - 2 .. +38 of the halo-3 image (conv row cy reads rows 2 cy - 3 .. 2 cy + 3), zeros outside
@@ -123,7 +122,7 @@ __global__ __launch_bounds__(NT) void stem_pool_kernel(const StemPoolParams p) {
         float f = acc[b][mi][r] + bv[mi][r];
         f = f > 0.f ? f : 0.f;
         mx = __builtin_fmaxf(mx, f);
-        f = f > 65504.f ? 65504.f : f;
+        f = clamp_h16_pos(f);
         h[r] = inside ? (half_t)f : (half_t)0.f;
       }
       if (!(DBG & 8)) *(half4*)(ol + px * OP + (mi * 16 + fq * 4) * 2) = h;
@@ -271,9 +270,8 @@ __global__ __launch_bounds__(NT, 3) void stem_pool_split_kernel(const StemPoolSp
           float f = acc[b][mb][r] * sv[r] + bv[r];
           f = f > 0.f ? f : 0.f;
           satc += own ? rs_sat_bad(f) : 0u;
-          f = f > 65504.f ? 65504.f : f;
-          const half_t h = (half_t)f, l = (half_t)(f - (float)h);
-          key[r] = inside ? pair_key(h, l) : pair_key((half_t)0.f, (half_t)0.f);
+          const HiLo s = split_round(clamp_h16_pos(f));
+          key[r] = inside ? pair_key(s.h, s.l) : pair_key((half_t)0.f, (half_t)0.f);
         }
         *(u32x4*)(ol + px * S_OP + fq * 16) = key;
       }
