@@ -24,23 +24,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-SHAPES = [(1, 13, 11), (2, 24, 20)]
-IGEMM = {0: 128, 1: 64, 3: 128, 4: 256, 7: 128, 8: 64, 9: 128, 10: 256, 14: 256}      # variant -> rows must be a multiple of
-DEEP_F16, DEEP_SPLIT = [12, 15, 16, 17, 18, 19, 20], [12, 15, 16, 17]
-WREG, WIDE = [22, 23, 25, 26], [28, 29, 30, 31]
-
-
-def _variants(split, cin, cout, k, stride, res, up, deconv, train=False, scatter=False):
-    rows = cout * (4 if deconv else 1)
-    out = [-1] + [v for v, mult in IGEMM.items() if rows % mult == 0]
-    if not deconv and rows % 256 == 0 and not scatter:
-        out += [12] if train else (DEEP_SPLIT if split else DEEP_F16)
-    one_by_one = k == 1 and stride == 1 and cin == 256 and not deconv and not train
-    if one_by_one and not split and rows % 256 == 0 and not (res and up):
-        out += WREG
-    if one_by_one and split and rows % 64 == 0 and not up:
-        out += WIDE
-    return out
+from tests.conv_cases import WIDE, _variants, IGEMM, tool_cases      # noqa: E402  (the case grid, shared with tests/test_gpu_conv_bounds.py)
+from tests.conv_cases import bneck_tag, conv_tag, deconv_predict_tag, dgrad_tag, dual_tag      # noqa: E402
 
 
 def _rng(name):
@@ -92,8 +77,7 @@ class Runner:
     def conv(self, split, n, h, w, cin, cout, k, stride, res, up, relu, deconv=False, out_f32=False):
         T = self.torch
         pad = k // 2
-        tag = "%s conv%dx%d s%d %d->%d %dx%dx%d%s%s%s%s%s" % ("split" if split else "fp16", k, k, stride, cin, cout, n, h, w, " res" if res else "",
-                                                            " up" if up else "", " relu" if relu else "", " deconv" if deconv else "", " f32out" if out_f32 else "")
+        tag = conv_tag(split, n, h, w, cin, cout, k, stride, res, up, relu, deconv, out_f32)
         rng = _rng(tag)
         ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
         oh, ow = (2 * ho, 2 * wo) if deconv else (ho, wo)
@@ -131,7 +115,7 @@ class Runner:
 
     # ---- conv3 + projection shortcut over two K sources (fp16)
     def dual(self, n, h, w, cin, cin2, cout, stride2):
-        tag = "fp16 dual 1x1 %d+%d->%d s2=%d %dx%dx%d" % (cin, cin2, cout, stride2, n, h, w)
+        tag = dual_tag(n, h, w, cin, cin2, cout, stride2)
         rng = _rng(tag)
         xd = self.up(_act(rng, n, h, w, cin, 0).astype(np.float16))
         x2 = self.up(_act(rng, n, h * stride2, w * stride2, cin2, 1).astype(np.float16))
@@ -146,8 +130,7 @@ class Runner:
     # ---- training epilogues: down / res32 / mask / out_stride through the input-gradient operator
     def dgrad(self, n, hi, wi, cin, cout, k, stride, res, res32, mask, down):
         T = self.torch
-        tag = "dgrad %dx%d s%d %d<-%d %dx%dx%d%s%s%s%s" % (k, k, stride, cin, cout, n, hi, wi, " res" if res else "", " res32" if res32 else "", " mask" if mask else "",
-                                                          " down" if down else "")
+        tag = dgrad_tag(n, hi, wi, cin, cout, k, stride, res, res32, mask, down)
         rng = _rng(tag)
         pad = k // 2
         ho, wo = (hi, wi) if stride == 1 else ((hi + stride - 1) // stride, (wi + stride - 1) // stride)
@@ -166,7 +149,7 @@ class Runner:
     # ---- mode 2 in the split mode: fused deconv + predictor, rows bounded by a device count below the capacity
     def deconv_predict(self, entries, count, side):
         T = self.torch
-        tag = "split deconv+predict %d of %d entries side %d" % (count, entries, side)
+        tag = deconv_predict_tag(entries, count, side)
         rng = _rng(tag)
         classes, slots = 3, entries + 2
         xd = self.up(_planes(np.abs(_act(rng, entries, side, side, 256, 1))))
@@ -185,7 +168,7 @@ class Runner:
     # ---- both bottleneck tails: CB 1 and 2, with / without the next conv1 and the projection shortcut
     def bneck(self, split, n, h, w, width, nxt, proj):
         T = self.torch
-        tag = "%s bneck tail width %d %dx%dx%d%s%s" % ("split" if split else "fp16", width, n, h, w, " next" if nxt else "", " proj" if proj else "")
+        tag = bneck_tag(split, n, h, w, width, nxt, proj)
         rng = _rng(tag)
         c4 = 4 * width
         t1 = _act(rng, n, h, w, width, 1)
@@ -214,32 +197,8 @@ class Runner:
 
 
 def run_all(r):
-    for split in (False, True):
-        for n, h, w in SHAPES:
-            for cin in (64, 256):
-                for cout in (64, 256, 1024):
-                    for k, stride in ((1, 1), (1, 2), (3, 1), (3, 2)):
-                        epis = [(False, False, False), (True, False, True), (False, True, True)] if (k, stride) == (1, 1) else [(False, False, True)]
-                        if (k, stride, cin, cout) == (3, 1, 256, 256):
-                            epis.append((True, True, True))
-                        for res, up, relu in epis:
-                            r.conv(split, n, h, w, cin, cout, k, stride, res, up, relu)
-            r.conv(split, n, h, w, 256, 256, 1, 1, False, False, True, deconv=True)            # mode 1
-            r.conv(split, n, h, w, 256, 16, 1, 1, False, False, False, out_f32=True)          # the fp32-out head tile
-            for width in (64, 128):
-                for nxt in (False, True):
-                    r.bneck(split, n, h, w, width, nxt, False)
-                    if width == 64:
-                        r.bneck(split, n, h, w, width, nxt, True)
-    for n, h, w in SHAPES:
-        r.dual(n, h, w, 64, 64, 256, 1)
-        r.dual(n, h, w, 256, 256, 1024, 2)
-        r.dgrad(n, h, w, 256, 256, 3, 1, False, True, True, True)
-        r.dgrad(n, h, w, 256, 256, 3, 1, True, False, False, False)
-        r.dgrad(n, h, w, 64, 256, 1, 1, False, True, True, False)
-        r.dgrad(n, h, w, 256, 1024, 1, 2, False, False, True, False)                            # out_stride 2
-    r.deconv_predict(5, 3, 14)
-    r.deconv_predict(9, 9, 7)
+    for method, args, kw in tool_cases():
+        getattr(r, method)(*args, **kw)
 
 
 def main(argv=None):
