@@ -303,6 +303,27 @@ int rs_op_conv2d_dual(const void* in, const void* in2, const void* w, const floa
 int rs_op_conv2d_dgrad(const void* dy, const void* w_t, void* dx, const void* res, const float* res32, const void* mask,
                        const void* down, int n, int hi, int wi, int cin, int ho, int wo, int cout, int kh, int kw, int stride,
                        int pad, int kpad, int halo, int variant, void* stream);
+/* The same input gradient for the reference-precision trainer with the product on the fp16 matrix cores ("input gradients on
+ * split operands").  Every tensor is fp32: dy, w_t [cin][kpad], dx, res, res32, mask (the saved activation, > 0 passes), down.  For the
+ * life of the call it allocates scratch, takes the abs-max of dy on the device (integer maximum, no read-back), writes
+ * hi = fp16(dy 2^e), lo = fp16(dy 2^e - hi) with e = 14 - floor(log2 amax) (0 for a zero or non-finite dy), splits w_t by rows
+ * (rs_op_split_rows) and runs three v_mfma_f32_16x16x32_f16 products (hi.lo, hi.hi, lo.hi) into one fp32 accumulator:
+ *   dx = mask( acc * inv_scale[row] * 2^-e + res + sum2x2(down) + res32 ),  stored fp32; two calls give the same bits.  Per element
+ *   |gemm - exact| <= 2^-20 sum|dy||w| + 2^-36 T max|dy| rowmax|w| + (the accumulation-order error of the fp32 kernel), T = kh kw cout.
+ * variant: -1 = the library's rule, or a tile by number: 7 (64 x 128), 14 (128 x 256), 4 (256 x 256; cin a multiple of 128 resp. 256) or
+ * 2 (256 x 16).  count_dev: optional device int, images computed = min(n, *count_dev), the others are not written.
+ * Refused before a device is touched, with the entry's name in rs_last_error: null dy / w_t / dx (RS_ERR_ARG), n < 1, cout (the K side) no
+ * multiple of 64, a halo below k - 1 - pad (RS_ERR_ARG), stride > 1 with a kernel that is not 1x1 (RS_ERR_UNSUPPORTED).
+ * rs_op_conv2d_dgrad_split_serves: 1 when a layer of this shape runs split (in the operator and in the trainer's mode), else 0: cin a
+ * multiple of 16, cout of 64, stride 1 or a 1x1 kernel.  Host only. */
+int rs_op_conv2d_dgrad_split(const void* dy, const void* w_t, void* dx, const void* res, const float* res32, const void* mask,
+                       const void* down, int n, int hi, int wi, int cin, int ho, int wo, int cout, int kh, int kw, int stride,
+                       int pad, int kpad, int halo, int variant, const int32_t* count_dev, void* stream);
+int rs_op_conv2d_dgrad_split_serves(int cin, int cout, int kh, int stride);
+/* Rows of a device fp32 matrix w [rows][k] as fp16 planes [2 * rows][k] (the hi rows, then the lo rows) of w 2^e(row), with
+ * inv_scale[row] = 2^-e(row): e = 13 - floor(log2 max|row|) clipped to [-100, 100], so the row maximum lies in [2^13, 2^14) (0 for a
+ * zero or non-finite row) -- bit for bit weights.split_planes.  The row maximum is an integer maximum over the bits of |w|. */
+int rs_op_split_rows(const float* w, int rows, int k, void* planes, float* inv_scale, void* stream);
 
 /* Training path: weight gradient of rs_op_conv2d's convolution (conv_wgrad.hip),
  *   grad[co][(kh,kw,ci)] = scale[co] * sum_{n,y,x} dy[n][y][x][co] * in[n][y*stride+kh-pad][x*stride+kw-pad][ci]
@@ -507,6 +528,16 @@ int rs_trainer_set_sampling(rs_trainer* t, int rpn_batch, float rpn_positive_fra
  * waits for the trainer's stream; a failed allocation leaves the mode as it was.  RS_ERR_UNSUPPORTED on an fp16 trainer, RS_ERR_ARG on a
  * null handle or another mode. */
 int rs_trainer_set_wgrad_mode(rs_trainer* t, int mode);
+/* Input-gradient product dX = dY * W^T of the reference-precision (fp32) trainer: 0 = fp32 matrix cores (default), 1 = split operands on
+ * the fp16 matrix cores (rs_op_conv2d_dgrad_split) for every `*.x` stage whose shape rs_op_conv2d_dgrad_split_serves accepts -- all of
+ * this model's; storage, forward, losses, addends and weight gradients do not change.  The mask deconvolution's input gradient and
+ * RoIAlign backward stay fp32.  Read when a stage launches.  The first switch to mode 1 allocates, on the current device, the dY plane
+ * scratch of the chain stream (separate from the weight-gradient mode's) and the planes + inverse row scales of every stage's W^T;
+ * every switch to mode 1 splits the current W^T, and while the mode is on every fold (rs_trainer_apply_sgd, rs_trainer_copy_state)
+ * splits again.  The abs-max and plane passes run inside the `*.x` stages, so rs_trainer_stage_info includes them.
+ * rs_trainer_copy_state carries the mode to the destination.  RS_ERR_UNSUPPORTED on an fp16 trainer, RS_ERR_ARG on a null handle or
+ * another mode. */
+int rs_trainer_set_dgrad_mode(rs_trainer* t, int mode);
 /* SGD with momentum on the flat buffers + refold.  The gradient is first checked for inf / nan (fp16 loss scale too large for
  * this batch): then the step is skipped on the device -- weights and momentum unchanged -- and the tensor "grad_overflow" [1]
  * reads 1; lower the scale with rs_trainer_set_loss_scale before the next forward (GradScaler semantics, no host sync here). */

@@ -202,9 +202,19 @@ struct ConvParams {
   const float* head_scale;    // its inverse row scales [16]
   ConvSeg seg[RS_MAX_SEGS];
   unsigned long long* sat;    // saturation counter (rs_sat_flush): += elements clamped to the fp16 range; nullptr = not counted
+  // ---- the fp32 trainer's input gradient on split operands (set together with `split`): `in` / in_lo are the hi / lo fp16
+  // planes of dY * 2^e_dy, `w` / w_lo / wscale the row-scaled planes of W^T, and dy_amax the two device words the abs-max pass left
+  // (bits of the largest finite |dY|, non-finite flag) from which the epilogue derives e_dy.  res / down / res32 / mask / out are fp32
+  // tensors, as in ref_f32.hip.  nullptr = not this flavour.
+  const unsigned* dy_amax;
 };
 
 int launch_conv(const ConvParams& p, hipStream_t stream, int force_variant /* -1 auto */, int use_glds);
+// Input gradient of the fp32 trainer on split operands (conv_igemm.hip, ConvParams::dy_amax): launch_conv routes here.  The tile variants it
+// runs are 7 (64x128), 14 (128x256), 4 (256x256) and 2 (256x16, rows that are no multiple of 128); conv_dgrad_split_variant is its rule.
+bool conv_dgrad_split_serves(int rows /* dx channels */, int k_channels /* dY channels */, int kh, int kw, int stride);
+int conv_dgrad_split_variant(const ConvParams& p);
+int launch_conv_dgrad_split(const ConvParams& p, hipStream_t stream, int force_variant);
 int conv_choose_variant(ConvParams& p, int force_variant, int use_glds);   // the dispatch rule (also sets p.stages / p.persist)
 extern thread_local int g_last_conv_variant;
 
@@ -312,6 +322,22 @@ struct WgradParams {
 constexpr size_t WGS_ZERO_OFFSET = 128;            // header: amax / non-finite words, then a zero row of 64 halfs (one channel chunk row)
 constexpr size_t WGS_HEAD_BYTES = 256;
 static inline size_t wgrad_split_scratch_bytes(long long dy_cap, long long x_cap) { return WGS_HEAD_BYTES + (size_t)(dy_cap + x_cap) * 4; }
+// The same two passes on the dY of an input-gradient GEMM `p` (p.in: the fp32 dY in its NHWC-with-halo geometry): abs-max over the whole
+// padded rows the GEMM reads for its (m_count-bounded) rows, then hi / lo planes of dY * 2^e behind a WGS_HEAD_BYTES header in `scratch`
+// ([2][cap] halfs; words 0 / 1 of the header are the abs-max bits and the non-finite flag).  Stream-ordered, no read-back.
+static inline size_t dgrad_split_scratch_bytes(long long cap) { return WGS_HEAD_BYTES + (size_t)cap * 4; }
+int launch_dgrad_split_planes(const ConvParams& p, void* scratch, long long cap, hipStream_t stream);
+// Rows of fp32 matrices as hi / lo fp16 planes with one power-of-two scale per row (weights.split_planes' rule: row maximum in
+// [2^13, 2^14), exponent clipped to +-100): planes [2 * rows][k] (hi rows, then lo rows), inv [rows] the inverse scales.
+struct SplitRowsDesc {
+  const float* w;
+  half_t* planes;
+  float* inv;
+  int rows, k;
+  unsigned row_start;      // first workgroup of this matrix in a table launch (one workgroup per row)
+};
+int launch_split_rows(const SplitRowsDesc& d, hipStream_t stream);
+int launch_split_rows_table(const SplitRowsDesc* table_dev, int n, unsigned total_rows, hipStream_t stream);
 bool wgrad_split_serves(const WgradParams& p);
 int wgrad_splits(const WgradParams& p);
 int launch_conv_wgrad(const WgradParams& p, hipStream_t stream);

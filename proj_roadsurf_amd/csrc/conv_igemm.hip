@@ -41,6 +41,8 @@ struct Tile {
 // accumulates an output in the same order) run on fragments of one stage.  K order: 32-channel slice
 // outer, taps inner.  The stem (SMALLC: per-chunk tap table) keeps three passes over its padded K instead (hi.hi, hi.lo, lo.hi).  Per-row weight
 // descale in the epilogue, outputs written as hi / lo planes.  Compiled out of the fp16 instantiations.
+// TRAIN && SPLIT: the fp32 trainer's input gradient on split operands (ConvParams::dy_amax, launch_conv_dgrad_split below): the split loop on the planes
+// of dY and of the row-scaled W^T, then conv_tile.h's epi_values_dgrad_split -- tensor and row scales undone, fp32 addends and mask, fp32 store.
 template <int WPX, int WCH, int MI, int NJ, bool SMALLC, bool GLDS, bool PERSIST, bool TRAIN = false, bool SPLIT = false>
 __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvParams p) {
   using T = Tile<WPX, WCH, MI, NJ>;
@@ -298,7 +300,12 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
     const int crow = n0c + ch_local;                 // row in the (possibly 4x grouped) weight matrix
     int g = 0, cb = crow;
     if (p.mode != 0) { g = crow / p.Cout; cb = crow % p.Cout; }
-    const EpiRows<MI, SPLIT> rw = epi_rows<MI, SPLIT>(p.bias, p.wscale, crow);
+    // TRAIN && SPLIT, the fp32 trainer's input gradient on split operands: no bias (its words are read from wscale and unused), the tensor
+    // scale of dY from the device words behind the abs-max pass, fp32 addends, fp32 store
+    constexpr bool DGRAD_SPLIT = TRAIN && SPLIT;
+    const EpiRows<MI, SPLIT> rw = epi_rows<MI, SPLIT>(DGRAD_SPLIT ? p.wscale : p.bias, p.wscale, crow);
+    int e_dy = 0;
+    if constexpr (DGRAD_SPLIT) e_dy = split_tensor_exp(p.dy_amax[0], p.dy_amax[1]);
     float dotp[NJ];
     long long dot_idx[NJ];
 #pragma unroll
@@ -314,7 +321,13 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
       else if (TRAIN && p.out_stride > 1) { oy = y * p.out_stride; ox = x * p.out_stride; }
       const long long opix = (long long)(n * p.out_Hp + oy + p.out_pad) * p.out_Wp + ox + p.out_pad;
       float v[4 * MI];
-      epi_values<MI, NJ, TRAIN, SPLIT>(v, p, acc, j, rw, opix, cb, x, y, n);
+      if constexpr (DGRAD_SPLIT) {
+        epi_values_dgrad_split<MI, NJ>(v, p, acc, j, rw, e_dy, opix, cb, x, y, n);
+        epi_store_f32<MI>((float*)p.out + opix * p.out_Cs + cb, v);
+        continue;
+      } else {
+        epi_values<MI, NJ, TRAIN, SPLIT>(v, p, acc, j, rw, opix, cb, x, y, n);
+      }
       if (p.mode == 2) {
         // fused mask predictor: partial dot product of this lane's 4*MI channels with the predicted class' weights
         const int slot = p.dot_slot[n];
@@ -432,7 +445,76 @@ int launch_variant(const ConvParams& p, hipStream_t stream, int use_glds) {
   return RS_OK;
 }
 
+// The TRAIN && SPLIT instantiation (input gradient of the fp32 trainer on split operands): LDS-DMA staging, one workgroup per tile.  Its
+// fragment arrays must stay in registers like those of the other split loops, so a build that spilled refuses to launch.
+template <int WPX, int WCH, int MI, int NJ>
+int launch_variant_dgrad_split(const ConvParams& p, hipStream_t stream) {
+  using T = Tile<WPX, WCH, MI, NJ>;
+  const long long nblk = (long long)cdiv(p.Cout, T::BN) * cdiv(p.M, T::BM);
+  RS_CHECK(nblk > 0 && nblk < (1ll << 31), RS_ERR_ARG, "conv (split input gradient): bad grid %lld", nblk);
+  RS_CHECK(p.Cout % T::BN == 0, RS_ERR_ARG, "conv (split input gradient): %d rows are no multiple of the tile's %d", p.Cout, T::BN);
+  const void* k = (const void*)conv_igemm_kernel<WPX, WCH, MI, NJ, false, true, false, true, true>;
+  static bool ready = false;
+  if (!ready) {
+    hipFuncAttributes a;
+    RS_HIP(hipFuncGetAttributes(&a, k));
+    RS_CHECK(a.localSizeBytes == 0, RS_ERR_UNSUPPORTED, "conv (split input gradient): the %d x %d tile was built with %zu bytes of scratch per thread (rebuild with the documented toolchain)",
+             T::BM, T::BN, (size_t)a.localSizeBytes);
+    RS_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS));
+    ready = true;
+  }
+  const int lds = (p.stages == 1 ? 1 : 2) * T::STAGE + 1024;
+  ConvParams pc = p;
+  void* args[] = {&pc};
+  RS_HIP(hipLaunchKernel(k, dim3((unsigned)nblk), dim3(T::NT), args, lds, stream));
+  return RS_OK;
+}
+
 }  // namespace
+
+// ---- the fp32 trainer's input gradient on split operands (ConvParams::dy_amax)
+bool conv_dgrad_split_serves(int rows, int k_channels, int kh, int kw, int stride) {
+  return rows >= 16 && rows % 16 == 0 && k_channels >= 64 && k_channels % 64 == 0 && kh == kw && kh >= 1 && (stride == 1 || (stride > 1 && kh == 1));
+}
+
+// Tile of a split input gradient; a rule of its own, so conv_choose_variant answers every other caller as before.  Rows that are no
+// multiple of 128 take the 16-row tile.  256-row multiples: the 256 x 256 tile from a full round of the chip on a deep K (it halves the
+// L2 -> LDS bytes per FLOP, the forward rule's reason), the 128 x 256 tile from a round of its own tiles, else 64 x 128, which keeps the
+// most workgroups in flight on the small maps (res5, the heads).
+int conv_dgrad_split_variant(const ConvParams& p) {
+  const int rows = p.Cout;
+  if (rows % 128 != 0) return 2;
+  const int nk = p.KH * p.KW * (p.Cin >> 6);
+  const int ncu = rs_device_cu_count();
+  if (rows % 256 == 0) {
+    if (nk >= 8 && (long long)cdiv(p.M, 256) * (rows / 256) >= ncu) return 4;
+    if ((long long)cdiv(p.M, 128) * (rows / 256) >= ncu) return 14;
+  }
+  return 7;
+}
+
+int launch_conv_dgrad_split(const ConvParams& p_in, hipStream_t stream, int force_variant) {
+  ConvParams p = p_in;
+  RS_CHECK(p.in && p.w && p.wscale && p.out && p.dy_amax && p.split, RS_ERR_ARG, "conv (split input gradient): null operand");
+  RS_CHECK(p.M > 0 && p.mode == 0 && !p.in2 && !p.up && !p.relu && p.stride == 1, RS_ERR_ARG, "conv (split input gradient): M %d, mode %d", p.M, p.mode);
+  RS_CHECK(conv_dgrad_split_serves(p.Cout, p.Cin, p.KH, p.KW, p.out_stride > 1 ? p.out_stride : 1), RS_ERR_UNSUPPORTED,
+           "conv (split input gradient): %d rows, K side %d, %dx%d kernel, stride %d", p.Cout, p.Cin, p.KH, p.KW, p.out_stride);
+  RS_CHECK(p.in_Cs % 8 == 0 && p.out_Cs % 4 == 0 && p.KH * p.KW * p.Cin <= p.Kpad && p.Kpad % 8 == 0, RS_ERR_ARG, "conv (split input gradient): channel pitches %d / %d, Kpad %d", p.in_Cs, p.out_Cs, p.Kpad);
+  p.stages = p.KH * p.KW * (p.Cin >> 6) <= 1 ? 1 : 2;      // conv_choose_variant's shallow-K rule on the tripled step count
+  p.persist = 0;
+  p.out_f32 = 1;
+  const int v = force_variant >= 0 ? force_variant : conv_dgrad_split_variant(p);
+  g_last_conv_variant = v;
+  switch (v) {
+    case 2: return launch_variant_dgrad_split<4, 1, 1, 4>(p, stream);      // 256 px x 16 rows
+    case 7: return launch_variant_dgrad_split<2, 2, 4, 2>(p, stream);      // 64 x 128
+    case 14: return launch_variant_dgrad_split<2, 4, 4, 4>(p, stream);     // 128 x 256
+    case 4: return launch_variant_dgrad_split<2, 4, 4, 8>(p, stream);      // 256 x 256
+    default:
+      rs_set_error("conv (split input gradient): variant %d (2, 7, 14 or 4)", v);
+      return RS_ERR_ARG;
+  }
+}
 
 // Tile variant picked by the most recent launch_conv() on this thread (-1 = fp32 validation kernel);
 // the engine tags its stages with it so that bench.py can attribute time and FLOPs per kernel symbol.
@@ -528,6 +610,10 @@ int launch_conv(const ConvParams& p_in, hipStream_t stream, int force_variant, i
     RS_CHECK(!p_in.in2, RS_ERR_UNSUPPORTED, "conv: the fp32 kernel has no second K source");
     g_last_conv_variant = -1;
     return launch_conv_f32(p_in, stream, use_glds == -2, force_variant);      // -2: the VALU cross-check kernel
+  }
+  if (p_in.split && p_in.dy_amax) {     // split operands with the fp32 training epilogue: the input gradient of the fp32 trainer
+    RS_CHECK(use_glds > 0, RS_ERR_UNSUPPORTED, "conv: the split input gradient needs LDS-DMA staging");
+    return launch_conv_dgrad_split(p_in, stream, force_variant);
   }
   ConvParams p = p_in;
   const int nk2 = p.in2 ? (p.Cin2 >> 6) : 0;

@@ -106,6 +106,16 @@ __device__ __forceinline__ void mfma_split3(f32x4& acc, const half8& wh, const h
   acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh, acc, 0, 0, 0);
 }
 
+// Exponent of a tensor-wide power-of-two scale from the abs-max pass's two device words (bits of the largest finite |v|, non-finite flag):
+// e = 14 - floor(log2 amax), so that the scaled maximum lies in [2^14, 2^15); 0 for an all-zero or a non-finite tensor.  The split weight
+// gradient (conv_wgrad.hip) and the split input gradient (epi_values_dgrad_split below) read it behind the pass, on the device.
+__device__ __forceinline__ int split_tensor_exp(unsigned amax_bits, unsigned nonfinite) {
+  if (nonfinite || amax_bits == 0) return 0;
+  const int be = (int)(amax_bits >> 23);
+  const int E = be ? be - 127 : (31 - __clz((int)amax_bits)) - 149;     // floor(log2(amax)), subnormal fp32 included
+  return 14 - E;
+}
+
 // ---- the epilogue of conv_igemm_kernel and conv_deep_tile: a lane holds channels crow .. crow + 4 MI - 1 of one pixel per 16-pixel block.
 // Saturation counting stays with the caller (a screen in conv_igemm, a per-lane counter in conv_deep: common.h) through epi_store_h16's functor.
 template <int MI, bool SPLIT>
@@ -198,6 +208,42 @@ __device__ __forceinline__ void epi_values(float (&v)[4 * MI], const ConvParams&
   if (p.relu) {
 #pragma unroll
     for (int e = 0; e < 4 * MI; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+  }
+}
+
+// Third flavour, the fp32 trainer's input gradient on split operands (ConvParams::dy_amax set; conv_igemm's TRAIN && SPLIT instantiation):
+// v = acc * wscale[row] * 2^-e_dy with e_dy from the device words behind the abs-max pass, then the fp32 addends in ref_f32.hip's order --
+// res, the 2x2 sum of `down`, res32 -- then the ReLU-backward mask (fp32 saved activation, > 0).  No bias: the product has none.
+template <int MI, int NJ>
+__device__ __forceinline__ void epi_values_dgrad_split(float (&v)[4 * MI], const ConvParams& p, const f32x4 (&acc)[MI][NJ], const int j, const EpiRows<MI, true>& rw,
+                                                       const int e_dy, const long long opix, const int cb, const int x, const int y, const int n) {
+#pragma unroll
+  for (int e = 0; e < 4 * MI; ++e) v[e] = ldexpf(acc[e >> 2][j][e & 3] * rw.wsc[e], -e_dy);      // both factors are powers of two
+  auto add_f32 = [&](const float* a) {
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+      const f32x4 h = *(const f32x4*)(a + i * 4);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[i * 4 + r] += h[r];
+    }
+  };
+  if (p.res) add_f32((const float*)p.res + opix * p.out_Cs + cb);
+  if (p.down) {
+#pragma unroll
+    for (int dd = 0; dd < 4; ++dd) {
+      const long long dpix = (long long)(n * p.down_Hp + 2 * y + (dd >> 1) + p.down_pad) * p.down_Wp + 2 * x + (dd & 1) + p.down_pad;
+      add_f32((const float*)p.down + dpix * p.down_Cs + cb);
+    }
+  }
+  if (p.res32) add_f32(p.res32 + opix * p.out_Cs + cb);
+  if (p.mask) {
+    const float* mp = (const float*)p.mask + opix * p.out_Cs + cb;
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+      const f32x4 h = *(const f32x4*)(mp + i * 4);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[i * 4 + r] = h[r] > 0.f ? v[i * 4 + r] : 0.f;
+    }
   }
 }
 

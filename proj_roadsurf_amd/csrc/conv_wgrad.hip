@@ -24,6 +24,8 @@
 //     adds the partials in a fixed order (bitwise reproducible; no float atomics), applies the per-output-channel
 //     FrozenBN scale (the trainable tensor is the UNFOLDED weight) and accumulates into the gradient.
 //   * rows of dY beyond M read a zero row (WgradParams::zeros), so the tail contributes nothing.
+#include <string.h>
+
 #include "conv_tile.h"
 
 namespace {
@@ -386,12 +388,7 @@ __host__ __device__ __forceinline__ void wgs_range(const WgradParams& p, int M, 
   *x_el = ((long long)n * p.in_Hp + y * p.stride + p.KH + p.in_off) * p.in_Wp * p.in_Cs;
 }
 __device__ __forceinline__ unsigned* wgs_words(const WgradParams& p) { return (unsigned*)p.split_scratch; }   // amax dY, flag dY, amax X, flag X
-__device__ __forceinline__ int wgs_exp(unsigned amax_bits, unsigned nonfinite) {
-  if (nonfinite || amax_bits == 0) return 0;
-  const int be = (int)(amax_bits >> 23);
-  const int E = be ? be - 127 : (31 - __clz((int)amax_bits)) - 149;     // floor(log2(amax)), subnormal fp32 included
-  return 14 - E;
-}
+__device__ __forceinline__ int wgs_exp(unsigned amax_bits, unsigned nonfinite) { return split_tensor_exp(amax_bits, nonfinite); }   // conv_tile.h
 
 __global__ __launch_bounds__(256) void wgrad_split_amax_kernel(const WgradParams p) {
   long long dy_el, x_el;
@@ -709,6 +706,86 @@ static int launch_conv_wgrad_split(const WgradParams& p, hipStream_t stream) {
   const long long n_el = (long long)p.Cout * p.Kpad;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)cdiv(n_el, 64)), dim3(256), 0, stream, p.partial, p.splits, n_el, p.Kpad,
                      p.scale, p.grad, p.accumulate);
+  RS_HIP(hipGetLastError());
+  return RS_OK;
+}
+
+// The dY of an input-gradient GEMM through passes 1 and 2 above (operand 0 only: gridDim.y = 1).  The GEMM's pixel (n, y, x) reads the
+// padded dY rows y + in_off .. y + in_off + KH - 1, so in wgs_range's terms the last row read is dy_pad = in_off + KH - 1.
+int launch_dgrad_split_planes(const ConvParams& p, void* scratch, long long cap, hipStream_t stream) {
+  RS_CHECK(p.in && scratch && p.M > 0 && p.Ho >= 1 && p.Wo >= 1 && p.in_Cs % 4 == 0 && p.Cin <= p.in_Cs, RS_ERR_ARG, "dgrad (split operands): bad dY");
+  WgradParams q;
+  memset(&q, 0, sizeof q);
+  q.dy = p.in; q.f32 = 1; q.split_ops = 1;
+  q.M = p.M; q.Ho = p.Ho; q.Wo = p.Wo; q.m_count = p.m_count; q.m_mul = p.m_mul;
+  q.dy_Hp = p.in_Hp; q.dy_Wp = p.in_Wp; q.dy_Cs = p.in_Cs; q.dy_pad = p.in_off + p.KH - 1; q.Cout = p.in_Cs;
+  q.stride = 1; q.KH = p.KH; q.KW = p.KW;
+  q.split_scratch = scratch; q.split_dy_cap = cap;
+  long long dy_el, x_el;
+  wgs_range(q, q.M, &dy_el, &x_el);
+  RS_CHECK(dy_el <= cap && dy_el < (1ll << 32), RS_ERR_ARG, "dgrad (split operands): dY of %lld elements exceeds the plane scratch (%lld)", dy_el, cap);
+  RS_HIP(hipMemsetAsync(scratch, 0, 16, stream));
+  int blocks = cdiv(dy_el, 4 * 256 * 4);
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(wgrad_split_amax_kernel, dim3(blocks > 512 ? 512 : blocks, 1), dim3(256), 0, stream, q);
+  RS_HIP(hipGetLastError());
+  hipLaunchKernelGGL(wgrad_split_planes_kernel, dim3(blocks, 1), dim3(256), 0, stream, q);
+  RS_HIP(hipGetLastError());
+  return RS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ row-scaled planes of a weight matrix
+// One workgroup per row.  The row abs-max is an integer maximum over the bits of |v| (order-free, so deterministic; no float atomics);
+// e = 13 - floor(log2 max) clipped to +-100 (0 for a zero or non-finite row), hi = fp16(v 2^e), lo = fp16(v 2^e - hi), inv = 2^-e.
+__device__ __forceinline__ void split_row(const SplitRowsDesc& d, int row) {
+  const float* src = d.w + (long long)row * d.k;
+  unsigned mx = 0;
+  for (int i = threadIdx.x; i < d.k; i += 256) {
+    const unsigned b = __float_as_uint(src[i]) & 0x7fffffffu;
+    mx = b > mx ? b : mx;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const unsigned o = (unsigned)__shfl_xor((int)mx, off);
+    mx = o > mx ? o : mx;
+  }
+  __shared__ unsigned part[4];
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mx;
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 4; ++k) mx = part[k] > mx ? part[k] : mx;
+  int e = 0;
+  if (mx != 0 && mx < 0x7f800000u) {
+    const int be = (int)(mx >> 23);
+    const int E = be ? be - 127 : (31 - __clz((int)mx)) - 149;
+    e = 13 - E;
+    e = e > 100 ? 100 : (e < -100 ? -100 : e);
+  }
+  half_t* hi = d.planes + (long long)row * d.k;
+  half_t* lo = hi + (long long)d.rows * d.k;
+  for (int i = threadIdx.x; i < d.k; i += 256) {
+    const HiLo hl = split_round(ldexpf(src[i], e));
+    hi[i] = hl.h;
+    lo[i] = hl.l;
+  }
+  if (threadIdx.x == 0) d.inv[row] = ldexpf(1.f, -e);
+}
+__global__ __launch_bounds__(256) void split_rows_kernel(const SplitRowsDesc d) { split_row(d, blockIdx.x); }
+__global__ __launch_bounds__(256) void split_rows_table_kernel(const SplitRowsDesc* tab, int n) {
+  int i = 0;
+  while (i + 1 < n && tab[i + 1].row_start <= blockIdx.x) ++i;      // block-uniform; a table has tens of entries
+  const SplitRowsDesc d = tab[i];
+  split_row(d, (int)(blockIdx.x - d.row_start));
+}
+int launch_split_rows(const SplitRowsDesc& d, hipStream_t stream) {
+  RS_CHECK(d.w && d.planes && d.inv && d.rows >= 1 && d.k >= 1, RS_ERR_ARG, "split_rows: bad argument");
+  hipLaunchKernelGGL(split_rows_kernel, dim3((unsigned)d.rows), dim3(256), 0, stream, d);
+  RS_HIP(hipGetLastError());
+  return RS_OK;
+}
+int launch_split_rows_table(const SplitRowsDesc* table_dev, int n, unsigned total_rows, hipStream_t stream) {
+  RS_CHECK(table_dev && n >= 1 && total_rows >= 1, RS_ERR_ARG, "split_rows: empty table");
+  hipLaunchKernelGGL(split_rows_table_kernel, dim3(total_rows), dim3(256), 0, stream, table_dev, n);
   RS_HIP(hipGetLastError());
   return RS_OK;
 }

@@ -288,6 +288,61 @@ int rs_op_conv2d_dgrad(const void* dy, const void* w_t, void* dx, const void* re
   return launch_conv(p, (hipStream_t)stream, variant, 1);
 }
 
+// The same input gradient from fp32 tensors (dy, w_t [cin][kpad] transposed and tap-flipped, dx, res, mask, down: all float) with the product
+// on the fp16 matrix cores: dY as hi + lo planes under one power-of-two scale per call, W^T as row-scaled planes, three products into one
+// fp32 accumulator (conv_igemm's TRAIN && SPLIT instantiation).  Scratch, abs-max, planes and row split live for the call.  count_dev
+// (optional, device): images computed = min(n, *count_dev); the others are not written.  Arguments are refused before a device is touched.
+int rs_op_conv2d_dgrad_split(const void* dy, const void* w_t, void* dx, const void* res, const float* res32, const void* mask,
+                             const void* down, int n, int hi, int wi, int cin, int ho, int wo, int cout, int kh, int kw, int stride,
+                             int pad, int kpad, int halo, int variant, const int32_t* count_dev, void* stream) {
+  RS_CHECK(dy && w_t && dx, RS_ERR_ARG, "rs_op_conv2d_dgrad_split: null operand");
+  RS_CHECK(n >= 1, RS_ERR_ARG, "rs_op_conv2d_dgrad_split: n %d", n);
+  RS_CHECK(cout >= 64 && cout % 64 == 0, RS_ERR_ARG, "rs_op_conv2d_dgrad_split: cout %d (the K side) must be a multiple of 64", cout);
+  RS_CHECK(stride == 1 || (stride > 1 && kh == 1 && kw == 1), RS_ERR_UNSUPPORTED, "rs_op_conv2d_dgrad_split: stride %d needs a 1x1 kernel", stride);
+  RS_CHECK(kh == kw && kh >= 1 && pad >= 0 && halo >= 0 && halo >= kh - 1 - pad, RS_ERR_ARG, "rs_op_conv2d_dgrad_split: halo %d below k - 1 - pad = %d", halo, kh - 1 - pad);
+  RS_CHECK(hi >= 1 && wi >= 1 && ho >= 1 && wo >= 1 && cin >= 16 && cin % 16 == 0 && kpad >= kh * kw * cout && kpad % 64 == 0, RS_ERR_ARG,
+           "rs_op_conv2d_dgrad_split: geometry (cin %d must be a multiple of 16, kpad %d at least kh * kw * cout and a multiple of 64)", cin, kpad);
+  RS_CHECK(conv_dgrad_split_serves(cin, cout, kh, kw, stride), RS_ERR_UNSUPPORTED, "rs_op_conv2d_dgrad_split: shape not served");
+  const int pad_t = kh - 1 - pad;
+  const int oh = stride == 1 ? ho + 2 * pad_t - kh + 1 : ho, ow = stride == 1 ? wo + 2 * pad_t - kw + 1 : wo;
+  RS_CHECK(stride == 1 ? (oh == hi && ow == wi) : ((ho - 1) * stride < hi && (wo - 1) * stride < wi), RS_ERR_ARG, "rs_op_conv2d_dgrad_split: geometry");
+  ConvParams p;
+  memset(&p, 0, sizeof p);
+  p.out = dx; p.res = (const half_t*)res; p.res32 = res32; p.mask = (const half_t*)mask; p.down = (const half_t*)down;
+  p.M = n * oh * ow; p.Ho = oh; p.Wo = ow;
+  p.in_Hp = ho + 2 * halo; p.in_Wp = wo + 2 * halo; p.in_Cs = cout; p.in_off = halo - pad_t;
+  p.stride = 1; p.KH = kh; p.KW = kw; p.Cin = cout; p.Kpad = kpad; p.Cout = cin;
+  p.out_Hp = hi + 2 * halo; p.out_Wp = wi + 2 * halo; p.out_Cs = cin; p.out_pad = halo;
+  p.out_stride = stride;
+  if (down) { p.down_Hp = 2 * hi + 2 * halo; p.down_Wp = 2 * wi + 2 * halo; p.down_Cs = cin; p.down_pad = halo; }
+  if (count_dev) { p.m_count = count_dev; p.m_mul = oh * ow; }
+  // one allocation: [dY header + planes | W^T planes | inverse row scales]
+  const long long cap = (long long)n * p.in_Hp * p.in_Wp * cout;
+  const size_t b_dy = (dgrad_split_scratch_bytes(cap) + 255) & ~(size_t)255, b_w = ((size_t)cin * kpad * 4 + 255) & ~(size_t)255;
+  hipStream_t s = (hipStream_t)stream;
+  OpScratch scratch(stream);
+  char* buf = nullptr;
+  { int rc = scratch.alloc((void**)&buf, b_dy + b_w + (size_t)cin * 4); if (rc) return rc; }
+  p.in = (const half_t*)dy;
+  { int rc = launch_dgrad_split_planes(p, buf, cap, s); if (rc) return rc; }
+  SplitRowsDesc d = {(const float*)w_t, (half_t*)(buf + b_dy), (float*)(buf + b_dy + b_w), cin, kpad, 0u};
+  { int rc = launch_split_rows(d, s); if (rc) return rc; }
+  p.split = 1; p.dy_amax = (const unsigned*)buf;
+  p.in = (const half_t*)(buf + WGS_HEAD_BYTES); p.in_lo = cap;
+  p.w = d.planes; p.w_lo = (long long)cin * kpad; p.wscale = d.inv;
+  return launch_conv(p, s, variant, 1);
+}
+// 1 when rs_op_conv2d_dgrad_split (and the trainer's split input-gradient mode) runs a layer of this shape on the fp16 matrix cores.  Host only.
+int rs_op_conv2d_dgrad_split_serves(int cin, int cout, int kh, int stride) {
+  return conv_dgrad_split_serves(cin, cout, kh, kh, stride) ? 1 : 0;
+}
+// w [rows][k] fp32 (device) -> planes [2 * rows][k] fp16 (hi rows, then lo rows) and inv_scale [rows], by weights.split_planes' rule
+int rs_op_split_rows(const float* w, int rows, int k, void* planes, float* inv_scale, void* stream) {
+  RS_CHECK(w && planes && inv_scale && rows >= 1 && k >= 1, RS_ERR_ARG, "rs_op_split_rows: bad argument");
+  SplitRowsDesc d = {w, (half_t*)planes, inv_scale, rows, k, 0u};
+  return launch_split_rows(d, (hipStream_t)stream);
+}
+
 static int op_conv2d_wgrad(const void* dy, const void* x, float* grad, const float* scale, int n, int hi, int wi, int cin, int in_halo,
                            int kh, int kw, int stride, int pad, int cout, int kpad, int dy_halo, int splits, void* stream, int f32);   // f32 = 2: split operands
 int rs_op_conv2d_wgrad(const void* dy, const void* x, float* grad, const float* scale, int n, int hi, int wi, int cin, int in_halo,

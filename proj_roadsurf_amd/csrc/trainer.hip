@@ -32,6 +32,9 @@ struct TrainLayer {
   float* b_fwd = nullptr;        // engine's fp32 bias
   half_t* w_bwd = nullptr;       // [Cin][KpadT] transposed, tap-flipped fp16 copy for the input gradient (null = not needed)
   const float* scale = nullptr;  // FrozenBN scale [Cout] (null = none)
+  half_t* w_bwd_planes = nullptr; // split input-gradient mode: [2 * Cin][KpadT] hi / lo fp16 planes of the row-scaled w_bwd (allocated at switch-on)
+  float* w_bwd_inv = nullptr;     //   and the inverse row scales [Cin]
+  bool x_stage = false;           // an add_dgrad stage reads w_bwd (the mask deconvolution's direct call does not go through it)
   int bias_tile = 1;             // forward bias = master bias repeated this many times (the 2x2 deconv as 4 GEMMs)
 };
 
@@ -82,6 +85,16 @@ struct rs_trainer {
     p.split_ops = f32 && wgrad_mode == 1;
     p.split_scratch = wgs_scratch; p.split_dy_cap = wgs_dy_cap; p.split_x_cap = wgs_x_cap;
   }
+  // input gradients on split operands (rs_trainer_set_dgrad_mode; fp32 trainer only): hi + lo fp16 planes of the dY of the `*.x` stage
+  // that is running.  Those stages follow one another on the chain stream, so one scratch of the chain's own serves them all (the
+  // weight-gradient scratch above belongs to the side stream); the planes of every w_bwd are rewritten behind each fold.
+  int dgrad_mode = 0;
+  void* dgs_scratch = nullptr;
+  long long dgs_cap = 0;           // elements of the largest dY of any add_dgrad stage
+  SplitRowsDesc* dgs_table = nullptr;
+  int dgs_n = 0;
+  unsigned dgs_rows = 0;
+  int split_w_bwd();               // w_bwd of every layer -> planes + inverse row scales, one launch on the chain stream
   float* zero_bias = nullptr;    // zero fp32 bias for input-gradient convolutions
   std::vector<void*> allocs;
   std::vector<TensorInfo> tensors;
@@ -308,7 +321,25 @@ int rs_trainer::add_dgrad(const std::string& stage, const std::string& layer, co
   st.name = stage;
   st.flops_per_image = 2.0 * mpi * (double)L.KH * L.KW * L.Cout * L.Cin;
   const int glds = f32 ? -1 : 1;
-  st.fn = [p, mpi, glds](int n, hipStream_t s) mutable { p.M = n * mpi; return launch_conv(p, s, -1, glds); };
+  const long long dy_el = (long long)dy.N * dy.Hp() * dy.Wp() * dy.C;
+  if (dy_el > dgs_cap) dgs_cap = dy_el;
+  // the mode is read when the stage launches: split operands where the kernel serves the shape, else (and in mode 0) the fp32 kernel
+  const bool served = f32 && conv_dgrad_split_serves(dx.C, dy.C, L.KH, L.KW, stride);
+  rs_trainer* self = this;
+  const int li = it->second;
+  layers[li].x_stage = true;
+  st.fn = [p, mpi, glds, served, self, li](int n, hipStream_t s) mutable {
+    p.M = n * mpi;
+    if (!(served && self->dgrad_mode == 1)) return launch_conv(p, s, -1, glds);
+    const TrainLayer& TL = self->layers[li];
+    ConvParams q = p;                          // q.in: the fp32 dY
+    int rc = launch_dgrad_split_planes(q, self->dgs_scratch, self->dgs_cap, s);
+    if (rc) return rc;
+    q.split = 1; q.dy_amax = (const unsigned*)self->dgs_scratch;
+    q.in = (const half_t*)((const char*)self->dgs_scratch + WGS_HEAD_BYTES); q.in_lo = self->dgs_cap;
+    q.w = TL.w_bwd_planes; q.w_lo = (long long)TL.Cin * TL.KpadT; q.wscale = TL.w_bwd_inv;
+    return launch_conv(q, s, -1, 1);
+  };
   (cur ? cur : &bwd)->push_back(st);
   return RS_OK;
 }
@@ -508,7 +539,14 @@ int rs_trainer::fold_all() {
     RS_HIP(hipStreamSynchronize(stream));      // tab is a local
     fold_n = (int)tab.size(); fold_blocks = blocks;
   }
-  return launch_fold_table(fold_table, fold_n, fold_blocks, stream);
+  int rc = launch_fold_table(fold_table, fold_n, fold_blocks, stream);
+  if (!rc && dgrad_mode == 1) rc = split_w_bwd();
+  return rc;
+}
+
+int rs_trainer::split_w_bwd() {
+  RS_CHECK(dgs_table && dgs_n > 0, RS_ERR_ARG, "trainer: the split input-gradient mode has no weight planes");
+  return launch_split_rows_table(dgs_table, dgs_n, dgs_rows, stream);
 }
 
 // FPN and res5..res3 backward from d:p2..d:p6 (FREEZE_AT 2: nothing flows into res2 / the stem)
@@ -1525,6 +1563,39 @@ int rs_trainer_set_wgrad_mode(rs_trainer* t, int mode) {
   return RS_OK;
 }
 
+// Mirrors rs_trainer_set_wgrad_mode for the input gradients of the add_dgrad stages.  The first switch to mode 1 allocates the dY plane
+// scratch and the planes of every w_bwd; every switch to mode 1 splits the current w_bwd (a fold in mode 0 does not).
+int rs_trainer_set_dgrad_mode(rs_trainer* t, int mode) {
+  RS_CHECK(t, RS_ERR_ARG, "rs_trainer_set_dgrad_mode: null trainer");
+  RS_CHECK(mode == 0 || mode == 1, RS_ERR_ARG, "rs_trainer_set_dgrad_mode: mode %d (0 = fp32 matrix cores, 1 = split operands)", mode);
+  RS_CHECK(t->f32 || mode == 0, RS_ERR_UNSUPPORTED, "rs_trainer_set_dgrad_mode: split operands serve the fp32 trainer; this one is fp16 and already on the fp16 matrix cores");
+  if (mode == 1 && !t->dgs_scratch) {
+    std::vector<SplitRowsDesc> tab;
+    unsigned rows = 0;
+    for (TrainLayer& L : t->layers) {
+      if (!L.x_stage || L.w_bwd_planes) continue;
+      int rc = t->alloc((void**)&L.w_bwd_planes, (size_t)L.Cin * L.KpadT * 4);
+      if (!rc) rc = t->alloc((void**)&L.w_bwd_inv, (size_t)L.Cin * 4);
+      if (rc) return rc;
+    }
+    for (const TrainLayer& L : t->layers) {
+      if (!L.x_stage) continue;
+      tab.push_back(SplitRowsDesc{(const float*)L.w_bwd, L.w_bwd_planes, L.w_bwd_inv, L.Cin, L.KpadT, rows});
+      rows += (unsigned)L.Cin;
+    }
+    RS_CHECK(!tab.empty(), RS_ERR_ARG, "rs_trainer_set_dgrad_mode: no layer has input-gradient weights");
+    if (!t->dgs_table) { int rc = t->alloc((void**)&t->dgs_table, tab.size() * sizeof(SplitRowsDesc)); if (rc) return rc; }
+    RS_HIP(hipMemcpyAsync(t->dgs_table, tab.data(), tab.size() * sizeof(SplitRowsDesc), hipMemcpyHostToDevice, t->stream));
+    RS_HIP(hipStreamSynchronize(t->stream));      // tab is a local
+    t->dgs_n = (int)tab.size(); t->dgs_rows = rows;
+    int rc = t->alloc(&t->dgs_scratch, dgrad_split_scratch_bytes(t->dgs_cap));
+    if (rc) return rc;
+  }
+  if (mode == 1) { int rc = t->split_w_bwd(); if (rc) return rc; }
+  t->dgrad_mode = mode;
+  return RS_OK;
+}
+
 int rs_trainer_sync(rs_trainer* t) {
   RS_CHECK(t, RS_ERR_ARG, "null trainer");
   { int rc = t->join_side(); if (rc) return rc; }
@@ -1600,6 +1671,10 @@ int rs_trainer_copy_state(rs_trainer* dst, rs_trainer* src) {
   RS_HIP(hipMemcpyAsync(dst->master, src->master, dst->n_params * 4, hipMemcpyDeviceToDevice, dst->stream));
   RS_HIP(hipMemcpyAsync(dst->mom, src->mom, dst->n_params * 4, hipMemcpyDeviceToDevice, dst->stream));
   dst->step_count = src->step_count;
+  if (dst->dgrad_mode != src->dgrad_mode) {       // the input-gradient mode travels with the state (its switch-on splits after the fold below)
+    if (src->dgrad_mode == 0) dst->dgrad_mode = 0;
+    else { int rc = dst->fold_all(); if (!rc) rc = rs_trainer_set_dgrad_mode(dst, src->dgrad_mode); return rc; }
+  }
   return dst->fold_all();
 }
 
