@@ -400,6 +400,27 @@ int rs_op_roi_align_bwd(float* const dfeats[4], const int32_t heights[4], const 
                         int nlevels, const float* rois, int n_rois, int rois_per_image, int P, int out_halo, const void* dout,
                         void* stream);
 
+/* The two RoIAlign operators with every form the engine and the trainer launch (same launchers, same kernels).
+ *  precision     0: fp16 maps and output; 1: fp32 maps and output (per-sample kernel); 2: split operands -- feats[l] / out are the hi
+ *                fp16 planes, the lo planes lie feat_lo[l] / out_lo ELEMENTS behind them.
+ *  n_entries_cap entries launched (the grid); out / dout: [n_entries_cap][P+2*out_halo]^2[256].  Entry e pools slot slot_list[e] (e itself
+ *                when slot_list is null) of rois [n_images * slots_per_image][4]; image = slot / slots_per_image.
+ *  n_entries     optional device int: entries past min(*n_entries, n_entries_cap) are neither read nor written.
+ *  per_image_count  optional device [n_images]: a slot whose rank in its image is >= the count is empty -- the forward writes zeros
+ *                (both planes), the backward nothing.
+ *  order         optional device permutation of [0, n_entries_cap): the order the windowed forward visits the entries in; every entry
+ *                still lands in its own slot of `out`.
+ *  grad_f32      backward: dout is float (1) or fp16 (0).
+ * RS_ROI_WINDOW / RS_ROI_BWD_ATOMIC choose between the kernel forms as in the engine. */
+int rs_op_roi_align_form(const void* const feats[4], const int64_t feat_lo[4], const int32_t heights[4], const int32_t widths[4],
+                         const float scales[4], int nlevels, const float* rois, int n_entries_cap, int slots_per_image, int P, int out_halo,
+                         int precision, void* out, int64_t out_lo, const int32_t* slot_list, const int32_t* n_entries,
+                         const int32_t* per_image_count, const int32_t* order, int32_t* levels_out, void* stream);
+int rs_op_roi_align_bwd_form(float* const dfeats[4], const int32_t heights[4], const int32_t widths[4], const float scales[4], int nlevels,
+                             const float* rois, int n_entries_cap, int slots_per_image, int n_images, int P, int out_halo, int grad_f32,
+                             const void* dout, const int32_t* slot_list, const int32_t* n_entries, const int32_t* per_image_count,
+                             void* stream);
+
 /* Training path, losses: each writes the gradient of the total loss w.r.t. its inputs (fp16, times loss_scale) and adds the
  * loss values to loss_out (fp32, for logging).  Label assignment / sampling happen before (oracle/train_oracle.py restates
  * them; their kernels are the next step).

@@ -331,8 +331,8 @@ def roi_align_diff(feat: Tensor, roi: Tensor, out_size: int, spatial_scale: floa
     bh, bw = rh / f32(out_size), rw / f32(out_size)
     gh, gw = max(int(math.ceil(rh / f32(out_size))), 0), max(int(math.ceil(rw / f32(out_size))), 0)
     count = max(gh * gw, 1)
-    Wy = torch.from_numpy(_axis_weights(sh, bh, gh, out_size, H))
-    Wx = torch.from_numpy(_axis_weights(sw, bw, gw, out_size, W))
+    Wy = torch.from_numpy(_axis_weights(sh, bh, gh, out_size, H)).to(feat.dtype)      # fp32 weights; float64 maps take them exactly
+    Wx = torch.from_numpy(_axis_weights(sw, bw, gw, out_size, W)).to(feat.dtype)
     return torch.einsum("ph,chw,qw->cpq", Wy, feat, Wx) / count
 
 

@@ -525,6 +525,52 @@ int rs_op_roi_align_bwd(float* const dfeats[4], const int32_t heights[4], const 
   return rc;
 }
 
+// The two operators above with everything the engine and the trainer put into RoiAlignParams: precision, compact entries, per-image
+// counts, the visiting order, the gradient's storage type.  Same launchers; tests/test_gpu_roi_bounds.py reaches every kernel form here.
+int rs_op_roi_align_form(const void* const feats[4], const int64_t feat_lo[4], const int32_t heights[4], const int32_t widths[4],
+                         const float scales[4], int nlevels, const float* rois, int n_entries_cap, int slots_per_image, int P, int out_halo,
+                         int precision, void* out, int64_t out_lo, const int32_t* slot_list, const int32_t* n_entries,
+                         const int32_t* per_image_count, const int32_t* order, int32_t* levels_out, void* stream) {
+  RS_CHECK(feats && rois && out && nlevels >= 1 && nlevels <= 4 && n_entries_cap > 0 && slots_per_image > 0, RS_ERR_ARG, "bad argument");
+  RS_CHECK(precision >= 0 && precision <= 2 && (precision != 2 || feat_lo), RS_ERR_ARG, "precision %d (0 fp16, 1 fp32, 2 split with feat_lo)", precision);
+  RoiAlignParams p;
+  memset(&p, 0, sizeof p);
+  for (int l = 0; l < nlevels; ++l) {
+    p.feat[l] = (const half_t*)feats[l]; p.H[l] = heights[l]; p.W[l] = widths[l]; p.scale[l] = scales[l];
+    if (precision == 2) p.feat_lo[l] = feat_lo[l];
+  }
+  p.nlevels = nlevels; p.C = 256; p.rois = rois; p.S = n_entries_cap; p.slots_per_image = slots_per_image;
+  p.slot_list = slot_list; p.n_entries = n_entries; p.per_image_count = per_image_count; p.order = order;
+  p.out = (half_t*)out; p.P = P; p.out_pad = out_halo; p.out_level = levels_out;
+  p.f32 = precision; p.out_lo = precision == 2 ? out_lo : 0;
+  rs_debug_reload();                                         // RS_ROI_WINDOW
+  return launch_roi_align(p, (hipStream_t)stream);
+}
+
+int rs_op_roi_align_bwd_form(float* const dfeats[4], const int32_t heights[4], const int32_t widths[4], const float scales[4], int nlevels,
+                             const float* rois, int n_entries_cap, int slots_per_image, int n_images, int P, int out_halo, int grad_f32,
+                             const void* dout, const int32_t* slot_list, const int32_t* n_entries, const int32_t* per_image_count,
+                             void* stream) {
+  RS_CHECK(dfeats && rois && dout && nlevels >= 1 && nlevels <= 4 && n_entries_cap > 0 && slots_per_image > 0 && n_images > 0, RS_ERR_ARG,
+           "bad argument");
+  RoiAlignParams p;
+  memset(&p, 0, sizeof p);
+  for (int l = 0; l < nlevels; ++l) { p.dfeat[l] = dfeats[l]; p.H[l] = heights[l]; p.W[l] = widths[l]; p.scale[l] = scales[l]; }
+  p.nlevels = nlevels; p.C = 256; p.rois = rois; p.S = n_entries_cap; p.slots_per_image = slots_per_image;
+  p.slot_list = slot_list; p.n_entries = n_entries; p.per_image_count = per_image_count;
+  p.out = (half_t*)dout; p.P = P; p.out_pad = out_halo; p.f32 = grad_f32 ? 1 : 0;
+  rs_debug_reload();                                         // RS_ROI_BWD_ATOMIC
+  p.n_images = n_images;
+  OpScratch scratch(stream);
+  void* ws = nullptr;
+  { int rc = scratch.alloc(&ws, (size_t)n_entries_cap * RS_ROI_BWD_TABLE_BYTES + 64); if (rc) return rc; }
+  p.bwd_overflow = (int*)ws;
+  p.bwd_tables = (char*)ws + 64;
+  const int rc = launch_roi_align_bwd(p, (hipStream_t)stream);
+  RS_HIP(scratch.sync());
+  return rc;
+}
+
 int rs_op_rpn_loss(const float* head, void* dhead, const int32_t* labels, const float* anchors, const float* matched_gt,
                    float* loss_out, int n, int hw, int num_anchors, int cs, int level_off, int total_anchors, float normalizer,
                    float loss_scale, void* stream) {

@@ -201,6 +201,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.rs_spec_batched_nms.argtypes = [C.POINTER(RsSpec)]
     lib.rs_op_roi_align.argtypes = [C.POINTER(vp), i32p, i32p, f32p, i32, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.rs_op_roi_align_bwd.argtypes = [C.POINTER(vp), i32p, i32p, f32p, i32, vp, i32, i32, i32, i32, vp, vp]
+    if hasattr(lib, "rs_op_roi_align_form"):          # RS_ENGINE_LIB may name an older build
+        lib.rs_op_roi_align_form.argtypes = [C.POINTER(vp), C.POINTER(i64), i32p, i32p, f32p, i32, vp, i32, i32, i32, i32, i32, vp, i64] + [vp] * 6
+        lib.rs_op_roi_align_bwd_form.argtypes = [C.POINTER(vp), i32p, i32p, f32p, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     f32 = C.c_float
     lib.rs_op_match.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, i32, i32, vp]
     lib.rs_op_subsample.argtypes = [vp, vp, vp, i32, i32, i32, f32, i32, i32, C.c_uint32, vp]

@@ -165,6 +165,248 @@ int rg_scatter64(const double* g, int Cn, int H, int W, const float* box, float 
   }
   return bad_y || bad_x;
 }
+
+// roi_align_kernel with its two forms: the samples of an axis prepared once into RS_ROI_MAXS-entry tables (`fast`) or recomputed per
+// use.  Returns 1 / 0 for the form taken, -1 if the fast form would index past its tables.
+int rg_pool_samples_lds(const float* feat, int Cn, int H, int W, const float* box, float sc, int P, float* out) {
+  const RoiBins rb = roi_bins(box[0], box[1], box[2], box[3], sc, P);
+  const bool fast = (P * rb.gh <= RS_ROI_MAXS) && (P * rb.gw <= RS_ROI_MAXS);
+  static RoiSample s_y[RS_ROI_MAXS], s_x[RS_ROI_MAXS];
+  if (fast) {
+    if (P * rb.gh > RS_ROI_MAXS || P * rb.gw > RS_ROI_MAXS) return -1;
+    for (int t = 0; t < P * rb.gh; ++t) s_y[t] = roi_sample(roi_coord(rb.start_h, rb.bin_h, t / rb.gh, t % rb.gh, rb.gh), H);
+    for (int t = 0; t < P * rb.gw; ++t) s_x[t] = roi_sample(roi_coord(rb.start_w, rb.bin_w, t / rb.gw, t % rb.gw, rb.gw), W);
+  }
+  for (int c = 0; c < Cn; ++c)
+    for (int ph = 0; ph < P; ++ph)
+      for (int pw = 0; pw < P; ++pw) {
+        const float* f = feat + c * H * W;
+        float acc = 0.f;
+        for (int iy = 0; iy < rb.gh; ++iy) {
+          const RoiSample sy = fast ? s_y[ph * rb.gh + iy] : roi_sample(roi_coord(rb.start_h, rb.bin_h, ph, iy, rb.gh), H);
+          for (int ix = 0; ix < rb.gw; ++ix) {
+            const RoiSample sx = fast ? s_x[pw * rb.gw + ix] : roi_sample(roi_coord(rb.start_w, rb.bin_w, pw, ix, rb.gw), W);
+            const float w1 = sy.h * sx.h, w2 = sy.h * sx.l, w3 = sy.l * sx.h, w4 = sy.l * sx.l;      // zero weights for a skipped sample
+            acc += w1 * f[sy.lo * W + sx.lo] + w2 * f[sy.lo * W + sx.hi] + w3 * f[sy.hi * W + sx.lo] + w4 * f[sy.hi * W + sx.hi];
+          }
+        }
+        out[(c * P + ph) * P + pw] = rg_div(acc, rb.count);
+      }
+  return fast ? 1 : 0;
+}
+
+// ---- what tests/roi_cases.py searches with: one axis of many candidate boxes at once.  Per candidate (a1, a2) on an axis of `size` cells:
+// flags (bit 0 a sample below -1, 1 above size, 2 in (-1, 0], 3 in (size-1, size], 4 exactly -1, 5 exactly size, 6 one float below -1,
+// 7 one float above size, 8 a sample strictly inside (0, size-1)), g, the longest table, the overflowing bins, org, end, bad, and the
+// widest window of a bin (first to last cell its samples read, not capped by the table).
+void rg_axis_scan(const float* a1, const float* a2, int n, float sc, int P, int size, int* out) {
+  const float m1 = -1.0f, sz = (float)size;
+  const float below = nextafterf(m1, -INFINITY), above = nextafterf(sz, INFINITY);
+  for (int k = 0; k < n; ++k) {
+    const RoiBins rb = roi_bins(a1[k], a1[k], a2[k], a2[k], sc, P);      // both axes alike; the row axis is read
+    int flags = 0, widest = 0;                       // widest: cells from the first to the last one a bin's samples read, uncapped
+    for (int b = 0; b < P; ++b) {
+      int first = -1, last = -1;
+      for (int i = 0; i < rb.gh; ++i) {
+        const float c = roi_coord(rb.start_h, rb.bin_h, b, i, rb.gh);
+        const RoiSample s = roi_sample(c, size);
+        if (s.ok) { if (first < 0) first = s.lo; last = s.hi; }
+        if (c < m1) flags |= 1;
+        if (c > sz) flags |= 2;
+        if (c > m1 && c <= 0.f) flags |= 4;
+        if (c > sz - 1.f && c < sz) flags |= 8;
+        if (c == m1) flags |= 16;
+        if (c == sz) flags |= 32;
+        if (c == below) flags |= 64;
+        if (c == above) flags |= 128;
+        if (c > 0.f && c < sz - 1.f) flags |= 256;
+      }
+      if (first >= 0 && last - first + 1 > widest) widest = last - first + 1;
+    }
+    Tables t = {};
+    for (int b = 0; b < P; ++b) roi_axis_table(rb.start_h, rb.bin_h, b, rb.gh, size, t.w[0][b], t.base[0][b], t.len[0][b]);
+    int longest = 0, over = 0, org, end;
+    for (int b = 0; b < P; ++b) { if (t.len[0][b] < 0) ++over; else if (t.len[0][b] > longest) longest = t.len[0][b]; }
+    const bool bad = roi_extent(t.base[0], t.len[0], P, org, end);
+    int* o = out + 8 * k;
+    o[0] = flags; o[1] = rb.gh; o[2] = longest; o[3] = over; o[4] = org; o[5] = end; o[6] = bad; o[7] = widest;
+  }
+}
+
+// ---- a whole backward call in fp32, in the kernels' own order (tests/test_roi_bounds_cpu.py).  Maps d[l]: [n_images][Cn][H][W] without
+// halo, accumulated into; gradient g: [S][Cn][P][P].
+struct BwdCall {
+  int nlevels, n_images, P, S, slots_per_image, Cn;
+  int H[4], W[4];
+  float scale[4];
+  const float* rois;
+  const int *slot_list, *n_entries, *per_image_count;
+  const float* g;
+  float* d[4];
+};
+struct BwdTab { int img, lvl, y0, y1, x0, x1; float count; RoiBins rb; Tables t; };
+// roi_bwd_prep_kernel: the table of every entry; returns how many are left to the atomic kernel
+static int bwd_prep(const BwdCall& c, BwdTab* tabs) {
+  const Entry p = {c.S, c.n_entries, c.slot_list, c.slots_per_image, c.per_image_count};
+  int n_over = 0;
+  for (int e = 0; e < c.S; ++e) {
+    BwdTab& T = tabs[e];
+    int slot, n;
+    if (roi_entry(p, e, slot, n) != 2) { T.img = -1; T.lvl = -1; continue; }
+    const float* r = c.rois + 4 * slot;
+    const int lvl = roi_level(r[0], r[1], r[2], r[3], c.nlevels);
+    T.rb = roi_bins(r[0], r[1], r[2], r[3], c.scale[lvl], c.P);
+    tables(T.rb, c.P, c.H[lvl], c.W[lvl], T.t);
+    int org[2], end[2];
+    bool bad = roi_extent(T.t.base[0], T.t.len[0], c.P, org[0], end[0]);
+    if (roi_extent(T.t.base[1], T.t.len[1], c.P, org[1], end[1])) bad = true;
+    T.img = n;
+    T.lvl = bad ? 4 + lvl : ((end[0] > org[0] && end[1] > org[1]) ? lvl : -1);
+    T.y0 = org[0]; T.y1 = end[0]; T.x0 = org[1]; T.x1 = end[1];
+    T.count = T.rb.count;
+    if (bad) ++n_over;
+  }
+  return n_over;
+}
+// roi_bwd_gather_kernel: per 8 x 8 region the entries that reach it in entry order, a register sum per cell, one add into the map
+int rg_bwd_gather32(const BwdCall* cp) {
+  const BwdCall& c = *cp;
+  BwdTab* tabs = new BwdTab[c.S];
+  const int n_over = bwd_prep(c, tabs);
+  int* list = new int[c.S];
+  const int P = c.P;
+  for (int n = 0; n < c.n_images; ++n)
+    for (int lvl = 0; lvl < 4; ++lvl) {
+      const int H = c.H[lvl], W = c.W[lvl];
+      for (int cy0 = 0; cy0 < H; cy0 += 8)
+        for (int cx0 = 0; cx0 < W; cx0 += 8) {
+          int e0, e1;
+          if (c.slot_list) { e0 = 0; e1 = c.S; if (c.n_entries) { const int k = *c.n_entries; e1 = k < e1 ? k : e1; } }
+          else { e0 = n * c.slots_per_image; e1 = e0 + c.slots_per_image; if (e1 > c.S) e1 = c.S; }
+          int cnt = 0;
+          for (int e = e0; e < e1; ++e) {
+            const BwdTab& T = tabs[e];
+            if (T.lvl == lvl && T.img == n && T.y0 < cy0 + 8 && T.y1 > cy0 && T.x0 < cx0 + 8 && T.x1 > cx0) list[cnt++] = e;
+          }
+          if (cnt == 0) continue;
+          for (int ch = 0; ch < c.Cn; ++ch)
+            for (int yy = 0; yy < 8; ++yy) {
+              const int y = cy0 + yy;
+              float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+              for (int k = 0; k < cnt; ++k) {
+                const BwdTab& T = tabs[list[k]];
+                const float inv = rg_div(1.0f, T.count);
+                int qlo = P, qhi = 0;
+                for (int pw = 0; pw < P; ++pw)
+                  if (T.t.len[1][pw] > 0 && T.t.base[1][pw] < cx0 + 8 && T.t.base[1][pw] + T.t.len[1][pw] > cx0) { qlo = qlo < pw ? qlo : pw; qhi = qhi > pw + 1 ? qhi : pw + 1; }
+                const float* gout = c.g + ((long long)list[k] * c.Cn + ch) * P * P;
+                for (int ph = 0; ph < P; ++ph) {
+                  const int jy = y - T.t.base[0][ph];
+                  if (jy < 0 || jy >= T.t.len[0][ph]) continue;
+                  const float wy = T.t.w[0][ph][jy];
+                  if (wy == 0.f) continue;
+                  const float wyc = wy * inv;
+                  for (int pw = qlo; pw < qhi; ++pw)
+                    for (int x = 0; x < 8; ++x) {
+                      const int jx = cx0 + x - T.t.base[1][pw];
+                      if (jx < 0 || jx >= T.t.len[1][pw]) continue;
+                      const float wgt = wyc * T.t.w[1][pw][jx];
+                      acc[x] += wgt * gout[ph * P + pw];
+                    }
+                }
+              }
+              if (y >= H) continue;
+              float* drow = c.d[lvl] + (((long long)n * c.Cn + ch) * H + y) * W;
+              for (int x = 0; x < 8; ++x) {
+                if (cx0 + x >= W) break;
+                drow[cx0 + x] += acc[x];
+              }
+            }
+        }
+    }
+  delete[] list;
+  delete[] tabs;
+  return n_over;
+}
+// roi_align_bwd_kernel: entry by entry (the atomics of different entries land in any order: `reverse` walks entries, cells and bins
+// backwards), the gather form per cell of the window or, where roi_extent says bad, the per-bin scatter; only_bad: the entries the
+// owner-computes form leaves to it.
+void rg_bwd_atomic32(const BwdCall* cp, int reverse, int only_bad) {
+  const BwdCall& c = *cp;
+  BwdTab* tabs = new BwdTab[c.S];
+  const int n_over = bwd_prep(c, tabs);
+  const int P = c.P;
+  for (int ee = 0; ee < c.S && !(only_bad && n_over == 0); ++ee) {
+    const int e = reverse ? c.S - 1 - ee : ee;
+    const BwdTab& T = tabs[e];
+    if (T.img < 0) continue;
+    const bool bad = T.lvl >= 4;
+    if (only_bad && !bad) continue;
+    const int lvl = T.lvl < 0 ? 0 : (bad ? T.lvl - 4 : T.lvl);
+    if (T.lvl < 0) continue;                         // an empty window: nothing to add
+    const int H = c.H[lvl], W = c.W[lvl];
+    for (int ch = 0; ch < c.Cn; ++ch) {
+      const float* gc = c.g + ((long long)e * c.Cn + ch) * P * P;
+      float* d = c.d[lvl] + ((long long)T.img * c.Cn + ch) * H * W;
+      if (!bad) {
+        const int ncell = (T.y1 - T.y0) * (T.x1 - T.x0), ew = T.x1 - T.x0;
+        for (int cc = 0; cc < ncell; ++cc) {
+          const int cell = reverse ? ncell - 1 - cc : cc;
+          const int y = T.y0 + cell / ew, x = T.x0 + cell % ew;
+          float acc = 0.f;
+          bool any = false;
+          for (int ph = 0; ph < P; ++ph) {
+            const int jy = y - T.t.base[0][ph];
+            if (jy < 0 || jy >= T.t.len[0][ph]) continue;
+            const float wy = T.t.w[0][ph][jy];
+            if (wy == 0.f) continue;
+            for (int pw = 0; pw < P; ++pw) {
+              const int jx = x - T.t.base[1][pw];
+              if (jx < 0 || jx >= T.t.len[1][pw]) continue;
+              const float wgt = wy * T.t.w[1][pw][jx];
+              if (wgt == 0.f) continue;
+              acc += wgt * rg_div(gc[ph * P + pw], T.count);
+              any = true;
+            }
+          }
+          if (any) d[y * W + x] += acc;
+        }
+        continue;
+      }
+      for (int bb = 0; bb < P * P; ++bb) {
+        const int b = reverse ? P * P - 1 - bb : bb;
+        const int ph = b / P, pw = b - ph * P;
+        const float gs = rg_div(gc[b], T.count);
+        const int ny = T.t.len[0][ph], nx = T.t.len[1][pw];
+        if (ny >= 0 && nx >= 0) {
+          for (int j = 0; j < ny; ++j) {
+            const float wj = T.t.w[0][ph][j];
+            if (wj == 0.f) continue;
+            for (int i = 0; i < nx; ++i) {
+              const float wgt = wj * T.t.w[1][pw][i];
+              if (wgt == 0.f) continue;
+              d[(T.t.base[0][ph] + j) * W + T.t.base[1][pw] + i] += wgt * gs;
+            }
+          }
+          continue;
+        }
+        for (int iy = 0; iy < T.rb.gh; ++iy) {
+          const RoiSample sy = roi_sample(roi_coord(T.rb.start_h, T.rb.bin_h, ph, iy, T.rb.gh), H);
+          if (!sy.ok) continue;
+          for (int ix = 0; ix < T.rb.gw; ++ix) {
+            const RoiSample sx = roi_sample(roi_coord(T.rb.start_w, T.rb.bin_w, pw, ix, T.rb.gw), W);
+            if (!sx.ok) continue;
+            d[sy.lo * W + sx.lo] += sy.h * sx.h * gs;
+            d[sy.lo * W + sx.hi] += sy.h * sx.l * gs;
+            d[sy.hi * W + sx.lo] += sy.l * sx.h * gs;
+            d[sy.hi * W + sx.hi] += sy.l * sx.l * gs;
+          }
+        }
+      }
+    }
+  }
+  delete[] tabs;
+}
 }
 """
 
