@@ -320,6 +320,27 @@ int rs_op_conv2d_dgrad_split(const void* dy, const void* w_t, void* dx, const vo
                        const void* down, int n, int hi, int wi, int cin, int ho, int wo, int cout, int kh, int kw, int stride,
                        int pad, int kpad, int halo, int variant, const int32_t* count_dev, void* stream);
 int rs_op_conv2d_dgrad_split_serves(int cin, int cout, int kh, int stride);
+/* The forward convolution / linear layer of the reference-precision trainer with the product on the fp16 matrix cores (DESIGN.md 8,
+ * "forward on split operands").  Every tensor is fp32: x [n][hi+2*in_halo][wi+2*in_halo][cin], w [cout][kpad] in the engine's layout
+ * (k = (kh, kw, cin), cin fastest; the FrozenBN scale already folded), bias [cout], y [n][ho+2*out_halo][wo+2*out_halo][cout] with
+ * ho = (hi + 2 pad - kh) / stride + 1, res (optional) in y's geometry, up (optional) [n][(ho+1)/2+2*out_halo][(wo+1)/2+2*out_halo][cout],
+ * added at (y >> 1, x >> 1).  For the life of the call it allocates scratch, takes the abs-max of x on the device (integer maximum, no
+ * read-back), writes hi = fp16(x 2^e), lo = fp16(x 2^e - hi) with e = 14 - floor(log2 amax) (0 for a zero or non-finite x), splits w
+ * by rows (rs_op_split_rows) and runs three v_mfma_f32_16x16x32_f16 products (hi.lo, hi.hi, lo.hi) into one fp32 accumulator:
+ *   y = relu?( acc * inv_scale[row] * 2^-e + bias + res + up ),  stored fp32; two calls give the same bits.  Per element
+ *   |gemm - exact| <= 2^-20 sum|x||w| + 2^-36 T max|x| rowmax|w| + (the accumulation-order error of the fp32 kernel), T = kh kw cin.
+ * stride is the input stride of the taps, any kernel size (the 1x1 stride-2 layers of res3..res5 are the model's case).
+ * variant: -1 = the library's rule, or a tile by number: 7 (64 px x 128 rows), 14 (128 x 256), 4 (256 x 256; cout a multiple of 128
+ * resp. 256) or 2 (256 x 16).  count_dev: optional device int, images computed = min(n, *count_dev), the others are not written.
+ * Refused before a device is touched, with the entry's name in rs_last_error (RS_ERR_ARG): null x / w / bias / y, n < 1, cin (the K
+ * side) no multiple of 64, cout (the rows) no multiple of 16, an input halo below the pad, a kernel that is not square, a kpad below
+ * kh kw cin or no multiple of 64.
+ * rs_op_conv2d_fwd_split_serves: 1 when a layer of this shape runs split (in the operator and in the trainer's mode), else 0: cout a
+ * multiple of 16, cin of 64.  The stem (cin 3 / 4) and the mask deconvolution are not served.  Host only. */
+int rs_op_conv2d_fwd_split(const void* x, const void* w, const float* bias, void* y, const void* res, const void* up, int n, int hi,
+                           int wi, int cin, int in_halo, int kh, int kw, int stride, int pad, int cout, int kpad, int out_halo,
+                           int relu, int variant, const int32_t* count_dev, void* stream);
+int rs_op_conv2d_fwd_split_serves(int cin, int cout, int k, int stride);
 /* Rows of a device fp32 matrix w [rows][k] as fp16 planes [2 * rows][k] (the hi rows, then the lo rows) of w 2^e(row), with
  * inv_scale[row] = 2^-e(row): e = 13 - floor(log2 max|row|) clipped to [-100, 100], so the row maximum lies in [2^13, 2^14) (0 for a
  * zero or non-finite row) -- bit for bit weights.split_planes.  The row maximum is an integer maximum over the bits of |w|. */
@@ -559,6 +580,18 @@ int rs_trainer_set_wgrad_mode(rs_trainer* t, int mode);
  * rs_trainer_copy_state carries the mode to the destination.  RS_ERR_UNSUPPORTED on an fp16 trainer, RS_ERR_ARG on a null handle or
  * another mode. */
 int rs_trainer_set_dgrad_mode(rs_trainer* t, int mode);
+/* Forward product Y = X * W of the reference-precision (fp32) trainer: 0 = fp32 matrix cores (default), 1 = split operands on the fp16
+ * matrix cores (rs_op_conv2d_fwd_split) for every forward convolution / linear stage whose shape rs_op_conv2d_fwd_split_serves accepts:
+ * res2..res5, the FPN, the RPN conv and heads, the box head and predictor, the mask convolutions and predictor.  The stem and the mask
+ * deconvolution stay fp32.  Storage stays fp32 (the activations the ReLU masks and the weight gradients read), and the losses, both
+ * backward products, the SGD step, the stage names and rs_trainer_stage_info's list do not change; the abs-max and plane passes run
+ * inside the forward stages.  Read when a stage launches.  The mode lives in the trainer's forward engine, so validation inference
+ * through rs_trainer_engine follows it.  The first switch to mode 1 allocates, on the current device, the X plane scratch of the chain
+ * stream (sized to the largest forward input) and the planes + inverse row scales of every served layer's weight; every switch to
+ * mode 1 splits every current weight, and while the mode is on every fold (rs_trainer_apply_sgd, rs_trainer_copy_state) splits the
+ * trainable layers again (the frozen res2 only at switch-on).  rs_trainer_copy_state carries the mode to the destination.
+ * RS_ERR_UNSUPPORTED on an fp16 trainer, RS_ERR_ARG on a null handle or another mode. */
+int rs_trainer_set_fwd_mode(rs_trainer* t, int mode);
 /* SGD with momentum on the flat buffers + refold.  The gradient is first checked for inf / nan (fp16 loss scale too large for
  * this batch): then the step is skipped on the device -- weights and momentum unchanged -- and the tensor "grad_overflow" [1]
  * reads 1; lower the scale with rs_trainer_set_loss_scale before the next forward (GradScaler semantics, no host sync here). */

@@ -207,6 +207,10 @@ struct ConvParams {
   // (bits of the largest finite |dY|, non-finite flag) from which the epilogue derives e_dy.  res / down / res32 / mask / out are fp32
   // tensors, as in ref_f32.hip.  nullptr = not this flavour.
   const unsigned* dy_amax;
+  // ---- the fp32 trainer's forward product on split operands (set together with `split`, never with dy_amax): `in` / in_lo
+  // are the hi / lo fp16 planes of X * 2^e_x, `w` / w_lo / wscale the row-scaled planes of the folded fp32 weight, x_amax the two device
+  // words the abs-max pass left for X.  bias / res / up / out are fp32, as in ref_f32.hip.  nullptr = not this flavour.
+  const unsigned* x_amax;
 };
 
 int launch_conv(const ConvParams& p, hipStream_t stream, int force_variant /* -1 auto */, int use_glds);
@@ -215,6 +219,11 @@ int launch_conv(const ConvParams& p, hipStream_t stream, int force_variant /* -1
 bool conv_dgrad_split_serves(int rows /* dx channels */, int k_channels /* dY channels */, int kh, int kw, int stride);
 int conv_dgrad_split_variant(const ConvParams& p);
 int launch_conv_dgrad_split(const ConvParams& p, hipStream_t stream, int force_variant);
+// Forward product of the fp32 trainer on split operands (conv_igemm.hip, ConvParams::x_amax): launch_conv routes here.  The same four
+// tiles; conv_fwd_split_variant is its rule.  `stride` is the input stride of the taps (the 1x1 stride-2 layers included).
+bool conv_fwd_split_serves(int rows /* Cout */, int k_channels /* Cin */, int kh, int kw, int stride);
+int conv_fwd_split_variant(const ConvParams& p);
+int launch_conv_fwd_split(const ConvParams& p, hipStream_t stream, int force_variant);
 int conv_choose_variant(ConvParams& p, int force_variant, int use_glds);   // the dispatch rule (also sets p.stages / p.persist)
 extern thread_local int g_last_conv_variant;
 
@@ -327,6 +336,9 @@ static inline size_t wgrad_split_scratch_bytes(long long dy_cap, long long x_cap
 // ([2][cap] halfs; words 0 / 1 of the header are the abs-max bits and the non-finite flag).  Stream-ordered, no read-back.
 static inline size_t dgrad_split_scratch_bytes(long long cap) { return WGS_HEAD_BYTES + (size_t)cap * 4; }
 int launch_dgrad_split_planes(const ConvParams& p, void* scratch, long long cap, hipStream_t stream);
+// ... and on the X of a forward GEMM `p` (p.in: the fp32 X, p.stride its input stride), into a scratch of the same layout
+int launch_fwd_split_planes(const ConvParams& p, void* scratch, long long cap, hipStream_t stream);
+long long fwd_split_x_elems(const ConvParams& p);      // elements of X the passes cover for p.M rows: what `cap` must reach
 // Rows of fp32 matrices as hi / lo fp16 planes with one power-of-two scale per row (weights.split_planes' rule: row maximum in
 // [2^13, 2^14), exponent clipped to +-100): planes [2 * rows][k] (hi rows, then lo rows), inv [rows] the inverse scales.
 struct SplitRowsDesc {

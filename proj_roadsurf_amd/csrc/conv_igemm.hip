@@ -43,7 +43,10 @@ struct Tile {
 // descale in the epilogue, outputs written as hi / lo planes.  Compiled out of the fp16 instantiations.
 // TRAIN && SPLIT: the fp32 trainer's input gradient on split operands (ConvParams::dy_amax, launch_conv_dgrad_split below): the split loop on the planes
 // of dY and of the row-scaled W^T, then conv_tile.h's epi_values_dgrad_split -- tensor and row scales undone, fp32 addends and mask, fp32 store.
-template <int WPX, int WCH, int MI, int NJ, bool SMALLC, bool GLDS, bool PERSIST, bool TRAIN = false, bool SPLIT = false>
+// TRAIN && SPLIT with FWD: that trainer's forward product (ConvParams::x_amax, launch_conv_fwd_split): the same loop on the planes of X and of
+// the row-scaled folded weight, input stride included, then epi_values_fwd_split -- scales undone, fp32 bias / res / up, ReLU, fp32 store.  A flag
+// of the template and not a branch: as a branch it cost the input gradient's 64 x 128 tile 18 VGPRs and a wave per SIMD.
+template <int WPX, int WCH, int MI, int NJ, bool SMALLC, bool GLDS, bool PERSIST, bool TRAIN = false, bool SPLIT = false, bool FWD = false>
 __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvParams p) {
   using T = Tile<WPX, WCH, MI, NJ>;
   constexpr int NW = T::NW, BM = T::BM, BN = T::BN;
@@ -302,10 +305,13 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
     if (p.mode != 0) { g = crow / p.Cout; cb = crow % p.Cout; }
     // TRAIN && SPLIT, the fp32 trainer's input gradient on split operands: no bias (its words are read from wscale and unused), the tensor
     // scale of dY from the device words behind the abs-max pass, fp32 addends, fp32 store
+    // FWD, the forward flavour: the fp32 bias, the tensor scale of X (x_amax)
     constexpr bool DGRAD_SPLIT = TRAIN && SPLIT;
-    const EpiRows<MI, SPLIT> rw = epi_rows<MI, SPLIT>(DGRAD_SPLIT ? p.wscale : p.bias, p.wscale, crow);
+    constexpr bool FWD_SPLIT = DGRAD_SPLIT && FWD;
+    const EpiRows<MI, SPLIT> rw = epi_rows<MI, SPLIT>(DGRAD_SPLIT && !FWD_SPLIT ? p.wscale : p.bias, p.wscale, crow);
     int e_dy = 0;
-    if constexpr (DGRAD_SPLIT) e_dy = split_tensor_exp(p.dy_amax[0], p.dy_amax[1]);
+    if constexpr (FWD_SPLIT) e_dy = split_tensor_exp(p.x_amax[0], p.x_amax[1]);
+    else if constexpr (DGRAD_SPLIT) e_dy = split_tensor_exp(p.dy_amax[0], p.dy_amax[1]);
     float dotp[NJ];
     long long dot_idx[NJ];
 #pragma unroll
@@ -322,7 +328,8 @@ __global__ __launch_bounds__(WPX* WCH * 64) void conv_igemm_kernel(const ConvPar
       const long long opix = (long long)(n * p.out_Hp + oy + p.out_pad) * p.out_Wp + ox + p.out_pad;
       float v[4 * MI];
       if constexpr (DGRAD_SPLIT) {
-        epi_values_dgrad_split<MI, NJ>(v, p, acc, j, rw, e_dy, opix, cb, x, y, n);
+        if constexpr (FWD_SPLIT) epi_values_fwd_split<MI, NJ>(v, p, acc, j, rw, e_dy, opix, cb, x, y, n);
+        else epi_values_dgrad_split<MI, NJ>(v, p, acc, j, rw, e_dy, opix, cb, x, y, n);
         epi_store_f32<MI>((float*)p.out + opix * p.out_Cs + cb, v);
         continue;
       } else {
@@ -447,19 +454,19 @@ int launch_variant(const ConvParams& p, hipStream_t stream, int use_glds) {
 
 // The TRAIN && SPLIT instantiation (input gradient of the fp32 trainer on split operands): LDS-DMA staging, one workgroup per tile.  Its
 // fragment arrays must stay in registers like those of the other split loops, so a build that spilled refuses to launch.
-template <int WPX, int WCH, int MI, int NJ>
-int launch_variant_dgrad_split(const ConvParams& p, hipStream_t stream) {
+template <int WPX, int WCH, int MI, int NJ, bool FWD = false>
+int launch_variant_dgrad_split(const ConvParams& p, hipStream_t stream, const char* what = "split input gradient") {
   using T = Tile<WPX, WCH, MI, NJ>;
   const long long nblk = (long long)cdiv(p.Cout, T::BN) * cdiv(p.M, T::BM);
-  RS_CHECK(nblk > 0 && nblk < (1ll << 31), RS_ERR_ARG, "conv (split input gradient): bad grid %lld", nblk);
-  RS_CHECK(p.Cout % T::BN == 0, RS_ERR_ARG, "conv (split input gradient): %d rows are no multiple of the tile's %d", p.Cout, T::BN);
-  const void* k = (const void*)conv_igemm_kernel<WPX, WCH, MI, NJ, false, true, false, true, true>;
+  RS_CHECK(nblk > 0 && nblk < (1ll << 31), RS_ERR_ARG, "conv (%s): bad grid %lld", what, nblk);
+  RS_CHECK(p.Cout % T::BN == 0, RS_ERR_ARG, "conv (%s): %d rows are no multiple of the tile's %d", what, p.Cout, T::BN);
+  const void* k = (const void*)conv_igemm_kernel<WPX, WCH, MI, NJ, false, true, false, true, true, FWD>;
   static bool ready = false;
   if (!ready) {
     hipFuncAttributes a;
     RS_HIP(hipFuncGetAttributes(&a, k));
-    RS_CHECK(a.localSizeBytes == 0, RS_ERR_UNSUPPORTED, "conv (split input gradient): the %d x %d tile was built with %zu bytes of scratch per thread (rebuild with the documented toolchain)",
-             T::BM, T::BN, (size_t)a.localSizeBytes);
+    RS_CHECK(a.localSizeBytes == 0, RS_ERR_UNSUPPORTED, "conv (%s): the %d x %d tile was built with %zu bytes of scratch per thread (rebuild with the documented toolchain)",
+             what, T::BM, T::BN, (size_t)a.localSizeBytes);
     RS_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS));
     ready = true;
   }
@@ -512,6 +519,51 @@ int launch_conv_dgrad_split(const ConvParams& p_in, hipStream_t stream, int forc
     case 4: return launch_variant_dgrad_split<2, 4, 4, 8>(p, stream);      // 256 x 256
     default:
       rs_set_error("conv (split input gradient): variant %d (2, 7, 14 or 4)", v);
+      return RS_ERR_ARG;
+  }
+}
+
+// ---- the fp32 trainer's forward product on split operands (ConvParams::x_amax)
+bool conv_fwd_split_serves(int rows, int k_channels, int kh, int kw, int stride) {
+  return rows >= 16 && rows % 16 == 0 && k_channels >= 64 && k_channels % 64 == 0 && kh == kw && kh >= 1 && stride >= 1;
+}
+
+// Tile of a split forward product: the input-gradient rule's reasoning on the forward's own rows (Cout) and pixels, kept apart from it so
+// that either can move without the other.  Rows that are no multiple of 128 (res2's 64, the 16-row heads) take the 16-row tile.
+int conv_fwd_split_variant(const ConvParams& p) {
+  const int rows = p.Cout;
+  if (rows % 128 != 0) return 2;
+  const int nk = p.KH * p.KW * (p.Cin >> 6);
+  const int ncu = rs_device_cu_count();
+  if (rows % 256 == 0) {
+    if (nk >= 8 && (long long)cdiv(p.M, 256) * (rows / 256) >= ncu) return 4;
+    if ((long long)cdiv(p.M, 128) * (rows / 256) >= ncu) return 14;
+  }
+  return 7;
+}
+
+int launch_conv_fwd_split(const ConvParams& p_in, hipStream_t stream, int force_variant) {
+  ConvParams p = p_in;
+  static const char* const what = "split forward";
+  RS_CHECK(p.in && p.w && p.wscale && p.bias && p.out && p.x_amax && !p.dy_amax && p.split, RS_ERR_ARG, "conv (split forward): null operand");
+  RS_CHECK(p.M > 0 && p.mode == 0 && !p.in2 && !p.down && !p.res32 && !p.mask && p.out_stride <= 1 && p.stride >= 1, RS_ERR_ARG, "conv (split forward): M %d, mode %d, stride %d", p.M, p.mode, p.stride);
+  RS_CHECK(conv_fwd_split_serves(p.Cout, p.Cin, p.KH, p.KW, p.stride), RS_ERR_UNSUPPORTED,
+           "conv (split forward): %d rows, K side %d, %dx%d kernel, stride %d", p.Cout, p.Cin, p.KH, p.KW, p.stride);
+  RS_CHECK(p.in_Cs % 8 == 0 && p.out_Cs % 4 == 0 && p.KH * p.KW * p.Cin <= p.Kpad && p.Kpad % 8 == 0 && (!p.up || p.up_Cs % 4 == 0), RS_ERR_ARG,
+           "conv (split forward): channel pitches %d / %d, Kpad %d", p.in_Cs, p.out_Cs, p.Kpad);
+  p.stages = p.KH * p.KW * (p.Cin >> 6) <= 1 ? 1 : 2;      // as the input gradient: conv_choose_variant's shallow-K rule on the tripled step count
+  p.persist = 0;
+  p.out_f32 = 1;
+  p.out_stride = 0;
+  const int v = force_variant >= 0 ? force_variant : conv_fwd_split_variant(p);
+  g_last_conv_variant = v;
+  switch (v) {
+    case 2: return launch_variant_dgrad_split<4, 1, 1, 4, true>(p, stream, what);      // 256 px x 16 rows
+    case 7: return launch_variant_dgrad_split<2, 2, 4, 2, true>(p, stream, what);      // 64 x 128
+    case 14: return launch_variant_dgrad_split<2, 4, 4, 4, true>(p, stream, what);     // 128 x 256
+    case 4: return launch_variant_dgrad_split<2, 4, 4, 8, true>(p, stream, what);      // 256 x 256
+    default:
+      rs_set_error("conv (split forward): variant %d (2, 7, 14 or 4)", v);
       return RS_ERR_ARG;
   }
 }
@@ -614,6 +666,10 @@ int launch_conv(const ConvParams& p_in, hipStream_t stream, int force_variant, i
   if (p_in.split && p_in.dy_amax) {     // split operands with the fp32 training epilogue: the input gradient of the fp32 trainer
     RS_CHECK(use_glds > 0, RS_ERR_UNSUPPORTED, "conv: the split input gradient needs LDS-DMA staging");
     return launch_conv_dgrad_split(p_in, stream, force_variant);
+  }
+  if (p_in.split && p_in.x_amax) {      // TRAIN && SPLIT with the forward epilogue: the forward product of the fp32 trainer
+    RS_CHECK(use_glds > 0, RS_ERR_UNSUPPORTED, "conv: the split forward needs LDS-DMA staging");
+    return launch_conv_fwd_split(p_in, stream, force_variant);
   }
   ConvParams p = p_in;
   const int nk2 = p.in2 ? (p.Cin2 >> 6) : 0;

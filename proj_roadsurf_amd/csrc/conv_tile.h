@@ -247,6 +247,33 @@ __device__ __forceinline__ void epi_values_dgrad_split(float (&v)[4 * MI], const
   }
 }
 
+// Fourth flavour, the fp32 trainer's forward product on split operands (ConvParams::x_amax set; conv_igemm's TRAIN && SPLIT instantiation with FWD):
+// v = acc * wscale[row] * 2^-e_x with e_x from the device words behind the abs-max pass of X, then in ref_f32.hip's order the fp32 bias,
+// the fp32 residual, the fp32 FPN top-down addend at (y >> 1, x >> 1), and ReLU.  rw.bias holds the bias here.
+template <int MI, int NJ>
+__device__ __forceinline__ void epi_values_fwd_split(float (&v)[4 * MI], const ConvParams& p, const f32x4 (&acc)[MI][NJ], const int j, const EpiRows<MI, true>& rw,
+                                                     const int e_x, const long long opix, const int cb, const int x, const int y, const int n) {
+#pragma unroll
+  for (int e = 0; e < 4 * MI; ++e) v[e] = ldexpf(acc[e >> 2][j][e & 3] * rw.wsc[e], -e_x) + rw.bias[e];      // both factors are powers of two
+  auto add_f32 = [&](const float* a) {
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+      const f32x4 h = *(const f32x4*)(a + i * 4);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[i * 4 + r] += h[r];
+    }
+  };
+  if (p.res) add_f32((const float*)p.res + opix * p.out_Cs + cb);
+  if (p.up) {
+    const long long upix = (long long)(n * p.up_Hp + (y >> 1) + p.up_pad) * p.up_Wp + (x >> 1) + p.up_pad;
+    add_f32((const float*)p.up + upix * p.up_Cs + cb);
+  }
+  if (p.relu) {
+#pragma unroll
+    for (int e = 0; e < 4 * MI; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+  }
+}
+
 template <int MI>
 __device__ __forceinline__ void epi_store_f32(float* op, const float (&v)[4 * MI]) {
 #pragma unroll

@@ -734,6 +734,44 @@ int launch_dgrad_split_planes(const ConvParams& p, void* scratch, long long cap,
   return RS_OK;
 }
 
+// The X of a forward GEMM through the same two passes.  Its pixel (n, y, x) reads the padded rows y * stride + in_off .. + KH - 1.  At
+// stride 1 that is the input gradient's case.  A strided row count must end on the last output row of an image (checked), where
+// y + dy_pad = (Ho - 1) * stride + in_off + KH - 1 with the dy_pad below: the last padded row the GEMM reads, as above.
+static WgradParams fwd_split_x_params(const ConvParams& p) {
+  WgradParams q;
+  memset(&q, 0, sizeof q);
+  q.dy = p.in; q.f32 = 1; q.split_ops = 1;
+  q.M = p.M; q.Ho = p.Ho; q.Wo = p.Wo; q.m_count = p.m_count; q.m_mul = p.m_mul;
+  q.dy_Hp = p.in_Hp; q.dy_Wp = p.in_Wp; q.dy_Cs = p.in_Cs; q.dy_pad = p.in_off + p.KH - 1 + (p.Ho - 1) * (p.stride - 1); q.Cout = p.in_Cs;
+  q.stride = 1; q.KH = p.KH; q.KW = p.KW;
+  return q;
+}
+// elements of X (from its first) that the two passes cover for the p.M rows of `p`: what a plane scratch must hold
+long long fwd_split_x_elems(const ConvParams& p) {
+  const WgradParams q = fwd_split_x_params(p);
+  long long x_el, unused;
+  wgs_range(q, q.M, &x_el, &unused);
+  return x_el;
+}
+int launch_fwd_split_planes(const ConvParams& p, void* scratch, long long cap, hipStream_t stream) {
+  RS_CHECK(p.in && scratch && p.M > 0 && p.Ho >= 1 && p.Wo >= 1 && p.stride >= 1 && p.in_Cs % 4 == 0 && p.Cin <= p.in_Cs, RS_ERR_ARG, "forward (split operands): bad X");
+  RS_CHECK(p.stride == 1 || (p.M % (p.Ho * p.Wo) == 0 && (!p.m_count || p.m_mul == p.Ho * p.Wo)), RS_ERR_ARG,
+           "forward (split operands): %d strided rows are no whole images of %d x %d", p.M, p.Ho, p.Wo);
+  RS_CHECK((p.Ho - 1) * p.stride + p.in_off + p.KH <= p.in_Hp && p.in_off >= 0, RS_ERR_ARG, "forward (split operands): the taps leave the padded X");
+  WgradParams q = fwd_split_x_params(p);
+  q.split_scratch = scratch; q.split_dy_cap = cap;
+  const long long x_el = fwd_split_x_elems(p);
+  RS_CHECK(x_el <= cap && x_el < (1ll << 32), RS_ERR_ARG, "forward (split operands): X of %lld elements exceeds the plane scratch (%lld)", x_el, cap);
+  RS_HIP(hipMemsetAsync(scratch, 0, 16, stream));
+  int blocks = cdiv(x_el, 4 * 256 * 4);
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(wgrad_split_amax_kernel, dim3(blocks > 512 ? 512 : blocks, 1), dim3(256), 0, stream, q);
+  RS_HIP(hipGetLastError());
+  hipLaunchKernelGGL(wgrad_split_planes_kernel, dim3(blocks, 1), dim3(256), 0, stream, q);
+  RS_HIP(hipGetLastError());
+  return RS_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ row-scaled planes of a weight matrix
 // One workgroup per row.  The row abs-max is an integer maximum over the bits of |v| (order-free, so deterministic; no float atomics);
 // e = 13 - floor(log2 max) clipped to +-100 (0 for a zero or non-finite row), hi = fp16(v 2^e), lo = fp16(v 2^e - hi), inv = 2^-e.

@@ -197,12 +197,91 @@ int rs_engine::add_conv(const std::string& name, const std::string& wname, const
     d.defer->p = p; d.defer->m_per_image = m_per_image; d.defer->flops = flops; d.defer->bytes = bytes;
     return RS_OK;
   }
-  const int glds = use_glds;
   Stage& st = add_stage(name, flops, bytes, &p.sat);   // before the lambda copies p
-  st.fn = [p, m_per_image, glds](int n, hipStream_t s) mutable {
+  st.fn = conv_stage_fn(p, m_per_image, -1, use_glds);
+  return RS_OK;
+}
+
+// The launch of a conv / linear stage.  Everywhere but in the forward engine of an fp32 trainer this is launch_conv(p, s, variant, glds)
+// and nothing else.  There, a stage whose shape the split forward serves also reads fwd_mode when it runs (engine_internal.h).
+std::function<int(int, hipStream_t)> rs_engine::conv_stage_fn(const ConvParams& p_in, int m_per_image, int variant, int glds) {
+  ConvParams p = p_in;
+  int li = -1;
+  if (fwd_split_capable && p.mode == 0 && !p.in2 && !p.koff && p.in_Cs == p.Cin && p.Kpad % 64 == 0 && p.in_off >= 0 &&
+      conv_fwd_split_serves(p.Cout, p.Cin, p.KH, p.KW, p.stride)) {
+    for (size_t i = 0; i < fws_layers.size(); ++i)
+      if (fws_layers[i].w == (const float*)p.w && fws_layers[i].rows == p.Cout && fws_layers[i].kpad == p.Kpad) li = (int)i;
+    if (li < 0) {
+      FwdSplitLayer L;
+      L.w = (const float*)p.w; L.rows = p.Cout; L.kpad = p.Kpad;
+      li = (int)fws_layers.size();
+      fws_layers.push_back(L);
+    }
+    ConvParams full = p;
+    full.M = max_batch * m_per_image;
+    full.m_count = nullptr;
+    const long long el = fwd_split_x_elems(full);
+    if (el > fws_cap) fws_cap = el;
+  }
+  if (li < 0) return [p, m_per_image, variant, glds](int n, hipStream_t s) mutable { p.M = n * m_per_image; return launch_conv(p, s, variant, glds); };
+  rs_engine* self = this;
+  return [p, m_per_image, variant, glds, li, self](int n, hipStream_t s) mutable {
     p.M = n * m_per_image;
-    return launch_conv(p, s, -1, glds);
+    if (self->fwd_mode != 1) return launch_conv(p, s, variant, glds);
+    const FwdSplitLayer& L = self->fws_layers[li];
+    ConvParams q = p;                          // q.in: the fp32 X
+    int rc = launch_fwd_split_planes(q, self->fws_scratch, self->fws_cap, s);
+    if (rc) return rc;
+    q.split = 1; q.x_amax = (const unsigned*)self->fws_scratch;
+    q.in = (const half_t*)((const char*)self->fws_scratch + WGS_HEAD_BYTES); q.in_lo = self->fws_cap;
+    q.w = L.planes; q.w_lo = (long long)L.rows * L.kpad; q.wscale = L.inv;
+    return launch_conv(q, s, -1, 1);           // the split rule picks the tile (a forced fp32 variant does not carry over)
   };
+}
+
+int rs_engine::fwd_split_weights(bool folded_only) {
+  RS_CHECK(fws_table && fws_n_all > 0, RS_ERR_ARG, "engine: the split forward mode has no weight planes");
+  if (folded_only) return fws_n_fold > 0 ? launch_split_rows_table(fws_table + fws_n_all, fws_n_fold, fws_rows_fold, stream) : RS_OK;
+  return launch_split_rows_table(fws_table, fws_n_all, fws_rows_all, stream);
+}
+
+int rs_engine::fwd_split_enable(const std::set<const void*>& folded) {
+  RS_CHECK(fwd_split_capable && !fws_layers.empty(), RS_ERR_UNSUPPORTED, "engine: only the forward engine of an fp32 trainer carries the split forward mode");
+  std::vector<SplitRowsDesc> tab;
+  for (FwdSplitLayer& L : fws_layers) {
+    if (L.planes) continue;
+    int rc = alloc((void**)&L.planes, (size_t)L.rows * L.kpad * 4);
+    if (!rc) rc = alloc((void**)&L.inv, (size_t)L.rows * 4);
+    if (rc) return rc;
+  }
+  unsigned rows = 0;
+  for (const FwdSplitLayer& L : fws_layers) {
+    tab.push_back(SplitRowsDesc{L.w, L.planes, L.inv, L.rows, L.kpad, rows});
+    rows += (unsigned)L.rows;
+  }
+  const int n_all = (int)tab.size();
+  unsigned rows_fold = 0;
+  for (const FwdSplitLayer& L : fws_layers) {
+    if (!folded.count((const void*)L.w)) continue;
+    tab.push_back(SplitRowsDesc{L.w, L.planes, L.inv, L.rows, L.kpad, rows_fold});
+    rows_fold += (unsigned)L.rows;
+  }
+  if (!fws_table) { int rc = alloc((void**)&fws_table, 2 * fws_layers.size() * sizeof(SplitRowsDesc)); if (rc) return rc; }
+  RS_HIP(hipMemcpyAsync(fws_table, tab.data(), tab.size() * sizeof(SplitRowsDesc), hipMemcpyHostToDevice, stream));
+  RS_HIP(hipStreamSynchronize(stream));      // tab is a local
+  fws_n_all = n_all; fws_n_fold = (int)tab.size() - n_all; fws_rows_all = rows; fws_rows_fold = rows_fold;
+  return alloc(&fws_scratch, dgrad_split_scratch_bytes(fws_cap));
+}
+
+// 0 = fp32 matrix cores, 1 = split operands.  Every switch to 1 splits every layer's current weight; a captured forward is dropped.
+int rs_engine::set_fwd_mode(int mode, const std::set<const void*>& folded) {
+  if (mode == 1 && !fws_scratch) { int rc = fwd_split_enable(folded); if (rc) return rc; }
+  if (mode == 1) { int rc = fwd_split_weights(false); if (rc) return rc; }
+  if (mode != fwd_mode) {
+    for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
+    graphs.clear();
+  }
+  fwd_mode = mode;
   return RS_OK;
 }
 
@@ -664,9 +743,8 @@ int rs_engine::build_rpn(Graph& g) {
       p.KH = p.KW = 1; p.Cin = 256; p.Kpad = (int)w->dims[1]; p.Cout = head_cs;
       p.out_Hp = t.H; p.out_Wp = t.W; p.out_Cs = head_cs; p.out_pad = 0; p.out_f32 = 1;
       const int mpi = t.H * t.W;
-      const int glds = use_glds;
-      add_stage("rpn.heads" + std::to_string(l + 2), 2.0 * mpi * 256 * 5 * A, (double)mpi * (256 * 2 + head_cs * 4)).fn =
-          [p, mpi, glds](int n, hipStream_t s) mutable { p.M = n * mpi; return launch_conv(p, s, 2, glds); };
+      Stage& st = add_stage("rpn.heads" + std::to_string(l + 2), 2.0 * mpi * 256 * 5 * A, (double)mpi * (256 * 2 + head_cs * 4));
+      st.fn = conv_stage_fn(p, mpi, 2, use_glds);
     }
     rp.head[l] = ho;
     rp.H[l] = P[l].H; rp.W[l] = P[l].W; rp.stride[l] = 4 << l;
@@ -767,11 +845,10 @@ int rs_engine::build_box_head(Graph& g) {
     if (out32) { p.out = out32; p.Cout = rows32; p.out_Cs = rows32; p.out_f32 = 1; }
     else { p.out = out.p; p.Cout = out.C; p.out_Cs = out.C; }
     RS_CHECK(wrows(w) >= p.Cout && p.Kpad >= in.C, RS_ERR_BLOB, "%s: weight shape", wn.c_str());
-    const int glds = use_glds;
     const int variant = out32 ? 2 : -1;
     Stage& st = add_stage(name, 2.0 * PC * (double)in.C * p.Cout, (double)PC * (in.C * 2 * planes() + p.Cout * (out32 ? 4 : 2 * planes())),
                           out32 ? nullptr : &p.sat);
-    st.fn = [p, glds, variant](int n, hipStream_t s) mutable { p.M = n * PC; return launch_conv(p, s, variant, glds); };
+    st.fn = conv_stage_fn(p, PC, variant, use_glds);
     return RS_OK;
   };
   if ((rc = add_fc("box.fc1", "roi_heads.box_head.fc1", fin, f1, true, nullptr, 0))) return rc;
@@ -1263,6 +1340,7 @@ int engine_create(const rs_spec* spec, const void* weights, size_t nbytes, int d
   // (the multi-map launches of the FPN output convolutions and of the RPN 3x3 stay: every map still gets its own output tensor; only the RPN heads
   //  leave the 3x3's epilogue, because the trainer differentiates through the 256-channel rpn_conv maps)
   e->frozen_fusions_only = for_trainer;
+  e->fwd_split_capable = for_trainer && e->f32;      // the opt-in split forward of the fp32 trainer (rs_trainer_set_fwd_mode)
   e->use_graph = rs_debug().use_graph;   // measured: replay == eager (11.54 ms/step either way), so off by default
   if (stream) { e->stream = (hipStream_t)stream; e->own_stream = false; }
   else {

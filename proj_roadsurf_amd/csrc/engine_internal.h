@@ -214,6 +214,29 @@ struct rs_engine {
     DeferredConv* defer = nullptr;   // filled instead of a stage: the caller merges it into a multi-map launch (add_merged_convs)
   };
   int add_conv(const std::string& name, const std::string& wname, const Act& in, const Act& out, const ConvDesc& d);
+  // ---- forward product on split operands (rs_trainer_set_fwd_mode): only the forward engine of an fp32 trainer carries it
+  // (fwd_split_capable); every other engine launches exactly as before.  A conv / linear stage's launch comes from conv_stage_fn, which
+  // reads fwd_mode when the stage runs: mode 1 on a shape conv_fwd_split_serves accepts = plane passes on X into fws_scratch, then the split
+  // kernel on the layer's weight planes; else launch_conv(p, s, variant, glds).  The stages follow one another on one stream, so one
+  // scratch serves them all.
+  struct FwdSplitLayer {
+    const float* w = nullptr;        // the folded fp32 forward weight [rows][kpad] (the blob's device copy; a trainer's fold rewrites it)
+    int rows = 0, kpad = 0;
+    half_t* planes = nullptr;        // [2 * rows][kpad], allocated at switch-on
+    float* inv = nullptr;            // inverse row scales [rows]
+  };
+  bool fwd_split_capable = false;
+  int fwd_mode = 0;
+  std::vector<FwdSplitLayer> fws_layers;   // one per distinct weight matrix (the RPN's shared conv is one layer under five stages)
+  void* fws_scratch = nullptr;
+  long long fws_cap = 0;                   // elements of the largest X of any served stage at max_batch
+  SplitRowsDesc* fws_table = nullptr;      // device: [all layers | the layers a fold rewrites]
+  int fws_n_all = 0, fws_n_fold = 0;
+  unsigned fws_rows_all = 0, fws_rows_fold = 0;
+  std::function<int(int, hipStream_t)> conv_stage_fn(const ConvParams& p, int m_per_image, int variant, int glds);
+  int fwd_split_enable(const std::set<const void*>& folded);   // first switch-on: scratch, planes, tables (`folded`: weights a fold rewrites)
+  int fwd_split_weights(bool folded_only);                     // one table launch on `stream`
+  int set_fwd_mode(int mode, const std::set<const void*>& folded);
   int add_merged_convs(const std::string& name, const std::vector<DeferredConv>& d);
   // ---- the graph builder: build() runs the sections below in order; `Graph` is what one section hands to the next
   // (the detections a forward returns are the det_* members above)

@@ -336,6 +336,53 @@ int rs_op_conv2d_dgrad_split(const void* dy, const void* w_t, void* dx, const vo
 int rs_op_conv2d_dgrad_split_serves(int cin, int cout, int kh, int stride) {
   return conv_dgrad_split_serves(cin, cout, kh, kh, stride) ? 1 : 0;
 }
+// The forward convolution / linear layer of the fp32 trainer from fp32 tensors (x, w [cout][kpad] in the engine's layout, bias, res, up, y:
+// all float) with the product on the fp16 matrix cores: X as hi + lo planes under one power-of-two scale per call, W as row-scaled planes,
+// three products into one fp32 accumulator (conv_igemm's TRAIN && SPLIT instantiation with the forward epilogue).  Scratch, abs-max,
+// planes and row split live for the call.  count_dev (optional, device): images computed = min(n, *count_dev); the others are not written.
+// Arguments are refused before a device is touched.
+int rs_op_conv2d_fwd_split(const void* x, const void* w, const float* bias, void* y, const void* res, const void* up, int n, int hi, int wi,
+                           int cin, int in_halo, int kh, int kw, int stride, int pad, int cout, int kpad, int out_halo, int relu, int variant,
+                           const int32_t* count_dev, void* stream) {
+  RS_CHECK(x && w && bias && y, RS_ERR_ARG, "rs_op_conv2d_fwd_split: null operand");
+  RS_CHECK(n >= 1, RS_ERR_ARG, "rs_op_conv2d_fwd_split: n %d", n);
+  RS_CHECK(cin >= 64 && cin % 64 == 0, RS_ERR_ARG, "rs_op_conv2d_fwd_split: cin %d (the K side) must be a multiple of 64", cin);
+  RS_CHECK(cout >= 16 && cout % 16 == 0, RS_ERR_ARG, "rs_op_conv2d_fwd_split: cout %d (the rows) must be a multiple of 16", cout);
+  RS_CHECK(kh == kw && kh >= 1 && stride >= 1 && pad >= 0 && out_halo >= 0 && in_halo >= pad, RS_ERR_ARG, "rs_op_conv2d_fwd_split: halo %d below the pad %d (or a kernel that is not square, stride %d)", in_halo, pad, stride);
+  RS_CHECK(hi >= 1 && wi >= 1 && hi + 2 * pad >= kh && wi + 2 * pad >= kw && kpad >= kh * kw * cin && kpad % 64 == 0, RS_ERR_ARG,
+           "rs_op_conv2d_fwd_split: geometry (%d x %d input, %dx%d kernel, kpad %d at least kh * kw * cin and a multiple of 64)", hi, wi, kh, kw, kpad);
+  RS_CHECK(conv_fwd_split_serves(cout, cin, kh, kw, stride), RS_ERR_UNSUPPORTED, "rs_op_conv2d_fwd_split: shape not served");
+  const int ho = (hi + 2 * pad - kh) / stride + 1, wo = (wi + 2 * pad - kw) / stride + 1;
+  ConvParams p;
+  memset(&p, 0, sizeof p);
+  p.bias = bias; p.out = y; p.res = (const half_t*)res; p.up = (const half_t*)up;
+  p.M = n * ho * wo; p.Ho = ho; p.Wo = wo;
+  p.in_Hp = hi + 2 * in_halo; p.in_Wp = wi + 2 * in_halo; p.in_Cs = cin; p.in_off = in_halo - pad;
+  p.stride = stride; p.KH = kh; p.KW = kw; p.Cin = cin; p.Kpad = kpad; p.Cout = cout;
+  p.out_Hp = ho + 2 * out_halo; p.out_Wp = wo + 2 * out_halo; p.out_Cs = cout; p.out_pad = out_halo;
+  if (up) { p.up_Hp = (ho + 1) / 2 + 2 * out_halo; p.up_Wp = (wo + 1) / 2 + 2 * out_halo; p.up_Cs = cout; p.up_pad = out_halo; }
+  p.relu = relu ? 1 : 0;
+  if (count_dev) { p.m_count = count_dev; p.m_mul = ho * wo; }
+  // one allocation: [X header + planes | W planes | inverse row scales]
+  const long long cap = (long long)n * p.in_Hp * p.in_Wp * cin;
+  const size_t b_x = (dgrad_split_scratch_bytes(cap) + 255) & ~(size_t)255, b_w = ((size_t)cout * kpad * 4 + 255) & ~(size_t)255;
+  hipStream_t s = (hipStream_t)stream;
+  OpScratch scratch(stream);
+  char* buf = nullptr;
+  { int rc = scratch.alloc((void**)&buf, b_x + b_w + (size_t)cout * 4); if (rc) return rc; }
+  p.in = (const half_t*)x;
+  { int rc = launch_fwd_split_planes(p, buf, cap, s); if (rc) return rc; }
+  SplitRowsDesc d = {(const float*)w, (half_t*)(buf + b_x), (float*)(buf + b_x + b_w), cout, kpad, 0u};
+  { int rc = launch_split_rows(d, s); if (rc) return rc; }
+  p.split = 1; p.x_amax = (const unsigned*)buf;
+  p.in = (const half_t*)(buf + WGS_HEAD_BYTES); p.in_lo = cap;
+  p.w = d.planes; p.w_lo = (long long)cout * kpad; p.wscale = d.inv;
+  return launch_conv(p, s, variant, 1);
+}
+// 1 when rs_op_conv2d_fwd_split (and the trainer's split forward mode) runs a layer of this shape on the fp16 matrix cores.  Host only.
+int rs_op_conv2d_fwd_split_serves(int cin, int cout, int k, int stride) {
+  return conv_fwd_split_serves(cout, cin, k, k, stride) ? 1 : 0;
+}
 // w [rows][k] fp32 (device) -> planes [2 * rows][k] fp16 (hi rows, then lo rows) and inv_scale [rows], by weights.split_planes' rule
 int rs_op_split_rows(const float* w, int rows, int k, void* planes, float* inv_scale, void* stream) {
   RS_CHECK(w && planes && inv_scale && rows >= 1 && k >= 1, RS_ERR_ARG, "rs_op_split_rows: bad argument");

@@ -95,6 +95,9 @@ struct rs_trainer {
   int dgs_n = 0;
   unsigned dgs_rows = 0;
   int split_w_bwd();               // w_bwd of every layer -> planes + inverse row scales, one launch on the chain stream
+  // forward product on split operands (rs_trainer_set_fwd_mode; fp32 trainer only): the mode, its X scratch and the weight planes live in
+  // the forward engine (rs_engine::fwd_mode), whose conv / linear stages read it when they launch; fold_all() re-splits behind the fold
+  std::set<const void*> folded_weights() const;
   float* zero_bias = nullptr;    // zero fp32 bias for input-gradient convolutions
   std::vector<void*> allocs;
   std::vector<TensorInfo> tensors;
@@ -541,7 +544,15 @@ int rs_trainer::fold_all() {
   }
   int rc = launch_fold_table(fold_table, fold_n, fold_blocks, stream);
   if (!rc && dgrad_mode == 1) rc = split_w_bwd();
+  if (!rc && eng->fwd_mode == 1) rc = eng->fwd_split_weights(/*folded_only=*/true);      // the split forward's planes of what the fold rewrote
   return rc;
+}
+
+// the forward weights a fold rewrites (everything else the forward engine reads is frozen: the stem and res2 at FREEZE_AT 2)
+std::set<const void*> rs_trainer::folded_weights() const {
+  std::set<const void*> s;
+  for (const TrainLayer& L : layers) s.insert((const void*)L.w_fwd);
+  return s;
 }
 
 int rs_trainer::split_w_bwd() {
@@ -1087,7 +1098,7 @@ int rs_trainer::build_mask_training() {
       const int glds = f32 ? -1 : 1;
       Stage s2;
       s2.name = name;
-      s2.fn = [p, mpi, variant, glds](int n, hipStream_t s) mutable { p.M = n * mpi; return launch_conv(p, s, variant, glds); };
+      s2.fn = eng->conv_stage_fn(p, mpi, variant, glds);      // launch_conv(p, s, variant, glds), or the split forward in that mode
       mask_fwd.push_back(s2);
       return RS_OK;
     };
@@ -1596,6 +1607,16 @@ int rs_trainer_set_dgrad_mode(rs_trainer* t, int mode) {
   return RS_OK;
 }
 
+// The forward product's mode lives in the forward engine (rs_engine::set_fwd_mode): the first switch to mode 1 allocates the X plane
+// scratch and the planes of every served layer's weight; every switch to mode 1 splits all of them (a fold in mode 0 does not).
+int rs_trainer_set_fwd_mode(rs_trainer* t, int mode) {
+  RS_CHECK(t, RS_ERR_ARG, "rs_trainer_set_fwd_mode: null trainer");
+  RS_CHECK(mode == 0 || mode == 1, RS_ERR_ARG, "rs_trainer_set_fwd_mode: mode %d (0 = fp32 matrix cores, 1 = split operands)", mode);
+  RS_CHECK(t->f32 || mode == 0, RS_ERR_UNSUPPORTED, "rs_trainer_set_fwd_mode: split operands serve the fp32 trainer; this one is fp16 and already on the fp16 matrix cores");
+  if (!t->f32) return RS_OK;
+  return t->eng->set_fwd_mode(mode, t->folded_weights());
+}
+
 int rs_trainer_sync(rs_trainer* t) {
   RS_CHECK(t, RS_ERR_ARG, "null trainer");
   { int rc = t->join_side(); if (rc) return rc; }
@@ -1671,11 +1692,21 @@ int rs_trainer_copy_state(rs_trainer* dst, rs_trainer* src) {
   RS_HIP(hipMemcpyAsync(dst->master, src->master, dst->n_params * 4, hipMemcpyDeviceToDevice, dst->stream));
   RS_HIP(hipMemcpyAsync(dst->mom, src->mom, dst->n_params * 4, hipMemcpyDeviceToDevice, dst->stream));
   dst->step_count = src->step_count;
+  // the forward mode travels with the state, as the input-gradient mode below: switched off at once, switched on behind the fold
+  const bool fwd_on = dst->eng->fwd_mode != src->eng->fwd_mode && src->eng->fwd_mode == 1;
+  if (dst->eng->fwd_mode != src->eng->fwd_mode && src->eng->fwd_mode == 0) { int rc = rs_trainer_set_fwd_mode(dst, 0); if (rc) return rc; }
   if (dst->dgrad_mode != src->dgrad_mode) {       // the input-gradient mode travels with the state (its switch-on splits after the fold below)
     if (src->dgrad_mode == 0) dst->dgrad_mode = 0;
-    else { int rc = dst->fold_all(); if (!rc) rc = rs_trainer_set_dgrad_mode(dst, src->dgrad_mode); return rc; }
+    else {
+      int rc = dst->fold_all();
+      if (!rc) rc = rs_trainer_set_dgrad_mode(dst, src->dgrad_mode);
+      if (!rc && fwd_on) rc = rs_trainer_set_fwd_mode(dst, 1);
+      return rc;
+    }
   }
-  return dst->fold_all();
+  int rc = dst->fold_all();
+  if (!rc && fwd_on) rc = rs_trainer_set_fwd_mode(dst, 1);
+  return rc;
 }
 
 int rs_trainer_set_grad_divisor(rs_trainer* t, float d) {

@@ -193,6 +193,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "rs_op_conv2d_dgrad_split"):      # RS_ENGINE_LIB may name an older build
         lib.rs_op_conv2d_dgrad_split.argtypes = [vp] * 7 + [i32] * 14 + [vp, vp]
         lib.rs_op_conv2d_dgrad_split_serves.argtypes = [i32, i32, i32, i32]
+    if hasattr(lib, "rs_op_conv2d_fwd_split"):
+        lib.rs_op_conv2d_fwd_split.argtypes = [vp] * 6 + [i32] * 14 + [vp, vp]
+        lib.rs_op_conv2d_fwd_split_serves.argtypes = [i32, i32, i32, i32]
         lib.rs_op_split_rows.argtypes = [vp, i32, i32, vp, vp, vp]
     lib.rs_op_nms.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, vp]
     lib.rs_op_batched_nms.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_float, i32, vp]
@@ -1138,6 +1141,7 @@ class Predictor:
 MASK_TARGET_MODES = ("host", "device")
 WGRAD_MODES = ("f32", "split")   # rs_trainer_set_wgrad_mode 0 / 1
 DGRAD_MODES = ("f32", "split")   # rs_trainer_set_dgrad_mode 0 / 1
+FWD_MODES = ("f32", "split")     # rs_trainer_set_fwd_mode 0 / 1
 RS_EVAL_DOES_NOT_FIT = 2       # include/rs_engine.h: rs_engine_fetch_eval_async, the batch's ground truth exceeds the device pool
 EVAL_GT_CAP = 128              # RS_EVAL_GT_CAP: ground truths per tile, and the row length of the count tables
 RS_POLYGONS_DO_NOT_FIT = 1     # include/rs_engine.h: rs_trainer_set_polygons, the batch's polygons exceed the device pool
@@ -1157,6 +1161,13 @@ def _check_dgrad(dgrad: str, spec: "EngineSpec") -> None:
         raise ValueError("dgrad='split' serves the fp32 trainer (precision='fp32'); the fp16 trainer already runs on the fp16 matrix cores")
 
 
+def _check_fwd(fwd: str, spec: "EngineSpec") -> None:
+    if fwd not in FWD_MODES:
+        raise ValueError(f"fwd must be one of {FWD_MODES}, got {fwd!r}")
+    if fwd == "split" and spec.precision == "fp16":
+        raise ValueError("fwd='split' serves the fp32 trainer (precision='fp32'); the fp16 trainer already runs on the fp16 matrix cores")
+
+
 class Trainer:
     """Training engine (include/rs_engine.h ``rs_trainer_*``): forward engine + flat fp32
     master / gradient / momentum buffers + backward stage list.  ``train_step`` = ``SimpleTrainer.run_step`` up to
@@ -1165,8 +1176,13 @@ class Trainer:
 
     def __init__(self, spec: EngineSpec, weights: Dict[str, np.ndarray], tile_shape: Tuple[int, int, int], batch: int = 2,
                  device: int = 0, loss_scale: float = 1.0, lib_path: Optional[str] = None, mask_targets: str = "host", wgrad: str = "f32",
-                 dgrad: str = "f32"):
-        """``dgrad``: the input-gradient product dX = dY * W^T of the fp32 trainer's convolution and linear stages, with the same two
+                 dgrad: str = "f32", fwd: str = "f32"):
+        """``fwd``: the forward product Y = X * W of the fp32 trainer's convolution and linear stages, with the same two values: "split"
+        runs it on the fp16 matrix cores from hi + lo fp16 planes of X and of the folded weight; activations stay fp32,
+        the stem and the mask deconvolution keep their fp32 kernels, and validation inference through ``inference_engine`` follows the
+        mode.  ``set_fwd_mode`` switches between steps.
+
+        ``dgrad``: the input-gradient product dX = dY * W^T of the fp32 trainer's convolution and linear stages, with the same two
         values: "split" runs it on the fp16 matrix cores from hi + lo fp16 planes; the mask deconvolution and RoIAlign
         backward stay fp32.  ``set_dgrad_mode`` switches between steps.
 
@@ -1183,6 +1199,7 @@ class Trainer:
             raise ValueError(f"mask_targets must be one of {MASK_TARGET_MODES}, got {mask_targets!r}")
         _check_wgrad(wgrad, spec)
         _check_dgrad(dgrad, spec)
+        _check_fwd(fwd, spec)
         self.mask_targets = mask_targets
         self.mask_target_fallbacks = 0
         self.lib = lib = load_library(lib_path)
@@ -1206,6 +1223,8 @@ class Trainer:
         lib.rs_trainer_set_wgrad_mode.argtypes = [vp, i32]
         if hasattr(lib, "rs_trainer_set_dgrad_mode"):
             lib.rs_trainer_set_dgrad_mode.argtypes = [vp, i32]
+        if hasattr(lib, "rs_trainer_set_fwd_mode"):
+            lib.rs_trainer_set_fwd_mode.argtypes = [vp, i32]
         lib.rs_trainer_set_grad_divisor.argtypes = [vp, C.c_float]
         lib.rs_trainer_copy_state.argtypes = [vp, vp]
         lib.rs_trainer_grad_buffer.argtypes = [vp]
@@ -1249,6 +1268,9 @@ class Trainer:
         self.dgrad = "f32"
         if dgrad != "f32":
             self.set_dgrad_mode(dgrad)
+        self.fwd = "f32"
+        if fwd != "f32":
+            self.set_fwd_mode(fwd)
 
     def _tensor_ptr(self, name: str, engine: bool = False):
         p, dt, nd, halo = C.c_void_p(), C.c_int32(), C.c_int32(), C.c_int32()
@@ -1438,6 +1460,7 @@ class Trainer:
         """Carry master weights + momentum over from ``other`` (a trainer of another input size) and refold."""
         _check(self.lib, self.lib.rs_trainer_copy_state(self._h, other._h), "rs_trainer_copy_state")
         self.dgrad = other.dgrad                 # rs_trainer_copy_state carries the input-gradient mode
+        self.fwd = other.fwd                     # ... and the forward mode
 
     def inference_engine(self) -> Engine:
         """The trainer's forward engine as an inference ``Engine`` (same device buffers, current weights): validation detections
@@ -1547,6 +1570,14 @@ class Trainer:
         _check(self.lib, self.lib.rs_trainer_set_dgrad_mode(self._h, DGRAD_MODES.index(mode)), "rs_trainer_set_dgrad_mode")
         self.dgrad = mode
 
+    def set_fwd_mode(self, mode: str) -> None:
+        """Forward product of the following steps (and of validation inference on this trainer's engine): one of ``FWD_MODES``.  An
+        fp16 trainer refuses "split" (``RsError``)."""
+        if mode not in FWD_MODES:
+            raise ValueError(f"fwd must be one of {FWD_MODES}, got {mode!r}")
+        _check(self.lib, self.lib.rs_trainer_set_fwd_mode(self._h, FWD_MODES.index(mode)), "rs_trainer_set_fwd_mode")
+        self.fwd = mode
+
     def set_sampling(self, rpn_batch: int = 256, rpn_positive_fraction: float = 0.5, roi_batch: int = 1024, roi_positive_fraction: float = 0.25) -> None:
         _check(self.lib, self.lib.rs_trainer_set_sampling(self._h, rpn_batch, rpn_positive_fraction, roi_batch, roi_positive_fraction), "rs_trainer_set_sampling")
 
@@ -1607,14 +1638,17 @@ class MultiScaleTrainer:
     (``rs_trainer_copy_state``)."""
 
     def __init__(self, spec: EngineSpec, weights: Dict[str, np.ndarray], tile_shape: Tuple[int, int, int], sizes: Sequence[int], batch: int = 1,
-                 device: int = 0, loss_scale: float = 1024.0, mask_targets: str = "host", wgrad: str = "f32", dgrad: str = "f32"):
+                 device: int = 0, loss_scale: float = 1024.0, mask_targets: str = "host", wgrad: str = "f32", dgrad: str = "f32",
+                 fwd: str = "f32"):
         if mask_targets not in MASK_TARGET_MODES:
             raise ValueError(f"mask_targets must be one of {MASK_TARGET_MODES}, got {mask_targets!r}")
         _check_wgrad(wgrad, spec)
         _check_dgrad(dgrad, spec)
+        _check_fwd(fwd, spec)
         self.mask_targets = mask_targets
         self.wgrad = wgrad
         self.dgrad = dgrad
+        self.fwd = fwd
         self.spec, self.weights, self.tile_shape, self.batch, self.device, self.loss_scale = spec, weights, tile_shape, batch, device, loss_scale
         self.sizes = [int(s) for s in sizes]
         self._t: Dict[int, Trainer] = {}
@@ -1638,6 +1672,12 @@ class MultiScaleTrainer:
         for t in self._t.values():
             t.set_dgrad_mode(mode)
 
+    def set_fwd_mode(self, mode: str) -> None:
+        _check_fwd(mode, self.spec)
+        self.fwd = mode
+        for t in self._t.values():
+            t.set_fwd_mode(mode)
+
     def set_loss_scale(self, loss_scale: float) -> None:
         self.loss_scale = float(loss_scale)
         for t in self._t.values():
@@ -1653,7 +1693,7 @@ class MultiScaleTrainer:
         """The trainer for shortest-edge ``size``, holding the up-to-date optimiser state."""
         if size not in self._t:
             t = Trainer(self.spec.replace(min_size_test=int(size)), self.weights, self.tile_shape, self.batch, self.device, self.loss_scale,
-                        mask_targets=self.mask_targets, wgrad=self.wgrad, dgrad=self.dgrad)
+                        mask_targets=self.mask_targets, wgrad=self.wgrad, dgrad=self.dgrad, fwd=self.fwd)
             if self._sampling:
                 t.set_sampling(*self._sampling)
             if getattr(self, "_rpn_topk", None):

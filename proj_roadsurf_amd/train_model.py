@@ -273,6 +273,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "into hi + lo fp16 planes, and the product runs on the fp16 matrix cores with an fp32 accumulator; storage, forward "
                          "and the addends stay fp32, the mask deconvolution and RoIAlign backward keep their fp32 kernels.  Refused when the "
                          "run resolves to the fp16 trainer")
+    ap.add_argument("--fwd", choices=("f32", "split"), default="f32",
+                    help="the forward product Y = X * W of the fp32 trainer's convolution and linear stages.  f32 (default): fp32 operands on "
+                         "the fp32 matrix cores.  split: X is scaled by a power of two per stage and the folded weight per row, both are "
+                         "split into hi + lo fp16 planes, and the product runs on the fp16 matrix cores with an fp32 accumulator; "
+                         "activations, bias and addends stay fp32, the stem and the mask deconvolution keep their fp32 kernels, and the "
+                         "validation inference of the run follows the mode.  Refused when the run resolves to the fp16 trainer")
     ap.add_argument("--val-ap", choices=("host", "device"), default="host",
                     help="where the validation AP's mask overlaps are counted.  host (default): every detection mask is copied back, every "
                          "ground-truth polygon rasterised on the host and the IoUs taken from the masks.  device: the ground truth is "
@@ -379,6 +385,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                          "matrix cores; drop --dgrad split or give --precision fp32")
     log.info("dgrad: %s", {"f32": "f32 (input gradients on the fp32 matrix cores)",
                            "split": "split (dY and W^T as hi + lo fp16 planes, input gradients on the fp16 matrix cores)"}[args.dgrad])
+    if args.fwd == "split" and precision != "fp32":
+        raise SystemExit("--fwd split serves the fp32 trainer, and this run resolves to the fp16 trainer "
+                         f"({'--precision fp16' if args.precision != 'auto' else 'SOLVER.AMP.ENABLED true'}), which already runs on the fp16 "
+                         "matrix cores; drop --fwd split or give --precision fp32")
+    log.info("fwd: %s", {"f32": "f32 (forward products on the fp32 matrix cores)",
+                         "split": "split (X and W as hi + lo fp16 planes, forward products on the fp16 matrix cores)"}[args.fwd])
     from .engine import MultiScaleTrainer      # fails loudly without librs_engine.so / a HIP device
     from .make_detections import read_tile
     first = read_tile(recs[0]["file_name"])
@@ -389,7 +401,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     if sv["min_size_sampling"] == "range" and len(sizes) == 2:
         sizes = list(range(sizes[0], sizes[1] + 1, 32))
     ms = MultiScaleTrainer(spec, W, first.shape, sizes, batch=per_rank, device=local_rank, loss_scale=args.loss_scale,
-                           mask_targets=args.mask_targets, wgrad=args.wgrad, dgrad=args.dgrad)
+                           mask_targets=args.mask_targets, wgrad=args.wgrad, dgrad=args.dgrad, fwd=args.fwd)
     log.info("mask_targets: %s", {"host": "host (sampled RoIs read back, rasterised on host threads)",
                                   "device": "device (polygons uploaded with the targets, rasterised on the GPU)"}[args.mask_targets])
     ms.set_sampling(sv["rpn_batch"], sv["rpn_pos"], sv["roi_batch"], sv["roi_pos"])
