@@ -485,6 +485,34 @@ int rs_op_sgd_momentum(float* w, float* momentum_buf, const float* grad, int64_t
 int rs_op_fold_weights(const float* w32, const float* scale, void* w_fwd, void* w_bwd, int cout, int cin, int kh, int kw, int kpad,
                        int kpad_t, void* stream);
 
+/* Training diagnostics of detectron2 0.6 as INTEGER counts (csrc/train_stats.h holds the per-element rules; the ratios are the
+ * caller's, in double).  The three operators take device pointers, enqueue on `stream` and do not wait; the three host entries take
+ * the same arguments as host pointers and need no device.  All six ADD into the counts (zero them first), and refuse, before
+ * anything is touched and with their own name in the error text: null pointers (the two optional ones excepted), negative counts,
+ * num_classes outside 1..8, 5 * num_classes + 1 > cs, side < 1, cs < 1 (RS_ERR_ARG); a label count or n_masks * side * side of 2^31 or
+ * more (RS_ERR_UNSUPPORTED).  Sums that would pass 2^31 - 1 are the caller's to avoid.
+ *  label counts: labels[count]; counts2 += {labels equal to 1, labels equal to 0}  (RPN.losses: num_pos_anchors, num_neg_anchors).
+ *  box stats   : pred [n_rois][cs] (columns [0, K] are the class logits, K = background; the deltas behind are not read),
+ *                gt_classes [n_rois].  A row counts when 0 <= class <= K.  Its prediction is the FIRST largest of the K + 1 logits
+ *                (torch.argmax; -0.0 equals +0.0).  counts7 += {fg, bg, inst, correct, fgn, fg_correct, fg_as_bg}: fg / bg are the sums
+ *                of sampled_counts [n_images][2] (nothing when it is NULL), inst the rows that count, correct those predicted as
+ *                their class, fgn those with class < K, fg_correct / fg_as_bg the foreground rows predicted as their class / as K
+ *                (FastRCNNOutputLayers' _log_classification_stats).
+ *  mask stats  : logits [n_masks][side*side][cs], targets [n_masks][side*side], gt_classes [n_masks]; the first
+ *                min(*n_masks_ptr, n_masks) entries (all n_masks when the pointer is NULL), an entry with a class outside [0, cs)
+ *                skipped.  Per pixel p = logit of the entry's class > 0 (as IEEE: true for the smallest positive denormal and +inf,
+ *                false for both zeros), g = target != 0.  counts5 += {pixels, p != g, g, p & !g, !p & g} (mask_rcnn_loss). */
+int rs_op_label_counts(const int32_t* labels, int64_t count, int32_t* counts2, void* stream);
+int rs_op_box_stats(const float* pred, const int32_t* gt_classes, int n_rois, int num_classes, int cs, const int32_t* sampled_counts,
+                    int n_images, int32_t* counts7, void* stream);
+int rs_op_mask_stats(const float* logits, const uint8_t* targets, const int32_t* gt_classes, const int32_t* n_masks_ptr, int n_masks,
+                     int side, int cs, int32_t* counts5, void* stream);
+int rs_host_label_counts(const int32_t* labels, int64_t count, int32_t* counts2);
+int rs_host_box_stats(const float* pred, const int32_t* gt_classes, int n_rois, int num_classes, int cs, const int32_t* sampled_counts,
+                      int n_images, int32_t* counts7);
+int rs_host_mask_stats(const float* logits, const uint8_t* targets, const int32_t* gt_classes, const int32_t* n_masks_ptr, int n_masks,
+                       int side, int cs, int32_t* counts5);
+
 /* ------------------------------------------------------------------ training engine
  * Owns a forward engine (same blob, packed with train=True: fp32 master weights `<layer>.m32`, FrozenBN scales `<layer>.s`),
  * one flat fp32 master / gradient / momentum buffer in the forward GEMM layout, a gradient buffer per activation, and the
@@ -592,6 +620,18 @@ int rs_trainer_set_dgrad_mode(rs_trainer* t, int mode);
  * trainable layers again (the frozen res2 only at switch-on).  rs_trainer_copy_state carries the mode to the destination.
  * RS_ERR_UNSUPPORTED on an fp16 trainer, RS_ERR_ARG on a null handle or another mode. */
 int rs_trainer_set_fwd_mode(rs_trainer* t, int mode);
+/* Training diagnostics of the step, counted on the device (opt-in, both precisions; off by default, and a trainer that never
+ * switches them on keeps its stage list and tensor table).  on = 1: three counting stages run on the chain stream behind the loss
+ * stages -- "box.stats" behind box.loss, "mask.stats" behind mask.loss (both mask backward entries), "rpn.stats" behind the RPN
+ * losses, where the labels are final -- and add into the tensor "train_stats", int32 [16], which is zeroed wherever "losses" is:
+ *   [0..1] pos, neg anchors   [2..3] fg, bg sampled RoIs   [4..8] inst, correct, fgn, fg_correct, fg_as_bg
+ *   [9..13] pixels, incorrect, positive, false_pos, false_neg   [14] images of the step   [15] 0
+ * with the operators' definitions above.  The tensor is allocated by the first switch-on and read by name through
+ * rs_trainer_tensor (it is not enumerated); the stages are listed by rs_trainer_stage_info, last, once switched on.  Losses and
+ * gradients do not change by a bit.  Read when a step runs, so it may be switched between steps; rs_trainer_copy_state does not
+ * carry it.  RS_ERR_ARG on a null handle or another value, RS_ERR_UNSUPPORTED on a trainer whose capacities would let a count
+ * reach 2^31. */
+int rs_trainer_set_train_stats(rs_trainer* t, int on);
 /* SGD with momentum on the flat buffers + refold.  The gradient is first checked for inf / nan (fp16 loss scale too large for
  * this batch): then the step is skipped on the device -- weights and momentum unchanged -- and the tensor "grad_overflow" [1]
  * reads 1; lower the scale with rs_trainer_set_loss_scale before the next forward (GradScaler semantics, no host sync here). */

@@ -8,6 +8,7 @@
 #include "detect.h"
 #include "polygon_pool.h"
 #include "train.h"
+#include "train_stats.h"
 #include "val_ap.h"
 
 namespace {
@@ -648,6 +649,98 @@ int rs_op_mask_loss(const float* logits, void* dlogits, const uint8_t* targets, 
   p.logits = logits; p.dlogits = (half_t*)dlogits; p.targets = targets; p.gt_classes = gt_classes; p.loss_out = loss_out;
   p.n_masks = n_masks; p.S = side; p.cs = cs; p.loss_scale = loss_scale;
   return launch_mask_loss(p, (hipStream_t)stream);
+}
+
+// ---- training diagnostics: the three counting kernels on caller-owned device buffers, and the same rules (train_stats.h) on host
+// pointers.  Both forms ADD into the counts and refuse null pointers and impossible geometry before anything is touched.
+static int stats_label_args(const char* who, const int32_t* labels, int64_t count, const int32_t* counts2) {
+  RS_CHECK(labels && counts2, RS_ERR_ARG, "%s: null argument", who);
+  RS_CHECK(count >= 0, RS_ERR_ARG, "%s: negative count", who);
+  RS_CHECK(count < (1ll << 31), RS_ERR_UNSUPPORTED, "%s: %lld labels do not fit a 32-bit count", who, (long long)count);
+  return RS_OK;
+}
+static int stats_box_args(const char* who, const float* pred, const int32_t* gt_classes, int n_rois, int num_classes, int cs, int n_images,
+                          const int32_t* counts7) {
+  RS_CHECK(pred && gt_classes && counts7, RS_ERR_ARG, "%s: null argument", who);
+  RS_CHECK(n_rois >= 0 && n_images >= 0, RS_ERR_ARG, "%s: negative count", who);
+  RS_CHECK(num_classes >= 1 && num_classes <= TS_MAX_CLASSES && 5 * num_classes + 1 <= cs, RS_ERR_ARG,
+           "%s: %d classes (1..%d) in rows of %d (at least 5K+1)", who, num_classes, TS_MAX_CLASSES, cs);
+  return RS_OK;
+}
+static int stats_mask_args(const char* who, const float* logits, const uint8_t* targets, const int32_t* gt_classes, int n_masks, int side, int cs,
+                           const int32_t* counts5) {
+  RS_CHECK(logits && targets && gt_classes && counts5, RS_ERR_ARG, "%s: null argument", who);
+  RS_CHECK(n_masks >= 0 && side >= 1 && cs >= 1, RS_ERR_ARG, "%s: %d entries of side %d in rows of %d", who, n_masks, side, cs);
+  RS_CHECK((long long)n_masks * side * side < (1ll << 31), RS_ERR_UNSUPPORTED, "%s: %d entries of %d x %d pixels do not fit a 32-bit count", who,
+           n_masks, side, side);
+  return RS_OK;
+}
+
+int rs_op_label_counts(const int32_t* labels, int64_t count, int32_t* counts2, void* stream) {
+  { int rc = stats_label_args("rs_op_label_counts", labels, count, counts2); if (rc) return rc; }
+  LabelCountsParams p;
+  memset(&p, 0, sizeof p);
+  p.labels = labels; p.count = (int)count; p.out = counts2;
+  return launch_label_counts(p, (hipStream_t)stream);
+}
+int rs_op_box_stats(const float* pred, const int32_t* gt_classes, int n_rois, int num_classes, int cs, const int32_t* sampled_counts,
+                    int n_images, int32_t* counts7, void* stream) {
+  { int rc = stats_box_args("rs_op_box_stats", pred, gt_classes, n_rois, num_classes, cs, n_images, counts7); if (rc) return rc; }
+  BoxStatsParams p;
+  memset(&p, 0, sizeof p);
+  p.pred = pred; p.gt_classes = gt_classes; p.sampled_counts = sampled_counts; p.out = counts7;
+  p.n_rois = n_rois; p.K = num_classes; p.cs = cs; p.n_images = n_images;
+  return launch_box_stats(p, (hipStream_t)stream);
+}
+int rs_op_mask_stats(const float* logits, const uint8_t* targets, const int32_t* gt_classes, const int32_t* n_masks_ptr, int n_masks, int side,
+                     int cs, int32_t* counts5, void* stream) {
+  { int rc = stats_mask_args("rs_op_mask_stats", logits, targets, gt_classes, n_masks, side, cs, counts5); if (rc) return rc; }
+  MaskStatsParams p;
+  memset(&p, 0, sizeof p);
+  p.logits = logits; p.targets = targets; p.gt_classes = gt_classes; p.n_masks_ptr = n_masks_ptr; p.out = counts5;
+  p.n_masks = n_masks; p.S = side; p.cs = cs;
+  return launch_mask_stats(p, (hipStream_t)stream);
+}
+
+int rs_host_label_counts(const int32_t* labels, int64_t count, int32_t* counts2) {
+  { int rc = stats_label_args("rs_host_label_counts", labels, count, counts2); if (rc) return rc; }
+  for (int64_t i = 0; i < count; ++i) {
+    counts2[0] += labels[i] == 1;
+    counts2[1] += labels[i] == 0;
+  }
+  return RS_OK;
+}
+int rs_host_box_stats(const float* pred, const int32_t* gt_classes, int n_rois, int num_classes, int cs, const int32_t* sampled_counts,
+                      int n_images, int32_t* counts7) {
+  { int rc = stats_box_args("rs_host_box_stats", pred, gt_classes, n_rois, num_classes, cs, n_images, counts7); if (rc) return rc; }
+  if (sampled_counts)
+    for (int i = 0; i < n_images; ++i) {
+      counts7[0] += sampled_counts[2 * i];
+      counts7[1] += sampled_counts[2 * i + 1];
+    }
+  for (int r = 0; r < n_rois; ++r) {
+    int f[5];
+    ts_box_row(pred + (size_t)r * cs, gt_classes[r], num_classes, f);
+    for (int c = 0; c < 5; ++c) counts7[2 + c] += f[c];
+  }
+  return RS_OK;
+}
+int rs_host_mask_stats(const float* logits, const uint8_t* targets, const int32_t* gt_classes, const int32_t* n_masks_ptr, int n_masks, int side,
+                       int cs, int32_t* counts5) {
+  { int rc = stats_mask_args("rs_host_mask_stats", logits, targets, gt_classes, n_masks, side, cs, counts5); if (rc) return rc; }
+  int n = n_masks;
+  if (n_masks_ptr && *n_masks_ptr < n) n = *n_masks_ptr;
+  const size_t per = (size_t)side * side;
+  for (int m = 0; m < n; ++m) {
+    const int cls = gt_classes[m];
+    if (!ts_mask_entry_counts(cls, cs)) continue;
+    for (size_t pix = 0; pix < per; ++pix) {
+      int f[5];
+      ts_mask_pixel(logits[((size_t)m * per + pix) * cs + cls], targets[(size_t)m * per + pix], f);
+      for (int c = 0; c < 5; ++c) counts5[c] += f[c];
+    }
+  }
+  return RS_OK;
 }
 
 int rs_op_match(const float* boxes, int per_image_boxes, const int32_t* box_count, const float* gt, const int32_t* gt_count,

@@ -159,3 +159,31 @@ struct MaskTargetsParams {
   int n_entries, n_inst, slots_per_image, S;
 };
 int launch_mask_targets(const MaskTargetsParams& p, hipStream_t s);
+
+// ---- training diagnostics (train_stats.h): integer counts ADDED into the caller's table, at most one atomicAdd per workgroup and
+// counter, so that two runs give the same table.  Nothing here writes a gradient or a loss.
+struct LabelCountsParams {
+  const int* labels;        // [count]: 1 positive, 0 negative, anything else not sampled
+  int count;
+  int* out;                 // [2] += pos, neg
+  int* images_out;          // optional [1] += images (the trainer's table carries the step's n)
+  int images;
+};
+struct BoxStatsParams {
+  const float* pred;        // [n_rois][cs] fp32: [0,K] logits (K = background); the deltas behind them are not read
+  const int* gt_classes;    // [n_rois]: class, K = background, anything outside [0, K] does not count
+  const int* sampled_counts;   // optional [n_images][2] (sampled foreground, background per image)
+  int* out;                 // [7] += fg, bg (from sampled_counts), inst, correct, fgn, fg_correct, fg_as_bg
+  int n_rois, K, cs, n_images;
+};
+struct MaskStatsParams {
+  const float* logits;      // [n_masks][S*S][cs] fp32, channel = class
+  const uint8_t* targets;   // [n_masks][S*S]
+  const int* gt_classes;    // [n_masks]: an entry with a class outside [0, cs) does not count
+  const int* n_masks_ptr;   // optional device count, clamped to n_masks (= capacity)
+  int* out;                 // [5] += pixels, incorrect, positive, false_pos, false_neg
+  int n_masks, S, cs;
+};
+int launch_label_counts(const LabelCountsParams& p, hipStream_t s);
+int launch_box_stats(const BoxStatsParams& p, hipStream_t s);
+int launch_mask_stats(const MaskStatsParams& p, hipStream_t s);

@@ -15,12 +15,15 @@
 //   fold_weights_kernel    fp32 master weight -> the two fp16 GEMM operands of the next step: the forward weight
 //                          [Cout][(kh,kw,ci)] with the FrozenBN scale folded in, and its transposed, tap-flipped copy
 //                          [Cin][(kh',kw',co)] for the input-gradient convolution
+//   label_counts_kernel / box_stats_kernel / mask_stats_kernel
+//                          detectron2's training diagnostics as integer counts (train_stats.h), opt-in behind the loss stages
 // Each loss kernel writes the GRADIENT of the (weighted) total loss w.r.t. its logits/deltas, scaled by `loss_scale`
 // (fp16 loss scaling), and accumulates the loss value itself into an fp32 scalar for logging (one float atomic per wave, or, given a
 // LossScratch, in a fixed order: grid_sum_to).
 #include "common.h"
 #include "mask_targets.h"
 #include "train.h"
+#include "train_stats.h"
 
 namespace {
 
@@ -715,7 +718,108 @@ __global__ __launch_bounds__(64) void mask_targets_kernel(const MaskTargetsParam
   for (int i = lane; i < SS / 4; i += 64) o[i] = s_out[i];
 }
 
+// ---- training diagnostics (train_stats.h holds the per-element rules; the host restates them in ops.hip).  Integer counts only:
+// NC values per thread -> wave sums (ballot + popcount for 0/1 flags, shuffles otherwise) -> one LDS slot per wave -> thread c adds
+// the four waves of counter c and issues the workgroup's ONE atomicAdd for it (none when the sum is 0).  Integer addition does not
+// depend on the order, so two runs leave the same table.  All 256 threads must call it.
+template <int NC, bool FLAGS>
+__device__ __forceinline__ void block_counts_add(const int (&v)[NC], int* dst) {
+  __shared__ int s_w[NC][4];
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    int x;
+    if (FLAGS) {
+      x = __popcll(__ballot(v[c] != 0));
+    } else {
+      x = v[c];
+      for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    }
+    if ((tid & 63) == 0) s_w[c][tid >> 6] = x;
+  }
+  __syncthreads();
+  if (tid < NC) {
+    const int t = (s_w[tid][0] + s_w[tid][1]) + (s_w[tid][2] + s_w[tid][3]);
+    if (t) atomicAdd(dst + tid, t);
+  }
+}
+
+// one thread per label: RPN.losses' num_pos_anchors / num_neg_anchors before the division by the images
+__global__ __launch_bounds__(256) void label_counts_kernel(const LabelCountsParams p) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  int v[2] = {0, 0};
+  if (i < p.count) {
+    const int l = p.labels[i];
+    v[0] = l == 1;
+    v[1] = l == 0;
+  }
+  block_counts_add<2, true>(v, p.out);
+  if (p.images_out && p.images && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(p.images_out, p.images);
+}
+
+// one thread per RoI row: _log_classification_stats' five counts; workgroup 0 also sums the sampled foreground / background counts
+__global__ __launch_bounds__(256) void box_stats_kernel(const BoxStatsParams p) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  int f[5] = {0, 0, 0, 0, 0};
+  if (r < p.n_rois) ts_box_row(p.pred + r * p.cs, p.gt_classes[r], p.K, f);
+  block_counts_add<5, true>(f, p.out + 2);
+  if (p.sampled_counts && blockIdx.x == 0) {      // the same for every thread of the workgroup
+    int s[2] = {0, 0};
+    for (int i = threadIdx.x; i < p.n_images; i += 256) {
+      s[0] += p.sampled_counts[2 * i];
+      s[1] += p.sampled_counts[2 * i + 1];
+    }
+    block_counts_add<2, false>(s, p.out);
+  }
+}
+
+// one workgroup per mask-head entry, striding over its S*S pixels: mask_rcnn_loss' accuracy counts on the gt class' logit
+__global__ __launch_bounds__(256) void mask_stats_kernel(const MaskStatsParams p) {
+  const int m = blockIdx.x;
+  int n_masks = p.n_masks;
+  if (p.n_masks_ptr) { const int c = *p.n_masks_ptr; n_masks = c < n_masks ? c : n_masks; }
+  int v[5] = {0, 0, 0, 0, 0};
+  if (m < n_masks) {
+    const int cls = p.gt_classes[m];
+    if (ts_mask_entry_counts(cls, p.cs)) {
+      const int per = p.S * p.S;
+      const long long base = (long long)m * per;
+      for (int pix = threadIdx.x; pix < per; pix += 256) {
+        int f[5];
+        ts_mask_pixel(p.logits[(base + pix) * p.cs + cls], p.targets[base + pix], f);
+#pragma unroll
+        for (int c = 0; c < 5; ++c) v[c] += f[c];
+      }
+    }
+  }
+  block_counts_add<5, false>(v, p.out);
+}
+
 }  // namespace
+
+int launch_label_counts(const LabelCountsParams& p, hipStream_t s) {
+  RS_CHECK(p.labels && p.out && p.count >= 0 && p.images >= 0, RS_ERR_ARG, "label_counts: bad arguments");
+  const unsigned blocks = p.count > 0 ? (unsigned)cdiv((long long)p.count, 256) : 1u;
+  hipLaunchKernelGGL(label_counts_kernel, dim3(blocks), dim3(256), 0, s, p);
+  RS_HIP(hipGetLastError());
+  return RS_OK;
+}
+int launch_box_stats(const BoxStatsParams& p, hipStream_t s) {
+  RS_CHECK(p.pred && p.gt_classes && p.out && p.n_rois >= 0 && p.n_images >= 0, RS_ERR_ARG, "box_stats: bad arguments");
+  RS_CHECK(p.K >= 1 && p.K <= TS_MAX_CLASSES && p.cs >= 5 * p.K + 1, RS_ERR_ARG, "box_stats: %d classes in rows of %d", p.K, p.cs);
+  const unsigned blocks = p.n_rois > 0 ? (unsigned)cdiv((long long)p.n_rois, 256) : 1u;
+  hipLaunchKernelGGL(box_stats_kernel, dim3(blocks), dim3(256), 0, s, p);
+  RS_HIP(hipGetLastError());
+  return RS_OK;
+}
+int launch_mask_stats(const MaskStatsParams& p, hipStream_t s) {
+  RS_CHECK(p.logits && p.targets && p.gt_classes && p.out && p.n_masks >= 0 && p.S >= 1 && p.cs >= 1, RS_ERR_ARG, "mask_stats: bad arguments");
+  RS_CHECK((long long)p.n_masks * p.S * p.S < (1ll << 31), RS_ERR_UNSUPPORTED, "mask_stats: %d entries of %d x %d pixels do not fit a 32-bit count", p.n_masks, p.S, p.S);
+  if (p.n_masks == 0) return RS_OK;
+  hipLaunchKernelGGL(mask_stats_kernel, dim3((unsigned)p.n_masks), dim3(256), 0, s, p);
+  RS_HIP(hipGetLastError());
+  return RS_OK;
+}
 
 int launch_rpn_loss(const RpnLossParams& p, int N, hipStream_t s) {
   RS_CHECK(p.head && p.dhead && p.labels && p.anchors && (p.matched_gt || (p.gt && p.matched)) && p.loss_out && p.n_anchors > 0 && p.cs >= 5 * p.A, RS_ERR_ARG, "rpn_loss: bad arguments");

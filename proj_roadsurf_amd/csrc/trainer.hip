@@ -20,6 +20,7 @@
 #include "engine_internal.h"
 #include "polygon_pool.h"
 #include "train.h"
+#include "train_stats.h"
 
 namespace {
 
@@ -164,6 +165,13 @@ struct rs_trainer {
   Stage mt_stage;                        // "mask.targets": listed by rs_trainer_stage_info once the pool exists
   bool mt_listed = false;
   std::vector<TensorInfo> named;         // readable through rs_trainer_tensor by name, not part of the enumerated table
+  // ---- training diagnostics (opt-in: rs_trainer_set_train_stats; train_stats.h).  Three counting stages behind the loss stages add
+  // into one int32 table, zeroed where `losses` is; table and stages exist from the first switch-on, outside the lists as mt_stage is
+  int train_stats_on = 0;
+  int* train_stats = nullptr;            // [TS_TABLE]
+  Stage ts_box, ts_mask, ts_rpn;         // "box.stats", "mask.stats", "rpn.stats": listed by rs_trainer_stage_info once switched on
+  bool ts_listed = false;
+  int run_stats(Stage& st, int n) { return train_stats_on ? run_stage(st, n, stream) : (int)RS_OK; }
   const int* ctx_m_count = nullptr;   // while set, add_dgrad / add_wgrad bound their rows by this device counter (entries)
   int build_mask_training();
   std::vector<std::pair<void*, size_t>> clear_list;   // gradient buffers that must be zero before a backward pass
@@ -1439,10 +1447,12 @@ int rs_trainer_rpn_step(rs_trainer* t, int n, uint32_t seed, int external_labels
   t->external_rpn_labels = external_labels != 0;
   if (!t->roi_grads_valid) {           // stand-alone RPN step: no RoI-head gradients to add, fresh loss accumulators
     RS_HIP(hipMemsetAsync(t->losses, 0, 8 * 4, t->stream));
+    if (t->train_stats_on) RS_HIP(hipMemsetAsync(t->train_stats, 0, TS_TABLE * 4, t->stream));
     for (int l = 0; l < 4; ++l) if (t->dP32[l]) RS_HIP(hipMemsetAsync(t->dP32[l], 0, t->dP32_bytes[l], t->stream));
   }
   t->roi_grads_valid = false;
   { int rc = t->run_list(t->rpn_bwd, n); if (rc) return rc; }
+  { int rc = t->run_stats(t->ts_rpn, n); if (rc) return rc; }      // behind every rpn.loss*: the labels are final
   return t->record_bucket(0);     // box / mask / RPN head gradients: rs_trainer_rpn_step is the last of the head steps
 }
 
@@ -1454,6 +1464,7 @@ int rs_trainer_roi_step(rs_trainer* t, int n, uint32_t seed) {
   rs_engine* e = t->eng;
   hipStream_t s = t->stream;
   RS_HIP(hipMemsetAsync(t->losses, 0, 8 * 4, s));
+  if (t->train_stats_on) RS_HIP(hipMemsetAsync(t->train_stats, 0, TS_TABLE * 4, s));
   for (int l = 0; l < 4; ++l) RS_HIP(hipMemsetAsync(t->dP32[l], 0, t->dP32_bytes[l], s));
   int rc;
   // proposals (detached): top PRE_NMS_TOPK_TRAIN per level, NMS, top POST_NMS_TOPK_TRAIN per image
@@ -1483,6 +1494,7 @@ int rs_trainer_roi_step(rs_trainer* t, int n, uint32_t seed) {
   if (t->ev_rois) RS_HIP(hipEventRecord(t->ev_rois, s));
   for (int i = t->box_first_stage; i <= t->box_last_stage; ++i) if ((rc = t->run_stage(e->stages[i], n, s))) return rc;      // box head forward
   if ((rc = t->run_list(t->roi_bwd, n))) return rc;
+  if ((rc = t->run_stats(t->ts_box, n))) return rc;               // behind box.loss, on the chain stream
   t->roi_grads_valid = true;
   return RS_OK;
 }
@@ -1508,7 +1520,8 @@ int rs_trainer_mask_backward(rs_trainer* t, int n, const uint8_t* targets_host, 
     RS_HIP(hipMemcpyAsync(t->m_targets, t->m_targets_pinned, (size_t)n_entries * side * side, hipMemcpyHostToDevice, t->stream));
     RS_HIP(hipEventRecord(t->ev_targets, t->stream));
   }
-  return t->run_list(t->mask_bwd, n);
+  { int rc = t->run_list(t->mask_bwd, n); if (rc) return rc; }
+  return t->run_stats(t->ts_mask, n);                              // behind mask.loss, on the chain stream
 }
 
 // rs_trainer_mask_backward with the targets rasterised on the device (mask_targets_kernel on the chain stream, behind mask.entries and
@@ -1517,7 +1530,8 @@ int rs_trainer_mask_backward_device(rs_trainer* t, int n) {
   RS_CHECK(t && n >= 1 && n <= t->N && !t->mask_bwd.empty(), RS_ERR_ARG, "bad argument / MASK_ON false");
   RS_CHECK(t->mt_set && t->mt_n == n, RS_ERR_ARG, "no polygons of this batch on the device: call rs_trainer_set_polygons after rs_trainer_set_targets");
   { int rc = t->run_stage(t->mt_stage, n, t->stream); if (rc) return rc; }
-  return t->run_list(t->mask_bwd, n);
+  { int rc = t->run_list(t->mask_bwd, n); if (rc) return rc; }
+  return t->run_stats(t->ts_mask, n);
 }
 
 // The sampled RoIs of the current rs_trainer_roi_step for the host-side mask targets: "roi_boxes" [n][1024][4], "roi_gt_index"
@@ -1615,6 +1629,65 @@ int rs_trainer_set_fwd_mode(rs_trainer* t, int mode) {
   RS_CHECK(t->f32 || mode == 0, RS_ERR_UNSUPPORTED, "rs_trainer_set_fwd_mode: split operands serve the fp32 trainer; this one is fp16 and already on the fp16 matrix cores");
   if (!t->f32) return RS_OK;
   return t->eng->set_fwd_mode(mode, t->folded_weights());
+}
+
+// Training diagnostics: the first switch-on allocates the table, names it and builds the three stages on the buffers the loss stages
+// read; later calls only flip the flag, which is read when a step runs.
+int rs_trainer_set_train_stats(rs_trainer* t, int on) {
+  RS_CHECK(t, RS_ERR_ARG, "rs_trainer_set_train_stats: null trainer");
+  RS_CHECK(on == 0 || on == 1, RS_ERR_ARG, "rs_trainer_set_train_stats: value %d (0 = off, 1 = on)", on);
+  if (on && !t->train_stats) {
+    const rs_spec& S = t->eng->spec;
+    const int K = S.num_classes, SD = 2 * S.mask_pooler_resolution;
+    const int pred_cs = (5 * K + 1 + 15) / 16 * 16;
+    const bool mask = !t->mask_bwd.empty();
+    // every counter is bounded by one of these products
+    const long long lim = 1ll << 31;
+    RS_CHECK((long long)t->N * t->A_total < lim && (long long)t->N * rs_trainer::PC < lim &&
+             (!mask || (long long)t->N * rs_trainer::MEI * SD * SD < lim), RS_ERR_UNSUPPORTED,
+             "rs_trainer_set_train_stats: a batch of %d lets a count reach 2^31 (%d anchors, %d RoI slots, %d x %d x %d mask pixels per image)",
+             t->N, t->A_total, rs_trainer::PC, rs_trainer::MEI, SD, SD);
+    RS_CHECK(K >= 1 && K <= TS_MAX_CLASSES, RS_ERR_UNSUPPORTED, "rs_trainer_set_train_stats: %d classes", K);
+    const float* pred = nullptr;
+    const float* logits = nullptr;
+    for (const TensorInfo& ti : t->eng->tensors) if (ti.name == "box_pred") pred = (const float*)ti.p;
+    for (const TensorInfo& ti : t->tensors) if (ti.name == "t:mask_logits") logits = (const float*)ti.p;
+    RS_CHECK(pred && (!mask || logits), RS_ERR_ARG, "rs_trainer_set_train_stats: the loss stages' tensors are missing");
+    int* table = nullptr;
+    { int rc = t->alloc((void**)&table, TS_TABLE * 4); if (rc) return rc; }      // zero-filled on the chain stream
+    rs_trainer* self = t;
+    t->ts_box.name = "box.stats";
+    t->ts_box.fn = [self, table, pred, K, pred_cs](int n, hipStream_t s) {
+      BoxStatsParams q;
+      memset(&q, 0, sizeof q);
+      q.pred = pred; q.gt_classes = self->rsp.out_classes; q.sampled_counts = self->roi_sampled_count; q.out = table + TS_ROI;
+      q.n_rois = n * rs_trainer::PC; q.K = K; q.cs = pred_cs; q.n_images = n;
+      return launch_box_stats(q, s);
+    };
+    t->ts_mask.name = "mask.stats";
+    t->ts_mask.fn = [self, table, logits, SD](int n, hipStream_t s) {
+      MaskStatsParams q;
+      memset(&q, 0, sizeof q);
+      q.logits = logits; q.targets = self->m_targets; q.gt_classes = self->m_cls; q.n_masks_ptr = self->m_total; q.out = table + TS_MASK;
+      q.n_masks = n * rs_trainer::MEI; q.S = SD; q.cs = 16;
+      return launch_mask_stats(q, s);
+    };
+    t->ts_rpn.name = "rpn.stats";
+    t->ts_rpn.fn = [self, table](int n, hipStream_t s) {
+      LabelCountsParams q;
+      memset(&q, 0, sizeof q);
+      q.labels = self->rpn_labels; q.count = n * self->A_total; q.out = table + TS_RPN; q.images_out = table + TS_IMAGES; q.images = n;
+      return launch_label_counts(q, s);
+    };
+    TensorInfo ti;
+    ti.name = "train_stats"; ti.p = table; ti.dtype = DT_I32; ti.ndim = 1; ti.halo = 0;
+    ti.dims[0] = TS_TABLE;
+    ti.bytes = TS_TABLE * 4;
+    t->named.push_back(ti);
+    t->train_stats = table;
+  }
+  t->train_stats_on = on;
+  return RS_OK;
 }
 
 int rs_trainer_sync(rs_trainer* t) {
@@ -1756,6 +1829,12 @@ int rs_trainer_set_profiling(rs_trainer* t, int on) {
       for (Stage& st : *l) t->all_stages.push_back(&st);
   }
   if (t->mt_pool && !t->mt_listed) { t->all_stages.push_back(&t->mt_stage); t->mt_listed = true; }   // last: the other indices stay
+  if (t->train_stats && !t->ts_listed) {
+    t->all_stages.push_back(&t->ts_box);
+    if (!t->mask_bwd.empty()) t->all_stages.push_back(&t->ts_mask);
+    t->all_stages.push_back(&t->ts_rpn);
+    t->ts_listed = true;
+  }
   if (on) {
     for (Stage* st : t->all_stages) { st->ms_total = 0; st->calls = 0; st->last_flops = 0; }
     if (t->pev.empty()) {

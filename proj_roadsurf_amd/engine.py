@@ -215,6 +215,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.rs_op_mask_loss.argtypes = [vp] * 5 + [i32, i32, i32, f32, vp]
     lib.rs_op_sgd_momentum.argtypes = [vp, vp, vp, C.c_int64, f32, f32, f32, f32, i32, vp]
     lib.rs_op_fold_weights.argtypes = [vp] * 4 + [i32] * 6 + [vp]
+    if hasattr(lib, "rs_op_label_counts"):            # RS_ENGINE_LIB may name an older build
+        lib.rs_op_label_counts.argtypes = [vp, C.c_int64, vp, vp]
+        lib.rs_op_box_stats.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, vp]
+        lib.rs_op_mask_stats.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
+        lib.rs_host_label_counts.argtypes = [vp, C.c_int64, vp]
+        lib.rs_host_box_stats.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp]
+        lib.rs_host_mask_stats.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+        lib.rs_trainer_set_train_stats.argtypes = [vp, i32]
     lib.rs_resize_shape.argtypes = [i32, i32, i32, i32, i32p, i32p]
     lib.rs_resize_shape.restype = None
     lib.rs_resize_coeffs.argtypes = [i32, i32, i32p, i32p]
@@ -1147,6 +1155,41 @@ EVAL_GT_CAP = 128              # RS_EVAL_GT_CAP: ground truths per tile, and the
 RS_POLYGONS_DO_NOT_FIT = 1     # include/rs_engine.h: rs_trainer_set_polygons, the batch's polygons exceed the device pool
 
 
+TRAIN_STATS_TABLE = 16         # csrc/train_stats.h TS_TABLE: int32 entries of the tensor "train_stats"
+TRAIN_STATS_KEYS = ("rpn/num_pos_anchors", "rpn/num_neg_anchors", "roi_head/num_fg_samples", "roi_head/num_bg_samples",
+                    "fast_rcnn/cls_accuracy", "fast_rcnn/fg_cls_accuracy", "fast_rcnn/false_negative",
+                    "mask_rcnn/accuracy", "mask_rcnn/false_positive", "mask_rcnn/false_negative")
+
+
+def train_stats_scalars(table: Sequence[int]) -> Dict[str, float]:
+    """The integer table of ``rs_trainer_set_train_stats`` (include/rs_engine.h: [0..1] pos, neg anchors; [2..3] fg, bg sampled RoIs;
+    [4..8] inst, correct, fgn, fg_correct, fg_as_bg; [9..13] pixels, incorrect, positive, false_pos, false_neg; [14] images) ->
+    detectron2 0.6's training scalars under its names (``TRAIN_STATS_KEYS``), every ratio formed here in Python floats.  Omitted, as
+    detectron2 omits them: the per-image means of a table without images, the three ``fast_rcnn/`` keys when no row counted, the two
+    foreground ones when no foreground row did, the three ``mask_rcnn/`` keys when no mask pixel was counted (no entries, or MASK_ON
+    false).  The values are those of ONE step: detectron2's 20-iteration median smoothing is not applied."""
+    t = [int(v) for v in table]
+    if len(t) != TRAIN_STATS_TABLE:
+        raise ValueError(f"train_stats table of {len(t)} entries, expected {TRAIN_STATS_TABLE}")
+    pos, neg, fg, bg, inst, correct, fgn, fg_correct, fg_as_bg, pixels, incorrect, positive, false_pos, false_neg, n = t[:15]
+    out: Dict[str, float] = {}
+    if n > 0:
+        out["rpn/num_pos_anchors"] = pos / n
+        out["rpn/num_neg_anchors"] = neg / n
+        out["roi_head/num_fg_samples"] = fg / n
+        out["roi_head/num_bg_samples"] = bg / n
+    if inst > 0:
+        out["fast_rcnn/cls_accuracy"] = correct / inst
+        if fgn > 0:
+            out["fast_rcnn/fg_cls_accuracy"] = fg_correct / fgn
+            out["fast_rcnn/false_negative"] = fg_as_bg / fgn
+    if pixels > 0:
+        out["mask_rcnn/accuracy"] = 1.0 - incorrect / max(pixels, 1)
+        out["mask_rcnn/false_positive"] = false_pos / max(pixels - positive, 1)
+        out["mask_rcnn/false_negative"] = false_neg / max(positive, 1)
+    return out
+
+
 def _check_wgrad(wgrad: str, spec: "EngineSpec") -> None:
     if wgrad not in WGRAD_MODES:
         raise ValueError(f"wgrad must be one of {WGRAD_MODES}, got {wgrad!r}")
@@ -1176,8 +1219,13 @@ class Trainer:
 
     def __init__(self, spec: EngineSpec, weights: Dict[str, np.ndarray], tile_shape: Tuple[int, int, int], batch: int = 2,
                  device: int = 0, loss_scale: float = 1.0, lib_path: Optional[str] = None, mask_targets: str = "host", wgrad: str = "f32",
-                 dgrad: str = "f32", fwd: str = "f32"):
-        """``fwd``: the forward product Y = X * W of the fp32 trainer's convolution and linear stages, with the same two values: "split"
+                 dgrad: str = "f32", fwd: str = "f32", train_stats: bool = False):
+        """``train_stats``: count detectron2's training diagnostics (anchor and RoI sample counts, the box head's classification
+        accuracies, the mask head's pixel accuracies) on the GPU behind the loss stages of every step; ``train_stats()`` returns them
+        under detectron2's names.  Off by default; losses and gradients are the same bits either way.  ``set_train_stats`` switches
+        between steps.
+
+        ``fwd``: the forward product Y = X * W of the fp32 trainer's convolution and linear stages, with the same two values: "split"
         runs it on the fp16 matrix cores from hi + lo fp16 planes of X and of the folded weight; activations stay fp32,
         the stem and the mask deconvolution keep their fp32 kernels, and validation inference through ``inference_engine`` follows the
         mode.  ``set_fwd_mode`` switches between steps.
@@ -1271,6 +1319,9 @@ class Trainer:
         self.fwd = "f32"
         if fwd != "f32":
             self.set_fwd_mode(fwd)
+        self.train_stats_on = False
+        if train_stats:
+            self.set_train_stats(True)
 
     def _tensor_ptr(self, name: str, engine: bool = False):
         p, dt, nd, halo = C.c_void_p(), C.c_int32(), C.c_int32(), C.c_int32()
@@ -1578,6 +1629,23 @@ class Trainer:
         _check(self.lib, self.lib.rs_trainer_set_fwd_mode(self._h, FWD_MODES.index(mode)), "rs_trainer_set_fwd_mode")
         self.fwd = mode
 
+    def set_train_stats(self, on: bool) -> None:
+        """Training diagnostics of the following steps on (counted on the GPU, ``train_stats()`` reads them) or off."""
+        if not hasattr(self.lib, "rs_trainer_set_train_stats"):
+            raise RsError("this librs_engine.so has no rs_trainer_set_train_stats (an older build)")
+        _check(self.lib, self.lib.rs_trainer_set_train_stats(self._h, 1 if on else 0), "rs_trainer_set_train_stats")
+        self.train_stats_on = bool(on)
+
+    def train_stats_table(self) -> np.ndarray:
+        """The int32 [16] table of the last step (include/rs_engine.h ``rs_trainer_set_train_stats``); synchronises the trainer's stream."""
+        if not self.train_stats_on:
+            raise RsError("training diagnostics are off: Trainer(..., train_stats=True) or set_train_stats(True) before the step")
+        return self.tensor("train_stats")
+
+    def train_stats(self) -> Dict[str, float]:
+        """detectron2's training scalars of the last step (``train_stats_scalars`` of the table): 64 bytes cross PCIe."""
+        return train_stats_scalars(self.train_stats_table())
+
     def set_sampling(self, rpn_batch: int = 256, rpn_positive_fraction: float = 0.5, roi_batch: int = 1024, roi_positive_fraction: float = 0.25) -> None:
         _check(self.lib, self.lib.rs_trainer_set_sampling(self._h, rpn_batch, rpn_positive_fraction, roi_batch, roi_positive_fraction), "rs_trainer_set_sampling")
 
@@ -1639,13 +1707,14 @@ class MultiScaleTrainer:
 
     def __init__(self, spec: EngineSpec, weights: Dict[str, np.ndarray], tile_shape: Tuple[int, int, int], sizes: Sequence[int], batch: int = 1,
                  device: int = 0, loss_scale: float = 1024.0, mask_targets: str = "host", wgrad: str = "f32", dgrad: str = "f32",
-                 fwd: str = "f32"):
+                 fwd: str = "f32", train_stats: bool = False):
         if mask_targets not in MASK_TARGET_MODES:
             raise ValueError(f"mask_targets must be one of {MASK_TARGET_MODES}, got {mask_targets!r}")
         _check_wgrad(wgrad, spec)
         _check_dgrad(dgrad, spec)
         _check_fwd(fwd, spec)
         self.mask_targets = mask_targets
+        self.train_stats_on = bool(train_stats)
         self.wgrad = wgrad
         self.dgrad = dgrad
         self.fwd = fwd
@@ -1678,6 +1747,17 @@ class MultiScaleTrainer:
         for t in self._t.values():
             t.set_fwd_mode(mode)
 
+    def set_train_stats(self, on: bool) -> None:
+        self.train_stats_on = bool(on)
+        for t in self._t.values():
+            t.set_train_stats(on)
+
+    def train_stats(self) -> Dict[str, float]:
+        """``Trainer.train_stats`` of the trainer that ran the last step."""
+        if self.current is None:
+            raise RsError("no trainer has run a step yet")
+        return self.current.train_stats()
+
     def set_loss_scale(self, loss_scale: float) -> None:
         self.loss_scale = float(loss_scale)
         for t in self._t.values():
@@ -1693,7 +1773,7 @@ class MultiScaleTrainer:
         """The trainer for shortest-edge ``size``, holding the up-to-date optimiser state."""
         if size not in self._t:
             t = Trainer(self.spec.replace(min_size_test=int(size)), self.weights, self.tile_shape, self.batch, self.device, self.loss_scale,
-                        mask_targets=self.mask_targets, wgrad=self.wgrad, dgrad=self.dgrad, fwd=self.fwd)
+                        mask_targets=self.mask_targets, wgrad=self.wgrad, dgrad=self.dgrad, fwd=self.fwd, train_stats=self.train_stats_on)
             if self._sampling:
                 t.set_sampling(*self._sampling)
             if getattr(self, "_rpn_topk", None):

@@ -21,7 +21,9 @@ ImageList.from_tensors do (``MultiScaleTrainer.select_batch``).
 Documented deviations: fp16 activations/weights with fp32 master weights and dynamic loss scaling (GradScaler's policy) instead of fp32 everywhere, the
 model-zoo name of ``model_weights.model_zoo_checkpoint_url`` is resolved in detectron2's local cache layout
 (``weights.resolve_zoo_checkpoint``: no download; else ``model_weights.pth_file`` or ``--synthetic-weights``).  Every TEST.EVAL_PERIOD iterations the validation loss and the COCO bbox / segm AP (coco_eval.py, a
-restatement of pycocotools' COCOeval) of the `val` set are logged to metrics.json.
+restatement of pycocotools' COCOeval) of the `val` set are logged to metrics.json.  ``--train-stats`` adds detectron2's ten training
+diagnostics (rpn/num_pos_anchors .. mask_rcnn/false_negative), counted on the GPU, to every record: the logged iteration's own values
+(no 20-iteration median), rank 0's own counts.
 """
 from __future__ import annotations
 
@@ -279,6 +281,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "split into hi + lo fp16 planes, and the product runs on the fp16 matrix cores with an fp32 accumulator; "
                          "activations, bias and addends stay fp32, the stem and the mask deconvolution keep their fp32 kernels, and the "
                          "validation inference of the run follows the mode.  Refused when the run resolves to the fp16 trainer")
+    ap.add_argument("--train-stats", action="store_true",
+                    help="add detectron2's training diagnostics to every metrics.json record: rpn/num_pos_anchors, rpn/num_neg_anchors, "
+                         "roi_head/num_fg_samples, roi_head/num_bg_samples, fast_rcnn/cls_accuracy, fast_rcnn/fg_cls_accuracy, "
+                         "fast_rcnn/false_negative, mask_rcnn/accuracy, mask_rcnn/false_positive, mask_rcnn/false_negative.  They are counted on "
+                         "the GPU behind the loss stages and one 16-integer table is read on logged iterations.  The values are those of the "
+                         "logged iteration (no 20-iteration median) and, under data parallelism, rank 0's own.  Off by default")
     ap.add_argument("--val-ap", choices=("host", "device"), default="host",
                     help="where the validation AP's mask overlaps are counted.  host (default): every detection mask is copied back, every "
                          "ground-truth polygon rasterised on the host and the IoUs taken from the masks.  device: the ground truth is "
@@ -401,7 +409,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     if sv["min_size_sampling"] == "range" and len(sizes) == 2:
         sizes = list(range(sizes[0], sizes[1] + 1, 32))
     ms = MultiScaleTrainer(spec, W, first.shape, sizes, batch=per_rank, device=local_rank, loss_scale=args.loss_scale,
-                           mask_targets=args.mask_targets, wgrad=args.wgrad, dgrad=args.dgrad, fwd=args.fwd)
+                           mask_targets=args.mask_targets, wgrad=args.wgrad, dgrad=args.dgrad, fwd=args.fwd, train_stats=args.train_stats)
+    if args.train_stats:
+        log.info("train_stats: on (detectron2's training diagnostics counted on the GPU; the logged iteration's own values, no smoothing; "
+                 "rank 0's own counts)")
     log.info("mask_targets: %s", {"host": "host (sampled RoIs read back, rasterised on host threads)",
                                   "device": "device (polygons uploaded with the targets, rasterised on the GPU)"}[args.mask_targets])
     ms.set_sampling(sv["rpn_batch"], sv["rpn_pos"], sv["roi_batch"], sv["roi_pos"])
@@ -574,11 +585,16 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 dist.destroy_process_group()
             raise SystemExit(f"iteration {it}: non-finite loss on {'this' if bad else 'another'} rank; every rank stops")
         do_eval = sv["eval_period"] > 0 and ((it + 1) % sv["eval_period"] == 0 or it == max_iter - 1)
+        # the training step's diagnostics, read on iterations that will be logged and BEFORE the validation pass runs its own steps on
+        # the same trainer
+        logged = rank == 0 and ((it + 1) % args.log_period == 0 or it == max_iter - 1 or (do_eval and bool(val_recs)))
+        stats = trainer.train_stats() if (args.train_stats and logged) else {}
         vloss = validation_loss(it) if do_eval else None
         vap = validation_ap() if (do_eval and vloss is not None) else {}
         if rank == 0 and ((it + 1) % args.log_period == 0 or it == max_iter - 1 or vloss is not None):
             rec = {"iteration": it, "total_loss": float(sum(losses.values())), "lr": lr, "time": (time.time() - t0) / (it + 1), **losses,
                    "loss_scale": ms.loss_scale, "skipped_steps": skipped_steps}
+            rec.update(stats)
             if vloss is not None:
                 rec["validation_loss"] = vloss
                 rec.update(vap)
