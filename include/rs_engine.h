@@ -371,6 +371,29 @@ int rs_op_conv2d_wgrad_split(const void* dy, const void* in, float* grad, const 
                        void* stream);
 int rs_op_conv2d_wgrad_split_serves(int cin, int cout);
 
+/* Backward of the stem (stem_bwd.hip; a trainer with freeze_at 0 runs both).
+ * rs_op_maxpool3x3s2_bwd: gradient of max_pool2d(3, 2, 1) fused with the ReLU mask of the pool's input,
+ *   dx[n][iy][ix][c] = (x[n][iy][ix][c] > 0) * sum of dq[n][oy][ox][c] over the windows (oy, ox) whose argmax is (iy, ix).
+ * x: [n][hc+2*x_halo][wc+2*x_halo][c] the pool's input (post-ReLU), dq: [n][hq+2*q_halo][wq+2*q_halo][c] with hq = (hc-1)/2+1,
+ * wq = (wc-1)/2+1, dx: x's geometry; fp16, or float with f32 != 0; c a multiple of 8 (fp16) or 4 (fp32).  The argmax is ATen's
+ * (max_pool2d_with_indices): the window is scanned in (row, column) order, a later element replaces the current one only if it is
+ * strictly greater or NaN, padding positions never win.  The at most four windows of a pixel are summed in fp32 in ascending
+ * (oy, ox) order, ATen's CPU scatter order, so the result is defined bit for bit (fp16: one final rounding).  No atomics; every
+ * interior element of dx is written, the halo of no tensor is read or written. */
+int rs_op_maxpool3x3s2_bwd(const void* x, const void* dq, void* dx, int n, int hc, int wc, int c, int x_halo, int q_halo, int f32,
+                           void* stream);
+/* rs_op_stem_wgrad: weight gradient of the 7x7 stride-2 pad-3 stem convolution,
+ *   grad[co][(kh,kw,ci)] = scale[co] * sum_{n,y,x} dy[n][y][x][co] * x0[n][2y+kh-3][2x+kw-3][ci]
+ * in the stem's forward GEMM layout: fp32 [64][256], column (kh * 8 + kw) * 4 + ci (taps padded 7 -> 8 per row, channels to 4, K to
+ * 256).  The padding columns -- kw = 7, columns >= 224, ci >= cin -- are written as exact zeros.  dy: [n][hc+2*dy_halo][wc+2*dy_halo][64],
+ * x0: [n][2*hc+2*x_halo][2*wc+2*x_halo][4] with x_halo >= 3; both fp16 (rs_op_stem_wgrad) or both float (rs_op_stem_wgrad_f32).
+ * Exact products, fp32 accumulation, the pixel axis split into `splits` partial sums (<= 0: chosen by the library, at most 512) that
+ * are added in a fixed order: two calls give the same bits.  scale: [64] or null. */
+int rs_op_stem_wgrad(const void* dy, const void* x0, float* grad, const float* scale, int n, int hc, int wc, int cin, int dy_halo,
+                     int x_halo, int splits, void* stream);
+int rs_op_stem_wgrad_f32(const void* dy, const void* x0, float* grad, const float* scale, int n, int hc, int wc, int cin, int dy_halo,
+                         int x_halo, int splits, void* stream);
+
 /* Greedy NMS over `segments` independent lists of up to `cap` (<= 2048) boxes in priority order
  * (torchvision.ops.nms: suppress when the fp32 IoU > thresh). keep: [segments][cap] 0/1.
  * The kernels compare the fp32 IoU with `thresh` in fp32.  torchvision compares it with a double threshold t; a
@@ -530,6 +553,20 @@ int rs_host_mask_stats(const float* logits, const uint8_t* targets, const int32_
 typedef struct rs_trainer rs_trainer;
 int rs_trainer_create(const rs_spec* spec, const void* weights, size_t nbytes, int device_ordinal, int batch, int tile_h,
                       int tile_w, int tile_c, float loss_scale, rs_trainer** out);
+/* Creation-time options of a trainer (they change its graph).  freeze_at = MODEL.BACKBONE.FREEZE_AT: 2 (rs_trainer_create's value)
+ * freezes the stem and res2; 1 trains res2 as well (its blocks unfused in the forward engine, weight gradients of every res2 layer,
+ * gradient group "res2"); 0 also trains the stem convolution (unfused stem.conv1 + stem.maxpool in the forward engine, input
+ * gradients of res2.0 into "d:stem", then the stages bwd.stem.maxpool and bwd.stem.conv1.w, gradient group "stem").  The blob must
+ * carry the `.m32` / `.s` entries of the layers trained (weights.train_tensors with the same freeze_at).  Any other value:
+ * RS_ERR_UNSUPPORTED, the message names MODEL.BACKBONE.FREEZE_AT.  The new groups finish after "res3", in the order res2, stem
+ * (rs_trainer_bucket_info); in the flat buffers they lie in front of res3.  opts null = the defaults. */
+typedef struct rs_train_options {
+  int32_t struct_size;            /* sizeof(rs_train_options), ABI check */
+  int32_t freeze_at;
+} rs_train_options;
+int rs_trainer_create2(const rs_spec* spec, const void* weights, size_t nbytes, int device_ordinal, int batch, int tile_h,
+                       int tile_w, int tile_c, float loss_scale, const rs_train_options* opts, rs_trainer** out);
+int rs_trainer_freeze_at(rs_trainer* t);
 void rs_trainer_destroy(rs_trainer* t);
 rs_engine* rs_trainer_engine(rs_trainer* t);
 int rs_trainer_forward_trunk(rs_trainer* t, const uint8_t* tiles_dev, int n);
@@ -643,7 +680,8 @@ int rs_trainer_tensor_count(rs_trainer* t);
 int rs_trainer_tensor_name(rs_trainer* t, int i, char* name_out);
 /* Multi-scale training (INPUT.MIN_SIZE_TRAIN sampling "choice", R:31-38): build one trainer per network-input size (same
  * weights, spec.min_size_test = that size) and, when the size of the next batch differs from the previous one's, carry the
- * optimiser state over: master weights + momentum are copied device to device and dst's fp16 operands refolded. */
+ * optimiser state over: master weights + momentum are copied device to device and dst's fp16 operands refolded.  Trainers whose
+ * freeze_at differ have different parameter layouts and are refused (RS_ERR_ARG). */
 int rs_trainer_copy_state(rs_trainer* dst, rs_trainer* src);
 /* Data parallel: every rank all-reduces (SUM) the flat gradient buffer (rs_trainer_grad_buffer, rs_trainer_param_count floats,
  * device memory) and sets the divisor to the world size, which rs_trainer_apply_sgd applies together with the loss scale

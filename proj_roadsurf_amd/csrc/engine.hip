@@ -473,7 +473,8 @@ int rs_engine::build_stem(Graph& g) {
   const BlobEntry* stem_w = findw(bu + "stem.conv1f");          // fragment-ordered copy of the 64 x 256 stem matrix
   const BlobEntry* stem_b = find(bu + "stem.conv1.b");
   const BlobEntry* stem_si = split ? find(bu + "stem.conv1.wsi") : nullptr;
-  if (fuse_stem && !f32 && use_glds > 0 && S.stem_out_channels == 64 && x0.C == 4 && x0.pad == 3 && stem_w && stem_b && (!split || stem_si) &&
+  const bool stem_frozen = !frozen_fusions_only || freeze_at >= 1;    // a trainer that differentiates the stem keeps stem_conv
+  if (fuse_stem && stem_frozen && !f32 && use_glds > 0 && S.stem_out_channels == 64 && x0.C == 4 && x0.pad == 3 && stem_w && stem_b && (!split || stem_si) &&
       (long long)stem_w->dims[0] * stem_w->dims[1] == planes() * 7 * 4 * 64 * 8 && (pad_h & 3) == 0 && (pad_w & 3) == 0) {
     // conv 7x7 s2 + FrozenBN + ReLU + max-pool 3x3 s2 in one launch (stem_fused.hip): the 400 x 400 x 64 map never reaches HBM
     const double flops = 2.0 * h2 * w2 * 49.0 * S.in_channels * 64;
@@ -548,7 +549,7 @@ int rs_engine::build_bottleneck(ResCursor& r, int si, int bi) {
   // Block 0 of the stage has a projection shortcut from the 64-channel stem output at the same resolution: the tail then adds
   // Wsc . x0 as two more K steps instead of the identity residual (needs the folded conv3sc bias = conv3's + the shortcut's; the split
   // mode takes conv3 | shortcut as one [256][128] operand, conv3scp).
-  const bool may_fuse = !frozen_fusions_only || si == 0;          // a trainer fuses only inside the frozen res2
+  const bool may_fuse = !frozen_fusions_only || (si == 0 && freeze_at >= 2);   // a trainer fuses only inside the frozen res2
   const bool fuse_bneck = this->fuse_bneck && may_fuse, fuse_shortcut = this->fuse_shortcut && may_fuse;
   const bool can_tail = !f32 && fuse_bneck && stride == 1 && (!split || (rs_debug().conv_deep && use_glds > 0));
   const bool tail_proj = can_tail && fuse_shortcut && bi == 0 && bott == 64 && cout == 256 && cur.C == 64 && find(wn + ".conv3sc.b") != nullptr &&
@@ -1303,9 +1304,9 @@ int rs_spec_batched_nms(const rs_spec* spec) {
 
 }  // extern "C"
 
-// rs_engine_create, or with `for_trainer` the forward engine of an rs_trainer (rs_engine::frozen_fusions_only)
+// rs_engine_create, or with `for_trainer` the forward engine of an rs_trainer (rs_engine::frozen_fusions_only, ::freeze_at)
 int engine_create(const rs_spec* spec, const void* weights, size_t nbytes, int device_ordinal, int max_batch,
-                  int tile_h, int tile_w, int tile_c, void* stream, bool for_trainer, rs_engine** out) {
+                  int tile_h, int tile_w, int tile_c, void* stream, bool for_trainer, rs_engine** out, int freeze_at) {
   RS_CHECK(spec && weights && out, RS_ERR_ARG, "null argument");
   const int nms_mode = rs_spec_batched_nms(spec);     // checks struct_size: the current struct, or the one that ends before batched_nms (mode 0)
   if (nms_mode < 0) return nms_mode;
@@ -1339,7 +1340,9 @@ int engine_create(const rs_spec* spec, const void* weights, size_t nbytes, int d
   // stem and res2 (FREEZE_AT 2, what rs_trainer implements) keep the inference engine's fused stem and fused bottleneck tails
   // (the multi-map launches of the FPN output convolutions and of the RPN 3x3 stay: every map still gets its own output tensor; only the RPN heads
   //  leave the 3x3's epilogue, because the trainer differentiates through the 256-channel rpn_conv maps)
+  // (a trainer with FREEZE_AT below 2 differentiates res2 as well, and at 0 the stem: those then run unfused too)
   e->frozen_fusions_only = for_trainer;
+  e->freeze_at = for_trainer ? freeze_at : 2;
   e->fwd_split_capable = for_trainer && e->f32;      // the opt-in split forward of the fp32 trainer (rs_trainer_set_fwd_mode)
   e->use_graph = rs_debug().use_graph;   // measured: replay == eager (11.54 ms/step either way), so off by default
   if (stream) { e->stream = (hipStream_t)stream; e->own_stream = false; }

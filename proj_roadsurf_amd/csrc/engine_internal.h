@@ -277,6 +277,7 @@ struct rs_engine {
   int fuse_bneck = 1;
   int fuse_stem = 1;      // stem conv + ReLU + max-pool as one launch (inference engines, fp16 path)
   bool frozen_fusions_only = false;   // a trainer's forward engine: layer fusions only where nothing is differentiated (stem + res2 at FREEZE_AT 2)
+  int freeze_at = 2;                  // ... and its MODEL.BACKBONE.FREEZE_AT: below 2 res2 is built unfused, at 0 the stem too (inference engines: 2)
   int merge_levels = 1;   // FPN output convs / RPN 3x3 of all levels as one multi-map launch each (inference engines, fp16 path)
   long long forward_index = 0;
   // Saturation counts: one u64 per stage, indexed like `stages`; inference engines only (a trainer's forward engine: null).
@@ -303,6 +304,6 @@ struct rs_engine {
   std::map<int, hipGraphExec_t> graphs;
 };
 
-// rs_engine_create, or with `for_trainer` the forward engine of an rs_trainer (rs_engine::frozen_fusions_only)
+// rs_engine_create, or with `for_trainer` the forward engine of an rs_trainer (rs_engine::frozen_fusions_only, ::freeze_at)
 int engine_create(const rs_spec* spec, const void* weights, size_t nbytes, int device_ordinal, int max_batch,
-                  int tile_h, int tile_w, int tile_c, void* stream, bool for_trainer, rs_engine** out);
+                  int tile_h, int tile_w, int tile_c, void* stream, bool for_trainer, rs_engine** out, int freeze_at = 2);

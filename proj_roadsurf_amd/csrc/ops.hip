@@ -460,6 +460,44 @@ static int op_conv2d_wgrad(const void* dy, const void* x, float* grad, const flo
   return launch_conv_wgrad(p, s);
 }
 
+// backward of the stem's max-pool fused with its ReLU mask (stem_bwd.hip)
+int rs_op_maxpool3x3s2_bwd(const void* x, const void* dq, void* dx, int n, int hc, int wc, int c, int x_halo, int q_halo, int f32, void* stream) {
+  RS_CHECK(x && dq && dx, RS_ERR_ARG, "rs_op_maxpool3x3s2_bwd: null operand");
+  RS_CHECK(n >= 1 && hc >= 1 && wc >= 1 && c >= 1 && x_halo >= 0 && q_halo >= 0, RS_ERR_ARG,
+           "rs_op_maxpool3x3s2_bwd: geometry (%d x %d x %d x %d, halos %d / %d)", n, hc, wc, c, x_halo, q_halo);
+  PoolBwdParams p;
+  memset(&p, 0, sizeof p);
+  p.x = x; p.dq = dq; p.dx = dx;
+  p.N = n; p.Hc = hc; p.Wc = wc; p.Hq = (hc - 1) / 2 + 1; p.Wq = (wc - 1) / 2 + 1; p.C = c; p.x_halo = x_halo; p.q_halo = q_halo;
+  p.f32 = f32 ? 1 : 0;
+  return launch_maxpool3x3s2_bwd(p, (hipStream_t)stream);
+}
+// weight gradient of the stem convolution in its forward GEMM layout (stem_bwd.hip); the partial sums live for the call
+static int op_stem_wgrad(const void* dy, const void* x0, float* grad, const float* scale, int n, int hc, int wc, int cin, int dy_halo,
+                         int x_halo, int splits, void* stream, int f32) {
+  RS_CHECK(dy && x0 && grad, RS_ERR_ARG, "rs_op_stem_wgrad: null operand");
+  RS_CHECK(n >= 1 && hc >= 1 && wc >= 1 && (long long)n * hc * wc < (1ll << 31) - 8 && 4 / wc < hc, RS_ERR_ARG, "rs_op_stem_wgrad: %d x %d x %d pixels", n, hc, wc);
+  RS_CHECK(cin >= 1 && cin <= 4 && dy_halo >= 0 && x_halo >= 3, RS_ERR_ARG, "rs_op_stem_wgrad: %d input channels of 4, halos %d / %d (input: at least 3)", cin, dy_halo, x_halo);
+  RS_CHECK(splits <= RS_STEM_WGRAD_MAX_SPLITS, RS_ERR_ARG, "rs_op_stem_wgrad: %d splits, at most %d", splits, RS_STEM_WGRAD_MAX_SPLITS);
+  StemWgradParams p;
+  memset(&p, 0, sizeof p);
+  p.dy = dy; p.x0 = x0; p.scale = scale; p.grad = grad;
+  p.N = n; p.Hc = hc; p.Wc = wc; p.dy_halo = dy_halo; p.x_halo = x_halo; p.cin = cin;
+  p.splits = splits > 0 ? splits : stem_wgrad_splits((long long)n * hc * wc);
+  p.f32 = f32;
+  OpScratch scratch(stream);
+  { int rc = scratch.alloc((void**)&p.partial, (size_t)p.splits * 64 * RS_STEM_KPAD * 4); if (rc) return rc; }
+  return launch_stem_wgrad(p, (hipStream_t)stream);
+}
+int rs_op_stem_wgrad(const void* dy, const void* x0, float* grad, const float* scale, int n, int hc, int wc, int cin, int dy_halo,
+                     int x_halo, int splits, void* stream) {
+  return op_stem_wgrad(dy, x0, grad, scale, n, hc, wc, cin, dy_halo, x_halo, splits, stream, 0);
+}
+int rs_op_stem_wgrad_f32(const void* dy, const void* x0, float* grad, const float* scale, int n, int hc, int wc, int cin, int dy_halo,
+                         int x_halo, int splits, void* stream) {
+  return op_stem_wgrad(dy, x0, grad, scale, n, hc, wc, cin, dy_halo, x_halo, splits, stream, 1);
+}
+
 int rs_op_nms(const float* boxes, const int32_t* counts, const uint8_t* valid, uint8_t* keep, int segments, int cap,
               float thresh, void* stream) {
   RS_CHECK(boxes && counts && keep && segments > 0, RS_ERR_ARG, "bad argument");

@@ -80,6 +80,31 @@ int launch_bias_grad(const half_t* dy, long long rows, int C, int cout, float* g
                      int m_mul, float* scratch, int f32 = 0);
 int launch_subsample2_bwd(const half_t* d_coarse, half_t* d_fine, int N, int Hf, int Wf, int Hc, int Wc, int C, hipStream_t s, int f32 = 0);
 
+// ---- backward of the stem (stem_bwd.hip; MODEL.BACKBONE.FREEZE_AT 0)
+// max_pool2d(3, 2, 1) backward fused with the ReLU mask of its input: dx = (x > 0) * sum of dq over the windows whose argmax the pixel is
+struct PoolBwdParams {
+  const void* x;            // [N][Hc + 2 x_halo][Wc + 2 x_halo][C] the pool's input, post-ReLU (fp16, or fp32 with f32)
+  const void* dq;           // [N][Hq + 2 q_halo][Wq + 2 q_halo][C] gradient of the pooled map
+  void* dx;                 // x's geometry: every interior element written, the halo not touched
+  int N, Hc, Wc, Hq, Wq, C, x_halo, q_halo;
+  int f32;
+};
+int launch_maxpool3x3s2_bwd(const PoolBwdParams& p, hipStream_t s);
+// weight gradient of the 7x7 stride-2 pad-3 stem convolution in its forward GEMM layout [64][RS_STEM_KPAD]: column (kh * 8 + kw) * 4 + ci
+#define RS_STEM_KPAD 256
+#define RS_STEM_WGRAD_MAX_SPLITS 512
+struct StemWgradParams {
+  const void* dy;           // [N][Hc + 2 dy_halo][Wc + 2 dy_halo][64] gradient of the convolution output (fp16, or fp32 with f32)
+  const void* x0;           // [N][2 Hc + 2 x_halo][2 Wc + 2 x_halo][4] the network input, x_halo >= 3
+  const float* scale;       // [64] FrozenBN scale, or null
+  float* partial;           // [splits][64][RS_STEM_KPAD] scratch
+  float* grad;              // [64][RS_STEM_KPAD]; the columns of the eighth tap and of the channels >= cin are written as zeros
+  int N, Hc, Wc, dy_halo, x_halo, cin, splits;
+  int f32;
+};
+int stem_wgrad_splits(long long pixels);
+int launch_stem_wgrad(const StemWgradParams& p, hipStream_t s);
+
 // ---- label assignment (Matcher + subsample_labels) ----
 struct MatchParams {
   const float* boxes;       // [n_boxes][4] shared by all images (anchors), or [N][n_boxes][4] when per_image_boxes

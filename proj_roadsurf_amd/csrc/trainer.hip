@@ -44,6 +44,8 @@ struct TrainLayer {
 struct rs_trainer {
   rs_engine* eng = nullptr;
   bool f32 = false;              // reference-precision trainer (rs_spec.precision = 1): activations, gradients and GEMM operands are fp32
+  int freeze_at = 2;             // MODEL.BACKBONE.FREEZE_AT (rs_train_options): 2 = stem and res2 frozen, 1 = res2 trained, 0 = the stem too
+  int first_stage() const { return freeze_at < 2 ? 0 : 1; }   // first trainable residual stage (index into rs_spec.res_blocks)
   size_t esz() const { return f32 ? 4 : 2; }
   int edt() const { return f32 ? DT_F32 : DT_F16; }
   int N = 0;
@@ -181,8 +183,9 @@ struct rs_trainer {
   float grad_divisor = 1.f;      // extra division of the gradients in the SGD step (world size after an all-reduce SUM)
   long long step_count = 0;
   // ---- gradient buckets (data-parallel all-reduce overlapped with the backward pass).  The flat gradient buffer is laid out
-  // [res3 | res4 | res5 | fpn | heads] (add_layer order); a step finishes the groups in the order heads (box, mask, RPN:
-  // complete after rs_trainer_rpn_step), fpn, res5, res4, res3 (trunk backward).  Each bucket is one contiguous range with two
+  // [res3 | res4 | res5 | fpn | heads] (add_layer order; with FREEZE_AT below 2 [res2 | in front of it, at 0 [stem | in front of that);
+  // a step finishes the groups in the order heads (box, mask, RPN: complete after rs_trainer_rpn_step), fpn, res5, res4, res3
+  // (trunk backward), then res2 and stem where they are trained.  Each bucket is one contiguous range with two
   // events (chain stream / weight-gradient side stream) recorded right after its last writer has been enqueued, so a collective
   // on another stream can start behind them while the rest of the backward is still running (rs_trainer_bucket_wait).
   struct GradBucket {
@@ -194,9 +197,10 @@ struct rs_trainer {
   std::vector<GradBucket> buckets;     // readiness order
   hipEvent_t ev_foreign = nullptr;
   int bucket_of(const std::string& layer) const {
-    const char* pre[] = {"backbone.bottom_up.res5", "backbone.bottom_up.res4", "backbone.bottom_up.res3"};
+    const char* pre[] = {"backbone.bottom_up.res5", "backbone.bottom_up.res4", "backbone.bottom_up.res3", "backbone.bottom_up.res2",
+                         "backbone.bottom_up.stem"};
     if (layer.rfind("backbone.fpn", 0) == 0) return 1;
-    for (int i = 0; i < 3; ++i) if (layer.rfind(pre[i], 0) == 0) return 2 + i;
+    for (int i = 0; i < 5; ++i) if (layer.rfind(pre[i], 0) == 0) return 2 + i;
     return 0;
   }
   int build_buckets();
@@ -486,9 +490,10 @@ int rs_trainer::record_bucket(int b) {
 }
 
 int rs_trainer::build_buckets() {
-  static const char* names[] = {"heads", "fpn", "res5", "res4", "res3"};
-  buckets.assign(5, GradBucket());
-  std::vector<size_t> lo(5, (size_t)-1), hi(5, 0);
+  static const char* names[] = {"heads", "fpn", "res5", "res4", "res3", "res2", "stem"};
+  const int nb = 5 + (2 - freeze_at);          // FREEZE_AT 1 adds res2, 0 also stem: they finish after res3, in this order
+  buckets.assign(nb, GradBucket());
+  std::vector<size_t> lo(nb, (size_t)-1), hi(nb, 0);
   for (size_t i = 0; i < layers.size(); ++i) {
     const TrainLayer& L = layers[i];
     const int b = bucket_of(L.name);
@@ -497,7 +502,7 @@ int rs_trainer::build_buckets() {
     if (end > hi[b]) hi[b] = end;
   }
   size_t covered = 0;
-  for (int b = 0; b < 5; ++b) {
+  for (int b = 0; b < nb; ++b) {
     RS_CHECK(lo[b] != (size_t)-1, RS_ERR_ARG, "trainer: gradient bucket %s is empty", names[b]);
     buckets[b].name = names[b]; buckets[b].off = lo[b]; buckets[b].count = hi[b] - lo[b];
     covered += buckets[b].count;
@@ -556,7 +561,7 @@ int rs_trainer::fold_all() {
   return rc;
 }
 
-// the forward weights a fold rewrites (everything else the forward engine reads is frozen: the stem and res2 at FREEZE_AT 2)
+// the forward weights a fold rewrites (everything else the forward engine reads is frozen: the stem and res2 at FREEZE_AT 2, the stem at 1)
 std::set<const void*> rs_trainer::folded_weights() const {
   std::set<const void*> s;
   for (const TrainLayer& L : layers) s.insert((const void*)L.w_fwd);
@@ -568,23 +573,38 @@ int rs_trainer::split_w_bwd() {
   return launch_split_rows_table(dgs_table, dgs_n, dgs_rows, stream);
 }
 
-// FPN and res5..res3 backward from d:p2..d:p6 (FREEZE_AT 2: nothing flows into res2 / the stem)
+// FPN and res5..res3 backward from d:p2..d:p6 (FREEZE_AT 2: nothing flows into res2 / the stem); FREEZE_AT 1 goes on through res2
+// (weight gradients only in res2.0, whose input is the frozen stem output), FREEZE_AT 0 through res2.0 into d:stem, the max-pool and
+// the stem's weight gradient (stem_bwd.hip).  The stem has no input gradient.
 int rs_trainer::build_trunk_backward() {
   const rs_spec& S = eng->spec;
   int rc;
   const std::string bu = "backbone.bottom_up.";
-  // ---- layers (execution order of the forward): res3..res5, FPN
-  for (int si = 1; si < 4; ++si) {
+  const int first = first_stage();
+  const bool stem_trained = freeze_at == 0;
+  // ---- layers (execution order of the forward): [stem, res2,] res3..res5, FPN
+  if (stem_trained) {
+    // the stem's [64][RS_STEM_KPAD] GEMM operand as a 1x1 layer over its 256 K columns: the fold scales its rows, nothing transposes it
+    RS_CHECK(S.stem_out_channels == 64, RS_ERR_UNSUPPORTED, "trainer: MODEL.BACKBONE.FREEZE_AT 0 needs a 64-channel stem, this one has %d", S.stem_out_channels);
+    if ((rc = add_layer(bu + "stem.conv1", 1, 1, false, false))) return rc;
+    const TrainLayer& L = layers.back();
+    RS_CHECK(L.Cout == 64 && L.Kpad == RS_STEM_KPAD, RS_ERR_BLOB, "trainer: stem weight is %d x %d, expected 64 x %d", L.Cout, L.Kpad, RS_STEM_KPAD);
+    const size_t pf = (size_t)RS_STEM_WGRAD_MAX_SPLITS * 64 * RS_STEM_KPAD;
+    if (pf > partial_floats) partial_floats = pf;
+  }
+  for (int si = first; si < 4; ++si) {
+    // block 0 of a stage needs its two input-gradient operands when something trainable lies below it
+    const bool below = si > first || (si == 0 && stem_trained);
     for (int bi = 0; bi < S.res_blocks[si]; ++bi) {
       const std::string wn = bu + "res" + std::to_string(si + 2) + "." + std::to_string(bi);
-      if (bi == 0) { if ((rc = add_layer(wn + ".shortcut", 1, 1, si > 1, false))) return rc; }
-      if ((rc = add_layer(wn + ".conv1", 1, 1, !(si == 1 && bi == 0), false))) return rc;   // res3.0 reads the frozen res2
+      if (bi == 0) { if ((rc = add_layer(wn + ".shortcut", 1, 1, below, false))) return rc; }
+      if ((rc = add_layer(wn + ".conv1", 1, 1, bi > 0 || below, false))) return rc;   // FREEZE_AT 2: res3.0 reads the frozen res2
       if ((rc = add_layer(wn + ".conv2", 3, 3, true, false))) return rc;
       if ((rc = add_layer(wn + ".conv3", 1, 1, true, false))) return rc;
     }
   }
   for (int l = 2; l <= 5; ++l) {
-    if ((rc = add_layer("backbone.fpn_lateral" + std::to_string(l), 1, 1, l >= 3, true))) return rc;
+    if ((rc = add_layer("backbone.fpn_lateral" + std::to_string(l), 1, 1, l - 2 >= first, true))) return rc;
     if ((rc = add_layer("backbone.fpn_output" + std::to_string(l), 3, 3, true, true))) return rc;
   }
 
@@ -616,8 +636,8 @@ int rs_trainer::build_trunk_backward() {
                         l > 0 ? &dInner[l - 1] : nullptr))) return rc;
     if ((rc = add_wgrad("bwd.fpn_lateral" + ln + ".w", "backbone.fpn_lateral" + ln, dInner[l], res[l], 1, 0))) return rc;
   }
-  // ---- res5 .. res3
-  for (int si = 3; si >= 1; --si) {
+  // ---- res5 .. res3 (.. res2)
+  for (int si = 3; si >= first; --si) {
     const std::string sn = "res" + std::to_string(si + 2);
     const int nb = S.res_blocks[si];
     // gradient w.r.t. the stage output: lateral input gradient + what the next stage's first block scattered, ReLU-masked
@@ -629,11 +649,12 @@ int rs_trainer::build_trunk_backward() {
     for (int bi = nb - 1; bi >= 0; --bi) {
       const std::string nm = sn + "." + std::to_string(bi);
       const std::string wn = bu + nm;
-      const int stride = (bi == 0) ? 2 : 1;
+      const int stride = (bi == 0 && si > 0) ? 2 : 1;      // res2.0 is a projection block at the stem output's resolution
       Act t1, t2, x, dT1, dT2;
       if ((rc = fwd_act(nm + ".conv1", &t1))) return rc;
       if ((rc = fwd_act(nm + ".conv2", &t2))) return rc;
-      const std::string xin = bi == 0 ? "res" + std::to_string(si + 1) : (bi - 1 == nb - 1 ? sn : sn + "." + std::to_string(bi - 1) + ".out");
+      const std::string xin = bi == 0 ? (si == 0 ? std::string("stem") : "res" + std::to_string(si + 1))
+                                      : (bi - 1 == nb - 1 ? sn : sn + "." + std::to_string(bi - 1) + ".out");
       if ((rc = fwd_act(xin, &x))) return rc;
       if ((rc = grad_act(nm + ".conv1", &dT1))) return rc;
       if ((rc = grad_act(nm + ".conv2", &dT2))) return rc;
@@ -651,16 +672,63 @@ int rs_trainer::build_trunk_backward() {
         G = dX;
       } else {
         if ((rc = add_wgrad("bwd." + nm + ".shortcut.w", wn + ".shortcut", G, x, stride, 0))) return rc;
-        if (si > 1) {
+        if (si > first) {
           // projection block: both 1x1 stride-2 input gradients land on the even pixels of d(res_{si-1}) (zeroed before the
           // pass); the lateral input gradient of that stage adds them up and applies the ReLU mask
           Act dX;
           if ((rc = grad_act(xin, &dX, true))) return rc;
           if ((rc = add_dgrad("bwd." + nm + ".conv1.x", wn + ".conv1", dT1, dX, stride, 0, nullptr, nullptr, nullptr))) return rc;
           if ((rc = add_dgrad("bwd." + nm + ".shortcut.x", wn + ".shortcut", G, dX, stride, 0, &dX, nullptr, nullptr))) return rc;
+        } else if (si == 0 && stem_trained) {
+          // res2.0 at stride 1: the two input gradients cover every pixel of d:stem, the second adds the first.  The stem output is a
+          // max-pool's, so there is no mask here: the ReLU mask is applied on stem_conv by the pool's backward.
+          Act dX;
+          if ((rc = grad_act(xin, &dX))) return rc;
+          if ((rc = add_dgrad("bwd." + nm + ".conv1.x", wn + ".conv1", dT1, dX, 1, 0, nullptr, nullptr, nullptr))) return rc;
+          if ((rc = add_dgrad("bwd." + nm + ".shortcut.x", wn + ".shortcut", G, dX, 1, 0, &dX, nullptr, nullptr))) return rc;
         }
       }
     }
+  }
+  if (stem_trained) {
+    // ---- stem: d:stem -> max-pool + ReLU backward -> d:stem_conv -> weight gradient against the network input
+    Act sc, x0, dS, dSC;
+    if ((rc = fwd_act("stem_conv", &sc))) return rc;
+    if ((rc = fwd_act("net_input", &x0))) return rc;
+    if ((rc = grad_act("stem", &dS))) return rc;
+    if ((rc = grad_act("stem_conv", &dSC))) return rc;
+    RS_CHECK(sc.C == 64 && x0.C == 4 && x0.pad >= 3 && x0.H == 2 * sc.H && x0.W == 2 * sc.W && dS.C == sc.C, RS_ERR_ARG, "trainer: stem geometry");
+    PoolBwdParams pp;
+    memset(&pp, 0, sizeof pp);
+    pp.x = sc.p; pp.dq = dS.p; pp.dx = dSC.p;
+    pp.Hc = sc.H; pp.Wc = sc.W; pp.Hq = dS.H; pp.Wq = dS.W; pp.C = sc.C; pp.x_halo = sc.pad; pp.q_halo = dS.pad;
+    pp.f32 = f32 ? 1 : 0;
+    Stage sp;
+    sp.name = "bwd.stem.maxpool";
+    sp.fn = [pp](int n, hipStream_t s) mutable { pp.N = n; return launch_maxpool3x3s2_bwd(pp, s); };
+    bwd.push_back(sp);
+    const std::string layer = bu + "stem.conv1";
+    const TrainLayer& L = layers[lidx[layer]];
+    StemWgradParams wp;
+    memset(&wp, 0, sizeof wp);
+    wp.dy = dSC.p; wp.x0 = x0.p; wp.scale = L.scale;
+    wp.Hc = sc.H; wp.Wc = sc.W; wp.dy_halo = dSC.pad; wp.x_halo = x0.pad; wp.cin = S.in_channels;
+    wp.f32 = f32 ? 1 : 0;
+    rs_trainer* self = this;
+    const size_t w_off = L.w_off;
+    Stage sw;
+    sw.name = "bwd.stem.conv1.w";
+    sw.flops_per_image = 2.0 * sc.H * sc.W * 49.0 * S.in_channels * 64;
+    sw.fn = [wp, self, w_off](int n, hipStream_t s) mutable {
+      wp.N = n;
+      wp.partial = self->partial;
+      wp.grad = self->grad + w_off;
+      wp.splits = stem_wgrad_splits((long long)n * wp.Hc * wp.Wc);
+      return launch_stem_wgrad(wp, s);
+    };
+    sw.grad_side = true;
+    sw.bucket = bucket_of(layer);
+    bwd.push_back(sw);
   }
   return RS_OK;
 }
@@ -1202,7 +1270,18 @@ extern "C" {
 
 int rs_trainer_create(const rs_spec* spec, const void* weights, size_t nbytes, int device_ordinal, int batch, int tile_h, int tile_w,
                       int tile_c, float loss_scale, rs_trainer** out) {
+  return rs_trainer_create2(spec, weights, nbytes, device_ordinal, batch, tile_h, tile_w, tile_c, loss_scale, nullptr, out);
+}
+
+int rs_trainer_freeze_at(rs_trainer* t) { return t ? t->freeze_at : -1; }
+
+int rs_trainer_create2(const rs_spec* spec, const void* weights, size_t nbytes, int device_ordinal, int batch, int tile_h, int tile_w,
+                       int tile_c, float loss_scale, const rs_train_options* opts, rs_trainer** out) {
   RS_CHECK(spec && weights && out && loss_scale > 0.f, RS_ERR_ARG, "bad argument");
+  RS_CHECK(!opts || opts->struct_size == (int32_t)sizeof(rs_train_options), RS_ERR_ARG, "rs_trainer_create2: rs_train_options.struct_size %d, expected %d",
+           opts ? opts->struct_size : 0, (int)sizeof(rs_train_options));
+  const int freeze_at = opts ? opts->freeze_at : 2;
+  RS_CHECK(freeze_at >= 0 && freeze_at <= 2, RS_ERR_UNSUPPORTED, "trainer: MODEL.BACKBONE.FREEZE_AT %d (rs_train_options.freeze_at): 0, 1 and 2 are implemented", freeze_at);
   RS_CHECK(spec->precision == 0 || spec->precision == 1, RS_ERR_UNSUPPORTED, "trainer: precision %d", spec->precision);
   RS_CHECK(spec->num_classes <= RS_TRAIN_MAX_CLASSES, RS_ERR_UNSUPPORTED, "trainer: NUM_CLASSES %d > %d (more classes, up to %d, run in inference engines only)",
            spec->num_classes, RS_TRAIN_MAX_CLASSES, RS_MAX_CLASSES);
@@ -1210,7 +1289,8 @@ int rs_trainer_create(const rs_spec* spec, const void* weights, size_t nbytes, i
   t->f32 = spec->precision == 1;
   t->N = batch;
   t->loss_scale = loss_scale;
-  int rc = engine_create(spec, weights, nbytes, device_ordinal, batch, tile_h, tile_w, tile_c, nullptr, /*for_trainer=*/true, &t->eng);
+  t->freeze_at = freeze_at;
+  int rc = engine_create(spec, weights, nbytes, device_ordinal, batch, tile_h, tile_w, tile_c, nullptr, /*for_trainer=*/true, &t->eng, freeze_at);
   if (rc) { delete t; return rc; }
   t->stream = t->eng->stream;
   {
@@ -1758,7 +1838,8 @@ int rs_trainer_tensor_name(rs_trainer* t, int i, char* name_out) {
 // `dst` the optimiser state of the trainer that ran the previous step is copied over (two device-to-device copies of the flat
 // buffers) and dst's fp16 operands are refolded.
 int rs_trainer_copy_state(rs_trainer* dst, rs_trainer* src) {
-  RS_CHECK(dst && src && dst->n_params == src->n_params && dst->layers.size() == src->layers.size(), RS_ERR_ARG, "trainers differ in their parameter layout");
+  RS_CHECK(dst && src && dst->freeze_at == src->freeze_at, RS_ERR_ARG, "trainers differ in MODEL.BACKBONE.FREEZE_AT (%d and %d)", dst ? dst->freeze_at : -1, src ? src->freeze_at : -1);
+  RS_CHECK(dst->n_params == src->n_params && dst->layers.size() == src->layers.size(), RS_ERR_ARG, "trainers differ in their parameter layout");
   if (dst == src) return RS_OK;
   { int rc = src->join_side(); if (!rc) rc = dst->join_side(); if (rc) return rc; }
   RS_HIP(hipStreamSynchronize(src->stream));

@@ -190,6 +190,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.rs_op_conv2d_wgrad.argtypes = [vp, vp, vp, vp] + [i32] * 13 + [vp]
     lib.rs_op_conv2d_wgrad_split.argtypes = lib.rs_op_conv2d_wgrad.argtypes
     lib.rs_op_conv2d_wgrad_split_serves.argtypes = [i32, i32]
+    if hasattr(lib, "rs_op_stem_wgrad"):              # RS_ENGINE_LIB may name an older build
+        lib.rs_op_maxpool3x3s2_bwd.argtypes = [vp, vp, vp] + [i32] * 7 + [vp]
+        lib.rs_op_stem_wgrad.argtypes = [vp, vp, vp, vp] + [i32] * 7 + [vp]
+        lib.rs_op_stem_wgrad_f32.argtypes = lib.rs_op_stem_wgrad.argtypes
     if hasattr(lib, "rs_op_conv2d_dgrad_split"):      # RS_ENGINE_LIB may name an older build
         lib.rs_op_conv2d_dgrad_split.argtypes = [vp] * 7 + [i32] * 14 + [vp, vp]
         lib.rs_op_conv2d_dgrad_split_serves.argtypes = [i32, i32, i32, i32]
@@ -1153,6 +1157,12 @@ FWD_MODES = ("f32", "split")     # rs_trainer_set_fwd_mode 0 / 1
 RS_EVAL_DOES_NOT_FIT = 2       # include/rs_engine.h: rs_engine_fetch_eval_async, the batch's ground truth exceeds the device pool
 EVAL_GT_CAP = 128              # RS_EVAL_GT_CAP: ground truths per tile, and the row length of the count tables
 RS_POLYGONS_DO_NOT_FIT = 1     # include/rs_engine.h: rs_trainer_set_polygons, the batch's polygons exceed the device pool
+FREEZE_AT_VALUES = (0, 1, 2)   # MODEL.BACKBONE.FREEZE_AT a trainer implements (rs_train_options.freeze_at)
+
+
+class RsTrainOptions(C.Structure):
+    """include/rs_engine.h ``rs_train_options``."""
+    _fields_ = [("struct_size", C.c_int32), ("freeze_at", C.c_int32)]
 
 
 TRAIN_STATS_TABLE = 16         # csrc/train_stats.h TS_TABLE: int32 entries of the tensor "train_stats"
@@ -1190,6 +1200,12 @@ def train_stats_scalars(table: Sequence[int]) -> Dict[str, float]:
     return out
 
 
+def _check_freeze_at(freeze_at: int) -> int:
+    if isinstance(freeze_at, bool) or not isinstance(freeze_at, (int, np.integer)) or int(freeze_at) not in FREEZE_AT_VALUES:
+        raise ValueError(f"MODEL.BACKBONE.FREEZE_AT (freeze_at) must be one of {FREEZE_AT_VALUES}, got {freeze_at!r}")
+    return int(freeze_at)
+
+
 def _check_wgrad(wgrad: str, spec: "EngineSpec") -> None:
     if wgrad not in WGRAD_MODES:
         raise ValueError(f"wgrad must be one of {WGRAD_MODES}, got {wgrad!r}")
@@ -1219,8 +1235,13 @@ class Trainer:
 
     def __init__(self, spec: EngineSpec, weights: Dict[str, np.ndarray], tile_shape: Tuple[int, int, int], batch: int = 2,
                  device: int = 0, loss_scale: float = 1.0, lib_path: Optional[str] = None, mask_targets: str = "host", wgrad: str = "f32",
-                 dgrad: str = "f32", fwd: str = "f32", train_stats: bool = False):
-        """``train_stats``: count detectron2's training diagnostics (anchor and RoI sample counts, the box head's classification
+                 dgrad: str = "f32", fwd: str = "f32", train_stats: bool = False, freeze_at: int = 2):
+        """``freeze_at``: detectron2's ``MODEL.BACKBONE.FREEZE_AT``, fixed at creation because it changes the graph.  2 (default): the
+        stem and res2 are frozen.  1: res2 is trained too.  0: the stem convolution as well -- what a detector with a fourth input band
+        needs, whose stem channel no public checkpoint holds.  The forward engine then runs res2 (and at 0 the stem) unfused, the
+        backward goes on below res3, and the flat buffers gain the groups "res2" and "stem" (``buckets()``).
+
+        ``train_stats``: count detectron2's training diagnostics (anchor and RoI sample counts, the box head's classification
         accuracies, the mask head's pixel accuracies) on the GPU behind the loss stages of every step; ``train_stats()`` returns them
         under detectron2's names.  Off by default; losses and gradients are the same bits either way.  ``set_train_stats`` switches
         between steps.
@@ -1248,11 +1269,13 @@ class Trainer:
         _check_wgrad(wgrad, spec)
         _check_dgrad(dgrad, spec)
         _check_fwd(fwd, spec)
+        self.freeze_at = _check_freeze_at(freeze_at)
         self.mask_targets = mask_targets
         self.mask_target_fallbacks = 0
         self.lib = lib = load_library(lib_path)
         vp, i32 = C.c_void_p, C.c_int
         lib.rs_trainer_create.argtypes = [C.POINTER(RsSpec), vp, C.c_size_t, i32, i32, i32, i32, i32, C.c_float, C.POINTER(vp)]
+        lib.rs_trainer_create2.argtypes = [C.POINTER(RsSpec), vp, C.c_size_t, i32, i32, i32, i32, i32, C.c_float, C.POINTER(RsTrainOptions), C.POINTER(vp)]
         lib.rs_trainer_destroy.argtypes = [vp]
         lib.rs_trainer_destroy.restype = None
         lib.rs_trainer_engine.argtypes = [vp]
@@ -1302,12 +1325,13 @@ class Trainer:
         self.spec = spec
         self.tile_h, self.tile_w, self.tile_c = (int(x) for x in tile_shape)
         self.batch = int(batch)
-        blob = pack_weights(spec, weights, train=True)
+        blob = pack_weights(spec, weights, train=True, freeze_at=self.freeze_at)
         rs = make_rs_spec(spec)
         h = C.c_void_p()
         buf = (C.c_char * len(blob)).from_buffer_copy(blob)
-        _check(lib, lib.rs_trainer_create(C.byref(rs), buf, len(blob), device, self.batch, self.tile_h, self.tile_w, self.tile_c,
-                                          float(loss_scale), C.byref(h)), "rs_trainer_create")
+        opts = RsTrainOptions(C.sizeof(RsTrainOptions), self.freeze_at)
+        _check(lib, lib.rs_trainer_create2(C.byref(rs), buf, len(blob), device, self.batch, self.tile_h, self.tile_w, self.tile_c,
+                                           float(loss_scale), C.byref(opts), C.byref(h)), "rs_trainer_create2")
         self._h = h
         self._eng = C.c_void_p(lib.rs_trainer_engine(h))
         self.wgrad = "f32"
@@ -1605,7 +1629,7 @@ class Trainer:
         """Current weights under detectron2's checkpoint key names: ``base`` (the weights the trainer was created from) with
         every trainable tensor replaced by its fp32 master copy, converted back from the engine's GEMM layouts."""
         from .weights import master_to_d2
-        return master_to_d2(self.spec, base, lambda name: self.tensor(name))
+        return master_to_d2(self.spec, base, lambda name: self.tensor(name), freeze_at=self.freeze_at)
 
     def set_wgrad_mode(self, mode: str) -> None:
         """Weight-gradient product of the following steps: one of ``WGRAD_MODES``.  An fp16 trainer refuses "split" (``RsError``)."""
@@ -1707,12 +1731,13 @@ class MultiScaleTrainer:
 
     def __init__(self, spec: EngineSpec, weights: Dict[str, np.ndarray], tile_shape: Tuple[int, int, int], sizes: Sequence[int], batch: int = 1,
                  device: int = 0, loss_scale: float = 1024.0, mask_targets: str = "host", wgrad: str = "f32", dgrad: str = "f32",
-                 fwd: str = "f32", train_stats: bool = False):
+                 fwd: str = "f32", train_stats: bool = False, freeze_at: int = 2):
         if mask_targets not in MASK_TARGET_MODES:
             raise ValueError(f"mask_targets must be one of {MASK_TARGET_MODES}, got {mask_targets!r}")
         _check_wgrad(wgrad, spec)
         _check_dgrad(dgrad, spec)
         _check_fwd(fwd, spec)
+        self.freeze_at = _check_freeze_at(freeze_at)
         self.mask_targets = mask_targets
         self.train_stats_on = bool(train_stats)
         self.wgrad = wgrad
@@ -1773,7 +1798,8 @@ class MultiScaleTrainer:
         """The trainer for shortest-edge ``size``, holding the up-to-date optimiser state."""
         if size not in self._t:
             t = Trainer(self.spec.replace(min_size_test=int(size)), self.weights, self.tile_shape, self.batch, self.device, self.loss_scale,
-                        mask_targets=self.mask_targets, wgrad=self.wgrad, dgrad=self.dgrad, fwd=self.fwd, train_stats=self.train_stats_on)
+                        mask_targets=self.mask_targets, wgrad=self.wgrad, dgrad=self.dgrad, fwd=self.fwd, train_stats=self.train_stats_on,
+                        freeze_at=self.freeze_at)
             if self._sampling:
                 t.set_sampling(*self._sampling)
             if getattr(self, "_rpn_topk", None):

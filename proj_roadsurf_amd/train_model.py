@@ -74,12 +74,14 @@ def load_solver(d2_yaml: str) -> Dict[str, Any]:
         "amp": bool((s.get("AMP", {}) or {}).get("ENABLED", False)),
         "lr_scheduler": str(s.get("LR_SCHEDULER_NAME", "WarmupMultiStepLR")),
         "sampler_train": str((cfg.get("DATALOADER", {}) or {}).get("SAMPLER_TRAIN", "TrainingSampler")),
+        "freeze_at": int((m.get("BACKBONE", {}) or {}).get("FREEZE_AT", 2)),
     }
 
 
 # capacities of the training engine (csrc/trainer.hip): ground-truth boxes per image, mask-head entries per image,
 # RoI slots per image, RPN candidates per level
 GT_CAP, MASK_ENTRIES_CAP, ROI_CAP, RPN_PRE_TOPK_CAP, RPN_POST_TOPK_CAP = 128, 256, 1024, 2048, 1024
+FREEZE_AT_VALUES = (0, 1, 2)    # MODEL.BACKBONE.FREEZE_AT the trainer implements (engine.FREEZE_AT_VALUES; kept here so that validation needs no library)
 
 
 def validate_solver(sv: Dict[str, Any], num_classes: Optional[int] = None) -> None:
@@ -121,6 +123,9 @@ def validate_solver(sv: Dict[str, Any], num_classes: Optional[int] = None) -> No
         errs.append(f"RPN.POST_NMS_TOPK_TRAIN {sv['post_nms_topk_train']} outside [1, {RPN_POST_TOPK_CAP}]")
     if sv["min_size_sampling"] not in ("choice", "range"):
         errs.append(f"INPUT.MIN_SIZE_TRAIN_SAMPLING {sv['min_size_sampling']!r}")
+    if sv.get("freeze_at", 2) not in FREEZE_AT_VALUES:
+        errs.append(f"MODEL.BACKBONE.FREEZE_AT {sv['freeze_at']} (only {', '.join(str(v) for v in FREEZE_AT_VALUES)}: the stem convolution and res2 can be "
+                    "trained, res3 and above cannot be frozen)")
     if errs:
         raise SystemExit("unsupported training configuration:\n  " + "\n  ".join(errs))
 
@@ -399,6 +404,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                          "matrix cores; drop --fwd split or give --precision fp32")
     log.info("fwd: %s", {"f32": "f32 (forward products on the fp32 matrix cores)",
                          "split": "split (X and W as hi + lo fp16 planes, forward products on the fp16 matrix cores)"}[args.fwd])
+    log.info("freeze_at: %d (MODEL.BACKBONE.FREEZE_AT: %s)", sv["freeze_at"],
+             {0: "everything is trained, the stem convolution included", 1: "the stem is frozen, res2 is trained", 2: "the stem and res2 are frozen"}[sv["freeze_at"]])
     from .engine import MultiScaleTrainer      # fails loudly without librs_engine.so / a HIP device
     from .make_detections import read_tile
     first = read_tile(recs[0]["file_name"])
@@ -409,7 +416,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     if sv["min_size_sampling"] == "range" and len(sizes) == 2:
         sizes = list(range(sizes[0], sizes[1] + 1, 32))
     ms = MultiScaleTrainer(spec, W, first.shape, sizes, batch=per_rank, device=local_rank, loss_scale=args.loss_scale,
-                           mask_targets=args.mask_targets, wgrad=args.wgrad, dgrad=args.dgrad, fwd=args.fwd, train_stats=args.train_stats)
+                           mask_targets=args.mask_targets, wgrad=args.wgrad, dgrad=args.dgrad, fwd=args.fwd, train_stats=args.train_stats,
+                           freeze_at=sv["freeze_at"])
     if args.train_stats:
         log.info("train_stats: on (detectron2's training diagnostics counted on the GPU; the logged iteration's own values, no smoothing; "
                  "rank 0's own counts)")

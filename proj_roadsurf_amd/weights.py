@@ -488,16 +488,22 @@ def train_tensors(spec: EngineSpec, W: Dict[str, np.ndarray], freeze_at: int = 2
     return T
 
 
-def master_to_d2(spec: EngineSpec, base: Dict[str, np.ndarray], fetch) -> Dict[str, np.ndarray]:
+def master_to_d2(spec: EngineSpec, base: Dict[str, np.ndarray], fetch, freeze_at: int = 2) -> Dict[str, np.ndarray]:
     """Inverse of ``train_tensors``: ``fetch("m:<layer>.w" | "m:<layer>.b")`` -> detectron2-keyed tensors (the layout
-    ``DetectionCheckpointer`` saves and ``load_checkpoint`` reads), on top of a copy of ``base`` for the frozen tensors."""
+    ``DetectionCheckpointer`` saves and ``load_checkpoint`` reads), on top of a copy of ``base`` for the frozen tensors.
+    ``freeze_at``: the value the trainer was created with (the layers it holds master copies of).  The stem's [64][256] operand goes
+    back to (64, C, 7, 7): the eighth tap of every row and the padding channels are dropped."""
     out = {k: np.array(v, copy=True) for k, v in base.items()}
     shapes = {n: (cin, cout, k) for n, cin, cout, k, _ in conv_layers(spec)}
     has_norm = {n: hn for n, _, _, _, hn in conv_layers(spec)}
     A, K = spec.num_anchors, spec.num_classes
-    for name in trainable_layers(spec):
+    for name in trainable_layers(spec, freeze_at):
         m = fetch(f"m:{name}.w")
-        if name in shapes:
+        if name.endswith("stem.conv1"):
+            cin, cout, k = shapes[name]
+            t = m[:cout, : k * STEM_KW_PAD * STEM_CIN_PAD].reshape(cout, k, STEM_KW_PAD, STEM_CIN_PAD)[:, :, :k, :cin]
+            out[name + ".weight"] = np.ascontiguousarray(t.transpose(0, 3, 1, 2)).astype(np.float32)
+        elif name in shapes:
             cin, cout, k = shapes[name]
             out[name + ".weight"] = m[:cout, : k * k * cin].reshape(cout, k, k, cin).transpose(0, 3, 1, 2).astype(np.float32)
             if not has_norm[name]:
@@ -530,15 +536,16 @@ def master_to_d2(spec: EngineSpec, base: Dict[str, np.ndarray], fetch) -> Dict[s
     return out
 
 
-def pack_weights(spec: EngineSpec, W: Dict[str, np.ndarray], train: bool = False) -> bytes:
-    return serialize(packed_tensors(spec, W, train))
+def pack_weights(spec: EngineSpec, W: Dict[str, np.ndarray], train: bool = False, freeze_at: int = 2) -> bytes:
+    return serialize(packed_tensors(spec, W, train, freeze_at))
 
 
-def packed_tensors(spec: EngineSpec, W: Dict[str, np.ndarray], train: bool = False) -> Dict[str, np.ndarray]:
-    """Every tensor of the blob ``pack_weights`` serialises, by name (the precision modes add theirs to the fp16 set)."""
+def packed_tensors(spec: EngineSpec, W: Dict[str, np.ndarray], train: bool = False, freeze_at: int = 2) -> Dict[str, np.ndarray]:
+    """Every tensor of the blob ``pack_weights`` serialises, by name (the precision modes add theirs to the fp16 set).
+    ``freeze_at`` (with ``train``): MODEL.BACKBONE.FREEZE_AT of the trainer the blob is for."""
     T = engine_tensors(spec, W)
     if train:
-        T.update(train_tensors(spec, W))
+        T.update(train_tensors(spec, W, freeze_at))
     if spec.precision == "fp32":
         # fp32 validation mode: same layout, GEMM weights additionally kept in fp32 ("<layer>.w32")
         T32 = engine_tensors(spec, W, w_dtype=np.float32)
