@@ -870,6 +870,61 @@ int rs_engine_fetch_eval_async(rs_engine* e, int n, rs_dets* dets_host, const do
                                const int32_t* inst_first, const int32_t* tile_first, rs_eval_counts* counts_host);
 int rs_engine_fetch_eval_wait(rs_engine* e);
 
+/* ------------------------------------------------------------------ COCOeval's evaluateImg on the device (csrc/coco_match.h)
+ * The step after the counts: per tile, kind (0 bbox, 1 segm), area range (all, small, medium, large) and IoU threshold, the greedy
+ * matching of detections to ground truths that proj_roadsurf_amd/coco_eval.py match_images runs on the host, with identical flags.
+ * csrc/coco_match.h states the rule once, for the kernels (csrc/val_ap.hip) and the host restatement: box IoU in float64 in
+ * coco_eval.box_iou's operation order (detection boxes are the engine's float32 values widened, ground-truth boxes float64 XYXY),
+ * mask IoU from the three pixel counts, the compiler's correctly rounded float64 division, no mul+add contraction; a ground truth is
+ * ignored when its area (bbox: the box's, segm: the pixel count) is < lo or > hi of the range; detections per category by descending
+ * score, ties to the lower slot; a detection takes the unmatched ground truth of its category with the highest IoU >=
+ * min(threshold, 1 - 1e-10), kept ones before ignored ones, of equal IoUs the LATER one; a detection matched to an ignored ground
+ * truth, or unmatched with its own area outside the range, is ignored.  Crowd regions and annotated areas are not modelled (such a
+ * batch is matched on the host); max_dets is the slot count.
+ *
+ * Tables: det_boxes [n_tiles][slots][4], det_scores / det_classes [n_tiles][slots], det_count [n_tiles] as rs_dets; gt_boxes
+ * [instances][4] double, gt_classes [instances], tile t owning instances tile_first[t] .. tile_first[t+1]-1 (at most gt_cap are
+ * read); inter / det_area / gt_area as rs_op_mask_pair_counts writes them; iou_thrs = ten doubles on the HOST in both entries (they
+ * travel by value: coco_eval.IOU_THRS as numpy holds them, 0.8999999999999999 among them).  Out, with W = (slots + 31) / 32:
+ *   order        [n_tiles][slots] int32   position -> slot, sorted by (category, score descending, slot); a class outside
+ *                                         [0, num_classes) sorts behind every category; positions >= det_count hold -1
+ *   class_first  [n_tiles][num_classes + 1] int32   first position of each category in `order`
+ *   gt_per_class [n_tiles][num_classes] int32       ground truths per category
+ *   matched, ignored [n_tiles][2][4][10][W] uint32  bit p % 32 of word p / 32 = the flag of position p; padding bits zero
+ *   npig         [n_tiles][2][4][num_classes] int32 ground truths the range does not ignore
+ * rs_op_coco_match takes device pointers, enqueues on `stream` and does not wait; rs_host_coco_match takes the same arguments as host
+ * pointers and needs no device.  Both refuse, before anything is touched: a null table, n_tiles < 1, num_classes outside
+ * [1, RS_MAX_CLASSES], slots or gt_cap < 1 (RS_ERR_ARG); slots > 1024 or gt_cap > RS_EVAL_GT_CAP (RS_ERR_UNSUPPORTED). */
+int rs_op_coco_match(const float* det_boxes, const float* det_scores, const int32_t* det_classes, const int32_t* det_count,
+                     const double* gt_boxes, const int32_t* gt_classes, const int32_t* tile_first, const int32_t* inter,
+                     const int32_t* det_area, const int32_t* gt_area, const double* iou_thrs, int n_tiles, int num_classes, int slots,
+                     int gt_cap, int32_t* order, int32_t* class_first, int32_t* gt_per_class, uint32_t* matched, uint32_t* ignored,
+                     int32_t* npig, void* stream);
+int rs_host_coco_match(const float* det_boxes, const float* det_scores, const int32_t* det_classes, const int32_t* det_count,
+                       const double* gt_boxes, const int32_t* gt_classes, const int32_t* tile_first, const int32_t* inter,
+                       const int32_t* det_area, const int32_t* gt_area, const double* iou_thrs, int n_tiles, int num_classes, int slots,
+                       int gt_cap, int32_t* order, int32_t* class_first, int32_t* gt_per_class, uint32_t* matched, uint32_t* ignored,
+                       int32_t* npig);
+
+/* The same behind the engine's last forward: rs_engine_fetch_eval_match_async enqueues what rs_engine_fetch_eval_async enqueues
+ * (polygon upload, rasteriser, pair counts), then the upload of the batch's ground-truth boxes and classes (gt_boxes [tile_first[n]][4],
+ * gt_classes [tile_first[n]], host), the order pass and the match pass, and the copies of count / boxes / scores / classes and of the
+ * five tables (gt_cap = RS_EVAL_GT_CAP, slots = D, num_classes = the engine's) into caller-allocated (rs_host_alloc) buffers; the
+ * inter / area tables stay on the device.  The same pool, the same RS_EVAL_DOES_NOT_FIT conditions (rs_engine_eval_fits; also D >
+ * 1024) and the same rule that a batch that does not fit enqueues nothing.  rs_engine_fetch_eval_match_wait waits for the copies. */
+typedef struct rs_eval_matches {
+  int32_t* order;         /* [n][D] */
+  int32_t* class_first;   /* [n][K + 1] */
+  int32_t* gt_per_class;  /* [n][K] */
+  uint32_t* matched;      /* [n][2][4][10][(D + 31) / 32] */
+  uint32_t* ignored;      /* [n][2][4][10][(D + 31) / 32] */
+  int32_t* npig;          /* [n][2][4][K] */
+} rs_eval_matches;
+int rs_engine_fetch_eval_match_async(rs_engine* e, int n, rs_dets* dets_host, const double* polys, const int64_t* poly_off,
+                                     const int32_t* poly_len, const int32_t* inst_first, const int32_t* tile_first, const double* gt_boxes,
+                                     const int32_t* gt_classes, const double* iou_thrs, rs_eval_matches* matches_host);
+int rs_engine_fetch_eval_match_wait(rs_engine* e);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,8 @@ brute-force statement of the definitions (oracle/coco_ap_oracle.py: declarative 
 test infrastructure, never imported here) to 1e-9.  Masks are numpy bool arrays here (the engine's
 ``Instances.pred_masks`` / rasterised ground-truth polygons), boxes XYXY.  For ``segm`` an image may carry integer pixel counts
 instead of masks (``mask_inter`` / ``mask_area``, counted on the device: ``Engine.eval_counts``); the IoUs, and so the match records,
-are the same bits (``mask_iou_from_counts``)."""
+are the same bits (``mask_iou_from_counts``).  ``records_from_tables`` rebuilds an image's match records from the tables of the device
+matcher (csrc/coco_match.h, ``Engine.eval_matches``), which runs ``_evaluate_img`` itself on the GPU; ``accumulate`` takes either."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -136,6 +137,32 @@ def match_images(gts: Sequence[Dict], dets: Sequence[Dict], num_classes: int, io
                 rec[(c, a)] = _evaluate_img(ious, sc, d_area, g_area, crowd, rng, max_dets)
         out.append(rec)
     return out
+
+
+def records_from_tables(scores: np.ndarray, order: np.ndarray, class_first: np.ndarray, gt_per_class: np.ndarray, matched: np.ndarray,
+                        ignored: np.ndarray, npig: np.ndarray, iou_type: str = "bbox") -> Dict:
+    """The record ``match_images`` returns for one image, rebuilt from the tables the device matcher leaves for that tile
+    (csrc/coco_match.h; ``rs_op_coco_match``, ``Engine.eval_matches``): ``scores`` (D,) the tile's detection scores by slot, ``order``
+    (D,) position -> slot sorted by (category, score descending, slot), ``class_first`` (K + 1,) the first position of each category,
+    ``gt_per_class`` (K,), ``matched`` / ``ignored`` (2, 4, 10, W) uint32 with bit p % 32 of word p / 32 = position p (kind bbox /
+    segm x area range in ``AREA_RNG``'s order x IoU threshold), ``npig`` (2, 4, K).  Keys exist for the categories that have a
+    detection or a ground truth in the tile, as in ``match_images``."""
+    assert iou_type in ("bbox", "segm")
+    kind = 1 if iou_type == "segm" else 0
+    first = np.asarray(class_first).reshape(-1)
+    K, T = first.size - 1, len(IOU_THRS)
+    bits = [np.unpackbits(np.ascontiguousarray(t[kind], "<u4").view(np.uint8).reshape(len(AREA_RNG), T, -1), axis=2, bitorder="little").astype(bool)
+            for t in (np.asarray(matched), np.asarray(ignored))]
+    sc = np.asarray(scores, np.float64).reshape(-1)
+    rec: Dict = {}
+    for c in range(K):
+        p0, p1 = int(first[c]), int(first[c + 1])
+        if p1 == p0 and not gt_per_class[c]:
+            continue
+        s = sc[np.asarray(order[p0:p1], np.int64)]
+        for ai, a in enumerate(AREA_RNG):
+            rec[(c, a)] = (s, bits[0][ai, :, p0:p1], bits[1][ai, :, p0:p1], int(npig[kind, ai, c]))
+    return rec
 
 
 def accumulate(per_image: Sequence[Dict], num_classes: int) -> Dict[str, float]:

@@ -1206,6 +1206,21 @@ int rs_engine::ensure_eval_buffers() {
   return alloc((void**)&eval_pool, L.bytes);      // last: its presence says that all of the above exists
 }
 
+int rs_engine::ensure_match_buffers() {
+  if (match_order) return RS_OK;
+  const size_t cap = (size_t)max_batch * RS_EVAL_GT_CAP, K = (size_t)spec.num_classes, W = ((size_t)D + 31) / 32;
+  const size_t rows = (size_t)max_batch * CM_KINDS * CM_RANGES;
+  int rc;
+  if ((rc = alloc((void**)&match_gt_boxes, cap * 36))) return rc;    // [cap][4] doubles, then [cap] classes
+  if ((rc = alloc((void**)&match_class_first, (size_t)max_batch * (K + 1) * 4))) return rc;
+  if ((rc = alloc((void**)&match_gt_per_class, (size_t)max_batch * K * 4))) return rc;
+  if ((rc = alloc((void**)&match_matched, rows * CM_THRS * W * 4))) return rc;
+  if ((rc = alloc((void**)&match_ignored, rows * CM_THRS * W * 4))) return rc;
+  if ((rc = alloc((void**)&match_npig, rows * K * 4))) return rc;
+  RS_HIP(hipHostMalloc((void**)&match_pinned, cap * 36, hipHostMallocDefault));
+  return alloc((void**)&match_order, (size_t)max_batch * D * 4);     // last: its presence says that all of the above exists
+}
+
 // upload of the packed pool, rasteriser, pair counts: on the copy stream, behind the forward and in front of the result copies
 int rs_engine::launch_eval_counts(int n, const void* layout, hipStream_t s) {
   const MtLayout& L = *(const MtLayout*)layout;
@@ -1380,6 +1395,7 @@ void rs_engine_destroy(rs_engine* e) {
   if (e->h_poly_totals) (void)hipHostFree(e->h_poly_totals);
   if (e->ev_eval_upload) (void)hipEventDestroy(e->ev_eval_upload);
   if (e->eval_pinned) (void)hipHostFree(e->eval_pinned);
+  if (e->match_pinned) (void)hipHostFree(e->match_pinned);
   if (e->h_sat_copy) (void)hipHostFree(e->h_sat_copy);
   if (e->ev_results) (void)hipEventDestroy(e->ev_results);
   if (e->ev_copied) (void)hipEventDestroy(e->ev_copied);
@@ -1591,6 +1607,59 @@ int rs_engine_fetch_eval_async(rs_engine* e, int n, rs_dets* o, const double* po
 }
 
 int rs_engine_fetch_eval_wait(rs_engine* e) { return rs_engine_fetch_wait(e); }
+
+// The counts' fetch, then COCOeval's evaluateImg on them (coco_match.h): only detections and match tables travel.
+int rs_engine_fetch_eval_match_async(rs_engine* e, int n, rs_dets* o, const double* polys, const int64_t* poly_off, const int32_t* poly_len,
+                                     const int32_t* inst_first, const int32_t* tile_first, const double* gt_boxes, const int32_t* gt_classes,
+                                     const double* iou_thrs, rs_eval_matches* m) {
+  RS_CHECK(e && o && o->count && m && m->order && m->class_first && m->gt_per_class && m->matched && m->ignored && m->npig && iou_thrs &&
+           n >= 1 && n <= e->max_batch, RS_ERR_ARG, "rs_engine_fetch_eval_match_async: bad argument");
+  { int rc = rs_engine_eval_fits(e, n, poly_off, poly_len, inst_first, tile_first); if (rc) return rc; }
+  if (e->D > CM_MAX_SLOTS) return RS_EVAL_DOES_NOT_FIT;
+  const int n_inst = tile_first[n], K = e->spec.num_classes, D = e->D, W = (D + 31) / 32;
+  RS_CHECK(n_inst == 0 || (gt_boxes && gt_classes), RS_ERR_ARG, "rs_engine_fetch_eval_match_async: null ground-truth boxes or classes");
+  MtLayout L;
+  { int rc = mt_measure(polys, poly_off, poly_len, inst_first, n_inst, n, &L); if (rc) return rc; }
+  hipStream_t s = nullptr;
+  int rc;
+  if ((rc = e->ensure_eval_buffers())) return rc;
+  if ((rc = e->ensure_match_buffers())) return rc;
+  RS_CHECK(L.bytes <= e->eval_pool_bytes, RS_ERR_ARG, "validation polygons: %zu bytes packed, the pool holds %zu", L.bytes, e->eval_pool_bytes);
+  if (e->eval_upload_pending) { RS_HIP(hipEventSynchronize(e->ev_eval_upload)); e->eval_upload_pending = false; }
+  mt_pack(e->eval_pinned, L, polys, poly_off, poly_len, inst_first, tile_first);
+  const size_t cap = (size_t)e->max_batch * RS_EVAL_GT_CAP;          // n_inst <= n * RS_EVAL_GT_CAP <= cap: rs_engine_eval_fits
+  if (n_inst) {
+    memcpy(e->match_pinned, gt_boxes, (size_t)n_inst * 32);
+    memcpy(e->match_pinned + cap * 32, gt_classes, (size_t)n_inst * 4);
+  }
+  if ((rc = e->begin_fetch(&s))) return rc;
+  if (n_inst) {     // in front of the pool's upload: the event recorded behind that one frees both stagings
+    RS_HIP(hipMemcpyAsync(e->match_gt_boxes, e->match_pinned, (size_t)n_inst * 32, hipMemcpyHostToDevice, s));
+    RS_HIP(hipMemcpyAsync((uint8_t*)e->match_gt_boxes + cap * 32, e->match_pinned + cap * 32, (size_t)n_inst * 4, hipMemcpyHostToDevice, s));
+  }
+  if ((rc = e->launch_eval_counts(n, &L, s))) return rc;
+  CocoMatchParams q;
+  memset(&q, 0, sizeof q);
+  q.det_boxes = e->det_boxes; q.det_scores = e->det_scores; q.det_classes = e->det_classes; q.det_count = e->det_count;
+  q.gt_boxes = e->match_gt_boxes; q.gt_classes = (const int*)((const uint8_t*)e->match_gt_boxes + cap * 32); q.tile_first = (const int*)e->eval_pool;
+  q.inter = e->eval_inter; q.det_area = e->eval_det_area; q.gt_area = e->eval_gt_area;
+  q.order = e->match_order; q.class_first = e->match_class_first; q.gt_per_class = e->match_gt_per_class;
+  q.matched = e->match_matched; q.ignored = e->match_ignored; q.npig = e->match_npig;
+  for (int i = 0; i < CM_THRS; ++i) q.thrs[i] = iou_thrs[i];
+  q.n = n; q.K = K; q.D = D; q.g_cap = RS_EVAL_GT_CAP;
+  if ((rc = launch_coco_match(q, s))) return rc;
+  if ((rc = e->enqueue_dets(o, n, s, false))) return rc;
+  const size_t flags = (size_t)n * CM_KINDS * CM_RANGES * CM_THRS * W * 4;
+  RS_HIP(hipMemcpyAsync(m->order, e->match_order, (size_t)n * D * 4, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(m->class_first, e->match_class_first, (size_t)n * (K + 1) * 4, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(m->gt_per_class, e->match_gt_per_class, (size_t)n * K * 4, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(m->matched, e->match_matched, flags, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(m->ignored, e->match_ignored, flags, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(m->npig, e->match_npig, (size_t)n * CM_KINDS * CM_RANGES * K * 4, hipMemcpyDeviceToHost, s));
+  return e->end_fetch(s, nullptr);            // the tables live in their own buffers: detections and canvases are free for the next forward
+}
+
+int rs_engine_fetch_eval_match_wait(rs_engine* e) { return rs_engine_fetch_wait(e); }
 
 int rs_engine_fetch_wait(rs_engine* e) {
   RS_CHECK(e, RS_ERR_ARG, "null engine");

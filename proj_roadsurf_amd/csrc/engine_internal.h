@@ -120,6 +120,13 @@ struct rs_engine {
   int *eval_inter = nullptr, *eval_det_area = nullptr, *eval_gt_area = nullptr;
   hipEvent_t ev_eval_upload = nullptr;          // recorded behind the pool's upload: the staging may be packed again after it
   bool eval_upload_pending = false;
+  // match tables (rs_engine_fetch_eval_match_*): allocated on the first call that asks for them
+  uint8_t* match_pinned = nullptr;              // pinned staging: gt boxes [max_batch * RS_EVAL_GT_CAP][4] doubles, then their classes
+  double* match_gt_boxes = nullptr;             // device (one allocation with the classes behind the boxes)
+  int* match_order = nullptr;                   // device: the five tables of coco_match.h behind each other, see ensure_match_buffers
+  int *match_class_first = nullptr, *match_gt_per_class = nullptr, *match_npig = nullptr;
+  uint32_t *match_matched = nullptr, *match_ignored = nullptr;
+  int ensure_match_buffers();
 
   // the steps of a result fetch, in the order the fetch entries enqueue them (engine.hip)
   int ensure_crop_header();

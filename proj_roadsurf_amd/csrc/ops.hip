@@ -261,6 +261,45 @@ int rs_op_mask_pair_counts(const uint8_t* det_masks, const int32_t* det_count, i
   return launch_mask_pair_counts(q, (hipStream_t)stream);
 }
 
+// COCOeval's evaluateImg on caller-owned tables (see include/rs_engine.h): device pointers enqueued on `stream`, or host pointers
+static_assert(CM_MAX_CLASSES == RS_MAX_CLASSES && CM_MAX_GT == RS_EVAL_GT_CAP, "coco_match.h restates the header's capacities");
+static int coco_match_params(const char* who, CocoMatchParams* q, const float* det_boxes, const float* det_scores, const int32_t* det_classes,
+                             const int32_t* det_count, const double* gt_boxes, const int32_t* gt_classes, const int32_t* tile_first,
+                             const int32_t* inter, const int32_t* det_area, const int32_t* gt_area, const double* iou_thrs, int n_tiles,
+                             int num_classes, int slots, int gt_cap, int32_t* order, int32_t* class_first, int32_t* gt_per_class,
+                             uint32_t* matched, uint32_t* ignored, int32_t* npig) {
+  RS_CHECK(iou_thrs, RS_ERR_ARG, "%s: null table (the IoU thresholds)", who);
+  memset(q, 0, sizeof *q);
+  q->det_boxes = det_boxes; q->det_scores = det_scores; q->det_classes = det_classes; q->det_count = det_count;
+  q->gt_boxes = gt_boxes; q->gt_classes = gt_classes; q->tile_first = tile_first; q->inter = inter; q->det_area = det_area; q->gt_area = gt_area;
+  q->order = order; q->class_first = class_first; q->gt_per_class = gt_per_class; q->matched = matched; q->ignored = ignored; q->npig = npig;
+  for (int i = 0; i < CM_THRS; ++i) q->thrs[i] = iou_thrs[i];
+  q->n = n_tiles; q->K = num_classes; q->D = slots; q->g_cap = gt_cap;
+  return coco_match_check(who, *q);
+}
+int rs_op_coco_match(const float* det_boxes, const float* det_scores, const int32_t* det_classes, const int32_t* det_count,
+                     const double* gt_boxes, const int32_t* gt_classes, const int32_t* tile_first, const int32_t* inter,
+                     const int32_t* det_area, const int32_t* gt_area, const double* iou_thrs, int n_tiles, int num_classes, int slots,
+                     int gt_cap, int32_t* order, int32_t* class_first, int32_t* gt_per_class, uint32_t* matched, uint32_t* ignored,
+                     int32_t* npig, void* stream) {
+  CocoMatchParams q;
+  { int rc = coco_match_params("rs_op_coco_match", &q, det_boxes, det_scores, det_classes, det_count, gt_boxes, gt_classes, tile_first, inter, det_area,
+                               gt_area, iou_thrs, n_tiles, num_classes, slots, gt_cap, order, class_first, gt_per_class, matched, ignored, npig);
+    if (rc) return rc; }
+  return launch_coco_match(q, (hipStream_t)stream);
+}
+int rs_host_coco_match(const float* det_boxes, const float* det_scores, const int32_t* det_classes, const int32_t* det_count,
+                       const double* gt_boxes, const int32_t* gt_classes, const int32_t* tile_first, const int32_t* inter,
+                       const int32_t* det_area, const int32_t* gt_area, const double* iou_thrs, int n_tiles, int num_classes, int slots,
+                       int gt_cap, int32_t* order, int32_t* class_first, int32_t* gt_per_class, uint32_t* matched, uint32_t* ignored,
+                       int32_t* npig) {
+  CocoMatchParams q;
+  { int rc = coco_match_params("rs_host_coco_match", &q, det_boxes, det_scores, det_classes, det_count, gt_boxes, gt_classes, tile_first, inter, det_area,
+                               gt_area, iou_thrs, n_tiles, num_classes, slots, gt_cap, order, class_first, gt_per_class, matched, ignored, npig);
+    if (rc) return rc; }
+  return host_coco_match(q);          // val_ap.hip: the float64 arithmetic is compiled there, without mul+add contraction
+}
+
 int rs_op_conv2d_dgrad(const void* dy, const void* w_t, void* dx, const void* res, const float* res32, const void* mask,
                        const void* down, int n, int hi, int wi, int cin, int ho, int wo, int cout, int kh, int kw, int stride,
                        int pad, int kpad, int halo, int variant, void* stream) {

@@ -4,6 +4,7 @@
 #include "common.h"
 // after common.h: the HIP runtime header defines what MT_HD expands to
 #include "canvas_raster.h"
+#include "coco_match.h"
 
 // One mask per instance, [n_inst][side][(side + 7) / 8] bytes, bit x % 8 of byte x / 8 = pixel x, padding bits zero: bit for bit
 // rs_rasterize_polygons_within_box(polygons of the instance, box (0, 0, side, side), mask_size side).  Tables as MaskTargetsParams
@@ -33,3 +34,33 @@ struct PairCountParams {
   long long bytes;
 };
 int launch_mask_pair_counts(const PairCountParams& p, hipStream_t s);
+
+// COCOeval's evaluateImg for every tile of a batch, bbox and segm (coco_match.h states the rule and the layout of the five tables).
+// Detections as the engine holds them ([n][D] slots, the first det_count[tile] in use); ground truths tile_first[tile] ..
+// tile_first[tile + 1] - 1 of gt_boxes [instances][4] (XYXY, float64) / gt_classes [instances], at most g_cap per tile; inter /
+// det_area / gt_area as PairCountParams writes them.  thrs: the ten IoU thresholds, carried by value.
+struct CocoMatchParams {
+  const float* det_boxes;   // [n][D][4]
+  const float* det_scores;  // [n][D]
+  const int* det_classes;   // [n][D]
+  const int* det_count;     // [n]
+  const double* gt_boxes;
+  const int* gt_classes;
+  const int* tile_first;    // [n + 1]
+  const int* inter;         // [n][D][g_cap]
+  const int* det_area;      // [n][D]
+  const int* gt_area;       // [n][g_cap]
+  int* order;               // [n][D]
+  int* class_first;         // [n][K + 1]
+  int* gt_per_class;        // [n][K]
+  uint32_t* matched;        // [n][2][4][10][W]
+  uint32_t* ignored;        // [n][2][4][10][W]
+  int* npig;                // [n][2][4][K]
+  double thrs[CM_THRS];
+  int n, K, D, g_cap;
+};
+// both refuse (before anything is touched) null tables, K outside [1, RS_MAX_CLASSES], D outside [1, CM_MAX_SLOTS], g_cap outside
+// [1, CM_MAX_GT]; `who` names the entry in the error text
+int coco_match_check(const char* who, const CocoMatchParams& p);
+int launch_coco_match(const CocoMatchParams& p, hipStream_t s);       // device pointers; enqueues the order pass and the match pass
+int host_coco_match(const CocoMatchParams& p);                        // host pointers; the plain loops of coco_eval._evaluate_img

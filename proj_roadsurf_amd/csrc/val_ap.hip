@@ -1,10 +1,14 @@
 // Validation AP on the device: the two kernels between the engine's bit-packed detection masks and the integer
-// tables coco_eval.match_images takes for `segm`.
+// tables coco_eval.match_images takes for `segm`, and the two that run match_images' own step (COCOeval's evaluateImg) behind them.
 //   canvas_raster_kernel      ground-truth polygons -> bit-packed canvases, bit for bit the host's rs_rasterize_polygons_within_box at
 //                             box (0, 0, side, side): the per-column closed form of canvas_raster.h, fp64 in the host's operand order
 //                             (compiled without mul+add contraction), integer LDS atomics only.
 //   mask_pair_counts_kernel   popcounts of detection AND ground truth for every pair of every tile of a batch, with both sides' own
 //                             areas.  Integers only.
+//   coco_order_kernel         per tile the detections' order by (category, score descending, slot) and the per-category counts.
+//   coco_match_kernel         one wave per (tile, kind, area range, IoU threshold): the greedy matching over coco_match.h's rules, float64
+//                             IoUs with the compiler's correctly rounded division, flags as bit words.  No atomics.
+// host_coco_match is the same rule as plain host loops (rs_host_coco_match); it lives here for the compile flags.
 #include "val_ap.h"
 
 namespace {
@@ -112,7 +116,243 @@ __global__ __launch_bounds__(256) void mask_pair_counts_kernel(const PairCountPa
   if (tid == 0) p.det_area[(long long)t * p.D + d] = s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
 
+// ---- COCOeval's evaluateImg (coco_match.h) ----
+
+// the ground truths of tile t that the kernels read: their first instance and their number, clamped to the capacity
+__device__ __forceinline__ int cm_tile_gts(const CocoMatchParams& p, int t, int* g0) {
+  *g0 = p.tile_first[t];
+  const int G = p.tile_first[t + 1] - *g0;
+  return G > p.g_cap ? p.g_cap : (G < 0 ? 0 : G);
+}
+__device__ __forceinline__ int cm_tile_dets(const CocoMatchParams& p, int t) {
+  const int c = p.det_count[t];
+  return c > p.D ? p.D : (c < 0 ? 0 : c);
+}
+// the area the range is checked against: bbox = the box's own in float64, segm = the pixel count
+__device__ __forceinline__ double cm_gt_area(const CocoMatchParams& p, int kind, int t, int g0, int g) {
+  return kind ? (double)p.gt_area[(long long)t * p.g_cap + g] : cm_box_area(p.gt_boxes + 4ll * (g0 + g));
+}
+
+// Order pass, one workgroup per tile: the rank of every detection by counting those that stand before it (cm_before), the first
+// position of every category, the ground truths per category and those each range keeps.  Every loop runs to a clamped count.
+__global__ __launch_bounds__(256) void coco_order_kernel(const CocoMatchParams p) {
+  __shared__ int s_cls[CM_MAX_SLOTS];
+  __shared__ float s_score[CM_MAX_SLOTS];
+  __shared__ int s_order[CM_MAX_SLOTS];
+  const int t = blockIdx.x, tid = threadIdx.x, K = p.K, D = p.D;
+  const int n = cm_tile_dets(p, t);
+  int g0;
+  const int G = cm_tile_gts(p, t, &g0);
+  for (int i = tid; i < D; i += 256) {
+    s_order[i] = -1;
+    if (i < n) {
+      s_cls[i] = cm_class(p.det_classes[(long long)t * D + i], K);
+      s_score[i] = p.det_scores[(long long)t * D + i];
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < n; i += 256) {
+    const int ci = s_cls[i];
+    const float si = s_score[i];
+    int rank = 0;
+    for (int j = 0; j < n; ++j) rank += cm_before(s_cls[j], s_score[j], j, ci, si, i);
+    s_order[rank] = i;                            // rank < n; scores that are not ordered (NaN) may share one, the others stay -1
+  }
+  for (int c = tid; c <= K; c += 256) {
+    int first = 0;
+    for (int j = 0; j < n; ++j) first += s_cls[j] < c;
+    p.class_first[(long long)t * (K + 1) + c] = first;
+  }
+  for (int c = tid; c < K; c += 256) {
+    int k = 0;
+    for (int g = 0; g < G; ++g) k += p.gt_classes[g0 + g] == c;
+    p.gt_per_class[(long long)t * K + c] = k;
+  }
+  for (int i = tid; i < CM_KINDS * CM_RANGES * K; i += 256) {
+    const int c = i % K, a = (i / K) % CM_RANGES, kind = i / (K * CM_RANGES);
+    int k = 0;
+    for (int g = 0; g < G; ++g) k += p.gt_classes[g0 + g] == c && !cm_out_of_range(cm_gt_area(p, kind, t, g0, g), a);
+    p.npig[(long long)t * CM_KINDS * CM_RANGES * K + i] = k;
+  }
+  __syncthreads();
+  for (int i = tid; i < D; i += 256) p.order[(long long)t * D + i] = s_order[i];
+}
+
+// Match pass, one wave per (tile, kind, area range, threshold).  The detections are walked in `order`; lane l holds ground truths l
+// and l + 64 of the tile (class, ignore flag, matched flag, box) in registers, computes its candidates' IoUs against the detection and
+// the wave reduces them to the one cm_replaces ranks highest.  The flags collect in LDS, one bit per position.
+__global__ __launch_bounds__(64) void coco_match_kernel(const CocoMatchParams p) {
+  __shared__ uint32_t s_m[CM_MAX_SLOTS / 32];
+  __shared__ uint32_t s_i[CM_MAX_SLOTS / 32];
+  const int t = blockIdx.y, lane = threadIdx.x, K = p.K, D = p.D, W = (D + 31) >> 5;
+  const int ti = blockIdx.x % CM_THRS, a = (blockIdx.x / CM_THRS) % CM_RANGES, kind = blockIdx.x / (CM_THRS * CM_RANGES);
+  const double need = cm_floor(p.thrs[ti]);
+  const int n = cm_tile_dets(p, t);
+  int g0;
+  const int G = cm_tile_gts(p, t, &g0);
+  for (int w = lane; w < W; w += 64) s_m[w] = s_i[w] = 0;
+  int gcls[2], grank[2];                          // grank: 2 = kept by the range, 1 = ignored, 0 = no such ground truth or matched
+  double gbox[2][4];
+  int garea[2];
+  for (int q = 0; q < 2; ++q) {
+    const int g = lane + 64 * q;
+    gcls[q] = -1; grank[q] = 0; garea[q] = 0;
+    gbox[q][0] = gbox[q][1] = gbox[q][2] = gbox[q][3] = 0.0;
+    if (g < G) {
+      gcls[q] = p.gt_classes[g0 + g];
+      grank[q] = cm_out_of_range(cm_gt_area(p, kind, t, g0, g), a) ? 1 : 2;
+      if (kind) garea[q] = p.gt_area[(long long)t * p.g_cap + g];
+      else for (int k = 0; k < 4; ++k) gbox[q][k] = p.gt_boxes[4ll * (g0 + g) + k];
+    }
+  }
+  __syncthreads();
+  for (int pos = 0; pos < n; ++pos) {
+    const int slot = p.order[(long long)t * D + pos];                // uniform
+    if (slot < 0 || slot >= D) continue;
+    const int c = p.det_classes[(long long)t * D + slot];
+    if (c < 0 || c >= K) continue;
+    double db[4];
+    for (int k = 0; k < 4; ++k) db[k] = (double)p.det_boxes[((long long)t * D + slot) * 4 + k];
+    const int darea = kind ? p.det_area[(long long)t * D + slot] : 0;
+    const int* irow = p.inter + ((long long)t * D + slot) * p.g_cap;
+    int rank = 0, who = -1;
+    double iou = 0.0;
+    for (int q = 0; q < 2; ++q) {
+      const int g = lane + 64 * q;
+      if (grank[q] == 0 || gcls[q] != c) continue;
+      const double v = kind ? cm_mask_iou(irow[g], darea, garea[q]) : cm_box_iou(db, gbox[q]);
+      if (v >= need && cm_replaces(grank[q], v, g, rank, iou, who)) { rank = grank[q]; iou = v; who = g; }
+    }
+    for (int off = 32; off > 0; off >>= 1) {      // butterfly: every lane ends with the winner
+      const int r2 = __shfl_xor(rank, off), w2 = __shfl_xor(who, off);
+      const double v2 = __shfl_xor(iou, off);
+      if (r2 > 0 && cm_replaces(r2, v2, w2, rank, iou, who)) { rank = r2; iou = v2; who = w2; }
+    }
+    bool ig;
+    if (rank > 0) {
+      ig = rank == 1;
+      if ((who & 63) == lane) grank[who >> 6] = 0;                   // matched: out of every later detection's walk
+    } else {
+      ig = cm_out_of_range(kind ? (double)darea : cm_box_area(db), a);
+    }
+    if (lane == 0) {
+      if (rank > 0) s_m[pos >> 5] |= 1u << (pos & 31);
+      if (ig) s_i[pos >> 5] |= 1u << (pos & 31);
+    }
+  }
+  __syncthreads();
+  const long long row = (((long long)t * CM_KINDS + kind) * CM_RANGES + a) * CM_THRS + ti;
+  for (int w = lane; w < W; w += 64) {
+    p.matched[row * W + w] = s_m[w];
+    p.ignored[row * W + w] = s_i[w];
+  }
+}
+
 }  // namespace
+
+int coco_match_check(const char* who, const CocoMatchParams& p) {
+  RS_CHECK(p.det_boxes && p.det_scores && p.det_classes && p.det_count && p.gt_boxes && p.gt_classes && p.tile_first && p.inter && p.det_area && p.gt_area && p.order &&
+           p.class_first && p.gt_per_class && p.matched && p.ignored && p.npig, RS_ERR_ARG, "%s: null table", who);
+  RS_CHECK(p.n >= 1 && p.n <= 65535, RS_ERR_ARG, "%s: %d tiles (1..65535)", who, p.n);
+  RS_CHECK(p.K >= 1 && p.K <= CM_MAX_CLASSES, RS_ERR_ARG, "%s: %d classes outside [1, %d]", who, p.K, CM_MAX_CLASSES);
+  RS_CHECK(p.D >= 1 && p.g_cap >= 1, RS_ERR_ARG, "%s: %d slots, %d ground truths per tile", who, p.D, p.g_cap);
+  RS_CHECK(p.D <= CM_MAX_SLOTS, RS_ERR_UNSUPPORTED, "%s: %d slots per tile, the kernels hold %d", who, p.D, CM_MAX_SLOTS);
+  RS_CHECK(p.g_cap <= CM_MAX_GT, RS_ERR_UNSUPPORTED, "%s: gt_cap %d, the kernels hold %d ground truths per tile", who, p.g_cap, CM_MAX_GT);
+  return RS_OK;
+}
+
+int launch_coco_match(const CocoMatchParams& p, hipStream_t s) {
+  { int rc = coco_match_check("coco match", p); if (rc) return rc; }
+  hipLaunchKernelGGL(coco_order_kernel, dim3((unsigned)p.n), dim3(256), 0, s, p);
+  RS_HIP(hipGetLastError());
+  hipLaunchKernelGGL(coco_match_kernel, dim3(CM_KINDS * CM_RANGES * CM_THRS, (unsigned)p.n), dim3(64), 0, s, p);
+  RS_HIP(hipGetLastError());
+  return RS_OK;
+}
+
+// The host restatement: coco_eval.match_images / _evaluate_img as plain loops over coco_match.h's per-element rules.  The order is
+// built by the kernel's counting rule; the greedy walk is Python's own (kept ground truths, then ignored ones, `best` carried along,
+// the early stop), not the kernel's reduction.
+int host_coco_match(const CocoMatchParams& p) {
+  { int rc = coco_match_check("rs_host_coco_match", p); if (rc) return rc; }
+  const int K = p.K, D = p.D, W = (D + 31) >> 5, cap = p.g_cap;
+  for (int t = 0; t < p.n; ++t) {
+    const int n = p.det_count[t] > D ? D : (p.det_count[t] < 0 ? 0 : p.det_count[t]);
+    const int g0 = p.tile_first[t];
+    int G = p.tile_first[t + 1] - g0;
+    G = G > cap ? cap : (G < 0 ? 0 : G);
+    const int* cls = p.det_classes + (size_t)t * D;
+    const float* sc = p.det_scores + (size_t)t * D;
+    int* order = p.order + (size_t)t * D;
+    int* first = p.class_first + (size_t)t * (K + 1);
+    for (int i = 0; i < D; ++i) order[i] = -1;
+    for (int i = 0; i < n; ++i) {
+      int rank = 0;
+      for (int j = 0; j < n; ++j) rank += cm_before(cm_class(cls[j], K), sc[j], j, cm_class(cls[i], K), sc[i], i);
+      order[rank] = i;
+    }
+    for (int c = 0; c <= K; ++c) {
+      first[c] = 0;
+      for (int j = 0; j < n; ++j) first[c] += cm_class(cls[j], K) < c;
+    }
+    for (int c = 0; c < K; ++c) {
+      int k = 0;
+      for (int g = 0; g < G; ++g) k += p.gt_classes[g0 + g] == c;
+      p.gt_per_class[(size_t)t * K + c] = k;
+    }
+    for (int kind = 0; kind < CM_KINDS; ++kind)
+      for (int a = 0; a < CM_RANGES; ++a) {
+        bool ign[CM_MAX_GT];
+        int walk[CM_MAX_GT];                      // np.argsort(g_ignore, kind="mergesort"): kept ones first, each group in order
+        int nw = 0;
+        for (int g = 0; g < G; ++g)
+          ign[g] = cm_out_of_range(kind ? (double)p.gt_area[(size_t)t * cap + g] : cm_box_area(p.gt_boxes + 4 * (size_t)(g0 + g)), a);
+        for (int pass = 0; pass < 2; ++pass)
+          for (int g = 0; g < G; ++g)
+            if (ign[g] == (pass == 1)) walk[nw++] = g;
+        int* npig = p.npig + (((size_t)t * CM_KINDS + kind) * CM_RANGES + a) * K;
+        for (int c = 0; c < K; ++c) {
+          npig[c] = 0;
+          for (int g = 0; g < G; ++g) npig[c] += p.gt_classes[g0 + g] == c && !ign[g];
+        }
+        for (int ti = 0; ti < CM_THRS; ++ti) {
+          const size_t row = ((((size_t)t * CM_KINDS + kind) * CM_RANGES + a) * CM_THRS + ti) * W;
+          for (int w = 0; w < W; ++w) p.matched[row + w] = p.ignored[row + w] = 0;
+          bool gtm[CM_MAX_GT] = {false};
+          for (int pos = 0; pos < n; ++pos) {
+            const int slot = order[pos];
+            if (slot < 0) continue;
+            const int c = cls[slot];
+            if (c < 0 || c >= K) continue;
+            double db[4];
+            for (int k = 0; k < 4; ++k) db[k] = (double)p.det_boxes[((size_t)t * D + slot) * 4 + k];
+            const int darea = p.det_area[(size_t)t * D + slot];
+            double best = cm_floor(p.thrs[ti]);
+            int m = -1;
+            for (int wi = 0; wi < nw; ++wi) {
+              const int g = walk[wi];
+              if (p.gt_classes[g0 + g] != c || gtm[g]) continue;
+              if (m > -1 && !ign[m] && ign[g]) break;
+              const double v = kind ? cm_mask_iou(p.inter[((size_t)t * D + slot) * cap + g], darea, p.gt_area[(size_t)t * cap + g])
+                                    : cm_box_iou(db, p.gt_boxes + 4 * (size_t)(g0 + g));
+              if (v < best) continue;
+              best = v; m = g;
+            }
+            bool ig;
+            if (m > -1) {
+              gtm[m] = true;
+              ig = ign[m];
+              p.matched[row + (pos >> 5)] |= 1u << (pos & 31);
+            } else {
+              ig = cm_out_of_range(kind ? (double)darea : cm_box_area(db), a);
+            }
+            if (ig) p.ignored[row + (pos >> 5)] |= 1u << (pos & 31);
+          }
+        }
+      }
+  }
+  return RS_OK;
+}
 
 int launch_canvas_raster(const CanvasRasterParams& p, hipStream_t s) {
   RS_CHECK(p.inst_first && p.out && p.n_inst >= 0, RS_ERR_ARG, "canvas raster: null table");

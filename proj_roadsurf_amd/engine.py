@@ -99,6 +99,11 @@ class RsEvalCounts(C.Structure):
     _fields_ = [("inter", C.POINTER(C.c_int32)), ("det_area", C.POINTER(C.c_int32)), ("gt_area", C.POINTER(C.c_int32))]
 
 
+class RsEvalMatches(C.Structure):
+    _fields_ = [("order", C.POINTER(C.c_int32)), ("class_first", C.POINTER(C.c_int32)), ("gt_per_class", C.POINTER(C.c_int32)),
+                ("matched", C.POINTER(C.c_uint32)), ("ignored", C.POINTER(C.c_uint32)), ("npig", C.POINTER(C.c_int32))]
+
+
 class PolygonTables:
     """Polygons of the instances of one tile as the device polygoniser leaves them (include/rs_engine.h, ``rs_op_polygonize``):
     ``header`` (n, 8) int32 per instance [flagged, polygons, rings, vertices, first polygon, first ring, first vertex, 0] with the
@@ -251,6 +256,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.rs_engine_eval_fits.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.rs_engine_fetch_eval_async.argtypes = [vp, i32, C.POINTER(RsDets), vp, vp, vp, vp, vp, C.POINTER(RsEvalCounts)]
     lib.rs_engine_fetch_eval_wait.argtypes = [vp]
+    if hasattr(lib, "rs_op_coco_match"):              # RS_ENGINE_LIB may name an older build
+        lib.rs_op_coco_match.argtypes = [vp] * 11 + [i32] * 4 + [vp] * 7
+        lib.rs_host_coco_match.argtypes = [vp] * 11 + [i32] * 4 + [vp] * 6
+        lib.rs_engine_fetch_eval_match_async.argtypes = [vp, i32, C.POINTER(RsDets)] + [vp] * 8 + [C.POINTER(RsEvalMatches)]
+        lib.rs_engine_fetch_eval_match_wait.argtypes = [vp]
     lib.rs_rasterize_polygons_within_box.argtypes = [f64p, i32p, i32, f64p, i32, u8p]
     lib.rs_memcpy_d2h.argtypes = [vp, vp, C.c_size_t]
     lib.rs_op_fdiv.argtypes = [vp, vp, vp, C.c_int64, vp]
@@ -507,7 +517,9 @@ class Engine:
         self._fetch_landed: Optional[str] = None
         # validation counts (rs_engine_fetch_eval_*): pinned tables, allocated on the first eval_counts; batches that did not fit
         self._eval_struct: Optional[RsEvalCounts] = None
+        self._match_struct: Optional[RsEvalMatches] = None
         self.eval_fallbacks = 0
+        self.eval_unpack_s = 0.0             # eval_matches: seconds spent turning the tables into records (tools/val_ap_ab.py reads it)
 
     def _dets_struct(self, want_probs: bool) -> RsDets:
         d = RsDets()
@@ -673,23 +685,10 @@ class Engine:
         non-square tile or one above 1024 px; MASK_ON false): then nothing was run or enqueued, ``eval_fallbacks`` counts it, and the
         caller evaluates this batch from ``infer``'s masks."""
         n = int(tiles_or_n) if np.isscalar(tiles_or_n) else int(tiles_or_n.shape[0])
-        if len(gt_polygons) != n or not 1 <= n <= self.max_batch:
-            raise ValueError(f"{len(gt_polygons)} ground-truth lists for a batch of {n} (1..{self.max_batch})")
-        arrs = [np.asarray(p, np.float64).reshape(-1) for img in gt_polygons for polys in img for p in polys]
-        lens = np.array([a.size for a in arrs] or [0], np.int32)
-        off = np.zeros(max(len(arrs), 1), np.int64)
-        if len(arrs) > 1:
-            off[1:] = np.cumsum(lens[:-1], dtype=np.int64)
-        flat = np.ascontiguousarray(np.concatenate(arrs)) if arrs else np.zeros(1)
-        inst_first = np.zeros(sum(len(img) for img in gt_polygons) + 1, np.int32)
-        inst_first[1:] = np.cumsum([len(polys) for img in gt_polygons for polys in img])
-        tile_first = np.zeros(n + 1, np.int32)
-        tile_first[1:] = np.cumsum([len(img) for img in gt_polygons])
-        rc = self.lib.rs_engine_eval_fits(self._h, n, off.ctypes.data, lens.ctypes.data, inst_first.ctypes.data, tile_first.ctypes.data)
-        if rc == RS_EVAL_DOES_NOT_FIT:
-            self.eval_fallbacks += 1
+        packed = self._eval_polygon_tables(n, gt_polygons)
+        if packed is None:
             return None
-        _check(self.lib, rc, "rs_engine_eval_fits")
+        flat, off, lens, inst_first, tile_first = packed
         if not np.isscalar(tiles_or_n):
             self.infer_device(self.upload_async(np.ascontiguousarray(tiles_or_n)), n)
         if self._eval_struct is None:
@@ -713,6 +712,91 @@ class Engine:
             inst = Instances((self.tile_h, self.tile_w), self._boxes[i, :c].copy(), self._scores[i, :c].copy(), self._classes[i, :c].astype(np.int64),
                              None, None)
             out.append((inst, self._eval_inter[i, :c, :g].copy(), self._eval_det_area[i, :c].copy(), self._eval_gt_area[i, :g].copy()))
+        return out
+
+    def _eval_polygon_tables(self, n: int, gt_polygons, extra_unfit: bool = False):
+        """The polygon tables of a validation batch as rs_engine_fetch_eval_* take them: (flat, off, lens, inst_first, tile_first), or
+        ``None`` -- counted in ``eval_fallbacks`` -- when the batch does not fit the device pool (or ``extra_unfit`` says so)."""
+        if len(gt_polygons) != n or not 1 <= n <= self.max_batch:
+            raise ValueError(f"{len(gt_polygons)} ground-truth lists for a batch of {n} (1..{self.max_batch})")
+        arrs = [np.asarray(p, np.float64).reshape(-1) for img in gt_polygons for polys in img for p in polys]
+        lens = np.array([a.size for a in arrs] or [0], np.int32)
+        off = np.zeros(max(len(arrs), 1), np.int64)
+        if len(arrs) > 1:
+            off[1:] = np.cumsum(lens[:-1], dtype=np.int64)
+        flat = np.ascontiguousarray(np.concatenate(arrs)) if arrs else np.zeros(1)
+        inst_first = np.zeros(sum(len(img) for img in gt_polygons) + 1, np.int32)
+        inst_first[1:] = np.cumsum([len(polys) for img in gt_polygons for polys in img])
+        tile_first = np.zeros(n + 1, np.int32)
+        tile_first[1:] = np.cumsum([len(img) for img in gt_polygons])
+        rc = self.lib.rs_engine_eval_fits(self._h, n, off.ctypes.data, lens.ctypes.data, inst_first.ctypes.data, tile_first.ctypes.data)
+        if rc == RS_EVAL_DOES_NOT_FIT or (rc == 0 and extra_unfit):
+            self.eval_fallbacks += 1
+            return None
+        _check(self.lib, rc, "rs_engine_eval_fits")
+        return flat, off, lens, inst_first, tile_first
+
+    def eval_matches(self, tiles_or_n, gt_boxes: Sequence[np.ndarray], gt_classes: Sequence[np.ndarray],
+                     gt_polygons: Sequence[Sequence[Sequence[np.ndarray]]], wait: bool = True):
+        """``eval_counts`` and the step after it on the device: COCOeval's ``evaluateImg`` for bbox and segm (csrc/coco_match.h), behind
+        the pair counts on the same stream.  gt_boxes[tile] (G_t, 4) XYXY float64 as the COCO file gives them, gt_classes[tile] (G_t,),
+        gt_polygons as for ``eval_counts``; no crowd regions, no annotated areas (the caller matches such a batch on the host).  Returns
+        per tile ``(Instances without masks, bbox records, segm records)``, the records being what ``coco_eval.match_images`` returns
+        for that image with ``max_dets`` = the engine's slot count -- only detections and match flags travel -- or ``None`` when the
+        batch does not fit (the conditions of ``eval_counts``): nothing was run or enqueued and ``eval_fallbacks`` counts it.
+        ``wait=False`` returns True once everything is enqueued; ``eval_matches_wait(n)`` then gives the result."""
+        from . import coco_eval
+        from .coco_match import MAX_SLOTS
+        n = int(tiles_or_n) if np.isscalar(tiles_or_n) else int(tiles_or_n.shape[0])
+        if len(gt_boxes) != n or len(gt_classes) != n:
+            raise ValueError(f"{len(gt_boxes)} box lists and {len(gt_classes)} class lists for a batch of {n}")
+        assert self.D == self.spec.detections_per_image       # max_dets of match_images: the cap never cuts
+        packed = self._eval_polygon_tables(n, gt_polygons, extra_unfit=self.D > MAX_SLOTS)
+        if packed is None:
+            return None
+        flat, off, lens, inst_first, tile_first = packed
+        boxes = [np.asarray(b, np.float64).reshape(-1, 4) for b in gt_boxes]
+        classes = [np.asarray(c, np.int32).reshape(-1) for c in gt_classes]
+        if [len(b) for b in boxes] != np.diff(tile_first).tolist() or [len(c) for c in classes] != np.diff(tile_first).tolist():
+            raise ValueError("ground-truth boxes, classes and polygons differ in number")
+        gb = np.ascontiguousarray(np.concatenate(boxes + [np.zeros((1, 4))]))
+        gc = np.ascontiguousarray(np.concatenate(classes + [np.zeros(1, np.int32)]))
+        if not np.isscalar(tiles_or_n):
+            self.infer_device(self.upload_async(np.ascontiguousarray(tiles_or_n)), n)
+        K, W = self.spec.num_classes, (self.D + 31) // 32
+        if self._match_struct is None:
+            N, T, A = self.max_batch, len(coco_eval.IOU_THRS), len(coco_eval.AREA_RNG)
+            self._match_tables = {"order": self._pinned((N, self.D), np.int32), "class_first": self._pinned((N, K + 1), np.int32),
+                                  "gt_per_class": self._pinned((N, K), np.int32), "matched": self._pinned((N, 2, A, T, W), np.uint32),
+                                  "ignored": self._pinned((N, 2, A, T, W), np.uint32), "npig": self._pinned((N, 2, A, K), np.int32)}
+            m = RsEvalMatches()
+            for k, a in self._match_tables.items():
+                setattr(m, k, a.ctypes.data_as(C.POINTER(C.c_uint32 if a.dtype == np.uint32 else C.c_int32)))
+            self._match_struct = m
+        d = self._dets_struct(False)
+        d.masks = None
+        thr = np.ascontiguousarray(coco_eval.IOU_THRS, np.float64)
+        rc = self.lib.rs_engine_fetch_eval_match_async(self._h, n, C.byref(d), flat.ctypes.data, off.ctypes.data, lens.ctypes.data, inst_first.ctypes.data,
+                                                       tile_first.ctypes.data, gb.ctypes.data, gc.ctypes.data, thr.ctypes.data, C.byref(self._match_struct))
+        _check(self.lib, rc, "rs_engine_fetch_eval_match_async")   # the fit was checked above: any other code here is an error
+        return self.eval_matches_wait(n) if wait else True
+
+    def eval_matches_wait(self, n: int):
+        """The second half of ``eval_matches(..., wait=False)``: waits for the copies and builds the records of tiles 0..n-1.  Other
+        work may be enqueued on the engine in between (the tables live in buffers of their own)."""
+        from . import coco_eval
+        from .coco_match import TABLES
+        _check(self.lib, self.lib.rs_engine_fetch_eval_match_wait(self._h), "rs_engine_fetch_eval_match_wait")
+        t0 = time.perf_counter()
+        out = []
+        for i in range(n):
+            c = int(self._count[i])
+            inst = Instances((self.tile_h, self.tile_w), self._boxes[i, :c].copy(), self._scores[i, :c].copy(), self._classes[i, :c].astype(np.int64),
+                             None, None)
+            t = [self._match_tables[k][i].copy() for k in TABLES]
+            out.append((inst, coco_eval.records_from_tables(self._scores[i].copy(), *t, iou_type="bbox"),
+                        coco_eval.records_from_tables(self._scores[i].copy(), *t, iou_type="segm")))
+        self.eval_unpack_s += time.perf_counter() - t0       # host time of this route's matching: unpacking the flag bits
         return out
 
     def infer_device(self, tiles_dev_ptr: int, n: int) -> None:

@@ -247,6 +247,23 @@ def validation_chunk(eng, spec, chunk: Sequence[Dict[str, Any]], tiles: np.ndarr
     return gts, dts, fell_back
 
 
+def validation_chunk_records(eng, spec, chunk: Sequence[Dict[str, Any]], tiles: np.ndarray):
+    """``--val-ap device-match``: inference on one chunk and its match records, (bbox records, segm records or None, fell_back), one
+    record per image as ``coco_eval.match_images`` returns them.  ``Engine.eval_matches`` matches on the GPU and only the flags
+    travel.  A chunk that does not fit the device pool, one with crowd regions or annotated areas (the device rule models neither),
+    and a model without masks are matched on the host with that chunk's own data (fell_back)."""
+    from .coco_eval import match_images
+    plain = spec.mask_on and not any(np.any(r.get("crowd", False)) or "area" in r for r in chunk)
+    if plain:
+        got = eng.eval_matches(tiles, [r["boxes"] for r in chunk], [r["classes"] for r in chunk], [r["polygons"] for r in chunk])
+        if got is not None:
+            return [g[1] for g in got], [g[2] for g in got], False
+    gts, dts, _ = validation_chunk(eng, spec, chunk, tiles, "host")
+    segm = spec.mask_on and all("masks" in g for g in gts)
+    return (match_images(gts, dts, spec.num_classes, "bbox", spec.detections_per_image),
+            match_images(gts, dts, spec.num_classes, "segm", spec.detections_per_image) if segm else None, True)
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("config_file", help="YAML with a 'train_model.py' section (R:config/config_obj_detec.yaml)")
@@ -292,11 +309,13 @@ def build_parser() -> argparse.ArgumentParser:
                          "fast_rcnn/false_negative, mask_rcnn/accuracy, mask_rcnn/false_positive, mask_rcnn/false_negative.  They are counted on "
                          "the GPU behind the loss stages and one 16-integer table is read on logged iterations.  The values are those of the "
                          "logged iteration (no 20-iteration median) and, under data parallelism, rank 0's own.  Off by default")
-    ap.add_argument("--val-ap", choices=("host", "device"), default="host",
+    ap.add_argument("--val-ap", choices=("host", "device", "device-match"), default="host",
                     help="where the validation AP's mask overlaps are counted.  host (default): every detection mask is copied back, every "
                          "ground-truth polygon rasterised on the host and the IoUs taken from the masks.  device: the ground truth is "
                          "rasterised and the pixel counts of every (detection, ground truth) pair are taken on the GPU; only integers "
-                         "travel and the match records are the same.  A chunk that does not fit the device pool is evaluated on the host")
+                         "travel and the match records are the same.  device-match: the detections are also matched to the ground truth "
+                         "on the GPU (COCOeval's evaluateImg, bbox and segm) and only the match flags travel; the records are the same "
+                         "again.  A chunk that does not fit the device pool is evaluated on the host")
     return ap
 
 
@@ -478,6 +497,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     val_ap_fallbacks = [0]                # chunks of a --val-ap device run that were evaluated on the host
     if args.val_ap == "device":
         log.info("val_ap: device (ground truth rasterised and mask pair counts taken on the GPU; only integers travel)")
+    elif args.val_ap == "device-match":
+        log.info("val_ap: device-match (mask pair counts and COCOeval's matching on the GPU; only detections and match flags travel)")
 
     def validation_ap() -> Dict[str, float]:
         """COCOEvaluator on the val set (bbox + segm AP; coco_eval.py) with the CURRENT weights.  As detectron2's
@@ -493,15 +514,24 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         eng = vt.inference_engine()
         mine = list(range(rank, len(val_recs), world))
         gts, dts = [], []
+        rec_bbox, rec_segm = [], []                           # device-match: the records come chunk by chunk, from the engine
         for k in range(0, len(mine), per_rank):
             chunk = [val_recs[i] for i in mine[k:k + per_rank]]
             tiles = np.stack([read_tile(r["file_name"]) for r in chunk])
-            g, d, fell_back = validation_chunk(eng, spec, chunk, tiles, args.val_ap)
-            gts += g; dts += d
+            if args.val_ap == "device-match":
+                rb, rs, fell_back = validation_chunk_records(eng, spec, chunk, tiles)
+                rec_bbox += rb
+                rec_segm = None if (rs is None or rec_segm is None) else rec_segm + rs
+            else:
+                g, d, fell_back = validation_chunk(eng, spec, chunk, tiles, args.val_ap)
+                gts += g; dts += d
             val_ap_fallbacks[0] += int(fell_back)            # that chunk alone took the host path; nothing is truncated
-        segm = spec.mask_on and all("masks" in g or "mask_area" in g for g in gts)
-        local = {"idx": mine, "bbox": match_images(gts, dts, spec.num_classes, "bbox", spec.detections_per_image),
-                 "segm": match_images(gts, dts, spec.num_classes, "segm", spec.detections_per_image) if segm else None}
+        if args.val_ap == "device-match":
+            local = {"idx": mine, "bbox": rec_bbox, "segm": rec_segm if spec.mask_on else None}
+        else:
+            segm = spec.mask_on and all("masks" in g or "mask_area" in g for g in gts)
+            local = {"idx": mine, "bbox": match_images(gts, dts, spec.num_classes, "bbox", spec.detections_per_image),
+                     "segm": match_images(gts, dts, spec.num_classes, "segm", spec.detections_per_image) if segm else None}
         parts = [local]
         if world > 1:
             import torch.distributed as dist
@@ -616,7 +646,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     loader.shutdown(wait=True)
     if ms.mask_target_fallbacks:
         log.info("mask_targets: %d steps rasterised on the host (their polygons did not fit the device pool)", ms.mask_target_fallbacks)
-    if args.val_ap == "device":
+    if args.val_ap in ("device", "device-match"):
         log.info("val_ap: %d chunks evaluated on the host (they did not fit the device pool)", val_ap_fallbacks[0])
     ms.close()
     if metrics:
