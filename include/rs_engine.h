@@ -508,6 +508,42 @@ int rs_op_sgd_momentum(float* w, float* momentum_buf, const float* grad, int64_t
 int rs_op_fold_weights(const float* w32, const float* scale, void* w_fwd, void* w_bwd, int cout, int cin, int kh, int kw, int kpad,
                        int kpad_t, void* stream);
 
+/* The optimiser step over a table of parameter tensors: detectron2 0.6's gradient clipping, Nesterov momentum and the bias groups of
+ * get_default_optimizer_params ([EXT d2: solver/build.py; torch/optim/sgd.py; torch/nn/utils/clip_grad.py]).  csrc/sgd_rule.h holds
+ * the per-element rule:
+ *     g = grad * inv_scale;  g = clip(g);  g += wd_seg * w;  b = mu * buf + g;  d = nesterov ? g + mu * b : b;  w -= lr_seg * d;  buf = b
+ * with lr_seg = lr * bias_lr_factor and wd_seg = weight_decay_bias (where has_weight_decay_bias) on a segment flagged as a bias, lr and
+ * weight_decay elsewhere.  clip_type: 0 none; 1 value, g clamped to +-clip_value; 2 norm, every tensor multiplied by its own
+ * c = min(1, clip_value / (norm + 1e-6)) in fp32 as torch.nn.utils.clip_grad_norm_ forms it; 3 full_model, one c from the norm over
+ * all tensors (not in detectron2 0.6's core: its DETR and Mask2Former projects add it).  norm_type: 2.0 or +inf (the largest
+ * magnitude), read by types 2 and 3.  Clipping acts on grad * inv_scale: the unscaled gradient, averaged over the ranks.  A norm is
+ * summed in float64 in a fixed order, rounded to fp32, then sqrtf; nothing goes through a float atomic, so two runs give the same bits,
+ * and nothing is read back by the host.  With clip_type 0, no Nesterov and factor 1 the result equals rs_op_sgd_momentum's bit for bit. */
+typedef struct rs_solver {
+  int32_t struct_size;            /* sizeof(rs_solver), ABI check */
+  int32_t nesterov;               /* 0 / 1 (SOLVER.NESTEROV); needs momentum > 0 */
+  float bias_lr_factor;           /* SOLVER.BIAS_LR_FACTOR, >= 0 */
+  float weight_decay_bias;        /* SOLVER.WEIGHT_DECAY_BIAS, >= 0; read when has_weight_decay_bias */
+  int32_t has_weight_decay_bias;  /* 0: biases decay as the weights do */
+  int32_t clip_type;              /* 0 none, 1 value, 2 norm, 3 full_model (SOLVER.CLIP_GRADIENTS.ENABLED / CLIP_TYPE) */
+  float clip_value;               /* SOLVER.CLIP_GRADIENTS.CLIP_VALUE, > 0 when clip_type != 0 */
+  float norm_type;                /* SOLVER.CLIP_GRADIENTS.NORM_TYPE: 2.0 or +inf, when clip_type is 2 or 3 */
+} rs_solver;
+/* One such step on caller-owned device buffers w / momentum_buf / grad of n floats (16-byte aligned).  The table is HOST memory:
+ * segment i holds seg_count[i] >= 1 values at seg_off[i], a multiple of 4; ascending, no overlap, inside [0, n); seg_flags[i] 0 = weight,
+ * 1 = bias.  Values in no segment take lr, weight_decay and no clipping.  skip (optional, device): when *skip != 0 nothing is written
+ * to w or momentum_buf.  norms_out / coef_out (optional, device, fp32 [n_seg]): every segment's norm and coefficient, written by types 2
+ * and 3 only.  RS_ERR_ARG, before anything is touched and with the entry's name in the text: a null pointer, a table that breaks one of
+ * the rules above, a solver rs_trainer_set_solver would refuse, Nesterov with momentum <= 0.  Enqueues on `stream`; returns after its
+ * scratch is released (it waits for the stream).  rs_host_sgd_segments: the same arguments as host pointers, no device; norms in plain
+ * float64 order. */
+int rs_op_sgd_segments(float* w, float* momentum_buf, const float* grad, int64_t n, const int64_t* seg_off, const int64_t* seg_count,
+                       const int32_t* seg_flags, int n_seg, float lr, float momentum, float weight_decay, float inv_scale,
+                       const rs_solver* solver, const int32_t* skip, float* norms_out, float* coef_out, void* stream);
+int rs_host_sgd_segments(float* w, float* momentum_buf, const float* grad, int64_t n, const int64_t* seg_off, const int64_t* seg_count,
+                         const int32_t* seg_flags, int n_seg, float lr, float momentum, float weight_decay, float inv_scale,
+                         const rs_solver* solver, const int32_t* skip, float* norms_out, float* coef_out);
+
 /* Training diagnostics of detectron2 0.6 as INTEGER counts (csrc/train_stats.h holds the per-element rules; the ratios are the
  * caller's, in double).  The three operators take device pointers, enqueue on `stream` and do not wait; the three host entries take
  * the same arguments as host pointers and need no device.  All six ADD into the counts (zero them first), and refuse, before
@@ -673,6 +709,25 @@ int rs_trainer_set_train_stats(rs_trainer* t, int on);
  * this batch): then the step is skipped on the device -- weights and momentum unchanged -- and the tensor "grad_overflow" [1]
  * reads 1; lower the scale with rs_trainer_set_loss_scale before the next forward (GradScaler semantics, no host sync here). */
 int rs_trainer_apply_sgd(rs_trainer* t, float lr, float momentum, float weight_decay);
+/* The solver of the following rs_trainer_apply_sgd calls (rs_solver above; opt-in, both precisions).  A trainer whose solver was never
+ * set runs exactly the two launches described above, and its stage list and tensor table do not change.  The first call cuts the flat
+ * buffers along the segment table below, uploads the chunk table and registers the tensors "grad_norms" and "clip_coef" (fp32
+ * [segments], enumerated by rs_trainer_tensor_name); from then on rs_trainer_apply_sgd runs the segmented step: for clip types 2 and
+ * 3 grad_norm_partial_kernel (which also raises "grad_overflow", replacing the separate check) + grad_norm_finish_kernel, then
+ * sgd_segments_kernel.  "grad_norms" / "clip_coef" hold the last such step's values (all 0 / unwritten for types 0 and 1).  A solver
+ * of all defaults (clip_type 0, no Nesterov, factor 1, no bias decay) leaves master weights and momentum bit-identical to a trainer
+ * never set.  SOLVER.WEIGHT_DECAY_NORM has no counterpart: every norm layer of this model is a FrozenBN without trainable values.
+ * RS_ERR_ARG on a null handle or solver, a struct_size mismatch, nesterov outside 0 / 1, a negative or non-finite bias_lr_factor or
+ * weight_decay_bias, clip_type outside 0..3, clip_value <= 0 with a clip_type other than 0, norm_type other than 2 or +inf with clip
+ * types 2 / 3.  Nesterov needs momentum > 0, which arrives with rs_trainer_apply_sgd: that call then returns RS_ERR_ARG before anything
+ * is launched.  rs_trainer_copy_state carries the solver to the destination.  Call it between steps from the thread that drives the
+ * trainer; the first call allocates on the current device and waits for the trainer's stream.
+ * Segment table: the trainable tensors in buffer order, "<layer>.w" = the [Cout][Kpad] block of "g:<layer>.w" (its padding columns
+ * hold an exactly zero gradient, so they do not change a norm) and "<layer>.b" = the Cout real values of the bias (not its 64-rounded
+ * slot).  rs_trainer_segment_info: offset / count in floats of the flat buffers, is_bias 0 / 1; valid without a solver. */
+int rs_trainer_set_solver(rs_trainer* t, const rs_solver* solver);
+int rs_trainer_segment_count(rs_trainer* t);
+int rs_trainer_segment_info(rs_trainer* t, int i, char* name_out /* >= 96 bytes */, int64_t* offset, int64_t* count, int* is_bias);
 int rs_trainer_set_loss_scale(rs_trainer* t, float loss_scale);
 int rs_trainer_sync(rs_trainer* t);
 int rs_trainer_tensor(rs_trainer* t, const char* name, void** dev_ptr, int* dtype, int* ndim, int64_t dims[5], int* halo);
@@ -681,7 +736,8 @@ int rs_trainer_tensor_name(rs_trainer* t, int i, char* name_out);
 /* Multi-scale training (INPUT.MIN_SIZE_TRAIN sampling "choice", R:31-38): build one trainer per network-input size (same
  * weights, spec.min_size_test = that size) and, when the size of the next batch differs from the previous one's, carry the
  * optimiser state over: master weights + momentum are copied device to device and dst's fp16 operands refolded.  Trainers whose
- * freeze_at differ have different parameter layouts and are refused (RS_ERR_ARG). */
+ * freeze_at differ have different parameter layouts and are refused (RS_ERR_ARG).  The solver (rs_trainer_set_solver) travels with
+ * the state: dst takes src's, or goes back to the plain step when src never had one. */
 int rs_trainer_copy_state(rs_trainer* dst, rs_trainer* src);
 /* Data parallel: every rank all-reduces (SUM) the flat gradient buffer (rs_trainer_grad_buffer, rs_trainer_param_count floats,
  * device memory) and sets the divisor to the world size, which rs_trainer_apply_sgd applies together with the loss scale

@@ -37,6 +37,31 @@ struct OpScratch {
 
 }  // namespace
 
+// ---- rs_solver: the checks rs_trainer_set_solver, rs_op_sgd_segments and rs_host_sgd_segments share, and the values of one launch
+int sgd_solver_check(const char* who, const rs_solver* sv) {
+  RS_CHECK(sv, RS_ERR_ARG, "%s: null solver", who);
+  RS_CHECK(sv->struct_size == (int32_t)sizeof(rs_solver), RS_ERR_ARG, "%s: rs_solver.struct_size %d, expected %d", who, sv->struct_size, (int)sizeof(rs_solver));
+  RS_CHECK(sv->nesterov == 0 || sv->nesterov == 1, RS_ERR_ARG, "%s: nesterov %d (0 / 1)", who, sv->nesterov);
+  RS_CHECK(sv->bias_lr_factor >= 0.f && sv->bias_lr_factor < INFINITY, RS_ERR_ARG, "%s: bias_lr_factor %g", who, (double)sv->bias_lr_factor);
+  RS_CHECK(sv->has_weight_decay_bias == 0 || sv->has_weight_decay_bias == 1, RS_ERR_ARG, "%s: has_weight_decay_bias %d (0 / 1)", who, sv->has_weight_decay_bias);
+  RS_CHECK(!sv->has_weight_decay_bias || (sv->weight_decay_bias >= 0.f && sv->weight_decay_bias < INFINITY), RS_ERR_ARG, "%s: weight_decay_bias %g", who,
+           (double)sv->weight_decay_bias);
+  RS_CHECK(sv->clip_type >= SGD_CLIP_NONE && sv->clip_type <= SGD_CLIP_FULL_MODEL, RS_ERR_ARG, "%s: clip_type %d (0 none, 1 value, 2 norm, 3 full_model)", who, sv->clip_type);
+  RS_CHECK(sv->clip_type == SGD_CLIP_NONE || (sv->clip_value > 0.f && sv->clip_value < INFINITY), RS_ERR_ARG, "%s: clip_value %g (must be > 0)", who, (double)sv->clip_value);
+  RS_CHECK(sv->clip_type < SGD_CLIP_NORM || sv->norm_type == 2.0f || sv->norm_type == INFINITY, RS_ERR_ARG, "%s: norm_type %g (2 or inf)", who, (double)sv->norm_type);
+  return RS_OK;
+}
+int sgd_solver_hyper(const char* who, const rs_solver& sv, float lr, float momentum, float weight_decay, float inv_scale, SgdHyper* h, int* norm_inf) {
+  RS_CHECK(!sv.nesterov || momentum > 0.f, RS_ERR_ARG, "%s: Nesterov momentum needs momentum > 0, got %g", who, (double)momentum);
+  h->lr = lr; h->lr_bias = lr * sv.bias_lr_factor;
+  h->wd = weight_decay; h->wd_bias = sv.has_weight_decay_bias ? sv.weight_decay_bias : weight_decay;
+  h->momentum = momentum; h->inv_scale = inv_scale;
+  h->clip_value = sv.clip_type == SGD_CLIP_NONE ? 0.f : sv.clip_value;
+  h->nesterov = sv.nesterov; h->clip_type = sv.clip_type;
+  *norm_inf = sv.clip_type >= SGD_CLIP_NORM && sv.norm_type == INFINITY;
+  return RS_OK;
+}
+
 extern "C" {
 
 // rs_fdiv (common.h) as an operator, for its test: out[i] = a[i] / b[i] through the device code's division
@@ -848,6 +873,90 @@ int rs_op_subsample(int32_t* labels, int32_t* sampled, int32_t* sampled_count, i
 int rs_op_sgd_momentum(float* w, float* momentum_buf, const float* grad, int64_t n, float lr, float momentum, float weight_decay,
                        float inv_loss_scale, int first_step, void* stream) {
   return launch_sgd_momentum(w, momentum_buf, grad, n, lr, momentum, weight_decay, inv_loss_scale, first_step, (hipStream_t)stream);
+}
+
+// ---- the optimiser step over a table of segments (sgd_rule.h): the kernels on caller-owned device buffers, and the same rule on host
+// pointers.  Both refuse a bad table or solver before anything is touched.
+static int sgd_segments_args(const char* who, const void* w, const void* buf, const void* grad, int64_t n, const rs_solver* solver, bool device) {
+  RS_CHECK(w && buf && grad, RS_ERR_ARG, "%s: null buffer", who);
+  RS_CHECK(n > 0, RS_ERR_ARG, "%s: %lld values", who, (long long)n);
+  RS_CHECK(!device || (((uintptr_t)w & 15) == 0 && ((uintptr_t)buf & 15) == 0 && ((uintptr_t)grad & 15) == 0), RS_ERR_ARG, "%s: the buffers must be 16-byte aligned", who);
+  return sgd_solver_check(who, solver);
+}
+
+int rs_op_sgd_segments(float* w, float* momentum_buf, const float* grad, int64_t n, const int64_t* seg_off, const int64_t* seg_count,
+                       const int32_t* seg_flags, int n_seg, float lr, float momentum, float weight_decay, float inv_scale,
+                       const rs_solver* solver, const int32_t* skip, float* norms_out, float* coef_out, void* stream) {
+  const char* who = "rs_op_sgd_segments";
+  { int rc = sgd_segments_args(who, w, momentum_buf, grad, n, solver, true); if (rc) return rc; }
+  SgdHyper h;
+  int norm_inf = 0;
+  { int rc = sgd_solver_hyper(who, *solver, lr, momentum, weight_decay, inv_scale, &h, &norm_inf); if (rc) return rc; }
+  std::vector<SgdChunk> chunks;
+  std::vector<int> seg_chunks;
+  std::vector<uint8_t> host;
+  { int rc = sgd_plan_cut(who, seg_off, seg_count, seg_flags, n_seg, n, &chunks, &seg_chunks); if (rc) return rc; }
+  sgd_plan_pack(chunks, seg_chunks, &host);
+  OpScratch scratch(stream);       // declared behind `host`: it waits for the stream before the staging vector goes
+  void* base = nullptr;
+  { int rc = scratch.alloc(&base, sgd_plan_bytes((int)chunks.size(), n_seg)); if (rc) return rc; }
+  SgdPlan p = sgd_plan_place(base, (int)chunks.size(), n_seg);
+  RS_HIP(hipMemcpyAsync(base, host.data(), host.size(), hipMemcpyHostToDevice, (hipStream_t)stream));
+  if (norms_out) p.norms = norms_out;
+  if (coef_out) p.coef = coef_out;
+  if (h.clip_type >= SGD_CLIP_NORM) {
+    int rc = launch_grad_norms(p, grad, h, norm_inf, nullptr, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  { int rc = launch_sgd_segments(p, w, momentum_buf, grad, h, skip, (hipStream_t)stream); if (rc) return rc; }
+  RS_HIP(scratch.sync());
+  return RS_OK;
+}
+
+int rs_host_sgd_segments(float* w, float* momentum_buf, const float* grad, int64_t n, const int64_t* seg_off, const int64_t* seg_count,
+                         const int32_t* seg_flags, int n_seg, float lr, float momentum, float weight_decay, float inv_scale,
+                         const rs_solver* solver, const int32_t* skip, float* norms_out, float* coef_out) {
+  const char* who = "rs_host_sgd_segments";
+  { int rc = sgd_segments_args(who, w, momentum_buf, grad, n, solver, false); if (rc) return rc; }
+  SgdHyper h;
+  int norm_inf = 0;
+  { int rc = sgd_solver_hyper(who, *solver, lr, momentum, weight_decay, inv_scale, &h, &norm_inf); if (rc) return rc; }
+  std::vector<SgdChunk> chunks;
+  std::vector<int> seg_chunks;
+  { int rc = sgd_plan_cut(who, seg_off, seg_count, seg_flags, n_seg, n, &chunks, &seg_chunks); if (rc) return rc; }
+  std::vector<float> coef((size_t)n_seg, 1.f);
+  if (h.clip_type >= SGD_CLIP_NORM) {
+    std::vector<double> sums((size_t)n_seg, 0.0);
+    double all = 0.0;
+    for (int s = 0; s < n_seg; ++s) {
+      double acc = 0.0;
+      for (int64_t i = 0; i < seg_count[s]; ++i) {
+        const double u = (double)(grad[seg_off[s] + i] * inv_scale);
+        acc = norm_inf ? fmax(acc, fabs(u)) : acc + u * u;
+      }
+      sums[s] = acc;
+      all = norm_inf ? fmax(all, acc) : all + acc;
+      const float norm = norm_inf ? (float)acc : sqrtf((float)acc);
+      if (norms_out) norms_out[s] = norm;
+      coef[s] = sgd_clip_clamp(h.clip_value / sgd_clip_denominator(norm));
+    }
+    if (h.clip_type == SGD_CLIP_FULL_MODEL) {
+      const float norm = norm_inf ? (float)all : sqrtf((float)all);
+      const float c = sgd_clip_clamp(h.clip_value / sgd_clip_denominator(norm));
+      for (int s = 0; s < n_seg; ++s) coef[s] = c;
+    }
+    if (coef_out) for (int s = 0; s < n_seg; ++s) coef_out[s] = coef[s];
+  }
+  if (skip && *skip) return RS_OK;
+  for (const SgdChunk& c : chunks) {
+    const bool in_seg = c.seg >= 0, bias = in_seg && (c.flags & SGD_SEG_BIAS);
+    const float lr_seg = bias ? h.lr_bias : h.lr, wd_seg = bias ? h.wd_bias : h.wd;
+    const int by_value = in_seg && h.clip_type == SGD_CLIP_VALUE;
+    const float cf = in_seg ? coef[c.seg] : 1.f;
+    for (int i = 0; i < c.count; ++i)
+      sgd_rule(w + c.off + i, momentum_buf + c.off + i, grad[c.off + i], h.inv_scale, lr_seg, wd_seg, h.momentum, h.nesterov, by_value, h.clip_value, cf);
+  }
+  return RS_OK;
 }
 
 int rs_op_fold_weights(const float* w32, const float* scale, void* w_fwd, void* w_bwd, int cout, int cin, int kh, int kw, int kpad,

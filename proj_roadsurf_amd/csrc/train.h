@@ -1,7 +1,9 @@
 // Training-path kernels (train_kernels.hip): parameter blocks and launchers.
 #pragma once
+#include <vector>
 #include "common.h"
 #include "mask_targets.h"
+#include "sgd_rule.h"
 
 // Optional scratch of a loss kernel: with it the logged loss is summed in a fixed order (one slot per workgroup, the last workgroup adds
 // them) instead of one float atomic per wave, so that two runs of a step report the same bits.  Null partial = the atomics.  One
@@ -60,6 +62,31 @@ int launch_mask_loss(const MaskLossParams& p, hipStream_t s);
 int launch_sgd_momentum(float* w, float* buf, const float* grad, long long n, float lr, float momentum, float weight_decay,
                         float inv_loss_scale, int first_step, hipStream_t s, const int* skip = nullptr);
 int launch_grad_nonfinite(const float* grad, long long n, int* flag, hipStream_t s);   // flag = 1 if any inf / nan
+// The segmented optimiser step (sgd_rule.h): device tables of one flat buffer.  sgd_plan_cut validates a segment table (ascending, no
+// overlap, offsets multiples of 4, counts >= 1, inside [0, n), flags 0 / SGD_SEG_BIAS) and cuts [0, n) into chunks, gaps included;
+// sgd_plan_pack lays chunks + the {first chunk, chunk count} pair of every segment out as they are uploaded to the front of ONE device
+// allocation of sgd_plan_bytes, which sgd_plan_place divides (every part 256-byte aligned).
+struct SgdPlan {
+  const SgdChunk* chunks;   // [n_chunks]
+  const int* seg_chunks;    // [n_seg][2]
+  double* partial;          // [n_chunks] grad_norm_partial_kernel's output
+  double* seg_sum;          // [n_seg] float64 sum of squares (or the maximum) of every segment
+  float* norms;             // [n_seg]
+  float* coef;              // [n_seg]
+  int n_chunks, n_seg;
+};
+int sgd_plan_cut(const char* who, const int64_t* seg_off, const int64_t* seg_count, const int32_t* seg_flags, int n_seg, long long n, std::vector<SgdChunk>* chunks,
+                 std::vector<int>* seg_chunks);
+size_t sgd_plan_table_bytes(int n_chunks, int n_seg);
+size_t sgd_plan_bytes(int n_chunks, int n_seg);
+void sgd_plan_pack(const std::vector<SgdChunk>& chunks, const std::vector<int>& seg_chunks, std::vector<uint8_t>* host);
+SgdPlan sgd_plan_place(void* base, int n_chunks, int n_seg);
+// rs_solver (include/rs_engine.h) -> checked, then the hyper-parameters of one launch (ops.hip).  `who` names the entry in the error text.
+struct rs_solver;
+int sgd_solver_check(const char* who, const rs_solver* sv);
+int sgd_solver_hyper(const char* who, const rs_solver& sv, float lr, float momentum, float weight_decay, float inv_scale, SgdHyper* h, int* norm_inf);
+int launch_grad_norms(const SgdPlan& p, const float* grad, const SgdHyper& h, int norm_inf, int* flag, hipStream_t s);
+int launch_sgd_segments(const SgdPlan& p, float* w, float* buf, const float* grad, const SgdHyper& h, const int* skip, hipStream_t s);
 // one layer of the fold (master fp32 -> fp16 GEMM operands); Cout == 0 marks a bias copy (w32 -> fwd32, Cin floats, KH times)
 struct FoldDesc {
   const float* w32;

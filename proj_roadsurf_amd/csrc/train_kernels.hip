@@ -12,6 +12,10 @@
 //                          all foreground masks and pixels  [EXT d2: modeling/roi_heads/mask_head.py]
 //   sgd_momentum_kernel    torch.optim.SGD step: g += wd*w; buf = mu*buf + g; w -= lr*buf (MOMENTUM 0.9, WEIGHT_DECAY 1e-4,
 //                          no Nesterov, R:281-282,303)  [EXT d2: solver/build.py; torch/optim/sgd.py]
+//   grad_norm_partial_kernel / grad_norm_finish_kernel / grad_norm_total_kernel / sgd_segments_kernel
+//                          the same step over a table of parameter tensors: detectron2's gradient clipping (value, norm, full_model),
+//                          Nesterov and the bias groups of get_default_optimizer_params (sgd_rule.h), opt-in through rs_trainer_set_solver
+//                          [EXT d2: solver/build.py; torch/nn/utils/clip_grad.py]
 //   fold_weights_kernel    fp32 master weight -> the two fp16 GEMM operands of the next step: the forward weight
 //                          [Cout][(kh,kw,ci)] with the FrozenBN scale folded in, and its transposed, tap-flipped copy
 //                          [Cin][(kh',kw',co)] for the input-gradient convolution
@@ -20,6 +24,7 @@
 // Each loss kernel writes the GRADIENT of the (weighted) total loss w.r.t. its logits/deltas, scaled by `loss_scale`
 // (fp16 loss scaling), and accumulates the loss value itself into an fp32 scalar for logging (one float atomic per wave, or, given a
 // LossScratch, in a fixed order: grid_sum_to).
+#include <string.h>
 #include "common.h"
 #include "mask_targets.h"
 #include "train.h"
@@ -795,7 +800,209 @@ __global__ __launch_bounds__(256) void mask_stats_kernel(const MaskStatsParams p
   block_counts_add<5, false>(v, p.out);
 }
 
+// ---- the segmented optimiser step (sgd_rule.h holds the per-element rule; the host restates it in ops.hip).  The flat buffer is cut,
+// once, into chunks of at most SGD_CHUNK values that never straddle a segment (a parameter tensor) or a gap between two; one workgroup
+// per chunk, 16-byte loads per lane where the chunk starts on a multiple of 4 (every segment does; a gap behind a segment of odd length
+// takes the scalar form).  No atomics on a float and a fixed order everywhere, so two runs give the same bits.
+//
+// Sum over the workgroup in a fixed order: butterfly inside each wave, the four waves added as (0 + 1) + (2 + 3).  MAX: the maximum.
+template <bool MAX>
+__device__ __forceinline__ double block_reduce_f64(double v) {
+  __shared__ double s_w[4];
+  for (int o = 32; o > 0; o >>= 1) {
+    const double u = __shfl_xor(v, o);
+    v = MAX ? fmax(v, u) : v + u;
+  }
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return MAX ? fmax(fmax(s_w[0], s_w[1]), fmax(s_w[2], s_w[3])) : (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+}
+
+// partial[chunk] = sum of (grad * inv_scale)^2 over the chunk in float64 (the square of an fp32 value is exact there), or the maximum of
+// |grad * inv_scale| (NORM_TYPE inf).  flag (optional): grad_nonfinite_kernel's test on the values it reads anyway -- the chunks cover the
+// whole buffer, so the flag means what it means there.
+template <bool INF>
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const float* grad, const SgdChunk* chunks, double* partial, float inv_scale, int* flag) {
+  const SgdChunk c = chunks[blockIdx.x];
+  const float* g = grad + c.off;
+  const int tid = threadIdx.x;
+  double acc = 0.0;
+  bool bad = false;
+  auto take = [&](float x) {
+    bad = bad || !(fabsf(x) <= 3.0e38f);
+    const double u = (double)(x * inv_scale);
+    acc = INF ? fmax(acc, fabs(u)) : acc + u * u;
+  };
+  if ((c.off & 3) == 0) {
+    for (int i = tid * 4; i < c.count; i += 1024) {
+      if (i + 3 < c.count) {
+        const f32x4 v = *(const f32x4*)(g + i);
+        take(v[0]); take(v[1]); take(v[2]); take(v[3]);
+      } else {
+        for (int j = i; j < c.count; ++j) take(g[j]);
+      }
+    }
+  } else {
+    for (int i = tid; i < c.count; i += 256) take(g[i]);
+  }
+  if (flag && __any(bad) && (tid & 63) == 0) atomicOr(flag, 1);
+  const double total = block_reduce_f64<INF>(acc);
+  if (tid == 0) partial[blockIdx.x] = total;
+}
+
+// one wave per segment: lane l takes the segment's partials l, l + 64, .. in chunk order, then the butterfly.  seg_sum keeps the float64
+// value for the full-model norm; norms[seg] = sqrtf of its fp32 rounding (inf: the maximum itself, exact); coef[seg] when `per_segment`.
+template <bool INF>
+__global__ __launch_bounds__(64) void grad_norm_finish_kernel(const double* partial, const int* seg_chunks, double* seg_sum, float* norms, float* coef,
+                                                              float max_norm, int per_segment) {
+  const int seg = blockIdx.x, lane = threadIdx.x;
+  const int first = seg_chunks[2 * seg], count = seg_chunks[2 * seg + 1];
+  double acc = 0.0;
+  for (int k = lane; k < count; k += 64) acc = INF ? fmax(acc, partial[first + k]) : acc + partial[first + k];
+  for (int o = 32; o > 0; o >>= 1) {
+    const double u = __shfl_xor(acc, o);
+    acc = INF ? fmax(acc, u) : acc + u;
+  }
+  if (lane == 0) {
+    seg_sum[seg] = acc;
+    const float s = (float)acc;
+    const float norm = INF ? s : sqrtf(s);
+    norms[seg] = norm;
+    if (per_segment) coef[seg] = sgd_clip_clamp(rs_fdiv(max_norm, sgd_clip_denominator(norm)));
+  }
+}
+
+// full_model: one wave; every lane adds the segment sums in segment order (the same value in every lane), then the lanes write the one
+// coefficient to every entry
+template <bool INF>
+__global__ __launch_bounds__(64) void grad_norm_total_kernel(const double* seg_sum, float* coef, int n_seg, float max_norm) {
+  double acc = 0.0;
+  for (int k = 0; k < n_seg; ++k) acc = INF ? fmax(acc, seg_sum[k]) : acc + seg_sum[k];
+  const float s = (float)acc;
+  const float norm = INF ? s : sqrtf(s);
+  const float c = sgd_clip_clamp(rs_fdiv(max_norm, sgd_clip_denominator(norm)));
+  for (int k = threadIdx.x; k < n_seg; k += 64) coef[k] = c;
+}
+
+// skip as in sgd_momentum_kernel: when set neither the weights nor the momentum buffer change.  coef null = 1 everywhere.
+__global__ __launch_bounds__(256) void sgd_segments_kernel(float* w, float* buf, const float* grad, const SgdChunk* chunks, const float* coef,
+                                                          const SgdHyper h, const int* skip) {
+  if (skip && *skip) return;
+  const SgdChunk c = chunks[blockIdx.x];
+  const bool in_seg = c.seg >= 0, bias = in_seg && (c.flags & SGD_SEG_BIAS);
+  const float lr = bias ? h.lr_bias : h.lr, wd = bias ? h.wd_bias : h.wd;
+  const int by_value = in_seg && h.clip_type == SGD_CLIP_VALUE;
+  const float cf = (in_seg && coef) ? coef[c.seg] : 1.f;
+  float* wp = w + c.off;
+  float* bp = buf + c.off;
+  const float* g = grad + c.off;
+  const int tid = threadIdx.x;
+  if ((c.off & 3) == 0) {
+    for (int i = tid * 4; i < c.count; i += 1024) {
+      if (i + 3 < c.count) {
+        f32x4 wv = *(const f32x4*)(wp + i), bv = *(const f32x4*)(bp + i);
+        const f32x4 gv = *(const f32x4*)(g + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float we = wv[e], be = bv[e];
+          sgd_rule(&we, &be, gv[e], h.inv_scale, lr, wd, h.momentum, h.nesterov, by_value, h.clip_value, cf);
+          wv[e] = we; bv[e] = be;
+        }
+        *(f32x4*)(wp + i) = wv;
+        *(f32x4*)(bp + i) = bv;
+      } else {
+        for (int j = i; j < c.count; ++j) sgd_rule(wp + j, bp + j, g[j], h.inv_scale, lr, wd, h.momentum, h.nesterov, by_value, h.clip_value, cf);
+      }
+    }
+  } else {
+    for (int i = tid; i < c.count; i += 256) sgd_rule(wp + i, bp + i, g[i], h.inv_scale, lr, wd, h.momentum, h.nesterov, by_value, h.clip_value, cf);
+  }
+}
+
 }  // namespace
+
+// ---- host side of the segmented step: cut the buffer, place the tables, launch
+int sgd_plan_cut(const char* who, const int64_t* seg_off, const int64_t* seg_count, const int32_t* seg_flags, int n_seg, long long n, std::vector<SgdChunk>* chunks,
+                 std::vector<int>* seg_chunks) {
+  RS_CHECK(seg_off && seg_count && seg_flags && chunks && seg_chunks, RS_ERR_ARG, "%s: null table", who);
+  RS_CHECK(n_seg >= 1 && n > 0, RS_ERR_ARG, "%s: %d segments over %lld values", who, n_seg, n);
+  chunks->clear();
+  seg_chunks->clear();
+  auto cut = [&](long long a, long long b, int seg, int flags) {
+    for (; a < b; a += SGD_CHUNK) {
+      SgdChunk c;
+      c.off = a; c.count = (int)(b - a < SGD_CHUNK ? b - a : SGD_CHUNK); c.seg = seg; c.flags = flags; c.pad = 0;
+      chunks->push_back(c);
+    }
+  };
+  long long pos = 0;
+  for (int s = 0; s < n_seg; ++s) {
+    const long long o = seg_off[s], k = seg_count[s];
+    RS_CHECK(o >= pos && o % 4 == 0, RS_ERR_ARG, "%s: segment %d starts at %lld (ascending, no overlap, a multiple of 4; the previous one ends at %lld)", who, s, o, pos);
+    RS_CHECK(k >= 1 && k <= n - o, RS_ERR_ARG, "%s: segment %d holds %lld values at %lld of %lld", who, s, k, o, n);
+    RS_CHECK(seg_flags[s] == 0 || seg_flags[s] == SGD_SEG_BIAS, RS_ERR_ARG, "%s: segment %d has flags %d (0 = weight, 1 = bias)", who, s, seg_flags[s]);
+    cut(pos, o, -1, 0);
+    const size_t first = chunks->size();
+    cut(o, o + k, s, seg_flags[s]);
+    seg_chunks->push_back((int)first);
+    seg_chunks->push_back((int)(chunks->size() - first));
+    pos = o + k;
+  }
+  cut(pos, n, -1, 0);
+  RS_CHECK(chunks->size() < (size_t)1 << 31, RS_ERR_UNSUPPORTED, "%s: %zu chunks", who, chunks->size());
+  return RS_OK;
+}
+
+static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+size_t sgd_plan_table_bytes(int n_chunks, int n_seg) { return up256((size_t)n_chunks * sizeof(SgdChunk)) + up256((size_t)n_seg * 2 * sizeof(int)); }
+size_t sgd_plan_bytes(int n_chunks, int n_seg) {
+  return sgd_plan_table_bytes(n_chunks, n_seg) + up256((size_t)n_chunks * 8) + up256((size_t)n_seg * 8) + 2 * up256((size_t)n_seg * 4);
+}
+void sgd_plan_pack(const std::vector<SgdChunk>& chunks, const std::vector<int>& seg_chunks, std::vector<uint8_t>* host) {
+  const int n_chunks = (int)chunks.size(), n_seg = (int)seg_chunks.size() / 2;
+  host->assign(sgd_plan_table_bytes(n_chunks, n_seg), 0);
+  memcpy(host->data(), chunks.data(), chunks.size() * sizeof(SgdChunk));
+  memcpy(host->data() + up256(chunks.size() * sizeof(SgdChunk)), seg_chunks.data(), seg_chunks.size() * sizeof(int));
+}
+SgdPlan sgd_plan_place(void* base, int n_chunks, int n_seg) {
+  SgdPlan p;
+  uint8_t* b = (uint8_t*)base;
+  p.chunks = (const SgdChunk*)b; b += up256((size_t)n_chunks * sizeof(SgdChunk));
+  p.seg_chunks = (const int*)b; b += up256((size_t)n_seg * 2 * sizeof(int));
+  p.partial = (double*)b; b += up256((size_t)n_chunks * 8);
+  p.seg_sum = (double*)b; b += up256((size_t)n_seg * 8);
+  p.norms = (float*)b; b += up256((size_t)n_seg * 4);
+  p.coef = (float*)b;
+  p.n_chunks = n_chunks; p.n_seg = n_seg;
+  return p;
+}
+
+// norms[seg], coef[seg] of the gradient as it stands; clip_type SGD_CLIP_NORM or SGD_CLIP_FULL_MODEL.  flag (optional) is zeroed and raised
+// as launch_grad_nonfinite does.
+int launch_grad_norms(const SgdPlan& p, const float* grad, const SgdHyper& h, int norm_inf, int* flag, hipStream_t s) {
+  RS_CHECK(grad && p.chunks && p.seg_chunks && p.partial && p.seg_sum && p.norms && p.coef && p.n_chunks > 0 && p.n_seg > 0, RS_ERR_ARG, "grad norms: bad arguments");
+  RS_CHECK(h.clip_type == SGD_CLIP_NORM || h.clip_type == SGD_CLIP_FULL_MODEL, RS_ERR_ARG, "grad norms: clip type %d", h.clip_type);
+  if (flag) RS_HIP(hipMemsetAsync(flag, 0, 4, s));
+  const int per_segment = h.clip_type == SGD_CLIP_NORM;
+  if (norm_inf) {
+    hipLaunchKernelGGL(grad_norm_partial_kernel<true>, dim3((unsigned)p.n_chunks), dim3(256), 0, s, grad, p.chunks, p.partial, h.inv_scale, flag);
+    hipLaunchKernelGGL(grad_norm_finish_kernel<true>, dim3((unsigned)p.n_seg), dim3(64), 0, s, p.partial, p.seg_chunks, p.seg_sum, p.norms, p.coef, h.clip_value, per_segment);
+    if (!per_segment) hipLaunchKernelGGL(grad_norm_total_kernel<true>, dim3(1), dim3(64), 0, s, p.seg_sum, p.coef, p.n_seg, h.clip_value);
+  } else {
+    hipLaunchKernelGGL(grad_norm_partial_kernel<false>, dim3((unsigned)p.n_chunks), dim3(256), 0, s, grad, p.chunks, p.partial, h.inv_scale, flag);
+    hipLaunchKernelGGL(grad_norm_finish_kernel<false>, dim3((unsigned)p.n_seg), dim3(64), 0, s, p.partial, p.seg_chunks, p.seg_sum, p.norms, p.coef, h.clip_value, per_segment);
+    if (!per_segment) hipLaunchKernelGGL(grad_norm_total_kernel<false>, dim3(1), dim3(64), 0, s, p.seg_sum, p.coef, p.n_seg, h.clip_value);
+  }
+  RS_HIP(hipGetLastError());
+  return RS_OK;
+}
+int launch_sgd_segments(const SgdPlan& p, float* w, float* buf, const float* grad, const SgdHyper& h, const int* skip, hipStream_t s) {
+  RS_CHECK(w && buf && grad && p.chunks && p.n_chunks > 0, RS_ERR_ARG, "sgd segments: bad arguments");
+  const float* coef = (h.clip_type == SGD_CLIP_NORM || h.clip_type == SGD_CLIP_FULL_MODEL) ? p.coef : nullptr;
+  hipLaunchKernelGGL(sgd_segments_kernel, dim3((unsigned)p.n_chunks), dim3(256), 0, s, w, buf, grad, p.chunks, coef, h, skip);
+  RS_HIP(hipGetLastError());
+  return RS_OK;
+}
 
 int launch_label_counts(const LabelCountsParams& p, hipStream_t s) {
   RS_CHECK(p.labels && p.out && p.count >= 0 && p.images >= 0, RS_ERR_ARG, "label_counts: bad arguments");

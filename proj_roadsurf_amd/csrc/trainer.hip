@@ -174,6 +174,28 @@ struct rs_trainer {
   Stage ts_box, ts_mask, ts_rpn;         // "box.stats", "mask.stats", "rpn.stats": listed by rs_trainer_stage_info once switched on
   bool ts_listed = false;
   int run_stats(Stage& st, int n) { return train_stats_on ? run_stage(st, n, stream) : (int)RS_OK; }
+  // ---- solver (opt-in: rs_trainer_set_solver; sgd_rule.h).  The segment table lists the trainable tensors in buffer order; the chunk
+  // table, the norm scratch and the tensors "grad_norms" / "clip_coef" exist from the first set_solver.  Never set: apply_sgd is the
+  // two launches it always was.
+  struct Segment { std::string name; size_t off = 0, count = 0; int bias = 0; };
+  std::vector<Segment> segments;
+  const std::vector<Segment>& segment_table() {
+    if (segments.empty())
+      for (const TrainLayer& L : layers) {
+        Segment w;
+        w.name = L.name + ".w"; w.off = L.w_off; w.count = (size_t)L.Cout * L.Kpad; w.bias = 0;
+        segments.push_back(w);
+        if (L.b_off != (size_t)-1) {
+          Segment b;
+          b.name = L.name + ".b"; b.off = L.b_off; b.count = (size_t)L.Cout; b.bias = 1;
+          segments.push_back(b);
+        }
+      }
+    return segments;
+  }
+  bool solver_on = false;
+  rs_solver solver = {};
+  SgdPlan sgd_plan = {};
   const int* ctx_m_count = nullptr;   // while set, add_dgrad / add_wgrad bound their rows by this device counter (entries)
   int build_mask_training();
   std::vector<std::pair<void*, size_t>> clear_list;   // gradient buffers that must be zero before a backward pass
@@ -1770,6 +1792,45 @@ int rs_trainer_set_train_stats(rs_trainer* t, int on) {
   return RS_OK;
 }
 
+// The solver of the following optimiser steps.  The first call cuts the flat buffers along the segment table, uploads the chunk table
+// behind everything enqueued so far and registers "grad_norms" / "clip_coef"; later calls only replace the values, which are read when
+// rs_trainer_apply_sgd runs.
+int rs_trainer_set_solver(rs_trainer* t, const rs_solver* solver) {
+  RS_CHECK(t, RS_ERR_ARG, "rs_trainer_set_solver: null trainer");
+  { int rc = sgd_solver_check("rs_trainer_set_solver", solver); if (rc) return rc; }
+  if (!t->sgd_plan.chunks) {
+    const auto& segs = t->segment_table();
+    std::vector<int64_t> off, cnt;
+    std::vector<int32_t> flags;
+    for (const auto& s : segs) { off.push_back((int64_t)s.off); cnt.push_back((int64_t)s.count); flags.push_back(s.bias ? SGD_SEG_BIAS : 0); }
+    std::vector<SgdChunk> chunks;
+    std::vector<int> seg_chunks;
+    std::vector<uint8_t> host;
+    { int rc = sgd_plan_cut("rs_trainer_set_solver", off.data(), cnt.data(), flags.data(), (int)segs.size(), (long long)t->n_params, &chunks, &seg_chunks); if (rc) return rc; }
+    sgd_plan_pack(chunks, seg_chunks, &host);
+    void* base = nullptr;
+    { int rc = t->alloc(&base, sgd_plan_bytes((int)chunks.size(), (int)segs.size())); if (rc) return rc; }      // zero-filled on the chain stream
+    RS_HIP(hipStreamSynchronize(t->stream));
+    RS_HIP(hipMemcpy(base, host.data(), host.size(), hipMemcpyHostToDevice));
+    t->sgd_plan = sgd_plan_place(base, (int)chunks.size(), (int)segs.size());
+    t->reg("grad_norms", t->sgd_plan.norms, DT_F32, {(int64_t)segs.size()}, 0);
+    t->reg("clip_coef", t->sgd_plan.coef, DT_F32, {(int64_t)segs.size()}, 0);
+  }
+  t->solver = *solver;
+  t->solver_on = true;
+  return RS_OK;
+}
+int rs_trainer_segment_count(rs_trainer* t) { return t ? (int)t->segment_table().size() : 0; }
+int rs_trainer_segment_info(rs_trainer* t, int i, char* name_out, int64_t* offset, int64_t* count, int* is_bias) {
+  RS_CHECK(t && i >= 0 && i < (int)t->segment_table().size(), RS_ERR_ARG, "segment index");
+  const auto& s = t->segments[i];
+  if (name_out) { strncpy(name_out, s.name.c_str(), 95); name_out[95] = 0; }
+  if (offset) *offset = (int64_t)s.off;
+  if (count) *count = (int64_t)s.count;
+  if (is_bias) *is_bias = s.bias;
+  return RS_OK;
+}
+
 int rs_trainer_sync(rs_trainer* t) {
   RS_CHECK(t, RS_ERR_ARG, "null trainer");
   { int rc = t->join_side(); if (rc) return rc; }
@@ -1780,8 +1841,25 @@ int rs_trainer_sync(rs_trainer* t) {
 // one SGD-momentum step on every trainable tensor from the current gradient buffer, then refold the fp16 operands
 int rs_trainer_apply_sgd(rs_trainer* t, float lr, float momentum, float weight_decay) {
   RS_CHECK(t, RS_ERR_ARG, "null trainer");
+  const float inv_scale = 1.f / (t->loss_scale * t->grad_divisor);
+  SgdHyper h;
+  int norm_inf = 0;
+  if (t->solver_on) {      // before anything is enqueued: Nesterov needs a momentum
+    int rc = sgd_solver_hyper("rs_trainer_apply_sgd", t->solver, lr, momentum, weight_decay, inv_scale, &h, &norm_inf);
+    if (rc) return rc;
+  }
   int rc = t->join_side();
   if (rc) return rc;
+  if (t->solver_on) {
+    // the segmented step (sgd_rule.h).  A norm pass reads the whole gradient anyway and raises "grad_overflow" itself; without one the
+    // separate check runs as below
+    if (h.clip_type >= SGD_CLIP_NORM) rc = launch_grad_norms(t->sgd_plan, t->grad, h, norm_inf, t->overflow, t->stream);
+    else rc = launch_grad_nonfinite(t->grad, (long long)t->n_params, t->overflow, t->stream);
+    if (!rc) rc = launch_sgd_segments(t->sgd_plan, t->master, t->mom, t->grad, h, t->overflow, t->stream);
+    if (rc) return rc;
+    ++t->step_count;
+    return t->fold_all();
+  }
   // a gradient with inf / nan (fp16 loss scale too large for this batch) must not reach the weights: the step is skipped on the
   // device (no host round trip); the caller reads "grad_overflow" with the losses and lowers the scale (rs_trainer_set_loss_scale)
   rc = launch_grad_nonfinite(t->grad, (long long)t->n_params, t->overflow, t->stream);
@@ -1846,6 +1924,9 @@ int rs_trainer_copy_state(rs_trainer* dst, rs_trainer* src) {
   RS_HIP(hipMemcpyAsync(dst->master, src->master, dst->n_params * 4, hipMemcpyDeviceToDevice, dst->stream));
   RS_HIP(hipMemcpyAsync(dst->mom, src->mom, dst->n_params * 4, hipMemcpyDeviceToDevice, dst->stream));
   dst->step_count = src->step_count;
+  // the solver travels with the state: the destination cuts its own (identical) table on first use
+  if (src->solver_on) { int rc = rs_trainer_set_solver(dst, &src->solver); if (rc) return rc; }
+  else dst->solver_on = false;
   // the forward mode travels with the state, as the input-gradient mode below: switched off at once, switched on behind the fold
   const bool fwd_on = dst->eng->fwd_mode != src->eng->fwd_mode && src->eng->fwd_mode == 1;
   if (dst->eng->fwd_mode != src->eng->fwd_mode && src->eng->fwd_mode == 0) { int rc = rs_trainer_set_fwd_mode(dst, 0); if (rc) return rc; }

@@ -104,6 +104,40 @@ class RsEvalMatches(C.Structure):
                 ("matched", C.POINTER(C.c_uint32)), ("ignored", C.POINTER(C.c_uint32)), ("npig", C.POINTER(C.c_int32))]
 
 
+class RsSolver(C.Structure):
+    """include/rs_engine.h ``rs_solver``."""
+    _fields_ = [("struct_size", C.c_int32), ("nesterov", C.c_int32), ("bias_lr_factor", C.c_float), ("weight_decay_bias", C.c_float),
+                ("has_weight_decay_bias", C.c_int32), ("clip_type", C.c_int32), ("clip_value", C.c_float), ("norm_type", C.c_float)]
+
+
+CLIP_TYPES = ("none", "value", "norm", "full_model")     # rs_solver.clip_type 0..3
+
+
+class SolverOptions:
+    """The optimiser step's options beyond lr / momentum / weight decay, under detectron2's SOLVER keys: ``nesterov`` (NESTEROV),
+    ``bias_lr_factor`` (BIAS_LR_FACTOR), ``weight_decay_bias`` (WEIGHT_DECAY_BIAS; ``None`` = biases decay as the weights do),
+    ``clip_type`` (CLIP_GRADIENTS: "none" = ENABLED false, "value" / "norm" per parameter tensor as detectron2 0.6 clips, "full_model" =
+    one norm over all of them, the extension of detectron2's DETR / Mask2Former projects), ``clip_value`` (CLIP_VALUE), ``norm_type``
+    (NORM_TYPE: 2.0 or ``float("inf")``).  The defaults are torch.optim.SGD as the trainer always ran it.  WEIGHT_DECAY_NORM has no
+    field: every norm layer of this model is a FrozenBN."""
+
+    def __init__(self, nesterov: bool = False, bias_lr_factor: float = 1.0, weight_decay_bias: Optional[float] = None,
+                 clip_type: str = "none", clip_value: float = 1.0, norm_type: float = 2.0):
+        if clip_type not in CLIP_TYPES:
+            raise ValueError(f"clip_type must be one of {CLIP_TYPES}, got {clip_type!r}")
+        self.nesterov, self.bias_lr_factor, self.weight_decay_bias = bool(nesterov), float(bias_lr_factor), weight_decay_bias
+        self.clip_type, self.clip_value, self.norm_type = clip_type, float(clip_value), float(norm_type)
+
+    def to_struct(self) -> RsSolver:
+        wdb = self.weight_decay_bias
+        return RsSolver(C.sizeof(RsSolver), int(self.nesterov), self.bias_lr_factor, 0.0 if wdb is None else float(wdb), 0 if wdb is None else 1,
+                        CLIP_TYPES.index(self.clip_type), self.clip_value, self.norm_type)
+
+    def __repr__(self) -> str:
+        return (f"SolverOptions(nesterov={self.nesterov}, bias_lr_factor={self.bias_lr_factor}, weight_decay_bias={self.weight_decay_bias}, "
+                f"clip_type={self.clip_type!r}, clip_value={self.clip_value}, norm_type={self.norm_type})")
+
+
 class PolygonTables:
     """Polygons of the instances of one tile as the device polygoniser leaves them (include/rs_engine.h, ``rs_op_polygonize``):
     ``header`` (n, 8) int32 per instance [flagged, polygons, rings, vertices, first polygon, first ring, first vertex, 0] with the
@@ -232,6 +266,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.rs_host_box_stats.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp]
         lib.rs_host_mask_stats.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
         lib.rs_trainer_set_train_stats.argtypes = [vp, i32]
+    if hasattr(lib, "rs_op_sgd_segments"):            # RS_ENGINE_LIB may name an older build
+        lib.rs_op_sgd_segments.argtypes = [vp, vp, vp, i64, vp, vp, vp, i32, f32, f32, f32, f32, C.POINTER(RsSolver), vp, vp, vp, vp]
+        lib.rs_host_sgd_segments.argtypes = [vp, vp, vp, i64, vp, vp, vp, i32, f32, f32, f32, f32, C.POINTER(RsSolver), vp, vp, vp]
+        lib.rs_trainer_set_solver.argtypes = [vp, C.POINTER(RsSolver)]
+        lib.rs_trainer_segment_count.argtypes = [vp]
+        lib.rs_trainer_segment_info.argtypes = [vp, i32, C.c_char_p, C.POINTER(i64), C.POINTER(i64), i32p]
     lib.rs_resize_shape.argtypes = [i32, i32, i32, i32, i32p, i32p]
     lib.rs_resize_shape.restype = None
     lib.rs_resize_coeffs.argtypes = [i32, i32, i32p, i32p]
@@ -1319,8 +1359,11 @@ class Trainer:
 
     def __init__(self, spec: EngineSpec, weights: Dict[str, np.ndarray], tile_shape: Tuple[int, int, int], batch: int = 2,
                  device: int = 0, loss_scale: float = 1.0, lib_path: Optional[str] = None, mask_targets: str = "host", wgrad: str = "f32",
-                 dgrad: str = "f32", fwd: str = "f32", train_stats: bool = False, freeze_at: int = 2):
-        """``freeze_at``: detectron2's ``MODEL.BACKBONE.FREEZE_AT``, fixed at creation because it changes the graph.  2 (default): the
+                 dgrad: str = "f32", fwd: str = "f32", train_stats: bool = False, freeze_at: int = 2, solver: Optional[SolverOptions] = None):
+        """``solver``: a ``SolverOptions`` -- gradient clipping, Nesterov momentum and the bias parameter groups of the optimiser step
+        (``set_solver``).  ``None`` (default): ``apply_sgd`` is plain SGD with momentum over the whole flat buffer, as it always was.
+
+        ``freeze_at``: detectron2's ``MODEL.BACKBONE.FREEZE_AT``, fixed at creation because it changes the graph.  2 (default): the
         stem and res2 are frozen.  1: res2 is trained too.  0: the stem convolution as well -- what a detector with a fourth input band
         needs, whose stem channel no public checkpoint holds.  The forward engine then runs res2 (and at 0 the stem) unfused, the
         backward goes on below res3, and the flat buffers gain the groups "res2" and "stem" (``buckets()``).
@@ -1430,6 +1473,9 @@ class Trainer:
         self.train_stats_on = False
         if train_stats:
             self.set_train_stats(True)
+        self.solver: Optional[SolverOptions] = None
+        if solver is not None:
+            self.set_solver(solver)
 
     def _tensor_ptr(self, name: str, engine: bool = False):
         p, dt, nd, halo = C.c_void_p(), C.c_int32(), C.c_int32(), C.c_int32()
@@ -1620,6 +1666,7 @@ class Trainer:
         _check(self.lib, self.lib.rs_trainer_copy_state(self._h, other._h), "rs_trainer_copy_state")
         self.dgrad = other.dgrad                 # rs_trainer_copy_state carries the input-gradient mode
         self.fwd = other.fwd                     # ... and the forward mode
+        self.solver = other.solver               # ... and the solver
 
     def inference_engine(self) -> Engine:
         """The trainer's forward engine as an inference ``Engine`` (same device buffers, current weights): validation detections
@@ -1744,6 +1791,36 @@ class Trainer:
         _check(self.lib, self.lib.rs_trainer_set_train_stats(self._h, 1 if on else 0), "rs_trainer_set_train_stats")
         self.train_stats_on = bool(on)
 
+    def set_solver(self, solver: SolverOptions) -> None:
+        """The solver of the following ``apply_sgd`` calls (include/rs_engine.h ``rs_trainer_set_solver``): clipping, Nesterov, bias groups.
+        The first call adds the tensors "grad_norms" and "clip_coef" to ``tensor_names()``."""
+        if not hasattr(self.lib, "rs_trainer_set_solver"):
+            raise RsError("this librs_engine.so has no rs_trainer_set_solver (an older build)")
+        if not isinstance(solver, SolverOptions):
+            raise TypeError(f"solver must be a SolverOptions, got {type(solver).__name__}")
+        st = solver.to_struct()
+        _check(self.lib, self.lib.rs_trainer_set_solver(self._h, C.byref(st)), "rs_trainer_set_solver")
+        self.solver = solver
+
+    def segments(self) -> List[Tuple[str, int, int, bool]]:
+        """The trainable tensors in buffer order: (name "<layer>.w" / "<layer>.b", offset, count in floats of the flat buffers, is_bias)."""
+        out = []
+        name = C.create_string_buffer(96)
+        off, cnt, bias = C.c_int64(), C.c_int64(), C.c_int32()
+        for i in range(self.lib.rs_trainer_segment_count(self._h)):
+            _check(self.lib, self.lib.rs_trainer_segment_info(self._h, i, name, C.byref(off), C.byref(cnt), C.byref(bias)), "rs_trainer_segment_info")
+            out.append((name.value.decode(), int(off.value), int(cnt.value), bool(bias.value)))
+        return out
+
+    def grad_norms(self) -> Dict[str, float]:
+        """Name -> gradient norm of every trainable tensor as the last ``apply_sgd`` measured it (unscaled, rank-averaged gradient; the
+        solver's NORM_TYPE).  Only a solver that clips by "norm" or "full_model" measures norms.  One small copy and a wait for the
+        trainer's stream: for diagnosis, not for every step."""
+        if self.solver is None or self.solver.clip_type not in ("norm", "full_model"):
+            raise RsError("gradient norms are measured by a solver with clip_type 'norm' or 'full_model' (set_solver)")
+        norms = self.tensor("grad_norms")
+        return {s[0]: float(norms[i]) for i, s in enumerate(self.segments())}
+
     def train_stats_table(self) -> np.ndarray:
         """The int32 [16] table of the last step (include/rs_engine.h ``rs_trainer_set_train_stats``); synchronises the trainer's stream."""
         if not self.train_stats_on:
@@ -1815,12 +1892,15 @@ class MultiScaleTrainer:
 
     def __init__(self, spec: EngineSpec, weights: Dict[str, np.ndarray], tile_shape: Tuple[int, int, int], sizes: Sequence[int], batch: int = 1,
                  device: int = 0, loss_scale: float = 1024.0, mask_targets: str = "host", wgrad: str = "f32", dgrad: str = "f32",
-                 fwd: str = "f32", train_stats: bool = False, freeze_at: int = 2):
+                 fwd: str = "f32", train_stats: bool = False, freeze_at: int = 2, solver: Optional[SolverOptions] = None):
         if mask_targets not in MASK_TARGET_MODES:
             raise ValueError(f"mask_targets must be one of {MASK_TARGET_MODES}, got {mask_targets!r}")
         _check_wgrad(wgrad, spec)
         _check_dgrad(dgrad, spec)
         _check_fwd(fwd, spec)
+        if solver is not None and not isinstance(solver, SolverOptions):
+            raise TypeError(f"solver must be a SolverOptions, got {type(solver).__name__}")
+        self.solver = solver
         self.freeze_at = _check_freeze_at(freeze_at)
         self.mask_targets = mask_targets
         self.train_stats_on = bool(train_stats)
@@ -1861,6 +1941,20 @@ class MultiScaleTrainer:
         for t in self._t.values():
             t.set_train_stats(on)
 
+    def set_solver(self, solver: SolverOptions) -> None:
+        """``Trainer.set_solver`` on every trainer, those built later included."""
+        if not isinstance(solver, SolverOptions):
+            raise TypeError(f"solver must be a SolverOptions, got {type(solver).__name__}")
+        self.solver = solver
+        for t in self._t.values():
+            t.set_solver(solver)
+
+    def grad_norms(self) -> Dict[str, float]:
+        """``Trainer.grad_norms`` of the trainer that ran the last step."""
+        if self.current is None:
+            raise RsError("no trainer has run a step yet")
+        return self.current.grad_norms()
+
     def train_stats(self) -> Dict[str, float]:
         """``Trainer.train_stats`` of the trainer that ran the last step."""
         if self.current is None:
@@ -1883,7 +1977,7 @@ class MultiScaleTrainer:
         if size not in self._t:
             t = Trainer(self.spec.replace(min_size_test=int(size)), self.weights, self.tile_shape, self.batch, self.device, self.loss_scale,
                         mask_targets=self.mask_targets, wgrad=self.wgrad, dgrad=self.dgrad, fwd=self.fwd, train_stats=self.train_stats_on,
-                        freeze_at=self.freeze_at)
+                        freeze_at=self.freeze_at, solver=self.solver)
             if self._sampling:
                 t.set_sampling(*self._sampling)
             if getattr(self, "_rpn_topk", None):

@@ -23,13 +23,16 @@ model-zoo name of ``model_weights.model_zoo_checkpoint_url`` is resolved in dete
 (``weights.resolve_zoo_checkpoint``: no download; else ``model_weights.pth_file`` or ``--synthetic-weights``).  Every TEST.EVAL_PERIOD iterations the validation loss and the COCO bbox / segm AP (coco_eval.py, a
 restatement of pycocotools' COCOeval) of the `val` set are logged to metrics.json.  ``--train-stats`` adds detectron2's ten training
 diagnostics (rpn/num_pos_anchors .. mask_rcnn/false_negative), counted on the GPU, to every record: the logged iteration's own values
-(no 20-iteration median), rank 0's own counts.
+(no 20-iteration median), rank 0's own counts.  ``--solver extended`` runs the optimiser step over a table of the parameter tensors and
+then honours SOLVER.CLIP_GRADIENTS, NESTEROV, BIAS_LR_FACTOR, WEIGHT_DECAY_BIAS, WARMUP_METHOD constant and WarmupCosineLR; without it a
+YAML that asks for one of them is refused.
 """
 from __future__ import annotations
 
 import argparse
 import json
 import logging
+import math
 import os
 import sys
 import time
@@ -71,6 +74,10 @@ def load_solver(d2_yaml: str) -> Dict[str, Any]:
         "warmup_method": str(s.get("WARMUP_METHOD", "linear")), "bias_lr_factor": float(s.get("BIAS_LR_FACTOR", 1.0)),
         "weight_decay_bias": s.get("WEIGHT_DECAY_BIAS", None), "nesterov": bool(s.get("NESTEROV", False)),
         "clip_gradients": bool((s.get("CLIP_GRADIENTS", {}) or {}).get("ENABLED", False)),
+        "clip_type": str((s.get("CLIP_GRADIENTS", {}) or {}).get("CLIP_TYPE", "value")),
+        "clip_value": float((s.get("CLIP_GRADIENTS", {}) or {}).get("CLIP_VALUE", 1.0)),
+        "norm_type": float((s.get("CLIP_GRADIENTS", {}) or {}).get("NORM_TYPE", 2.0)),
+        "weight_decay_norm": s.get("WEIGHT_DECAY_NORM", None),      # read, no effect: every norm layer is a FrozenBN
         "amp": bool((s.get("AMP", {}) or {}).get("ENABLED", False)),
         "lr_scheduler": str(s.get("LR_SCHEDULER_NAME", "WarmupMultiStepLR")),
         "sampler_train": str((cfg.get("DATALOADER", {}) or {}).get("SAMPLER_TRAIN", "TrainingSampler")),
@@ -84,28 +91,64 @@ GT_CAP, MASK_ENTRIES_CAP, ROI_CAP, RPN_PRE_TOPK_CAP, RPN_POST_TOPK_CAP = 128, 25
 FREEZE_AT_VALUES = (0, 1, 2)    # MODEL.BACKBONE.FREEZE_AT the trainer implements (engine.FREEZE_AT_VALUES; kept here so that validation needs no library)
 
 
-def validate_solver(sv: Dict[str, Any], num_classes: Optional[int] = None) -> None:
+EXTENDED_SOLVER_HINT = "honoured with --solver extended"
+CLIP_TYPES = ("value", "norm", "full_model")      # SOLVER.CLIP_GRADIENTS.CLIP_TYPE with --solver extended (engine.CLIP_TYPES without "none")
+LR_SCHEDULERS = ("WarmupMultiStepLR", "WarmupCosineLR")
+WARMUP_METHODS = ("linear", "constant")
+
+
+def weight_decay_bias_of(sv: Dict[str, Any]) -> Optional[float]:
+    """SOLVER.WEIGHT_DECAY_BIAS as a number, None where the file is silent (detectron2 then decays biases as the weights)."""
+    v = sv.get("weight_decay_bias")
+    return None if v in (None, "None") else float(v)
+
+
+def validate_solver(sv: Dict[str, Any], num_classes: Optional[int] = None, extended: bool = False) -> None:
     """Reject, up front, every solver / sampler value the training engine does not implement -- never clamp or ignore one
     silently (the same rule as ``EngineSpec.check_supported`` for the model keys).  Values of the reference YAML
     (R:config/detectron2_config_3bands.yaml:268-305, :29, :178, :192, :248-250) all pass.  ``num_classes``: the classes of the
     run where known (COCO categories / checkpoint heads) -- inference engines run up to spec.MAX_CLASSES, the trainer's losses and
-    its box-head backward stop at TRAIN_MAX_CLASSES (rs_trainer_create returns RS_ERR_UNSUPPORTED above)."""
+    its box-head backward stop at TRAIN_MAX_CLASSES (rs_trainer_create returns RS_ERR_UNSUPPORTED above).  ``extended`` (``--solver
+    extended``): the optimiser step's segmented form is on, which honours CLIP_GRADIENTS (value, norm, full_model; NORM_TYPE 2 or inf),
+    NESTEROV, BIAS_LR_FACTOR, WEIGHT_DECAY_BIAS, WARMUP_METHOD constant and LR_SCHEDULER_NAME WarmupCosineLR; only impossible
+    combinations of them remain errors.  Without it those keys are refused, and the message names the switch."""
     errs = []
+    hint = f"; {EXTENDED_SOLVER_HINT}"
     if num_classes is not None and num_classes > TRAIN_MAX_CLASSES:
         errs.append(f"ROI_HEADS.NUM_CLASSES {num_classes} > {TRAIN_MAX_CLASSES}: more than {TRAIN_MAX_CLASSES} classes run in inference only "
                     f"(make_detections, up to {MAX_CLASSES}); the training engine is not built for them")
-    if sv["lr_scheduler"] != "WarmupMultiStepLR":
-        errs.append(f"SOLVER.LR_SCHEDULER_NAME {sv['lr_scheduler']!r} (only WarmupMultiStepLR)")
-    if sv["warmup_method"] != "linear":
-        errs.append(f"SOLVER.WARMUP_METHOD {sv['warmup_method']!r} (only linear)")
-    if sv["bias_lr_factor"] != 1.0:
-        errs.append(f"SOLVER.BIAS_LR_FACTOR {sv['bias_lr_factor']} (only 1.0: one SGD launch over the flat parameter buffer)")
-    if sv["weight_decay_bias"] not in (None, "None") and float(sv["weight_decay_bias"]) != sv["weight_decay"]:
-        errs.append(f"SOLVER.WEIGHT_DECAY_BIAS {sv['weight_decay_bias']} != WEIGHT_DECAY {sv['weight_decay']}")
-    if sv["nesterov"]:
-        errs.append("SOLVER.NESTEROV true")
-    if sv["clip_gradients"]:
-        errs.append("SOLVER.CLIP_GRADIENTS.ENABLED true")
+    if extended:
+        if sv["lr_scheduler"] not in LR_SCHEDULERS:
+            errs.append(f"SOLVER.LR_SCHEDULER_NAME {sv['lr_scheduler']!r} (only {', '.join(LR_SCHEDULERS)})")
+        if sv["warmup_method"] not in WARMUP_METHODS:
+            errs.append(f"SOLVER.WARMUP_METHOD {sv['warmup_method']!r} (only {', '.join(WARMUP_METHODS)})")
+        if not (0.0 <= sv["bias_lr_factor"] < math.inf):
+            errs.append(f"SOLVER.BIAS_LR_FACTOR {sv['bias_lr_factor']} (a finite factor >= 0)")
+        wdb = weight_decay_bias_of(sv)
+        if wdb is not None and not (0.0 <= wdb < math.inf):
+            errs.append(f"SOLVER.WEIGHT_DECAY_BIAS {wdb} (finite, >= 0)")
+        if sv["nesterov"] and not sv["momentum"] > 0:
+            errs.append(f"SOLVER.NESTEROV true with MOMENTUM {sv['momentum']} (Nesterov momentum needs a momentum > 0)")
+        if sv["clip_gradients"]:
+            if sv["clip_type"] not in CLIP_TYPES:
+                errs.append(f"SOLVER.CLIP_GRADIENTS.CLIP_TYPE {sv['clip_type']!r} (only {', '.join(CLIP_TYPES)})")
+            if not (0.0 < sv["clip_value"] < math.inf):
+                errs.append(f"SOLVER.CLIP_GRADIENTS.CLIP_VALUE {sv['clip_value']} (must be > 0)")
+            if sv["clip_type"] in ("norm", "full_model") and sv["norm_type"] not in (2.0, math.inf):
+                errs.append(f"SOLVER.CLIP_GRADIENTS.NORM_TYPE {sv['norm_type']} (only 2.0 and inf)")
+    else:
+        if sv["lr_scheduler"] != "WarmupMultiStepLR":
+            errs.append(f"SOLVER.LR_SCHEDULER_NAME {sv['lr_scheduler']!r} (only WarmupMultiStepLR{hint if sv['lr_scheduler'] in LR_SCHEDULERS else ''})")
+        if sv["warmup_method"] != "linear":
+            errs.append(f"SOLVER.WARMUP_METHOD {sv['warmup_method']!r} (only linear{hint if sv['warmup_method'] in WARMUP_METHODS else ''})")
+        if sv["bias_lr_factor"] != 1.0:
+            errs.append(f"SOLVER.BIAS_LR_FACTOR {sv['bias_lr_factor']} (only 1.0: one SGD launch over the flat parameter buffer{hint})")
+        if sv["weight_decay_bias"] not in (None, "None") and float(sv["weight_decay_bias"]) != sv["weight_decay"]:
+            errs.append(f"SOLVER.WEIGHT_DECAY_BIAS {sv['weight_decay_bias']} != WEIGHT_DECAY {sv['weight_decay']} ({EXTENDED_SOLVER_HINT})")
+        if sv["nesterov"]:
+            errs.append(f"SOLVER.NESTEROV true ({EXTENDED_SOLVER_HINT})")
+        if sv["clip_gradients"]:
+            errs.append(f"SOLVER.CLIP_GRADIENTS.ENABLED true ({EXTENDED_SOLVER_HINT})")
     if sv["crop"]:
         errs.append("INPUT.CROP.ENABLED true")
     if sv["sampler_train"] != "TrainingSampler":
@@ -140,13 +183,26 @@ def check_gt_capacity(recs: Sequence[Dict[str, Any]], what: str) -> None:
 
 
 def lr_at(sv: Dict[str, Any], it: int) -> float:
-    """WarmupMultiStepLR ([EXT d2: solver/lr_scheduler.py]): linear warm-up factor times gamma^(milestones passed)."""
+    """WarmupMultiStepLR / WarmupCosineLR ([EXT d2: solver/lr_scheduler.py]): the warm-up factor (linear: from WARMUP_FACTOR to 1 over
+    WARMUP_ITERS; constant: WARMUP_FACTOR until then) times gamma^(milestones passed), or times 0.5 * (1 + cos(pi * it / MAX_ITER))."""
     if it < sv["warmup_iters"]:
-        alpha = it / sv["warmup_iters"]
-        wf = sv["warmup_factor"] * (1 - alpha) + alpha
+        if sv.get("warmup_method", "linear") == "constant":
+            wf = sv["warmup_factor"]
+        else:
+            alpha = it / sv["warmup_iters"]
+            wf = sv["warmup_factor"] * (1 - alpha) + alpha
     else:
         wf = 1.0
+    if sv.get("lr_scheduler", "WarmupMultiStepLR") == "WarmupCosineLR":
+        return sv["base_lr"] * wf * 0.5 * (1.0 + math.cos(math.pi * it / sv["max_iter"]))
     return sv["base_lr"] * wf * sv["gamma"] ** sum(1 for s in sv["steps"] if s <= it)
+
+
+def solver_options(sv: Dict[str, Any]):
+    """``engine.SolverOptions`` of a validated solver (``--solver extended``)."""
+    from .engine import SolverOptions
+    return SolverOptions(nesterov=sv["nesterov"], bias_lr_factor=sv["bias_lr_factor"], weight_decay_bias=weight_decay_bias_of(sv),
+                         clip_type=sv["clip_type"] if sv["clip_gradients"] else "none", clip_value=sv["clip_value"], norm_type=sv["norm_type"])
 
 
 def load_coco_training_set(path: str) -> Tuple[List[Dict[str, Any]], List[int]]:
@@ -309,6 +365,13 @@ def build_parser() -> argparse.ArgumentParser:
                          "fast_rcnn/false_negative, mask_rcnn/accuracy, mask_rcnn/false_positive, mask_rcnn/false_negative.  They are counted on "
                          "the GPU behind the loss stages and one 16-integer table is read on logged iterations.  The values are those of the "
                          "logged iteration (no 20-iteration median) and, under data parallelism, rank 0's own.  Off by default")
+    ap.add_argument("--solver", choices=("default", "extended"), default="default",
+                    help="the optimiser step.  default: SGD with momentum in one launch over the flat parameter buffer; a detectron2 YAML "
+                         "that asks for more is refused.  extended: the step runs over a table of the parameter tensors and honours "
+                         "SOLVER.CLIP_GRADIENTS (CLIP_TYPE value or norm per tensor as detectron2 0.6, or full_model: one norm over all, as "
+                         "detectron2's DETR and Mask2Former projects; NORM_TYPE 2.0 or inf), NESTEROV, BIAS_LR_FACTOR, WEIGHT_DECAY_BIAS, "
+                         "WARMUP_METHOD constant and LR_SCHEDULER_NAME WarmupCosineLR.  Norms are summed on the GPU in a fixed order, "
+                         "without a host read-back.  WEIGHT_DECAY_NORM is read and has no effect: every norm layer is a FrozenBN")
     ap.add_argument("--val-ap", choices=("host", "device", "device-match"), default="host",
                     help="where the validation AP's mask overlaps are counted.  host (default): every detection mask is copied back, every "
                          "ground-truth polygon rasterised on the host and the IoUs taken from the masks.  device: the ground truth is "
@@ -396,7 +459,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         spec = load_d2_yaml(cfg["detectron2_config_file"], num_classes=k)
     else:
         raise SystemExit("model_weights needs pth_file or model_zoo_checkpoint_url (or --synthetic-weights)")
-    validate_solver(sv, num_classes=spec.num_classes)     # the class count is known here: COCO categories, or the checkpoint's heads
+    validate_solver(sv, num_classes=spec.num_classes, extended=args.solver == "extended")     # the class count is known here: COCO categories, or the checkpoint's heads
+    sv["max_iter"] = max_iter                             # WarmupCosineLR's horizon follows --max-iter
 
     precision = args.precision if args.precision != "auto" else ("fp16" if sv["amp"] else "fp32")
     spec = spec.replace(precision=precision, batched_nms=args.batched_nms.replace("-", "_"))
@@ -436,7 +500,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         sizes = list(range(sizes[0], sizes[1] + 1, 32))
     ms = MultiScaleTrainer(spec, W, first.shape, sizes, batch=per_rank, device=local_rank, loss_scale=args.loss_scale,
                            mask_targets=args.mask_targets, wgrad=args.wgrad, dgrad=args.dgrad, fwd=args.fwd, train_stats=args.train_stats,
-                           freeze_at=sv["freeze_at"])
+                           freeze_at=sv["freeze_at"], solver=solver_options(sv) if args.solver == "extended" else None)
+    if args.solver == "extended":
+        log.info("solver: extended (%r, warm-up %s, %s)", ms.solver, sv["warmup_method"], sv["lr_scheduler"])
     if args.train_stats:
         log.info("train_stats: on (detectron2's training diagnostics counted on the GPU; the logged iteration's own values, no smoothing; "
                  "rank 0's own counts)")
