@@ -981,6 +981,54 @@ int rs_engine_fetch_eval_match_async(rs_engine* e, int n, rs_dets* dets_host, co
                                      const int32_t* gt_classes, const double* iou_thrs, rs_eval_matches* matches_host);
 int rs_engine_fetch_eval_match_wait(rs_engine* e);
 
+/* ------------------------------------------------------------------ the road cover vote on the device (csrc/road_vote.h)
+ * The project's deliverable is a cover class per road: the reference overlays the tile-clipped road labels with the detections,
+ * weights every (road, detection) pair by round(area(intersection) / area(label), 2), keeps the pairs above 0.05 whose score reaches
+ * a threshold and sums, per road and class, weighted scores and weights (proj_roadsurf_amd/raster_vote.py weighted_scores,
+ * determine_detected_class).  A road label in tile pixels is the same object as a ground-truth instance of the validation counts, so
+ * the stage runs on the tables rs_op_mask_pair_counts writes, one label per "ground truth".  Areas are whole pixels of the tile grid
+ * and polygon simplification does not enter.  csrc/road_vote.h states the rule once, for the kernel (csrc/val_ap.hip) and the host
+ * restatement: for every tile t, label g < min(tile_first[t+1] - tile_first[t], gt_cap) with A = gt_area[t][g] > 0 and class c, the
+ * slots d = 0 .. det_count[t] - 1 in ascending order; with I = inter[t][d][g] > 0 and det_classes[t][d] == c,
+ * frac = rint((double)I / (double)A * 100.0) / 100.0 (numpy's round(I / A, 2)); a pair with frac > 0.05 and (double)score >=
+ * threshold adds frac * (double)score to wscore, frac to wfrac and 1 to pairs.  float64, the compiler's correctly rounded division,
+ * no mul+add contraction, no atomics: the bits do not depend on the run.
+ *
+ * Tables: det_scores / det_classes [n_tiles][slots], det_count [n_tiles] as rs_dets; tile_first [n_tiles + 1]; inter
+ * [n_tiles][slots][gt_cap] and gt_area [n_tiles][gt_cap] as rs_op_mask_pair_counts writes them.  Out: wscore, wfrac
+ * [n_tiles][gt_cap][num_classes] double, pairs [n_tiles][gt_cap][num_classes] int32; rows of labels past the tile's own and of
+ * labels with area 0 are zero, a detection whose class lies outside [0, num_classes) votes for nothing.
+ * rs_op_road_votes takes device pointers, clears its outputs, enqueues on `stream` and does not wait; rs_host_road_votes takes the
+ * same arguments as host pointers and needs no device.  Both refuse, before anything is touched: a null table, n_tiles < 1,
+ * num_classes outside [1, RS_MAX_CLASSES], slots or gt_cap < 1, a threshold that is not finite (RS_ERR_ARG); slots > 1024 or gt_cap
+ * > RS_EVAL_GT_CAP (RS_ERR_UNSUPPORTED). */
+int rs_op_road_votes(const float* det_scores, const int32_t* det_classes, const int32_t* det_count, const int32_t* tile_first,
+                     const int32_t* inter, const int32_t* gt_area, int n_tiles, int num_classes, int slots, int gt_cap, double threshold,
+                     double* wscore, double* wfrac, int32_t* pairs, void* stream);
+int rs_host_road_votes(const float* det_scores, const int32_t* det_classes, const int32_t* det_count, const int32_t* tile_first,
+                       const int32_t* inter, const int32_t* gt_area, int n_tiles, int num_classes, int slots, int gt_cap, double threshold,
+                       double* wscore, double* wfrac, int32_t* pairs);
+
+/* The same behind the engine's last forward.  rs_engine_fetch_votes_async is an add-on, not a fetch form: it carries no rs_dets and
+ * may follow any rs_engine_fetch*_async of the same forward (plain, crops, polygons) or stand alone.  It packs the road labels of the
+ * batch's n tiles (the polygon tables of rs_engine_fetch_eval_async: one instance per label, tile pixels) and enqueues, on the copy
+ * stream behind the forward and behind that fetch: their upload, the rasteriser, the pair counts, the vote (gt_cap = RS_EVAL_GT_CAP,
+ * slots = D, num_classes = the engine's) and the copies of the three vote tables and of gt_area into caller-allocated
+ * (rs_host_alloc) buffers.  No mask leaves the device and `inter` stays there.  It shares the pool of the validation counts and its
+ * limits, and returns RS_EVAL_DOES_NOT_FIT with nothing enqueued under the conditions of rs_engine_eval_fits (also D > 1024): vote
+ * on that batch from fetched masks.  The next forward on the engine is ordered behind it as behind rs_engine_fetch_eval_async.  An
+ * engine that never calls it allocates nothing for it.  rs_engine_fetch_votes_wait waits for the copies (and for whatever else is
+ * on the copy stream in front of them); a crops or polygons fetch in flight is still completed by its own wait. */
+typedef struct rs_road_votes {
+  double* wscore;       /* [n][RS_EVAL_GT_CAP][K] */
+  double* wfrac;        /* [n][RS_EVAL_GT_CAP][K] */
+  int32_t* pairs;       /* [n][RS_EVAL_GT_CAP][K] */
+  int32_t* label_area;  /* [n][RS_EVAL_GT_CAP] */
+} rs_road_votes;
+int rs_engine_fetch_votes_async(rs_engine* e, int n, const double* polys, const int64_t* poly_off, const int32_t* poly_len,
+                                const int32_t* inst_first, const int32_t* tile_first, double threshold, rs_road_votes* votes_host);
+int rs_engine_fetch_votes_wait(rs_engine* e);
+
 #ifdef __cplusplus
 }
 #endif

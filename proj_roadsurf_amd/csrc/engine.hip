@@ -1221,6 +1221,14 @@ int rs_engine::ensure_match_buffers() {
   return alloc((void**)&match_order, (size_t)max_batch * D * 4);     // last: its presence says that all of the above exists
 }
 
+int rs_engine::ensure_vote_buffers() {
+  if (vote_pairs) return RS_OK;
+  vote_cells = (size_t)max_batch * RS_EVAL_GT_CAP * (size_t)spec.num_classes;
+  int rc;
+  if ((rc = alloc((void**)&vote_wscore, vote_cells * 16))) return rc;        // wscore, then wfrac
+  return alloc((void**)&vote_pairs, vote_cells * 4);   // last: its presence says that all of the above exists
+}
+
 // upload of the packed pool, rasteriser, pair counts: on the copy stream, behind the forward and in front of the result copies
 int rs_engine::launch_eval_counts(int n, const void* layout, hipStream_t s) {
   const MtLayout& L = *(const MtLayout*)layout;
@@ -1660,6 +1668,43 @@ int rs_engine_fetch_eval_match_async(rs_engine* e, int n, rs_dets* o, const doub
 }
 
 int rs_engine_fetch_eval_match_wait(rs_engine* e) { return rs_engine_fetch_wait(e); }
+
+// The counts of the road labels against the last forward's masks, then the cover vote on them (road_vote.h): only the vote tables and
+// the labels' areas travel.  An add-on behind whatever fetch of this forward is already on the copy stream: it copies no detections.
+int rs_engine_fetch_votes_async(rs_engine* e, int n, const double* polys, const int64_t* poly_off, const int32_t* poly_len,
+                                const int32_t* inst_first, const int32_t* tile_first, double threshold, rs_road_votes* v) {
+  RS_CHECK(e && v && v->wscore && v->wfrac && v->pairs && v->label_area && n >= 1 && n <= e->max_batch, RS_ERR_ARG,
+           "rs_engine_fetch_votes_async: bad argument");
+  RS_CHECK(threshold - threshold == 0.0, RS_ERR_ARG, "rs_engine_fetch_votes_async: the threshold is not finite");
+  { int rc = rs_engine_eval_fits(e, n, poly_off, poly_len, inst_first, tile_first); if (rc) return rc; }
+  if (e->D > RV_MAX_SLOTS) return RS_EVAL_DOES_NOT_FIT;
+  const int K = e->spec.num_classes;
+  MtLayout L;
+  { int rc = mt_measure(polys, poly_off, poly_len, inst_first, tile_first[n], n, &L); if (rc) return rc; }
+  hipStream_t s = nullptr;
+  int rc;
+  if ((rc = e->ensure_eval_buffers())) return rc;
+  if ((rc = e->ensure_vote_buffers())) return rc;
+  RS_CHECK(L.bytes <= e->eval_pool_bytes, RS_ERR_ARG, "road labels: %zu bytes packed, the pool holds %zu", L.bytes, e->eval_pool_bytes);
+  if (e->eval_upload_pending) { RS_HIP(hipEventSynchronize(e->ev_eval_upload)); e->eval_upload_pending = false; }
+  mt_pack(e->eval_pinned, L, polys, poly_off, poly_len, inst_first, tile_first);
+  if ((rc = e->begin_fetch(&s))) return rc;
+  if ((rc = e->launch_eval_counts(n, &L, s))) return rc;
+  RoadVoteParams q;
+  memset(&q, 0, sizeof q);
+  q.det_scores = e->det_scores; q.det_classes = e->det_classes; q.det_count = e->det_count; q.tile_first = (const int*)e->eval_pool;
+  q.inter = e->eval_inter; q.gt_area = e->eval_gt_area; q.wscore = e->vote_wscore; q.wfrac = e->vote_wscore + e->vote_cells;
+  q.pairs = e->vote_pairs; q.threshold = threshold; q.n = n; q.K = K; q.D = e->D; q.g_cap = RS_EVAL_GT_CAP;
+  if ((rc = launch_road_votes(q, s))) return rc;
+  const size_t cells = (size_t)n * RS_EVAL_GT_CAP * K;
+  RS_HIP(hipMemcpyAsync(v->wscore, q.wscore, cells * 8, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(v->wfrac, q.wfrac, cells * 8, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(v->pairs, q.pairs, cells * 4, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(v->label_area, e->eval_gt_area, (size_t)n * RS_EVAL_GT_CAP * 4, hipMemcpyDeviceToHost, s));
+  return e->end_fetch(s, nullptr);            // the tables live in their own buffers: detections and canvases are free for the next forward
+}
+
+int rs_engine_fetch_votes_wait(rs_engine* e) { return rs_engine_fetch_wait(e); }
 
 int rs_engine_fetch_wait(rs_engine* e) {
   RS_CHECK(e, RS_ERR_ARG, "null engine");

@@ -127,6 +127,11 @@ struct rs_engine {
   int *match_class_first = nullptr, *match_gt_per_class = nullptr, *match_npig = nullptr;
   uint32_t *match_matched = nullptr, *match_ignored = nullptr;
   int ensure_match_buffers();
+  // vote tables (rs_engine_fetch_votes_*, road_vote.h): allocated on the first call
+  double* vote_wscore = nullptr;                // device: wscore [max_batch][RS_EVAL_GT_CAP][K], then wfrac of the same shape
+  int* vote_pairs = nullptr;
+  size_t vote_cells = 0;
+  int ensure_vote_buffers();
 
   // the steps of a result fetch, in the order the fetch entries enqueue them (engine.hip)
   int ensure_crop_header();

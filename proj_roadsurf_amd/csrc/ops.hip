@@ -325,6 +325,36 @@ int rs_host_coco_match(const float* det_boxes, const float* det_scores, const in
   return host_coco_match(q);          // val_ap.hip: the float64 arithmetic is compiled there, without mul+add contraction
 }
 
+// The road cover vote on caller-owned tables (see include/rs_engine.h): device pointers enqueued on `stream`, or host pointers
+static_assert(RV_MAX_CLASSES == RS_MAX_CLASSES && RV_MAX_GT == RS_EVAL_GT_CAP && RV_MAX_SLOTS == CM_MAX_SLOTS, "road_vote.h restates the header's capacities");
+static int road_vote_params(const char* who, RoadVoteParams* q, const float* det_scores, const int32_t* det_classes, const int32_t* det_count,
+                            const int32_t* tile_first, const int32_t* inter, const int32_t* gt_area, int n_tiles, int num_classes, int slots,
+                            int gt_cap, double threshold, double* wscore, double* wfrac, int32_t* pairs) {
+  memset(q, 0, sizeof *q);
+  q->det_scores = det_scores; q->det_classes = det_classes; q->det_count = det_count; q->tile_first = tile_first; q->inter = inter;
+  q->gt_area = gt_area; q->wscore = wscore; q->wfrac = wfrac; q->pairs = pairs; q->threshold = threshold;
+  q->n = n_tiles; q->K = num_classes; q->D = slots; q->g_cap = gt_cap;
+  return road_vote_check(who, *q);
+}
+int rs_op_road_votes(const float* det_scores, const int32_t* det_classes, const int32_t* det_count, const int32_t* tile_first,
+                     const int32_t* inter, const int32_t* gt_area, int n_tiles, int num_classes, int slots, int gt_cap, double threshold,
+                     double* wscore, double* wfrac, int32_t* pairs, void* stream) {
+  RoadVoteParams q;
+  { int rc = road_vote_params("rs_op_road_votes", &q, det_scores, det_classes, det_count, tile_first, inter, gt_area, n_tiles, num_classes, slots, gt_cap,
+                              threshold, wscore, wfrac, pairs);
+    if (rc) return rc; }
+  return launch_road_votes(q, (hipStream_t)stream);
+}
+int rs_host_road_votes(const float* det_scores, const int32_t* det_classes, const int32_t* det_count, const int32_t* tile_first,
+                       const int32_t* inter, const int32_t* gt_area, int n_tiles, int num_classes, int slots, int gt_cap, double threshold,
+                       double* wscore, double* wfrac, int32_t* pairs) {
+  RoadVoteParams q;
+  { int rc = road_vote_params("rs_host_road_votes", &q, det_scores, det_classes, det_count, tile_first, inter, gt_area, n_tiles, num_classes, slots, gt_cap,
+                              threshold, wscore, wfrac, pairs);
+    if (rc) return rc; }
+  return host_road_votes(q);          // val_ap.hip: the float64 arithmetic is compiled there, without mul+add contraction
+}
+
 int rs_op_conv2d_dgrad(const void* dy, const void* w_t, void* dx, const void* res, const float* res32, const void* mask,
                        const void* down, int n, int hi, int wi, int cin, int ho, int wo, int cout, int kh, int kw, int stride,
                        int pad, int kpad, int halo, int variant, void* stream) {

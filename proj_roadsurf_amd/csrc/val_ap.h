@@ -5,6 +5,7 @@
 // after common.h: the HIP runtime header defines what MT_HD expands to
 #include "canvas_raster.h"
 #include "coco_match.h"
+#include "road_vote.h"
 
 // One mask per instance, [n_inst][side][(side + 7) / 8] bytes, bit x % 8 of byte x / 8 = pixel x, padding bits zero: bit for bit
 // rs_rasterize_polygons_within_box(polygons of the instance, box (0, 0, side, side), mask_size side).  Tables as MaskTargetsParams
@@ -64,3 +65,24 @@ struct CocoMatchParams {
 int coco_match_check(const char* who, const CocoMatchParams& p);
 int launch_coco_match(const CocoMatchParams& p, hipStream_t s);       // device pointers; enqueues the order pass and the match pass
 int host_coco_match(const CocoMatchParams& p);                        // host pointers; the plain loops of coco_eval._evaluate_img
+
+// The road cover vote for every tile of a batch (road_vote.h states the rule and the layout of the three tables).  Detections as the
+// engine holds them; inter / gt_area as PairCountParams writes them, one "ground truth" per road label.  threshold travels by value.
+struct RoadVoteParams {
+  const float* det_scores;  // [n][D]
+  const int* det_classes;   // [n][D]
+  const int* det_count;     // [n]
+  const int* tile_first;    // [n + 1]
+  const int* inter;         // [n][D][g_cap]
+  const int* gt_area;       // [n][g_cap]
+  double* wscore;           // [n][g_cap][K]
+  double* wfrac;            // [n][g_cap][K]
+  int* pairs;               // [n][g_cap][K]
+  double threshold;
+  int n, K, D, g_cap;
+};
+// both refuse (before anything is touched) null tables, n < 1, K outside [1, RS_MAX_CLASSES], D or g_cap < 1, a threshold that is not
+// finite (RS_ERR_ARG); D > RV_MAX_SLOTS or g_cap > RV_MAX_GT (RS_ERR_UNSUPPORTED); `who` names the entry in the error text
+int road_vote_check(const char* who, const RoadVoteParams& p);
+int launch_road_votes(const RoadVoteParams& p, hipStream_t s);        // device pointers; clears the three tables and enqueues the kernel
+int host_road_votes(const RoadVoteParams& p);                         // host pointers; the plain loops

@@ -8,7 +8,12 @@
 //   coco_order_kernel         per tile the detections' order by (category, score descending, slot) and the per-category counts.
 //   coco_match_kernel         one wave per (tile, kind, area range, IoU threshold): the greedy matching over coco_match.h's rules, float64
 //                             IoUs with the compiler's correctly rounded division, flags as bit words.  No atomics.
-// host_coco_match is the same rule as plain host loops (rs_host_coco_match); it lives here for the compile flags.
+//   road_vote_kernel          the road cover vote (road_vote.h) on the same pair counts, one road label per "ground truth": one work
+//                             item per (label, class) cell, float64 in numpy's order.  No atomics.
+// host_coco_match and host_road_votes are the same rules as plain host loops (rs_host_coco_match, rs_host_road_votes); they live
+// here for the compile flags.
+#include <string.h>
+
 #include "val_ap.h"
 
 namespace {
@@ -248,7 +253,83 @@ __global__ __launch_bounds__(64) void coco_match_kernel(const CocoMatchParams p)
   }
 }
 
+// ---- the road cover vote (road_vote.h) ----
+
+// One work item per cell (label g, class c) of tile blockIdx.y, neighbouring lanes on neighbouring labels: the walk over the tile's
+// detection slots reads one row of `inter` per slot, coalesced, and the slot's class and score as one value for the wave.  No atomics:
+// the cell has one owner and the slots come in ascending order.  The tables were zeroed by the launcher; a cell without a label, or
+// of a label without area, stays as it is.
+__global__ __launch_bounds__(256) void road_vote_kernel(const RoadVoteParams p) {
+  const int t = blockIdx.y, cell = blockIdx.x * 256 + threadIdx.x;
+  if (cell >= p.g_cap * p.K) return;
+  const int c = cell / p.g_cap, g = cell - c * p.g_cap;
+  if (g >= rv_tile_labels(p.tile_first, t, p.g_cap)) return;
+  const int area = p.gt_area[(long long)t * p.g_cap + g];
+  if (area <= 0) return;
+  const int n = rv_tile_dets(p.det_count, t, p.D);
+  const int* col = p.inter + (long long)t * p.D * p.g_cap + g;
+  const int* cls = p.det_classes + (long long)t * p.D;
+  const float* sc = p.det_scores + (long long)t * p.D;
+  RvCell a;
+  rv_clear(&a);
+  for (int d = 0; d < n; ++d) rv_pair(&a, col[(long long)d * p.g_cap], area, cls[d], sc[d], c, p.threshold);
+  const long long o = ((long long)t * p.g_cap + g) * p.K + c;
+  p.wscore[o] = a.ws;
+  p.wfrac[o] = a.wa;
+  p.pairs[o] = a.pairs;
+}
+
 }  // namespace
+
+int road_vote_check(const char* who, const RoadVoteParams& p) {
+  RS_CHECK(p.det_scores && p.det_classes && p.det_count && p.tile_first && p.inter && p.gt_area && p.wscore && p.wfrac && p.pairs, RS_ERR_ARG,
+           "%s: null table", who);
+  RS_CHECK(p.n >= 1 && p.n <= 65535, RS_ERR_ARG, "%s: %d tiles (1..65535)", who, p.n);
+  RS_CHECK(p.K >= 1 && p.K <= RV_MAX_CLASSES, RS_ERR_ARG, "%s: %d classes outside [1, %d]", who, p.K, RV_MAX_CLASSES);
+  RS_CHECK(p.D >= 1 && p.g_cap >= 1, RS_ERR_ARG, "%s: %d slots, %d labels per tile", who, p.D, p.g_cap);
+  RS_CHECK(p.threshold - p.threshold == 0.0, RS_ERR_ARG, "%s: the threshold is not finite", who);
+  RS_CHECK(p.D <= RV_MAX_SLOTS, RS_ERR_UNSUPPORTED, "%s: %d slots per tile, the stage holds %d", who, p.D, RV_MAX_SLOTS);
+  RS_CHECK(p.g_cap <= RV_MAX_GT, RS_ERR_UNSUPPORTED, "%s: gt_cap %d, the stage holds %d labels per tile", who, p.g_cap, RV_MAX_GT);
+  return RS_OK;
+}
+
+int launch_road_votes(const RoadVoteParams& p, hipStream_t s) {
+  { int rc = road_vote_check("road votes", p); if (rc) return rc; }
+  const size_t cells = (size_t)p.n * p.g_cap * p.K;
+  RS_HIP(hipMemsetAsync(p.wscore, 0, cells * 8, s));
+  RS_HIP(hipMemsetAsync(p.wfrac, 0, cells * 8, s));
+  RS_HIP(hipMemsetAsync(p.pairs, 0, cells * 4, s));
+  hipLaunchKernelGGL(road_vote_kernel, dim3((unsigned)cdiv(p.g_cap * p.K, 256), (unsigned)p.n), dim3(256), 0, s, p);
+  RS_HIP(hipGetLastError());
+  return RS_OK;
+}
+
+// The host restatement: the sequential loop over tiles, labels, classes and slots, on road_vote.h's per-pair rule.
+int host_road_votes(const RoadVoteParams& p) {
+  { int rc = road_vote_check("rs_host_road_votes", p); if (rc) return rc; }
+  const size_t cells = (size_t)p.n * p.g_cap * p.K;
+  memset(p.wscore, 0, cells * 8);
+  memset(p.wfrac, 0, cells * 8);
+  memset(p.pairs, 0, cells * 4);
+  for (int t = 0; t < p.n; ++t) {
+    const int G = rv_tile_labels(p.tile_first, t, p.g_cap), n = rv_tile_dets(p.det_count, t, p.D);
+    for (int g = 0; g < G; ++g) {
+      const int area = p.gt_area[(size_t)t * p.g_cap + g];
+      if (area <= 0) continue;
+      for (int c = 0; c < p.K; ++c) {
+        RvCell a;
+        rv_clear(&a);
+        for (int d = 0; d < n; ++d)
+          rv_pair(&a, p.inter[((size_t)t * p.D + d) * p.g_cap + g], area, p.det_classes[(size_t)t * p.D + d], p.det_scores[(size_t)t * p.D + d], c, p.threshold);
+        const size_t o = ((size_t)t * p.g_cap + g) * p.K + c;
+        p.wscore[o] = a.ws;
+        p.wfrac[o] = a.wa;
+        p.pairs[o] = a.pairs;
+      }
+    }
+  }
+  return RS_OK;
+}
 
 int coco_match_check(const char* who, const CocoMatchParams& p) {
   RS_CHECK(p.det_boxes && p.det_scores && p.det_classes && p.det_count && p.gt_boxes && p.gt_classes && p.tile_first && p.inter && p.det_area && p.gt_area && p.order &&

@@ -104,6 +104,11 @@ class RsEvalMatches(C.Structure):
                 ("matched", C.POINTER(C.c_uint32)), ("ignored", C.POINTER(C.c_uint32)), ("npig", C.POINTER(C.c_int32))]
 
 
+class RsRoadVotes(C.Structure):
+    _fields_ = [("wscore", C.POINTER(C.c_double)), ("wfrac", C.POINTER(C.c_double)), ("pairs", C.POINTER(C.c_int32)),
+                ("label_area", C.POINTER(C.c_int32))]
+
+
 class RsSolver(C.Structure):
     """include/rs_engine.h ``rs_solver``."""
     _fields_ = [("struct_size", C.c_int32), ("nesterov", C.c_int32), ("bias_lr_factor", C.c_float), ("weight_decay_bias", C.c_float),
@@ -301,6 +306,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.rs_host_coco_match.argtypes = [vp] * 11 + [i32] * 4 + [vp] * 6
         lib.rs_engine_fetch_eval_match_async.argtypes = [vp, i32, C.POINTER(RsDets)] + [vp] * 8 + [C.POINTER(RsEvalMatches)]
         lib.rs_engine_fetch_eval_match_wait.argtypes = [vp]
+    if hasattr(lib, "rs_op_road_votes"):              # RS_ENGINE_LIB may name an older build
+        lib.rs_op_road_votes.argtypes = [vp] * 6 + [i32] * 4 + [C.c_double] + [vp] * 4
+        lib.rs_host_road_votes.argtypes = [vp] * 6 + [i32] * 4 + [C.c_double] + [vp] * 3
+        lib.rs_engine_fetch_votes_async.argtypes = [vp, i32] + [vp] * 5 + [C.c_double, C.POINTER(RsRoadVotes)]
+        lib.rs_engine_fetch_votes_wait.argtypes = [vp]
     lib.rs_rasterize_polygons_within_box.argtypes = [f64p, i32p, i32, f64p, i32, u8p]
     lib.rs_memcpy_d2h.argtypes = [vp, vp, C.c_size_t]
     lib.rs_op_fdiv.argtypes = [vp, vp, vp, C.c_int64, vp]
@@ -560,6 +570,10 @@ class Engine:
         self._match_struct: Optional[RsEvalMatches] = None
         self.eval_fallbacks = 0
         self.eval_unpack_s = 0.0             # eval_matches: seconds spent turning the tables into records (tools/val_ap_ab.py reads it)
+        # road votes (rs_engine_fetch_votes_*): pinned tables, allocated on the first road_votes; batches that did not fit
+        self._vote_struct: Optional[RsRoadVotes] = None
+        self._vote_labels: List[int] = []
+        self.vote_fallbacks = 0
 
     def _dets_struct(self, want_probs: bool) -> RsDets:
         d = RsDets()
@@ -839,6 +853,84 @@ class Engine:
         self.eval_unpack_s += time.perf_counter() - t0       # host time of this route's matching: unpacking the flag bits
         return out
 
+    def road_votes(self, tiles_or_n, labels: Sequence[Sequence[Sequence[np.ndarray]]], threshold: float = 0.0, wait: bool = True):
+        """The road cover vote of a batch, counted and summed on the device (csrc/road_vote.h): ``tiles_or_n`` as for ``eval_counts``
+        (tiles: a forward is run on them; n: the forward already enqueued, whether or not a ``fetch_async`` of it is in flight);
+        labels[tile][label] = list of rings ([x0, y0, x1, y1, ...], tile pixels), the road labels clipped to the tile.  The labels are
+        rasterised on the GPU exactly as ``raster_vote.label_rasters`` does on the host, and neither a mask nor a pair count travels.
+        Returns per tile ``(Instances without masks, wscore (L_t, K) float64, wfrac (L_t, K) float64, pairs (L_t, K) int32, label_area
+        (L_t,) int32)`` -- per label and class the sum of weighted scores, the sum of weights and the number of (label, detection) pairs
+        with ``score >= threshold``; ``raster_vote.reduce_votes`` turns them into the road table -- or ``None`` when the batch does not
+        fit the device pool (the conditions of ``eval_counts``, shared with it; also more than 1024 slots): then nothing was enqueued,
+        nothing is truncated, ``vote_fallbacks`` counts it and the caller votes on this batch with ``raster_vote.vote_tables_host``.
+        Without a ``fetch_async`` in flight the detections (no masks) are fetched too; with one, its copies bring them.
+        ``wait=False`` returns True once everything is enqueued; ``road_votes_wait(n)`` then gives the result."""
+        n = int(tiles_or_n) if np.isscalar(tiles_or_n) else int(tiles_or_n.shape[0])
+        if not np.isfinite(threshold):                # before the forward: a refused call enqueues nothing
+            raise ValueError(f"vote threshold {threshold!r} is not finite")
+        packed = self._vote_label_tables(n, labels)
+        if packed is None:
+            return None
+        if not np.isscalar(tiles_or_n):
+            self.infer_device(self.upload_async(np.ascontiguousarray(tiles_or_n)), n)
+        self._vote_labels = self._vote_enqueue(n, packed, threshold)
+        return self.road_votes_wait(n) if wait else True
+
+    def _vote_label_tables(self, n: int, labels):
+        """The label tables of a batch as rs_engine_fetch_votes_async takes them, or ``None`` -- counted in ``vote_fallbacks`` -- when the
+        batch does not fit the device pool.  The pool and its check are those of the validation counts; the counters are not."""
+        from .coco_match import MAX_SLOTS
+        before = self.eval_fallbacks
+        packed = self._eval_polygon_tables(n, labels, extra_unfit=self.D > MAX_SLOTS)
+        self.eval_fallbacks = before
+        if packed is None:
+            self.vote_fallbacks += 1
+        return packed
+
+    def _vote_enqueue(self, n: int, packed, threshold: float) -> List[int]:
+        """Enqueue the vote of ``_vote_label_tables``' tables behind the last forward (and behind its fetch, when one is in flight);
+        returns the labels per tile."""
+        if not np.isfinite(threshold):
+            raise ValueError(f"vote threshold {threshold!r} is not finite")
+        flat, off, lens, inst_first, tile_first = packed
+        if self._fetch_pending is None:               # no fetch of this forward in flight: bring the detections (no masks) along
+            d = self._dets_struct(False)
+            d.masks = None
+            _check(self.lib, self.lib.rs_engine_fetch_async(self._h, n, C.byref(d)), "rs_engine_fetch_async")
+        K = self.spec.num_classes
+        if self._vote_struct is None:
+            self._vote_tables = {"wscore": self._pinned((self.max_batch, EVAL_GT_CAP, K), np.float64),
+                                 "wfrac": self._pinned((self.max_batch, EVAL_GT_CAP, K), np.float64),
+                                 "pairs": self._pinned((self.max_batch, EVAL_GT_CAP, K), np.int32),
+                                 "label_area": self._pinned((self.max_batch, EVAL_GT_CAP), np.int32)}
+            v = RsRoadVotes()
+            for k, a in self._vote_tables.items():
+                setattr(v, k, a.ctypes.data_as(C.POINTER(C.c_double if a.dtype == np.float64 else C.c_int32)))
+            self._vote_struct = v
+        rc = self.lib.rs_engine_fetch_votes_async(self._h, n, flat.ctypes.data, off.ctypes.data, lens.ctypes.data, inst_first.ctypes.data,
+                                                  tile_first.ctypes.data, float(threshold), C.byref(self._vote_struct))
+        _check(self.lib, rc, "rs_engine_fetch_votes_async")        # the fit was checked above: any other code here is an error
+        return np.diff(tile_first).tolist()
+
+    def road_votes_wait(self, n: int, with_instances: bool = True, label_counts: Optional[Sequence[int]] = None):
+        """The second half of ``road_votes(..., wait=False)``: waits for the copies and returns the tables of tiles 0..n-1.  A
+        ``fetch_async`` of the same forward that is in flight keeps its own ``wait_results``, before or after this call.
+        ``with_instances=False`` leaves the detections to that fetch and gives ``(wscore, wfrac, pairs, label_area)`` per tile.
+        ``label_counts``: the labels per tile of the batch the tables belong to, for a caller that has enqueued another since."""
+        _check(self.lib, self.lib.rs_engine_fetch_votes_wait(self._h), "rs_engine_fetch_votes_wait")
+        t = self._vote_tables
+        counts = self._vote_labels if label_counts is None else label_counts
+        out = []
+        for i in range(n):
+            g = int(counts[i])
+            row = (t["wscore"][i, :g].copy(), t["wfrac"][i, :g].copy(), t["pairs"][i, :g].copy(), t["label_area"][i, :g].copy())
+            if with_instances:
+                c = int(self._count[i])
+                row = (Instances((self.tile_h, self.tile_w), self._boxes[i, :c].copy(), self._scores[i, :c].copy(),
+                                 self._classes[i, :c].astype(np.int64), None, None),) + row
+            out.append(row)
+        return out
+
     def infer_device(self, tiles_dev_ptr: int, n: int) -> None:
         """Enqueue a forward on tiles already in device memory (no wait)."""
         _check(self.lib, self.lib.rs_engine_infer_device(self._h, C.c_void_p(tiles_dev_ptr), n), "rs_engine_infer_device")
@@ -1022,10 +1114,11 @@ class LanePipeline:
         self._pending: Optional[Tuple[int, int, int]] = None     # shared form: (lane, tiles ptr, n) whose phase 2 is still to be enqueued
         # saturation counts (Engine.saturation) of the batch ``run`` yielded last: set before the batch is yielded
         self.last_saturation: Dict[str, int] = {}
+        self.vote_fallbacks = 0                      # batches of the last ``run(..., labels=...)`` that were voted on the host
 
-    def _fetch_async(self, e: Engine, n: int) -> None:
+    def _fetch_async(self, e: Engine, n: int, masks: bool = False) -> None:
         if self.vectorize == "device" and e.spec.mask_on:
-            e.fetch_async(n, polygons=True, rdp_epsilon=self.rdp_epsilon, masks=self.want_masks)
+            e.fetch_async(n, polygons=True, rdp_epsilon=self.rdp_epsilon, masks=self.want_masks or masks)
         else:
             e.fetch_async(n)
 
@@ -1056,19 +1149,54 @@ class LanePipeline:
         """Enqueue the outstanding mask-head phase; after this every submitted batch is fully enqueued."""
         self._finish_pending()
 
-    def run(self, batches) -> "Iterator[List[Instances]]":
+    def run(self, batches, labels=None, vote_threshold: float = 0.0) -> "Iterator[List[Instances]]":
         """Stream host batches ((n,h,w,c) uint8 arrays) through the lanes and yield their detections in order.  Uploads go
         through pinned staging on the lane's stream, every batch's results come back on its lane's copy stream behind an event,
         and the generator runs ``lanes`` batches ahead of what it yields, so host-side collection overlaps the GPU.  Independent lanes:
             submit(k): upload(k), forward(k), fetch_async(k);   then collect + yield batch k - lanes
         shared stream:
-            submit(k): upload(k), phase0(k), phase2(k-1) + fetch_async(k-1), phase1(k);   then collect + yield batch k-2."""
+            submit(k): upload(k), phase0(k), phase2(k-1) + fetch_async(k-1), phase1(k);   then collect + yield batch k-2.
+        ``labels``: an iterable parallel to ``batches``, per batch the road labels of its tiles as ``Engine.road_votes`` takes them.
+        Then every yielded ``Instances`` carries ``road_votes`` = (wscore, wfrac, pairs, label_area) of its tile: the vote fetch is
+        enqueued right behind the batch's result fetch on the batch's lane, and a batch that does not fit the device pool is fetched
+        with its masks and voted on the host (``raster_vote.vote_tables_host``), counted in ``vote_fallbacks``."""
         L = len(self.engines)
+        lab_it = iter(labels) if labels is not None else None
+        lab_of: Dict[int, Any] = {}                 # lane -> the labels of the batch it was given last
+        vote_of: Dict[int, Any] = {}                # lane -> ("device", labels per tile) / ("host", labels) of the fetch in flight
+        if lab_it is not None:
+            self.vote_fallbacks = 0
+
+        def fetch(lane: int, n: int) -> None:
+            eng = self.engines[lane]
+            if lab_it is None:
+                return self._fetch_async(eng, n)
+            packed = eng._vote_label_tables(n, lab_of[lane])
+            if packed is None:
+                self.vote_fallbacks += 1
+                self._fetch_async(eng, n, masks=True)
+                vote_of[lane] = ("host", lab_of[lane])
+            else:
+                self._fetch_async(eng, n)
+                vote_of[lane] = ("device", eng._vote_enqueue(n, packed, vote_threshold))
+
+        def voted(lane: int, res: List[Instances]) -> List[Instances]:
+            if lab_it is None:
+                return res
+            from . import raster_vote
+            kind, what = vote_of.pop(lane)
+            if kind == "device":
+                rows = self.engines[lane].road_votes_wait(len(res), False, what)
+            else:
+                rows = raster_vote.vote_tables_host(res, what, self.engines[lane].spec.num_classes, vote_threshold)
+            for inst, row in zip(res, rows):
+                inst.road_votes = row
+            return res
 
         def counted(eng: Engine, res: List[Instances]) -> List[Instances]:
             # the lane's counts were published by its wait_results and stay until its next one: read them with the batch's results
             self.last_saturation = eng.saturation()
-            return res
+            return voted(self.engines.index(eng), res)
         inflight = []                               # (lane, n) of submitted batches not yet yielded
         T = self.timing = {"pull": 0.0, "wait_results": 0.0, "upload": 0.0, "enqueue": 0.0, "collect": 0.0, "batches": 0}
         clock = time.perf_counter
@@ -1084,9 +1212,11 @@ class LanePipeline:
             lane = self.k % L
             e = self.engines[lane]
             self.k += 1
+            if lab_it is not None:
+                lab_of[lane] = next(lab_it)
             if L == 1:                              # one lane has one set of host buffers: no look-ahead
                 e.infer_device(e.upload_async(np.ascontiguousarray(tiles)), n)
-                self._fetch_async(e, n)
+                fetch(lane, n)
                 yield counted(e, e.fetch_wait(n))
                 continue
             done = None
@@ -1111,7 +1241,7 @@ class LanePipeline:
                     res = counted(self.engines[done[0]], self.engines[done[0]].collect_results(done[1]))
                     T["collect"] += clock() - t0
                 t1 = clock()
-                self._fetch_async(e, n)
+                fetch(lane, n)
                 T["enqueue"] += clock() - t1
                 inflight.append((lane, n))
                 if res is not None:
@@ -1121,7 +1251,7 @@ class LanePipeline:
             if self._pending is not None:
                 pl, pp, pn = self._pending
                 self.engines[pl].infer_phase(pp, pn, 2)
-                self._fetch_async(self.engines[pl], pn)
+                fetch(pl, pn)
                 self._pending = None
             e.infer_phase(ptr, n, 1)
             T["enqueue"] += clock() - t1
@@ -1135,7 +1265,7 @@ class LanePipeline:
         if self._pending is not None:
             pl, pp, pn = self._pending
             self.engines[pl].infer_phase(pp, pn, 2)
-            self._fetch_async(self.engines[pl], pn)
+            fetch(pl, pn)
             self._pending = None
         for ol, on in inflight:
             yield counted(self.engines[ol], self.engines[ol].fetch_wait(on))
@@ -1172,6 +1302,7 @@ class Predictor:
         self.spec, self.weights, self.max_batch, self.device, self.lanes = spec, weights, max_batch, device, lanes
         self.on_saturation = on_saturation
         self.last_saturation: Dict[str, int] = {}
+        self.vote_fallbacks = 0                     # batches of the last ``predict_stream(..., labels=...)`` that were voted on the host
         self._pipes: Dict[Tuple[int, int, int], LanePipeline] = {}
 
     def _saturated(self, sat: Dict[str, int], what: str) -> None:
@@ -1231,39 +1362,57 @@ class Predictor:
         self.last_saturation = total
         return out
 
-    def predict_stream(self, batches) -> "Iterator[List[Dict[str, Instances]]]":
+    def predict_stream(self, batches, labels=None, vote_threshold: float = 0.0) -> "Iterator[List[Dict[str, Instances]]]":
         """Streaming form for a whole tileset: ``batches`` is an iterator of image lists (each at most ``max_batch`` images);
         yields one result list per batch, in order.  Consecutive batches of one tile shape flow through ONE
         ``LanePipeline.run`` generator, so the upload, forward and result copy of batch k+1 overlap batch k (calling
         ``predict_batch`` once per batch would drain the pipeline after every batch).  The iterator is pulled lazily, two
-        batches ahead of what is yielded."""
+        batches ahead of what is yielded.  ``labels``: an iterable parallel to ``batches``, per batch the road labels of its tiles
+        (``LanePipeline.run``); every yielded ``Instances`` then carries ``road_votes``, and ``vote_fallbacks`` counts the batches
+        of the stream that were voted on the host.  Labels need batches of one tile shape."""
         it = iter(batches)
-        carry: List[Any] = []            # a batch read ahead that does not fit the running pipeline
+        lab_src = iter(labels) if labels is not None else None
+        lab_q: List[Any] = []            # labels of the batches handed to the running pipeline and not yet taken by it
+        carry: List[Any] = []            # a batch read ahead that does not fit the running pipeline (with its labels)
         k = 0                            # batches yielded
+        self.vote_fallbacks = 0
 
         def next_batch():
-            return carry.pop() if carry else next(it, None)
+            if carry:
+                return carry.pop()
+            b = next(it, None)
+            return (None, None) if b is None else (b, next(lab_src) if lab_src is not None else None)
+
+        def taken_labels():
+            while True:
+                yield lab_q.pop(0)
 
         while True:
-            first = next_batch()
+            first, first_lab = next_batch()
             if first is None:
                 return
             shapes = {tuple(im.shape) for im in first}
             if len(shapes) != 1 or len(first) > self.max_batch:
+                if lab_src is not None:
+                    raise ValueError("road labels need batches of one tile shape, at most max_batch tiles each")
                 yield self.predict_batch(first)          # mixed shapes inside one batch: no streaming for it
                 k += 1
                 continue
             shape = shapes.pop()
 
-            def run_of_shape(b=first):
+            def run_of_shape(b=first, lab=first_lab):
                 while b is not None:
                     if len(b) > self.max_batch or any(tuple(im.shape) != shape for im in b):
-                        carry.append(b)
+                        carry.append((b, lab))
                         return
+                    lab_q.append(lab)
                     yield b if isinstance(b, np.ndarray) else np.stack(b)      # a decoded batch in shared memory is used in place
-                    b = next_batch()
+                    b, lab = next_batch()
             pipe = self._pipe(shape)
-            for res in pipe.run(run_of_shape()):
+            before = pipe.vote_fallbacks if lab_src is None else 0
+            for res in pipe.run(run_of_shape(), labels=taken_labels() if lab_src is not None else None, vote_threshold=vote_threshold):
+                self.vote_fallbacks += pipe.vote_fallbacks - before
+                before = pipe.vote_fallbacks
                 self._saturated(pipe.last_saturation, f"batch {k} of the stream")
                 k += 1
                 yield [{"instances": r} for r in res]

@@ -28,7 +28,7 @@ import yaml
 
 from .decode_pool import DecodePool, TileShapeError, read_tile, tile_header_shape
 from .gpkg import GpkgWriter
-from .shard import run_sharded
+from .shard import run_sharded, shard_range
 from .spec import BATCHED_NMS_HELP, load_d2_yaml
 from .vectorize import instances_to_features, instances_to_gpkg_rows
 from .weights import infer_num_classes, load_checkpoint, synthetic_weights
@@ -75,6 +75,29 @@ def _close_pools(pools: Dict[Tuple[int, ...], DecodePool]) -> None:
         finally:
             pl.close()
     pools.clear()
+
+
+def road_labels(coco: Dict[str, Any], dataset: str = "") -> Dict[Any, Tuple[List[Any], List[List[np.ndarray]]]]:
+    """The road labels of a COCO file for ``--road-votes``: image id -> (road ids, labels), one label per polygon annotation in the
+    file's order, a label being the list of its rings ([x0, y0, x1, y1, ...], tile pixels).  The road is the annotation's ``road_id``
+    where present, else its ``id``.  Crowd and RLE annotations, and rings of fewer than three points, are skipped with a log line."""
+    out: Dict[Any, Tuple[List[Any], List[List[np.ndarray]]]] = {}
+    skipped = 0
+    for a in coco.get("annotations", []):
+        seg = a.get("segmentation")
+        if a.get("iscrowd") or not isinstance(seg, list):
+            skipped += 1
+            continue
+        rings = [np.asarray(r, np.float64).reshape(-1) for r in seg if len(r) >= 6 and len(r) % 2 == 0]
+        if not rings:
+            skipped += 1
+            continue
+        ids, labs = out.setdefault(a["image_id"], ([], []))
+        ids.append(a.get("road_id", a.get("id")))
+        labs.append(rings)
+    if skipped:
+        log.info("%s: %d annotation(s) are crowd regions, RLE masks or have no polygon: they are no road labels", dataset, skipped)
+    return out
 
 
 def thr_tag(thr: float) -> str:
@@ -126,6 +149,13 @@ def build_parser() -> argparse.ArgumentParser:
                     help="tagged preview PNGs per dataset in sample_tagged_img_subfolder (0 = none)")
     ap.add_argument("--max-tiles", type=int, default=0, help="debug: only the first N tiles of every dataset")
     ap.add_argument("--batched-nms", choices=("per-category", "torchvision"), default="per-category", help=BATCHED_NMS_HELP)
+    ap.add_argument("--road-votes", action="store_true",
+                    help="also write <dataset>_road_votes.json, the cover class per road (raster_vote.reduce_votes): the polygon annotations of the "
+                         "dataset's COCO file are the road labels of their tile (tile pixels; 'road_id' where present, else 'id'), counted against "
+                         "the detection masks on the GPU behind every batch's forward (csrc/road_vote.h); a batch beyond the device pool is voted "
+                         "on the host from its masks.  Needs datasets of one tile shape.  Every other output is unchanged")
+    ap.add_argument("--vote-threshold", type=float, default=None,
+                    help="score a detection needs to vote (default: 'threshold' of the YAML's 'determine_class.py' section where it exists, else 0)")
     return ap
 
 
@@ -137,7 +167,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                                               args.decode_procs, args.host_workers, args.vector_threads, share)
 
     with open(args.config_file) as f:
-        cfg = yaml.safe_load(f)[SECTION]
+        whole_cfg = yaml.safe_load(f)
+    cfg = whole_cfg[SECTION]
+    vote_thr = float(args.vote_threshold if args.vote_threshold is not None else (whole_cfg.get("determine_class.py") or {}).get("threshold", 0))
+    votes: Dict[str, Any] = {"labels": None, "by_file": {}}      # --road-votes: the running dataset's labels per batch, its tables per tile
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -221,7 +254,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
 
     def predict_stream(batches):
         # the whole dataset through one lane pipeline: batch k+1 uploads and runs while batch k's results come back
-        it = predictor.predict_stream(batches)
+        if votes["labels"] is None:
+            it = predictor.predict_stream(batches)
+        else:
+            it = predictor.predict_stream(batches, labels=iter(votes["labels"]), vote_threshold=vote_thr)
         while True:
             t = time.perf_counter()
             out = next(it, None)
@@ -240,6 +276,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             ext, epsg_t = tile_extent(meta, e["file_name"])
             name = os.path.basename(e["file_name"])
             rdp_on, eps = bool(rdp_cfg.get("enabled", False)), float(rdp_cfg.get("epsilon", 0.75))
+            if votes["labels"] is not None:
+                votes["by_file"][e["file_name"]] = o["instances"].road_votes
             carried = getattr(o["instances"], "_polygons", None)
             if carried is not None:
                 fell_back["instances"] += int(len(carried.flagged))
@@ -296,6 +334,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                         return
                     yield b
             source = pool_source if pool is not None else None
+        if args.road_votes:
+            lo, hi = shard_range(len(images), rank, world)
+            by_image = road_labels(d, dataset)
+            votes["by_file"] = {}
+            votes["labels"] = [[by_image.get(e["id"], ([], []))[1] for e in images[i:min(i + args.batch, hi)]] for i in range(lo, hi, args.batch)]
         try:
             try:
                 per_tile = run_sharded(images, predict_batch, args.batch, rank, world, gather=False, prepare=prepare, finish=finish,
@@ -324,6 +367,30 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                         "-- detections of those batches may be wrong, --precision fp32 never clamps", dataset, len(saturated),
                         os.path.basename(first), top)
             saturated.clear()
+        if args.road_votes:
+            # every rank's per-(tile, label) tables travel to rank 0, which reduces them in global tile order: the file does not depend
+            # on the world size
+            mine = [(by_image.get(e["id"], ([], []))[0], votes["by_file"][e["file_name"]][:3]) for e in images[lo:hi]]
+            parts: List[Any] = [(mine, predictor.vote_fallbacks)]
+            if world > 1:
+                import torch.distributed as dist
+                parts = [None] * world if rank == 0 else None
+                dist.gather_object((mine, predictor.vote_fallbacks), parts, dst=0)
+            if rank == 0:
+                from .raster_vote import CLASS_NAMES, reduce_votes
+                rows = [t for part, _ in parts for t in part]             # rank order == tile order for contiguous blocks
+                K = spec.num_classes
+                by_id = {c["id"]: c.get("name") for c in d.get("categories", [])}
+                names = {i: by_id.get(cid) for i, cid in enumerate(cats)}
+                if len(names) != K or not all(names.values()):
+                    names = dict(CLASS_NAMES) if K == len(CLASS_NAMES) else {i: str(i) for i in range(K)}
+                table = reduce_votes([t for _, t in rows], [ids for ids, _ in rows], names)
+                with open(f"{dataset}_road_votes.json", "w") as f:
+                    f.write(json.dumps(table))
+                log.info("%s: %d road labels on %d tiles -> %d roads in %s_road_votes.json (vote threshold %g); %d of %d batches were voted on the host",
+                         dataset, sum(len(ids) for ids, _ in rows), len(rows), len(table), dataset, vote_thr, sum(fb for _, fb in parts),
+                         sum(len(range(*shard_range(len(images), r, world), args.batch)) for r in range(world)))
+            votes["labels"] = None
         # Every rank writes the rows of ITS block of tiles into its own GeoPackage shard (rank 0: the output file itself); rank 0 then appends the
         # other ranks' shards in rank order = tile order with SQLite ATTACH -- no row travels between processes ("each rank ...
         # its own output shard; host merges shards into one GeoPackage per dataset").  The ranks of one node share the working directory.

@@ -10,7 +10,12 @@ rows, the detection masks never leave HBM), everything after the counts is resta
 
 Differences from the vector form, by construction: areas are counted in whole pixels of the tile grid (0.4 m at z18,
 R:config/config_obj_detec.yaml:20,45), and RDP simplification (ε 0.75 px) does not enter.  The numpy statement of the device kernel (the
-oracle of its test) is ``oracle/host_tail_oracle.py::overlap_counts``."""
+oracle of its test) is ``oracle/host_tail_oracle.py::overlap_counts``.
+
+The streamed form (second half of this module) runs the whole vote behind the engine's forward: road labels as polygons in
+tile pixels, rasterised and counted on the device, the per-(tile, label, class) sums formed by ``road_vote_kernel`` (csrc/road_vote.h), and
+only those tables travel (``Engine.road_votes``, ``LanePipeline.run(..., labels=...)``).  ``vote_tables_host`` is the numpy route to the
+same tables from fetched masks, ``reduce_votes`` the vectorised step from the tables of all tiles to the road table."""
 from __future__ import annotations
 
 import ctypes as C
@@ -118,4 +123,144 @@ def determine_detected_class(rows: Sequence[Dict], road_ids: Sequence, threshold
         cover = "undetermined" if art == nat else ("artificial" if art > nat else "natural")
         out.append({"road_id": rid, "cover_type": cover, "nat_score": round(nat, 3), "art_score": round(art, 3),
                     "diff_score": 0 if art == nat else abs(art - nat)})
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- the streamed form
+# csrc/road_vote.h states the vote as a rule per (tile, label, class) cell; ``rs_op_road_votes`` / ``rs_engine_fetch_votes_async`` run
+# it on the device behind the forward, ``rs_host_road_votes`` and ``vote_tables_host`` on the host.  ``reduce_votes`` is the step
+# from the per-(tile, label) tables to the road table.
+_POP8 = np.array([bin(i).count("1") for i in range(256)], np.int32)
+TABLE_KEYS = ("det_scores", "det_classes", "det_count", "tile_first", "inter", "gt_area")
+
+
+def votes_from_counts(inter: np.ndarray, label_area: np.ndarray, scores: np.ndarray, classes: np.ndarray, num_classes: int,
+                      threshold: float = 0.0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The rule of csrc/road_vote.h on one tile's counts in numpy: inter (D, L) and label_area (L,) pixel counts, scores / classes
+    (D,) -> wscore, wfrac (L, K) float64 and pairs (L, K) int32.  The detections are walked in ascending order, so every cell is the
+    sequential float64 sum the kernel forms."""
+    L, K = int(label_area.shape[0]), int(num_classes)
+    ws, wa, pairs = np.zeros((L, K)), np.zeros((L, K)), np.zeros((L, K), np.int32)
+    area = np.asarray(label_area, np.int64)
+    ok = area > 0
+    for d in range(int(scores.shape[0])):
+        c, s = int(classes[d]), float(scores[d])
+        if not 0 <= c < K or not s >= threshold:
+            continue
+        i = np.asarray(inter[d], np.int64)
+        frac = np.zeros(L)
+        frac[ok] = np.round(i[ok] / area[ok], 2)
+        keep = ok & (i > 0) & (frac > 0.05)
+        ws[keep, c] += frac[keep] * s
+        wa[keep, c] += frac[keep]
+        pairs[keep, c] += 1
+    return ws, wa, pairs
+
+
+def vote_tables_host(instances: Sequence, labels: Sequence[Sequence[Sequence[np.ndarray]]], num_classes: int,
+                     threshold: float = 0.0) -> List[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
+    """The numpy route to the tables ``Engine.road_votes`` gives, from fetched masks: per tile, ``label_rasters`` of labels[tile] (lists
+    of rings in tile pixels), popcounts of the packed label AND the packed detection masks of instances[tile] (``Instances`` with
+    masks), then ``votes_from_counts``.  Returns per tile ``(wscore (L, K), wfrac (L, K), pairs (L, K), label_area (L,))``.  The
+    fallback of a batch that does not fit the device pool."""
+    if len(instances) != len(labels):
+        raise ValueError(f"{len(labels)} label lists for {len(instances)} tiles")
+    out = []
+    for inst, labs in zip(instances, labels):
+        h, w = inst.image_size
+        det = inst._packed
+        if det is None:
+            raise ValueError("the host vote needs the detections' masks (MASK_ON, and a fetch that brings them)")
+        lab = label_rasters(labs, h, w)
+        inter = np.zeros((len(inst), len(labs)), np.int32)
+        for g in range(len(labs)):
+            inter[:, g] = _POP8[det & lab[g][None]].sum(axis=(1, 2), dtype=np.int64)
+        area = _POP8[lab].sum(axis=(1, 2), dtype=np.int64).astype(np.int32) if len(labs) else np.zeros(0, np.int32)
+        out.append(votes_from_counts(inter, area, inst.scores, inst.pred_classes, num_classes, threshold) + (area,))
+    return out
+
+
+def _vote_call(entry: str, b: Dict[str, np.ndarray], num_classes: int, threshold: float, prefill: float, device: bool):
+    from .engine import _check, load_library
+    lib = load_library()
+    n, slots = b["det_scores"].shape
+    cap = int(b["gt_area"].shape[1])
+    tabs = [np.ascontiguousarray(b["det_scores"], np.float32), np.ascontiguousarray(b["det_classes"], np.int32),
+            np.ascontiguousarray(b["det_count"], np.int32), np.ascontiguousarray(b["tile_first"], np.int32),
+            np.ascontiguousarray(b["inter"], np.int32), np.ascontiguousarray(b["gt_area"], np.int32)]
+    outs = [np.full((n, cap, num_classes), prefill, np.float64), np.full((n, cap, num_classes), prefill, np.float64),
+            np.full((n, cap, num_classes), int(prefill), np.int32)]
+    if not device:
+        _check(lib, lib.rs_host_road_votes(*[a.ctypes.data for a in tabs], n, num_classes, slots, cap, float(threshold),
+                                           *[a.ctypes.data for a in outs]), entry)
+        return tuple(outs)
+    import torch
+    dev = [torch.from_numpy(a).cuda() for a in tabs + outs]
+    torch.cuda.synchronize()
+    _check(lib, lib.rs_op_road_votes(*[a.data_ptr() for a in dev[:6]], n, num_classes, slots, cap, float(threshold),
+                                     *[a.data_ptr() for a in dev[6:]], None), entry)
+    torch.cuda.synchronize()
+    return tuple(a.cpu().numpy() for a in dev[6:])
+
+
+def road_votes_host(b: Dict[str, np.ndarray], num_classes: int, threshold: float = 0.0, prefill: float = 0.0):
+    """``rs_host_road_votes`` on a dict of the tables ``TABLE_KEYS`` (det_scores / det_classes (n, slots), det_count (n,), tile_first
+    (n + 1,), inter (n, slots, gt_cap), gt_area (n, gt_cap)) -> wscore, wfrac (n, gt_cap, K) float64, pairs (n, gt_cap, K) int32.
+    ``prefill``: what the output buffers hold before the call (the entry clears them itself).  Needs no device."""
+    return _vote_call("rs_host_road_votes", b, num_classes, threshold, prefill, False)
+
+
+def road_votes_device(b: Dict[str, np.ndarray], num_classes: int, threshold: float = 0.0, prefill: float = 0.0):
+    """``rs_op_road_votes`` on the same dict, uploaded through torch: the kernel's tables."""
+    return _vote_call("rs_op_road_votes", b, num_classes, threshold, prefill, True)
+
+
+def reduce_votes(tables: Sequence[Sequence[np.ndarray]], road_ids: Sequence[Sequence], class_names: Dict[int, str] = CLASS_NAMES,
+                 ndigits: int = 3) -> List[Dict]:
+    """From the per-(tile, label) vote tables to the road table.  tables[tile] = (wscore (L, K), wfrac (L, K), pairs (L, K), ...) as
+    ``Engine.road_votes`` / ``vote_tables_host`` give them (a leading ``Instances`` and a trailing label_area are ignored), road_ids[tile]
+    = the road of each of the tile's labels.  A road's pieces -- its labels over all tiles -- are summed per class in (tile index, label
+    index) order with sequential float64 adds, then ``index = 0 if ws == 0 else ws / wa`` and the cover rule of
+    ``determine_detected_class``: "undetected" for a road without pairs, "undetermined" on a tie, scores rounded to ``ndigits``.  With
+    the reference's two classes the dicts carry its keys (road_id, cover_type, nat_score, art_score, diff_score); with another class
+    list one ``<name>_score`` per class, the unique maximum as the cover and ``diff_score`` = best minus second.  Roads come in order
+    of first appearance.  Linear in labels and roads."""
+    names = [class_names.get(c, str(c)) for c in range(len(class_names))] if isinstance(class_names, dict) else list(class_names)
+    K = len(names)
+    if len(tables) != len(road_ids):
+        raise ValueError(f"{len(road_ids)} road id lists for {len(tables)} tiles")
+    index: Dict = {}
+    rows, ws_all, wa_all, pairs_all = [], [], [], []
+    for t, ids in zip(tables, road_ids):
+        t = [a for a in t if isinstance(a, np.ndarray) and a.ndim == 2]
+        if len(t) != 3 or any(a.shape != (len(ids), K) for a in t):
+            raise ValueError(f"a tile's vote tables must be three ({len(ids)}, {K}) arrays")
+        rows.extend(index.setdefault(rid, len(index)) for rid in ids)
+        ws_all.append(t[0]); wa_all.append(t[1]); pairs_all.append(t[2])
+    R = len(index)
+    ws, wa, pairs = np.zeros((R, K)), np.zeros((R, K)), np.zeros((R, K), np.int64)
+    if rows:
+        at = np.asarray(rows, np.int64)
+        np.add.at(ws, at, np.concatenate(ws_all))          # unbuffered: one add per piece, in (tile, label) order
+        np.add.at(wa, at, np.concatenate(wa_all))
+        np.add.at(pairs, at, np.concatenate(pairs_all))
+    reference = sorted(names) == ["artificial", "natural"]
+    out = []
+    for rid, r in index.items():
+        if not pairs[r].any():
+            zero = {"nat_score": 0, "art_score": 0} if reference else {f"{nm}_score": 0 for nm in names}
+            out.append({"road_id": rid, "cover_type": "undetected", **zero, "diff_score": 0})
+            continue
+        idx = [0 if ws[r, c] == 0 else float(ws[r, c] / wa[r, c]) for c in range(K)]
+        if reference:
+            nat, art = idx[names.index("natural")], idx[names.index("artificial")]
+            cover = "undetermined" if art == nat else ("artificial" if art > nat else "natural")
+            out.append({"road_id": rid, "cover_type": cover, "nat_score": round(nat, ndigits), "art_score": round(art, ndigits),
+                        "diff_score": 0 if art == nat else abs(art - nat)})
+            continue
+        order = sorted(range(K), key=lambda c: -idx[c])
+        best, second = idx[order[0]], (idx[order[1]] if K > 1 else 0)
+        unique = K == 1 or best > second
+        out.append({"road_id": rid, "cover_type": names[order[0]] if unique else "undetermined",
+                    **{f"{nm}_score": round(idx[c], ndigits) for c, nm in enumerate(names)}, "diff_score": best - second if unique else 0})
     return out
