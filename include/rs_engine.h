@@ -1029,6 +1029,48 @@ int rs_engine_fetch_votes_async(rs_engine* e, int n, const double* polys, const 
                                 const int32_t* inst_first, const int32_t* tile_first, double threshold, rs_road_votes* votes_host);
 int rs_engine_fetch_votes_wait(rs_engine* e);
 
+/* ------------------------------------------------------------------ band histograms under the road labels (csrc/band_hist.h)
+ * The reference's second answer for a road's cover is statistical: scripts/statistical_analysis collects, per road, the pixels of
+ * every band under the road's polygon over all tiles the road touches, drops the nodata pixels (without a nodata value in the TIFF:
+ * the pixels whose bands are all 0) and tabulates min, max, median, mean, std and count per road and band, then per cover type.
+ * Every one of those is an exact function of a 256-bin histogram per (road, band), and integer histograms add exactly over tiles,
+ * batches and ranks.  csrc/band_hist.h states the rule once, for the kernel (csrc/band_hist.hip) and the host restatement: for tile t,
+ * label instance g in tile_first[t] .. tile_first[t+1]-1, band c < channels and value v < 256, hist[g][c][v] is the number of pixels
+ * (x, y) of tile t whose bit x % 8 of byte x / 8 of row y of canvas g is set, whose bands are not all 0, and whose band c equals v.  A
+ * pixel with some bands 0 and others not is counted, in bin 0 of its zero bands.  Integers only: the bits do not depend on the run.
+ *
+ * Tables: tiles [n_tiles][side][side][channels] uint8, interleaved; label_masks [n_inst][side][(side+7)/8] in the layout
+ * rs_op_rasterize_canvas writes; tile_first [n_tiles + 1] with tile_first[n_tiles] = n_inst.  Out: hist [n_inst][channels][256]
+ * uint32, compact by instance (not padded to RS_EVAL_GT_CAP); a count is at most side * side <= 2^20.
+ * rs_op_band_hist takes device pointers, clears hist, enqueues on `stream` and does not wait; rs_host_band_hist takes the same
+ * arguments as host pointers, is plain loops over the rule and needs no device.  Both refuse, before anything is touched: a null
+ * table (label_masks and hist may be null when n_inst is 0), n_tiles < 1, n_inst < 0, side outside [1, 1024], channels outside [1, 4]
+ * (RS_ERR_ARG); canvases that are not whole 32-bit words, side * ((side+7)/8) % 4 != 0 (RS_ERR_UNSUPPORTED, as
+ * rs_op_mask_pair_counts).  The device entry also needs label_masks 4-byte aligned. */
+int rs_op_band_hist(const uint8_t* tiles, const uint8_t* label_masks, const int32_t* tile_first, int n_tiles, int n_inst, int side,
+                    int channels, uint32_t* hist, void* stream);
+int rs_host_band_hist(const uint8_t* tiles, const uint8_t* label_masks, const int32_t* tile_first, int n_tiles, int n_inst, int side,
+                      int channels, uint32_t* hist);
+
+/* The same behind the engine's last forward, on the tiles that forward read.  rs_engine_fetch_band_hist_async is an add-on like
+ * rs_engine_fetch_votes_async: it carries no rs_dets and may follow any rs_engine_fetch*_async of the same forward, the vote add-on,
+ * or stand alone.  It packs the road labels of the batch's n tiles (the polygon tables of rs_engine_fetch_eval_async) and enqueues on
+ * the copy stream, in this order: their upload, the canvas rasteriser, the histogram kernel over the engine's tile buffer, and one
+ * copy of tile_first[n] * C * 256 uint32 (C = the engine's tile channels) into the caller-allocated (rs_host_alloc) out->hist, whose
+ * capacity is max_batch * RS_EVAL_GT_CAP * C * 256.  No pair counts are formed.  It shares the pool of the validation counts and the
+ * conditions of rs_engine_eval_fits, and returns RS_EVAL_DOES_NOT_FIT with nothing enqueued when the batch does not fit: form that
+ * batch's histograms on the host (rs_host_band_hist).  An engine that never calls it allocates nothing for it.
+ * The tile buffer: the kernel reads the engine's tiles on the copy stream, while the next rs_engine_upload_async, rs_engine_infer and
+ * the staging copy of rs_engine_infer_device / _phase write them on the engine's stream.  An event recorded behind the kernel orders
+ * those writes behind it while a band-histogram fetch is outstanding; an engine that never uses the add-on enqueues what it always
+ * did.  rs_engine_fetch_band_hist_wait waits for the copy (and for whatever else is on the copy stream in front of it). */
+typedef struct rs_band_hist {
+  uint32_t* hist;       /* [tile_first[n]][C][256], capacity max_batch * RS_EVAL_GT_CAP * C * 256 */
+} rs_band_hist;
+int rs_engine_fetch_band_hist_async(rs_engine* e, int n, const double* polys, const int64_t* poly_off, const int32_t* poly_len,
+                                    const int32_t* inst_first, const int32_t* tile_first, rs_band_hist* out);
+int rs_engine_fetch_band_hist_wait(rs_engine* e);
+
 #ifdef __cplusplus
 }
 #endif

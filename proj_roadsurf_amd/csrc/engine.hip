@@ -1104,6 +1104,7 @@ int rs_engine::run(const uint8_t* tiles, int n, int phase) {
   if (phase <= 0) {
     if (tiles != tiles_dev) {
       // tiles already resident elsewhere on the device: stage them into the engine's input buffer
+      { int rc = wait_band_tiles(); if (rc) return rc; }
       RS_HIP(hipMemcpyAsync(tiles_dev, tiles, (size_t)n * tile_h * tile_w * tile_c, hipMemcpyDeviceToDevice, stream));
     }
     const long long idx = forward_index++;
@@ -1229,8 +1230,22 @@ int rs_engine::ensure_vote_buffers() {
   return alloc((void**)&vote_pairs, vote_cells * 4);   // last: its presence says that all of the above exists
 }
 
-// upload of the packed pool, rasteriser, pair counts: on the copy stream, behind the forward and in front of the result copies
-int rs_engine::launch_eval_counts(int n, const void* layout, hipStream_t s) {
+int rs_engine::ensure_band_buffers() {
+  if (band_hist_dev) return RS_OK;
+  RS_HIP(hipEventCreateWithFlags(&ev_band_tiles, hipEventDisableTiming));
+  return alloc((void**)&band_hist_dev, (size_t)max_batch * RS_EVAL_GT_CAP * tile_c * BH_BINS * 4);   // last: its presence says that all of the above exists
+}
+
+// The histogram kernel reads tiles_dev on the copy stream; everything that writes tiles_dev does so on `stream` and calls this first.
+int rs_engine::wait_band_tiles() {
+  if (!band_tiles_pending) return RS_OK;
+  RS_HIP(hipStreamWaitEvent(stream, ev_band_tiles, 0));
+  band_tiles_pending = false;
+  return RS_OK;
+}
+
+// upload of the packed pool and the rasteriser: on the copy stream, behind the forward and in front of whatever reads the canvases
+int rs_engine::launch_eval_labels(const void* layout, hipStream_t s) {
   const MtLayout& L = *(const MtLayout*)layout;
   RS_HIP(hipMemcpyAsync(eval_pool, eval_pinned, L.bytes, hipMemcpyHostToDevice, s));
   RS_HIP(hipEventRecord(ev_eval_upload, s));
@@ -1239,13 +1254,22 @@ int rs_engine::launch_eval_counts(int n, const void* layout, hipStream_t s) {
   memset(&q, 0, sizeof q);
   q.inst_first = (const int*)(eval_pool + L.o_inst); q.poly_off = (const int*)(eval_pool + L.o_off); q.poly_len = (const int*)(eval_pool + L.o_len);
   q.polys = (const double*)(eval_pool + L.o_xy); q.out = eval_gt_masks; q.n_inst = L.n_inst; q.side = tile_h;
-  { int rc = launch_canvas_raster(q, s); if (rc) return rc; }
+  return launch_canvas_raster(q, s);
+}
+
+// the pair counts of the forward's masks against those canvases, in front of the result copies
+int rs_engine::launch_eval_pairs(int n, hipStream_t s) {
   PairCountParams c;
   memset(&c, 0, sizeof c);
   c.det_masks = masks; c.det_count = det_count; c.gt_masks = eval_gt_masks; c.tile_first = (const int*)eval_pool;
   c.inter = eval_inter; c.det_area = eval_det_area; c.gt_area = eval_gt_area; c.n = n; c.D = D; c.g_cap = RS_EVAL_GT_CAP;
   c.bytes = (long long)tile_h * ((tile_w + 7) / 8);
   return launch_mask_pair_counts(c, s);
+}
+
+int rs_engine::launch_eval_counts(int n, const void* layout, hipStream_t s) {
+  { int rc = launch_eval_labels(layout, s); if (rc) return rc; }
+  return launch_eval_pairs(n, s);
 }
 
 int rs_engine::begin_fetch(hipStream_t* s) {
@@ -1402,6 +1426,7 @@ void rs_engine_destroy(rs_engine* e) {
   if (e->ev_poly_hdr) (void)hipEventDestroy(e->ev_poly_hdr);
   if (e->h_poly_totals) (void)hipHostFree(e->h_poly_totals);
   if (e->ev_eval_upload) (void)hipEventDestroy(e->ev_eval_upload);
+  if (e->ev_band_tiles) (void)hipEventDestroy(e->ev_band_tiles);
   if (e->eval_pinned) (void)hipHostFree(e->eval_pinned);
   if (e->match_pinned) (void)hipHostFree(e->match_pinned);
   if (e->h_sat_copy) (void)hipHostFree(e->h_sat_copy);
@@ -1490,6 +1515,7 @@ int rs_host_unregister(void* p) {
 
 int rs_engine_upload_async(rs_engine* e, const uint8_t* tiles_host, int n) {
   RS_CHECK(e && tiles_host && n >= 1 && n <= e->max_batch, RS_ERR_ARG, "bad argument");
+  { int rc = e->wait_band_tiles(); if (rc) return rc; }
   RS_HIP(hipMemcpyAsync(e->tiles_dev, tiles_host, (size_t)n * e->tile_h * e->tile_w * e->tile_c, hipMemcpyHostToDevice, e->stream));
   return RS_OK;
 }
@@ -1706,9 +1732,43 @@ int rs_engine_fetch_votes_async(rs_engine* e, int n, const double* polys, const 
 
 int rs_engine_fetch_votes_wait(rs_engine* e) { return rs_engine_fetch_wait(e); }
 
+// The band histograms of the road labels under the last forward's tiles (band_hist.h): upload, rasteriser, histogram kernel, one copy.
+// An add-on like the vote: no detections, no pair counts.  The kernel is the one reader of tiles_dev on the copy stream: the event
+// behind it holds back the next write into the buffer (wait_band_tiles).
+int rs_engine_fetch_band_hist_async(rs_engine* e, int n, const double* polys, const int64_t* poly_off, const int32_t* poly_len,
+                                    const int32_t* inst_first, const int32_t* tile_first, rs_band_hist* o) {
+  RS_CHECK(e && o && o->hist && n >= 1 && n <= e->max_batch, RS_ERR_ARG, "rs_engine_fetch_band_hist_async: bad argument");
+  { int rc = rs_engine_eval_fits(e, n, poly_off, poly_len, inst_first, tile_first); if (rc) return rc; }
+  RS_CHECK(e->tile_c >= 1 && e->tile_c <= BH_MAX_CHANNELS, RS_ERR_UNSUPPORTED, "rs_engine_fetch_band_hist_async: %d tile channels, the stage holds %d",
+           e->tile_c, BH_MAX_CHANNELS);
+  MtLayout L;
+  { int rc = mt_measure(polys, poly_off, poly_len, inst_first, tile_first[n], n, &L); if (rc) return rc; }
+  hipStream_t s = nullptr;
+  int rc;
+  if ((rc = e->ensure_eval_buffers())) return rc;
+  if ((rc = e->ensure_band_buffers())) return rc;
+  RS_CHECK(L.bytes <= e->eval_pool_bytes, RS_ERR_ARG, "road labels: %zu bytes packed, the pool holds %zu", L.bytes, e->eval_pool_bytes);
+  if (e->eval_upload_pending) { RS_HIP(hipEventSynchronize(e->ev_eval_upload)); e->eval_upload_pending = false; }
+  mt_pack(e->eval_pinned, L, polys, poly_off, poly_len, inst_first, tile_first);
+  if ((rc = e->begin_fetch(&s))) return rc;
+  if ((rc = e->launch_eval_labels(&L, s))) return rc;
+  BandHistParams q;
+  memset(&q, 0, sizeof q);
+  q.tiles = e->tiles_dev; q.label_masks = e->eval_gt_masks; q.tile_first = (const int*)e->eval_pool; q.hist = e->band_hist_dev;
+  q.n = n; q.n_inst = tile_first[n]; q.side = e->tile_h; q.C = e->tile_c;
+  if ((rc = launch_band_hist(q, s))) return rc;
+  RS_HIP(hipEventRecord(e->ev_band_tiles, s));
+  e->band_tiles_pending = true;
+  if (q.n_inst) RS_HIP(hipMemcpyAsync(o->hist, e->band_hist_dev, (size_t)q.n_inst * q.C * BH_BINS * 4, hipMemcpyDeviceToHost, s));
+  return e->end_fetch(s, nullptr);            // the histograms live in a buffer of their own
+}
+
+int rs_engine_fetch_band_hist_wait(rs_engine* e) { return rs_engine_fetch_wait(e); }
+
 int rs_engine_fetch_wait(rs_engine* e) {
   RS_CHECK(e, RS_ERR_ARG, "null engine");
   if (e->copy_stream) RS_HIP(hipStreamSynchronize(e->copy_stream));
+  e->band_tiles_pending = false;              // the histogram kernel has run: tiles_dev is free
   e->sat_publish();
   return RS_OK;
 }
@@ -1717,6 +1777,7 @@ int rs_engine_infer(rs_engine* e, const uint8_t* tiles_host, int n, rs_dets* out
   RS_CHECK(e && tiles_host && out_host, RS_ERR_ARG, "null argument");
   RS_CHECK(n >= 1 && n <= e->max_batch, RS_ERR_ARG, "batch %d outside [1, %d]", n, e->max_batch);
   RS_HIP(hipSetDevice(e->device));
+  { int rc = e->wait_band_tiles(); if (rc) return rc; }
   RS_HIP(hipMemcpyAsync(e->tiles_dev, tiles_host, (size_t)n * e->tile_h * e->tile_w * e->tile_c, hipMemcpyHostToDevice, e->stream));
   int rc = e->run(e->tiles_dev, n);
   if (rc) return rc;

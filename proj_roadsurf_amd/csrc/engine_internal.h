@@ -132,12 +132,20 @@ struct rs_engine {
   int* vote_pairs = nullptr;
   size_t vote_cells = 0;
   int ensure_vote_buffers();
+  // band histograms (rs_engine_fetch_band_hist_*, band_hist.h): allocated on the first call
+  uint32_t* band_hist_dev = nullptr;            // device: [max_batch * RS_EVAL_GT_CAP][tile_c][256]
+  hipEvent_t ev_band_tiles = nullptr;           // recorded on the copy stream behind the histogram kernel, the one reader of tiles_dev there
+  bool band_tiles_pending = false;              // a write into tiles_dev on `stream` must wait for ev_band_tiles first
+  int ensure_band_buffers();
+  int wait_band_tiles();                        // in front of every write into tiles_dev; enqueues nothing unless band_tiles_pending
 
   // the steps of a result fetch, in the order the fetch entries enqueue them (engine.hip)
   int ensure_crop_header();
   int ensure_polygon_buffers();
   int ensure_eval_buffers();
-  int launch_eval_counts(int n, const void* layout, hipStream_t s);   // layout: the MtLayout of what eval_pinned holds
+  int launch_eval_labels(const void* layout, hipStream_t s);         // layout: the MtLayout of what eval_pinned holds; upload + canvas rasteriser
+  int launch_eval_pairs(int n, hipStream_t s);                       // the pair counts of the last forward's masks against those canvases
+  int launch_eval_counts(int n, const void* layout, hipStream_t s);  // both, in this order
   int begin_fetch(hipStream_t* s);                       // creates the copy stream on first use; it waits for the work enqueued on `stream` so far
   int launch_crops(int n, hipStream_t s);
   int launch_polygons(int n, double rdp_epsilon, hipStream_t s);

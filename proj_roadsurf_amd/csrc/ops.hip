@@ -355,6 +355,29 @@ int rs_host_road_votes(const float* det_scores, const int32_t* det_classes, cons
   return host_road_votes(q);          // val_ap.hip: the float64 arithmetic is compiled there, without mul+add contraction
 }
 
+// The band histograms under label canvases on caller-owned tables (see include/rs_engine.h): device pointers enqueued on `stream`, or
+// host pointers
+static_assert(BH_MAX_SIDE == CR_MAX_SIDE, "band_hist.h restates the canvases' capacity");
+static int band_hist_params(const char* who, BandHistParams* q, const uint8_t* tiles, const uint8_t* label_masks, const int32_t* tile_first,
+                            int n_tiles, int n_inst, int side, int channels, uint32_t* hist) {
+  memset(q, 0, sizeof *q);
+  q->tiles = tiles; q->label_masks = label_masks; q->tile_first = tile_first; q->hist = hist;
+  q->n = n_tiles; q->n_inst = n_inst; q->side = side; q->C = channels;
+  return band_hist_check(who, *q);
+}
+int rs_op_band_hist(const uint8_t* tiles, const uint8_t* label_masks, const int32_t* tile_first, int n_tiles, int n_inst, int side,
+                    int channels, uint32_t* hist, void* stream) {
+  BandHistParams q;
+  { int rc = band_hist_params("rs_op_band_hist", &q, tiles, label_masks, tile_first, n_tiles, n_inst, side, channels, hist); if (rc) return rc; }
+  return launch_band_hist(q, (hipStream_t)stream);
+}
+int rs_host_band_hist(const uint8_t* tiles, const uint8_t* label_masks, const int32_t* tile_first, int n_tiles, int n_inst, int side,
+                      int channels, uint32_t* hist) {
+  BandHistParams q;
+  { int rc = band_hist_params("rs_host_band_hist", &q, tiles, label_masks, tile_first, n_tiles, n_inst, side, channels, hist); if (rc) return rc; }
+  return host_band_hist(q);
+}
+
 int rs_op_conv2d_dgrad(const void* dy, const void* w_t, void* dx, const void* res, const float* res32, const void* mask,
                        const void* down, int n, int hi, int wi, int cin, int ho, int wo, int cout, int kh, int kw, int stride,
                        int pad, int kpad, int halo, int variant, void* stream) {

@@ -6,6 +6,7 @@
 #include "canvas_raster.h"
 #include "coco_match.h"
 #include "road_vote.h"
+#include "band_hist.h"
 
 // One mask per instance, [n_inst][side][(side + 7) / 8] bytes, bit x % 8 of byte x / 8 = pixel x, padding bits zero: bit for bit
 // rs_rasterize_polygons_within_box(polygons of the instance, box (0, 0, side, side), mask_size side).  Tables as MaskTargetsParams
@@ -86,3 +87,18 @@ struct RoadVoteParams {
 int road_vote_check(const char* who, const RoadVoteParams& p);
 int launch_road_votes(const RoadVoteParams& p, hipStream_t s);        // device pointers; clears the three tables and enqueues the kernel
 int host_road_votes(const RoadVoteParams& p);                         // host pointers; the plain loops
+
+// The band histograms of the road labels of a batch of tiles (band_hist.h states the rule and the layout).  tiles as the engine holds
+// them, label_masks as CanvasRasterParams writes them, one canvas per label instance.
+struct BandHistParams {
+  const uint8_t* tiles;        // [n][side][side][C]
+  const uint8_t* label_masks;  // [n_inst][side][(side + 7) / 8]
+  const int* tile_first;       // [n + 1]
+  uint32_t* hist;              // [n_inst][C][256]
+  int n, n_inst, side, C;
+};
+// both refuse (before anything is touched) a null table, n < 1, n_inst < 0, side outside [1, BH_MAX_SIDE], C outside [1,
+// BH_MAX_CHANNELS] (RS_ERR_ARG); canvases that are not whole 32-bit words (RS_ERR_UNSUPPORTED); `who` names the entry in the error text
+int band_hist_check(const char* who, const BandHistParams& p);
+int launch_band_hist(const BandHistParams& p, hipStream_t s);         // device pointers; clears hist and enqueues the kernel
+int host_band_hist(const BandHistParams& p);                          // host pointers; the plain loops

@@ -109,6 +109,10 @@ class RsRoadVotes(C.Structure):
                 ("label_area", C.POINTER(C.c_int32))]
 
 
+class RsBandHist(C.Structure):
+    _fields_ = [("hist", C.POINTER(C.c_uint32))]
+
+
 class RsSolver(C.Structure):
     """include/rs_engine.h ``rs_solver``."""
     _fields_ = [("struct_size", C.c_int32), ("nesterov", C.c_int32), ("bias_lr_factor", C.c_float), ("weight_decay_bias", C.c_float),
@@ -311,6 +315,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.rs_host_road_votes.argtypes = [vp] * 6 + [i32] * 4 + [C.c_double] + [vp] * 3
         lib.rs_engine_fetch_votes_async.argtypes = [vp, i32] + [vp] * 5 + [C.c_double, C.POINTER(RsRoadVotes)]
         lib.rs_engine_fetch_votes_wait.argtypes = [vp]
+    if hasattr(lib, "rs_op_band_hist"):               # RS_ENGINE_LIB may name an older build
+        lib.rs_op_band_hist.argtypes = [vp] * 3 + [i32] * 4 + [vp, vp]
+        lib.rs_host_band_hist.argtypes = [vp] * 3 + [i32] * 4 + [vp]
+        lib.rs_engine_fetch_band_hist_async.argtypes = [vp, i32] + [vp] * 5 + [C.POINTER(RsBandHist)]
+        lib.rs_engine_fetch_band_hist_wait.argtypes = [vp]
     lib.rs_rasterize_polygons_within_box.argtypes = [f64p, i32p, i32, f64p, i32, u8p]
     lib.rs_memcpy_d2h.argtypes = [vp, vp, C.c_size_t]
     lib.rs_op_fdiv.argtypes = [vp, vp, vp, C.c_int64, vp]
@@ -574,6 +583,11 @@ class Engine:
         self._vote_struct: Optional[RsRoadVotes] = None
         self._vote_labels: List[int] = []
         self.vote_fallbacks = 0
+        # band histograms (rs_engine_fetch_band_hist_*): one pinned table, allocated on the first band_hist; batches that did not fit
+        self._band_struct: Optional[RsBandHist] = None
+        self._band_labels: List[int] = []
+        self._band_pending = False           # a band_hist fetch the host has not waited for: the device may still be reading the tiles
+        self.band_fallbacks = 0
 
     def _dets_struct(self, want_probs: bool) -> RsDets:
         d = RsDets()
@@ -931,6 +945,64 @@ class Engine:
             out.append(row)
         return out
 
+    def band_hist(self, tiles_or_n, labels: Sequence[Sequence[Sequence[np.ndarray]]], wait: bool = True):
+        """The band histograms under the road labels of a batch, counted on the device (csrc/band_hist.h): ``tiles_or_n`` and ``labels``
+        as for ``road_votes``.  The labels are rasterised on the GPU exactly as ``raster_vote.label_rasters`` does on the host and
+        counted against the uint8 tiles of the forward; only the histograms travel.  Returns per tile an ``(L_t, C, 256)`` uint32
+        array -- per label, band and value the number of the label's pixels that are not nodata (every band 0);
+        ``band_stats.reduce_band_hist`` and ``stats_from_hist`` turn them into the reference's table -- or ``None`` when the batch does
+        not fit the device pool (the conditions of ``eval_counts``, shared with it): then nothing was enqueued, ``band_fallbacks``
+        counts it and the caller uses ``band_stats.band_hist_host`` on this batch.  It carries no detections and may follow any
+        ``fetch_async`` and ``road_votes(..., wait=False)`` of the same forward.  ``wait=False`` returns True once everything is
+        enqueued; ``band_hist_wait(n)`` then gives the result, and tiles uploaded in between are ordered behind the kernel."""
+        n = int(tiles_or_n) if np.isscalar(tiles_or_n) else int(tiles_or_n.shape[0])
+        packed = self._band_label_tables(n, labels)
+        if packed is None:
+            return None
+        if not np.isscalar(tiles_or_n):
+            self.infer_device(self.upload_async(np.ascontiguousarray(tiles_or_n)), n)
+        self._band_labels = self._band_enqueue(n, packed)
+        return self.band_hist_wait(n) if wait else True
+
+    def _band_label_tables(self, n: int, labels):
+        """The label tables of a batch as rs_engine_fetch_band_hist_async takes them, or ``None`` -- counted in ``band_fallbacks`` --
+        when the batch does not fit the device pool.  The pool and its check are those of the validation counts; the counters are not."""
+        before = self.eval_fallbacks
+        packed = self._eval_polygon_tables(n, labels)
+        self.eval_fallbacks = before
+        if packed is None:
+            self.band_fallbacks += 1
+        return packed
+
+    def _band_enqueue(self, n: int, packed) -> List[int]:
+        """Enqueue the histograms of ``_band_label_tables``' tables behind the last forward (and behind whatever fetch of it is in
+        flight); returns the labels per tile."""
+        flat, off, lens, inst_first, tile_first = packed
+        if self._band_struct is None:
+            self._band_table = self._pinned((self.max_batch * EVAL_GT_CAP, self.tile_c, 256), np.uint32)
+            b = RsBandHist()
+            b.hist = self._band_table.ctypes.data_as(C.POINTER(C.c_uint32))
+            self._band_struct = b
+        rc = self.lib.rs_engine_fetch_band_hist_async(self._h, n, flat.ctypes.data, off.ctypes.data, lens.ctypes.data, inst_first.ctypes.data,
+                                                      tile_first.ctypes.data, C.byref(self._band_struct))
+        _check(self.lib, rc, "rs_engine_fetch_band_hist_async")    # the fit was checked above: any other code here is an error
+        self._band_pending = True
+        return np.diff(tile_first).tolist()
+
+    def band_hist_wait(self, n: int, label_counts: Optional[Sequence[int]] = None) -> List[np.ndarray]:
+        """The second half of ``band_hist(..., wait=False)``: waits for the copy and returns the histograms of tiles 0..n-1.  A
+        ``fetch_async`` of the same forward that is in flight keeps its own ``wait_results``, before or after this call.
+        ``label_counts``: the labels per tile of the batch the table belongs to, for a caller that has enqueued another since."""
+        _check(self.lib, self.lib.rs_engine_fetch_band_hist_wait(self._h), "rs_engine_fetch_band_hist_wait")
+        self._band_pending = False
+        counts = self._band_labels if label_counts is None else label_counts
+        out, g0 = [], 0
+        for i in range(n):
+            g = int(counts[i])
+            out.append(self._band_table[g0:g0 + g].copy())
+            g0 += g
+        return out
+
     def infer_device(self, tiles_dev_ptr: int, n: int) -> None:
         """Enqueue a forward on tiles already in device memory (no wait)."""
         _check(self.lib, self.lib.rs_engine_infer_device(self._h, C.c_void_p(tiles_dev_ptr), n), "rs_engine_infer_device")
@@ -1007,6 +1079,9 @@ class Engine:
         tiles = np.ascontiguousarray(tiles)
         assert tiles.dtype == np.uint8 and tiles.shape[1:] == (self.tile_h, self.tile_w, self.tile_c) and tiles.shape[0] <= self.max_batch
         ptr, _, _, _ = self.tensor_ptr("tiles")
+        if self._band_pending:               # this copy is on no stream of the engine's: let the histogram kernel finish with the tiles first
+            _check(self.lib, self.lib.rs_engine_fetch_band_hist_wait(self._h), "rs_engine_fetch_band_hist_wait")
+            self._band_pending = False
         _check(self.lib, self.lib.rs_memcpy_h2d(C.c_void_p(ptr), tiles.ctypes.data_as(C.c_void_p), tiles.nbytes), "rs_memcpy_h2d")
         return ptr
 
@@ -1115,6 +1190,7 @@ class LanePipeline:
         # saturation counts (Engine.saturation) of the batch ``run`` yielded last: set before the batch is yielded
         self.last_saturation: Dict[str, int] = {}
         self.vote_fallbacks = 0                      # batches of the last ``run(..., labels=...)`` that were voted on the host
+        self.band_fallbacks = 0                      # batches of the last ``run(..., band_stats=True)`` whose histograms the host formed
 
     def _fetch_async(self, e: Engine, n: int, masks: bool = False) -> None:
         if self.vectorize == "device" and e.spec.mask_on:
@@ -1149,7 +1225,7 @@ class LanePipeline:
         """Enqueue the outstanding mask-head phase; after this every submitted batch is fully enqueued."""
         self._finish_pending()
 
-    def run(self, batches, labels=None, vote_threshold: float = 0.0) -> "Iterator[List[Instances]]":
+    def run(self, batches, labels=None, vote_threshold: float = 0.0, band_stats: bool = False, road_votes: bool = True) -> "Iterator[List[Instances]]":
         """Stream host batches ((n,h,w,c) uint8 arrays) through the lanes and yield their detections in order.  Uploads go
         through pinned staging on the lane's stream, every batch's results come back on its lane's copy stream behind an event,
         and the generator runs ``lanes`` batches ahead of what it yields, so host-side collection overlaps the GPU.  Independent lanes:
@@ -1159,18 +1235,41 @@ class LanePipeline:
         ``labels``: an iterable parallel to ``batches``, per batch the road labels of its tiles as ``Engine.road_votes`` takes them.
         Then every yielded ``Instances`` carries ``road_votes`` = (wscore, wfrac, pairs, label_area) of its tile: the vote fetch is
         enqueued right behind the batch's result fetch on the batch's lane, and a batch that does not fit the device pool is fetched
-        with its masks and voted on the host (``raster_vote.vote_tables_host``), counted in ``vote_fallbacks``."""
+        with its masks and voted on the host (``raster_vote.vote_tables_host``), counted in ``vote_fallbacks``.
+        ``band_stats=True`` (needs ``labels``): every yielded ``Instances`` also carries ``band_hist``, the (L_t, C, 256) histograms of
+        its tile's labels (``Engine.band_hist``), enqueued behind the batch's other fetches on its lane; a batch that does not fit gets
+        them from ``band_stats.band_hist_host`` on its own host tiles, which the pipeline keeps until the batch is yielded, counted in
+        ``band_fallbacks``.  ``road_votes=False`` leaves the vote out: labels then serve the histograms alone."""
+        if band_stats and labels is None:
+            raise ValueError("band_stats needs the road labels of every batch")
+        want_votes = labels is not None and bool(road_votes)
         L = len(self.engines)
         lab_it = iter(labels) if labels is not None else None
         lab_of: Dict[int, Any] = {}                 # lane -> the labels of the batch it was given last
         vote_of: Dict[int, Any] = {}                # lane -> ("device", labels per tile) / ("host", labels) of the fetch in flight
-        if lab_it is not None:
+        tiles_of: Dict[int, Any] = {}               # lane -> the host tiles of the batch it was given last (band_stats: the host route reads them)
+        band_of: Dict[int, Any] = {}                # lane -> ("device", labels per tile) / ("host", labels, tiles) of the histograms in flight
+        if want_votes:
             self.vote_fallbacks = 0
+        if band_stats:
+            self.band_fallbacks = 0
+
+        def fetch_band(lane: int, n: int) -> None:
+            eng = self.engines[lane]
+            packed = eng._band_label_tables(n, lab_of[lane])
+            if packed is None:
+                self.band_fallbacks += 1
+                band_of[lane] = ("host", lab_of[lane], tiles_of[lane])
+            else:
+                band_of[lane] = ("device", eng._band_enqueue(n, packed))
 
         def fetch(lane: int, n: int) -> None:
             eng = self.engines[lane]
-            if lab_it is None:
-                return self._fetch_async(eng, n)
+            if not want_votes:
+                self._fetch_async(eng, n)
+                if band_stats:
+                    fetch_band(lane, n)
+                return
             packed = eng._vote_label_tables(n, lab_of[lane])
             if packed is None:
                 self.vote_fallbacks += 1
@@ -1179,10 +1278,25 @@ class LanePipeline:
             else:
                 self._fetch_async(eng, n)
                 vote_of[lane] = ("device", eng._vote_enqueue(n, packed, vote_threshold))
+            if band_stats:
+                fetch_band(lane, n)
+
+        def with_band(lane: int, res: List[Instances]) -> List[Instances]:
+            if not band_stats:
+                return res
+            what = band_of.pop(lane)
+            if what[0] == "device":
+                tables = self.engines[lane].band_hist_wait(len(res), what[1])
+            else:
+                from . import band_stats as band_mod
+                tables = band_mod.band_hist_host(what[2], what[1])
+            for inst, h in zip(res, tables):
+                inst.band_hist = h
+            return res
 
         def voted(lane: int, res: List[Instances]) -> List[Instances]:
-            if lab_it is None:
-                return res
+            if not want_votes:
+                return with_band(lane, res)
             from . import raster_vote
             kind, what = vote_of.pop(lane)
             if kind == "device":
@@ -1191,7 +1305,7 @@ class LanePipeline:
                 rows = raster_vote.vote_tables_host(res, what, self.engines[lane].spec.num_classes, vote_threshold)
             for inst, row in zip(res, rows):
                 inst.road_votes = row
-            return res
+            return with_band(lane, res)
 
         def counted(eng: Engine, res: List[Instances]) -> List[Instances]:
             # the lane's counts were published by its wait_results and stay until its next one: read them with the batch's results
@@ -1214,6 +1328,8 @@ class LanePipeline:
             self.k += 1
             if lab_it is not None:
                 lab_of[lane] = next(lab_it)
+            if band_stats:
+                tiles_of[lane] = tiles
             if L == 1:                              # one lane has one set of host buffers: no look-ahead
                 e.infer_device(e.upload_async(np.ascontiguousarray(tiles)), n)
                 fetch(lane, n)
@@ -1303,6 +1419,7 @@ class Predictor:
         self.on_saturation = on_saturation
         self.last_saturation: Dict[str, int] = {}
         self.vote_fallbacks = 0                     # batches of the last ``predict_stream(..., labels=...)`` that were voted on the host
+        self.band_fallbacks = 0                     # batches of the last ``predict_stream(..., band_stats=True)`` counted on the host
         self._pipes: Dict[Tuple[int, int, int], LanePipeline] = {}
 
     def _saturated(self, sat: Dict[str, int], what: str) -> None:
@@ -1362,20 +1479,26 @@ class Predictor:
         self.last_saturation = total
         return out
 
-    def predict_stream(self, batches, labels=None, vote_threshold: float = 0.0) -> "Iterator[List[Dict[str, Instances]]]":
+    def predict_stream(self, batches, labels=None, vote_threshold: float = 0.0, band_stats: bool = False,
+                       road_votes: bool = True) -> "Iterator[List[Dict[str, Instances]]]":
         """Streaming form for a whole tileset: ``batches`` is an iterator of image lists (each at most ``max_batch`` images);
         yields one result list per batch, in order.  Consecutive batches of one tile shape flow through ONE
         ``LanePipeline.run`` generator, so the upload, forward and result copy of batch k+1 overlap batch k (calling
         ``predict_batch`` once per batch would drain the pipeline after every batch).  The iterator is pulled lazily, two
         batches ahead of what is yielded.  ``labels``: an iterable parallel to ``batches``, per batch the road labels of its tiles
         (``LanePipeline.run``); every yielded ``Instances`` then carries ``road_votes``, and ``vote_fallbacks`` counts the batches
-        of the stream that were voted on the host.  Labels need batches of one tile shape."""
+        of the stream that were voted on the host.  Labels need batches of one tile shape.  ``band_stats=True``: every yielded
+        ``Instances`` also carries ``band_hist`` (``LanePipeline.run``), ``band_fallbacks`` counts the batches whose histograms the
+        host formed; ``road_votes=False`` leaves the vote out and the labels serve the histograms alone."""
+        if band_stats and labels is None:
+            raise ValueError("band_stats needs the road labels of every batch")
         it = iter(batches)
         lab_src = iter(labels) if labels is not None else None
         lab_q: List[Any] = []            # labels of the batches handed to the running pipeline and not yet taken by it
         carry: List[Any] = []            # a batch read ahead that does not fit the running pipeline (with its labels)
         k = 0                            # batches yielded
         self.vote_fallbacks = 0
+        self.band_fallbacks = 0
 
         def next_batch():
             if carry:
@@ -1410,9 +1533,13 @@ class Predictor:
                     b, lab = next_batch()
             pipe = self._pipe(shape)
             before = pipe.vote_fallbacks if lab_src is None else 0
-            for res in pipe.run(run_of_shape(), labels=taken_labels() if lab_src is not None else None, vote_threshold=vote_threshold):
+            band_before = 0
+            for res in pipe.run(run_of_shape(), labels=taken_labels() if lab_src is not None else None, vote_threshold=vote_threshold,
+                                band_stats=band_stats, road_votes=road_votes):
                 self.vote_fallbacks += pipe.vote_fallbacks - before
                 before = pipe.vote_fallbacks
+                self.band_fallbacks += pipe.band_fallbacks - band_before
+                band_before = pipe.band_fallbacks
                 self._saturated(pipe.last_saturation, f"batch {k} of the stream")
                 k += 1
                 yield [{"instances": r} for r in res]

@@ -100,6 +100,20 @@ def road_labels(coco: Dict[str, Any], dataset: str = "") -> Dict[Any, Tuple[List
     return out
 
 
+def road_covers(coco: Dict[str, Any]) -> Dict[Any, str]:
+    """For ``--road-stats``: road -> the category name of its first label (the annotations ``road_labels`` takes, in the file's order).
+    Empty where the file names no categories: then no per-cover table is written."""
+    names = {c["id"]: c.get("name") for c in coco.get("categories", []) if c.get("name")}
+    out: Dict[Any, str] = {}
+    for a in coco.get("annotations", []):
+        seg = a.get("segmentation")
+        if a.get("iscrowd") or not isinstance(seg, list) or not any(len(r) >= 6 and len(r) % 2 == 0 for r in seg):
+            continue
+        if a.get("category_id") in names:
+            out.setdefault(a.get("road_id", a.get("id")), names[a["category_id"]])
+    return out
+
+
 def thr_tag(thr: float) -> str:
     return str(thr).replace(".", "dot")
 
@@ -154,6 +168,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "dataset's COCO file are the road labels of their tile (tile pixels; 'road_id' where present, else 'id'), counted against "
                          "the detection masks on the GPU behind every batch's forward (csrc/road_vote.h); a batch beyond the device pool is voted "
                          "on the host from its masks.  Needs datasets of one tile shape.  Every other output is unchanged")
+    ap.add_argument("--road-stats", action="store_true",
+                    help="also write <dataset>_road_stats.json, the band statistics per road of the reference's statistical route (band_stats.py: "
+                         "min, max, median, mean, count, std and margin per road and band, and per cover type where the annotations carry a "
+                         "category): the road labels of --road-votes (which it does not need), their pixels counted into histograms on the GPU "
+                         "behind every batch's forward (csrc/band_hist.h); a batch beyond the device pool is counted on the host.  Needs "
+                         "datasets of one tile shape.  Every other output is unchanged")
     ap.add_argument("--vote-threshold", type=float, default=None,
                     help="score a detection needs to vote (default: 'threshold' of the YAML's 'determine_class.py' section where it exists, else 0)")
     return ap
@@ -170,7 +190,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         whole_cfg = yaml.safe_load(f)
     cfg = whole_cfg[SECTION]
     vote_thr = float(args.vote_threshold if args.vote_threshold is not None else (whole_cfg.get("determine_class.py") or {}).get("threshold", 0))
-    votes: Dict[str, Any] = {"labels": None, "by_file": {}}      # --road-votes: the running dataset's labels per batch, its tables per tile
+    votes: Dict[str, Any] = {"labels": None, "by_file": {}}      # --road-votes / --road-stats: the running dataset's labels per batch, its vote tables per tile
+    band_by_file: Dict[str, Any] = {}                            # --road-stats: the running dataset's histograms per tile
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -257,7 +278,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         if votes["labels"] is None:
             it = predictor.predict_stream(batches)
         else:
-            it = predictor.predict_stream(batches, labels=iter(votes["labels"]), vote_threshold=vote_thr)
+            it = predictor.predict_stream(batches, labels=iter(votes["labels"]), vote_threshold=vote_thr, band_stats=args.road_stats,
+                                          road_votes=args.road_votes)
         while True:
             t = time.perf_counter()
             out = next(it, None)
@@ -276,8 +298,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             ext, epsg_t = tile_extent(meta, e["file_name"])
             name = os.path.basename(e["file_name"])
             rdp_on, eps = bool(rdp_cfg.get("enabled", False)), float(rdp_cfg.get("epsilon", 0.75))
-            if votes["labels"] is not None:
+            if votes["labels"] is not None and args.road_votes:
                 votes["by_file"][e["file_name"]] = o["instances"].road_votes
+            if votes["labels"] is not None and args.road_stats:
+                band_by_file[e["file_name"]] = o["instances"].band_hist
             carried = getattr(o["instances"], "_polygons", None)
             if carried is not None:
                 fell_back["instances"] += int(len(carried.flagged))
@@ -334,10 +358,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                         return
                     yield b
             source = pool_source if pool is not None else None
-        if args.road_votes:
+        if args.road_votes or args.road_stats:
             lo, hi = shard_range(len(images), rank, world)
             by_image = road_labels(d, dataset)
             votes["by_file"] = {}
+            band_by_file.clear()
             votes["labels"] = [[by_image.get(e["id"], ([], []))[1] for e in images[i:min(i + args.batch, hi)]] for i in range(lo, hi, args.batch)]
         try:
             try:
@@ -390,7 +415,33 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 log.info("%s: %d road labels on %d tiles -> %d roads in %s_road_votes.json (vote threshold %g); %d of %d batches were voted on the host",
                          dataset, sum(len(ids) for ids, _ in rows), len(rows), len(table), dataset, vote_thr, sum(fb for _, fb in parts),
                          sum(len(range(*shard_range(len(images), r, world), args.batch)) for r in range(world)))
-            votes["labels"] = None
+        if args.road_stats:
+            # every rank sums its own tiles' histograms per road; the per-road sums travel to rank 0, which adds them in rank order =
+            # tile order.  Integer sums: the file does not depend on the world size
+            from . import band_stats
+            mine_h = band_stats.reduce_band_hist([band_by_file[e["file_name"]] for e in images[lo:hi]],
+                                                 [by_image.get(e["id"], ([], []))[0] for e in images[lo:hi]])
+            parts_h: List[Any] = [(mine_h, predictor.band_fallbacks)]
+            if world > 1:
+                import torch.distributed as dist
+                parts_h = [None] * world if rank == 0 else None
+                dist.gather_object((mine_h, predictor.band_fallbacks), parts_h, dst=0)
+            if rank == 0:
+                by_road: Dict[Any, Any] = {}
+                for part, _ in parts_h:
+                    for rid, h in part.items():
+                        by_road[rid] = by_road[rid] + h if rid in by_road else h
+                doc: Dict[str, Any] = {"columns": list(band_stats.COLUMNS),
+                                       "roads": [{"road_id": rid, "bands": band_stats.json_rows(band_stats.stats_from_hist(h))} for rid, h in by_road.items()]}
+                covers = road_covers(d)
+                if covers:
+                    doc["covers"] = [{"cover_type": c, "bands": band_stats.json_rows(rows)} for c, rows in band_stats.cover_stats(by_road, covers).items()]
+                with open(f"{dataset}_road_stats.json", "w") as f:
+                    f.write(json.dumps(doc))
+                log.info("%s: band statistics of %d roads%s in %s_road_stats.json; %d of %d batches were counted on the host", dataset, len(by_road),
+                         f" and {len(doc['covers'])} cover types" if covers else "", dataset, sum(fb for _, fb in parts_h),
+                         sum(len(range(*shard_range(len(images), r, world), args.batch)) for r in range(world)))
+        votes["labels"] = None
         # Every rank writes the rows of ITS block of tiles into its own GeoPackage shard (rank 0: the output file itself); rank 0 then appends the
         # other ranks' shards in rank order = tile order with SQLite ATTACH -- no row travels between processes ("each rank ...
         # its own output shard; host merges shards into one GeoPackage per dataset").  The ranks of one node share the working directory.
