@@ -1029,6 +1029,42 @@ int rs_engine_fetch_votes_async(rs_engine* e, int n, const double* polys, const 
                                 const int32_t* inst_first, const int32_t* tile_first, double threshold, rs_road_votes* votes_host);
 int rs_engine_fetch_votes_wait(rs_engine* e);
 
+/* The vote for a list of score thresholds at once.  The reference's published number is the balanced F1 of the road cover classes at
+ * the best of 20 thresholds (scripts/road_segmentation/final_metrics.py runs determine_detected_class once per value of
+ * np.arange(0, 1., 0.05)); proj_roadsurf_amd/road_metrics.py restates its metrics on the road tables.  thresholds[0 .. n_thresholds - 1]
+ * is a HOST pointer in every entry below and is copied into the launch parameters: 1 <= n_thresholds <= RS_VOTE_SWEEP_MAX, any finite
+ * doubles in any order, duplicates allowed.  Out: wscore, wfrac [n_tiles][n_thresholds][gt_cap][num_classes] double and pairs of the
+ * same shape int32.  Slice j has the bits of rs_op_road_votes' tables at threshold thresholds[j]: the same walk over the slots, the
+ * same float64 arithmetic, once per threshold (csrc/road_vote.h, THE SWEEP; road_vote_sweep_kernel in csrc/val_ap.hip carries the
+ * threshold's index in the grid, so the compare is against one value per wave).  rs_op_road_votes_sweep takes device tables, clears
+ * its outputs, enqueues on `stream` and does not wait; rs_host_road_votes_sweep takes host tables and needs no device.  Both refuse,
+ * before anything is touched, what the single-threshold entries refuse, and also a null list, n_thresholds outside
+ * [1, RS_VOTE_SWEEP_MAX] and an entry that is not finite (RS_ERR_ARG). */
+#define RS_VOTE_SWEEP_MAX 32
+int rs_op_road_votes_sweep(const float* det_scores, const int32_t* det_classes, const int32_t* det_count, const int32_t* tile_first,
+                           const int32_t* inter, const int32_t* gt_area, int n_tiles, int num_classes, int slots, int gt_cap,
+                           const double* thresholds, int n_thresholds, double* wscore, double* wfrac, int32_t* pairs, void* stream);
+int rs_host_road_votes_sweep(const float* det_scores, const int32_t* det_classes, const int32_t* det_count, const int32_t* tile_first,
+                             const int32_t* inter, const int32_t* gt_area, int n_tiles, int num_classes, int slots, int gt_cap,
+                             const double* thresholds, int n_thresholds, double* wscore, double* wfrac, int32_t* pairs);
+
+/* The sweep behind the engine's last forward: an add-on exactly like rs_engine_fetch_votes_async (label upload, rasteriser, pair
+ * counts, the sweep and the copies on the copy stream, behind the forward and behind any fetch of it; the same pool, the same limits,
+ * RS_EVAL_DOES_NOT_FIT with nothing enqueued under the same conditions; the next forward is ordered behind it in the same way).  The
+ * rasteriser and the pair counts run once for all thresholds.  The device tables are allocated on the first call, sized for
+ * RS_VOTE_SWEEP_MAX thresholds; an engine that never calls it allocates nothing for it, and its stages and tensors are unchanged.
+ * The caller's (rs_host_alloc) tables hold n * n_thresholds * RS_EVAL_GT_CAP * K cells each, label_area n * RS_EVAL_GT_CAP. */
+typedef struct rs_road_vote_sweep {
+  double* wscore;       /* [n][T][RS_EVAL_GT_CAP][K] */
+  double* wfrac;        /* [n][T][RS_EVAL_GT_CAP][K] */
+  int32_t* pairs;       /* [n][T][RS_EVAL_GT_CAP][K] */
+  int32_t* label_area;  /* [n][RS_EVAL_GT_CAP] */
+} rs_road_vote_sweep;
+int rs_engine_fetch_vote_sweep_async(rs_engine* e, int n, const double* polys, const int64_t* poly_off, const int32_t* poly_len,
+                                     const int32_t* inst_first, const int32_t* tile_first, const double* thresholds, int n_thresholds,
+                                     rs_road_vote_sweep* sweep_host);
+int rs_engine_fetch_vote_sweep_wait(rs_engine* e);
+
 /* ------------------------------------------------------------------ band histograms under the road labels (csrc/band_hist.h)
  * The reference's second answer for a road's cover is statistical: scripts/statistical_analysis collects, per road, the pixels of
  * every band under the road's polygon over all tiles the road touches, drops the nodata pixels (without a nodata value in the TIFF:

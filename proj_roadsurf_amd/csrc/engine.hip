@@ -1230,6 +1230,14 @@ int rs_engine::ensure_vote_buffers() {
   return alloc((void**)&vote_pairs, vote_cells * 4);   // last: its presence says that all of the above exists
 }
 
+int rs_engine::ensure_vote_sweep_buffers() {
+  if (sweep_pairs) return RS_OK;
+  sweep_cells = (size_t)max_batch * RS_VOTE_SWEEP_MAX * RS_EVAL_GT_CAP * (size_t)spec.num_classes;
+  int rc;
+  if ((rc = alloc((void**)&sweep_wscore, sweep_cells * 16))) return rc;      // wscore, then wfrac
+  return alloc((void**)&sweep_pairs, sweep_cells * 4); // last: its presence says that all of the above exists
+}
+
 int rs_engine::ensure_band_buffers() {
   if (band_hist_dev) return RS_OK;
   RS_HIP(hipEventCreateWithFlags(&ev_band_tiles, hipEventDisableTiming));
@@ -1731,6 +1739,47 @@ int rs_engine_fetch_votes_async(rs_engine* e, int n, const double* polys, const 
 }
 
 int rs_engine_fetch_votes_wait(rs_engine* e) { return rs_engine_fetch_wait(e); }
+
+// The same add-on for a list of thresholds (road_vote.h, THE SWEEP): one upload, one rasteriser pass and one pair count for all of them.
+int rs_engine_fetch_vote_sweep_async(rs_engine* e, int n, const double* polys, const int64_t* poly_off, const int32_t* poly_len,
+                                     const int32_t* inst_first, const int32_t* tile_first, const double* thresholds, int n_thresholds,
+                                     rs_road_vote_sweep* v) {
+  RS_CHECK(e && v && v->wscore && v->wfrac && v->pairs && v->label_area && n >= 1 && n <= e->max_batch, RS_ERR_ARG,
+           "rs_engine_fetch_vote_sweep_async: bad argument");
+  RS_CHECK(thresholds && n_thresholds >= 1 && n_thresholds <= RS_VOTE_SWEEP_MAX, RS_ERR_ARG,
+           "rs_engine_fetch_vote_sweep_async: %d thresholds outside [1, %d], or a null list", n_thresholds, RS_VOTE_SWEEP_MAX);
+  for (int j = 0; j < n_thresholds; ++j)
+    RS_CHECK(thresholds[j] - thresholds[j] == 0.0, RS_ERR_ARG, "rs_engine_fetch_vote_sweep_async: threshold %d is not finite", j);
+  { int rc = rs_engine_eval_fits(e, n, poly_off, poly_len, inst_first, tile_first); if (rc) return rc; }
+  if (e->D > RV_MAX_SLOTS) return RS_EVAL_DOES_NOT_FIT;
+  const int K = e->spec.num_classes, T = n_thresholds;
+  MtLayout L;
+  { int rc = mt_measure(polys, poly_off, poly_len, inst_first, tile_first[n], n, &L); if (rc) return rc; }
+  hipStream_t s = nullptr;
+  int rc;
+  if ((rc = e->ensure_eval_buffers())) return rc;
+  if ((rc = e->ensure_vote_sweep_buffers())) return rc;
+  RS_CHECK(L.bytes <= e->eval_pool_bytes, RS_ERR_ARG, "road labels: %zu bytes packed, the pool holds %zu", L.bytes, e->eval_pool_bytes);
+  if (e->eval_upload_pending) { RS_HIP(hipEventSynchronize(e->ev_eval_upload)); e->eval_upload_pending = false; }
+  mt_pack(e->eval_pinned, L, polys, poly_off, poly_len, inst_first, tile_first);
+  if ((rc = e->begin_fetch(&s))) return rc;
+  if ((rc = e->launch_eval_counts(n, &L, s))) return rc;
+  RoadVoteSweepParams q;
+  memset(&q, 0, sizeof q);
+  q.det_scores = e->det_scores; q.det_classes = e->det_classes; q.det_count = e->det_count; q.tile_first = (const int*)e->eval_pool;
+  q.inter = e->eval_inter; q.gt_area = e->eval_gt_area; q.wscore = e->sweep_wscore; q.wfrac = e->sweep_wscore + e->sweep_cells;
+  q.pairs = e->sweep_pairs; q.T = T; q.n = n; q.K = K; q.D = e->D; q.g_cap = RS_EVAL_GT_CAP;
+  for (int j = 0; j < T; ++j) q.thresholds[j] = thresholds[j];
+  if ((rc = launch_road_votes_sweep(q, s))) return rc;
+  const size_t cells = (size_t)n * T * RS_EVAL_GT_CAP * K;           // <= sweep_cells: n <= max_batch, T <= RS_VOTE_SWEEP_MAX
+  RS_HIP(hipMemcpyAsync(v->wscore, q.wscore, cells * 8, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(v->wfrac, q.wfrac, cells * 8, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(v->pairs, q.pairs, cells * 4, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(v->label_area, e->eval_gt_area, (size_t)n * RS_EVAL_GT_CAP * 4, hipMemcpyDeviceToHost, s));
+  return e->end_fetch(s, nullptr);            // the tables live in their own buffers: detections and canvases are free for the next forward
+}
+
+int rs_engine_fetch_vote_sweep_wait(rs_engine* e) { return rs_engine_fetch_wait(e); }
 
 // The band histograms of the road labels under the last forward's tiles (band_hist.h): upload, rasteriser, histogram kernel, one copy.
 // An add-on like the vote: no detections, no pair counts.  The kernel is the one reader of tiles_dev on the copy stream: the event

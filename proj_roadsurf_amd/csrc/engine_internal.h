@@ -132,6 +132,11 @@ struct rs_engine {
   int* vote_pairs = nullptr;
   size_t vote_cells = 0;
   int ensure_vote_buffers();
+  // the sweep's tables (rs_engine_fetch_vote_sweep_*): allocated on the first call, for RS_VOTE_SWEEP_MAX thresholds
+  double* sweep_wscore = nullptr;               // device: wscore [max_batch][RS_VOTE_SWEEP_MAX][RS_EVAL_GT_CAP][K], then wfrac of the same shape
+  int* sweep_pairs = nullptr;
+  size_t sweep_cells = 0;
+  int ensure_vote_sweep_buffers();
   // band histograms (rs_engine_fetch_band_hist_*, band_hist.h): allocated on the first call
   uint32_t* band_hist_dev = nullptr;            // device: [max_batch * RS_EVAL_GT_CAP][tile_c][256]
   hipEvent_t ev_band_tiles = nullptr;           // recorded on the copy stream behind the histogram kernel, the one reader of tiles_dev there

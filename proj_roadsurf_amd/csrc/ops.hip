@@ -355,6 +355,39 @@ int rs_host_road_votes(const float* det_scores, const int32_t* det_classes, cons
   return host_road_votes(q);          // val_ap.hip: the float64 arithmetic is compiled there, without mul+add contraction
 }
 
+// The vote for a list of thresholds (road_vote.h, THE SWEEP): `thresholds` is a host pointer in both entries, copied into the parameters
+static_assert(RV_SWEEP_MAX == RS_VOTE_SWEEP_MAX, "road_vote.h restates the header's sweep capacity");
+static int road_vote_sweep_params(const char* who, RoadVoteSweepParams* q, const float* det_scores, const int32_t* det_classes,
+                                  const int32_t* det_count, const int32_t* tile_first, const int32_t* inter, const int32_t* gt_area, int n_tiles,
+                                  int num_classes, int slots, int gt_cap, const double* thresholds, int n_thresholds, double* wscore,
+                                  double* wfrac, int32_t* pairs) {
+  memset(q, 0, sizeof *q);
+  q->det_scores = det_scores; q->det_classes = det_classes; q->det_count = det_count; q->tile_first = tile_first; q->inter = inter;
+  q->gt_area = gt_area; q->wscore = wscore; q->wfrac = wfrac; q->pairs = pairs;
+  q->n = n_tiles; q->K = num_classes; q->D = slots; q->g_cap = gt_cap; q->T = n_thresholds;
+  RS_CHECK(thresholds, RS_ERR_ARG, "%s: null threshold list", who);
+  for (int j = 0; j < n_thresholds && j < RV_SWEEP_MAX; ++j) q->thresholds[j] = thresholds[j];
+  return road_vote_sweep_check(who, *q);
+}
+int rs_op_road_votes_sweep(const float* det_scores, const int32_t* det_classes, const int32_t* det_count, const int32_t* tile_first,
+                           const int32_t* inter, const int32_t* gt_area, int n_tiles, int num_classes, int slots, int gt_cap,
+                           const double* thresholds, int n_thresholds, double* wscore, double* wfrac, int32_t* pairs, void* stream) {
+  RoadVoteSweepParams q;
+  { int rc = road_vote_sweep_params("rs_op_road_votes_sweep", &q, det_scores, det_classes, det_count, tile_first, inter, gt_area, n_tiles, num_classes,
+                                    slots, gt_cap, thresholds, n_thresholds, wscore, wfrac, pairs);
+    if (rc) return rc; }
+  return launch_road_votes_sweep(q, (hipStream_t)stream);
+}
+int rs_host_road_votes_sweep(const float* det_scores, const int32_t* det_classes, const int32_t* det_count, const int32_t* tile_first,
+                             const int32_t* inter, const int32_t* gt_area, int n_tiles, int num_classes, int slots, int gt_cap,
+                             const double* thresholds, int n_thresholds, double* wscore, double* wfrac, int32_t* pairs) {
+  RoadVoteSweepParams q;
+  { int rc = road_vote_sweep_params("rs_host_road_votes_sweep", &q, det_scores, det_classes, det_count, tile_first, inter, gt_area, n_tiles,
+                                    num_classes, slots, gt_cap, thresholds, n_thresholds, wscore, wfrac, pairs);
+    if (rc) return rc; }
+  return host_road_votes_sweep(q);    // val_ap.hip: the float64 arithmetic is compiled there, without mul+add contraction
+}
+
 // The band histograms under label canvases on caller-owned tables (see include/rs_engine.h): device pointers enqueued on `stream`, or
 // host pointers
 static_assert(BH_MAX_SIDE == CR_MAX_SIDE, "band_hist.h restates the canvases' capacity");

@@ -14,6 +14,12 @@
 // TABLES, per tile, K = classes: wscore [gt_cap][K] double, wfrac [gt_cap][K] double, pairs [gt_cap][K] int32.  Rows of labels at or
 // past the tile's own (tile_first[t + 1] - tile_first[t], at most gt_cap) and rows of labels with area 0 are zero; a detection whose
 // class lies outside [0, K) votes for nothing.  One cell has one owner and a fixed order: two runs give the same bits.
+//
+// THE SWEEP (R:scripts/road_segmentation/final_metrics.py runs determine_detected_class once per score threshold): a list
+// thresholds[0 .. T - 1], 1 <= T <= RV_SWEEP_MAX, any finite doubles in any order, duplicates allowed.  Entry j of every cell is what
+// the walk above accumulates with threshold = thresholds[j] -- rv_pair itself, slot for slot, so slice j of the sweep's tables
+// (wscore, wfrac [T][gt_cap][K] double and pairs [T][gt_cap][K] int32 per tile) has the bits of the single-threshold tables at
+// thresholds[j].  road_vote_sweep_kernel walks the slots once per (cell, threshold) with the threshold as one value for the wave.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -27,6 +33,7 @@
 #define RV_MAX_SLOTS 1024      // detection slots per tile (= CM_MAX_SLOTS, the capacity of the tables in front of this stage)
 #define RV_MAX_GT 128          // labels per tile (= RS_EVAL_GT_CAP)
 #define RV_MAX_CLASSES 80      // = RS_MAX_CLASSES
+#define RV_SWEEP_MAX 32        // thresholds per sweep (= RS_VOTE_SWEEP_MAX)
 
 struct RvCell {
   double ws, wa;

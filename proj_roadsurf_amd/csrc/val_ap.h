@@ -88,6 +88,28 @@ int road_vote_check(const char* who, const RoadVoteParams& p);
 int launch_road_votes(const RoadVoteParams& p, hipStream_t s);        // device pointers; clears the three tables and enqueues the kernel
 int host_road_votes(const RoadVoteParams& p);                         // host pointers; the plain loops
 
+// The same for a list of thresholds at once (road_vote.h, THE SWEEP): slice j of the three tables has the bits of RoadVoteParams'
+// tables at thresholds[j].  The list travels by value; entries at and past T are not read.
+struct RoadVoteSweepParams {
+  const float* det_scores;  // [n][D]
+  const int* det_classes;   // [n][D]
+  const int* det_count;     // [n]
+  const int* tile_first;    // [n + 1]
+  const int* inter;         // [n][D][g_cap]
+  const int* gt_area;       // [n][g_cap]
+  double* wscore;           // [n][T][g_cap][K]
+  double* wfrac;            // [n][T][g_cap][K]
+  int* pairs;               // [n][T][g_cap][K]
+  double thresholds[RV_SWEEP_MAX];
+  int T;
+  int n, K, D, g_cap;
+};
+// both refuse (before anything is touched) what road_vote_check refuses, T outside [1, RV_SWEEP_MAX] and an entry below T that is
+// not finite (RS_ERR_ARG); `who` names the entry in the error text
+int road_vote_sweep_check(const char* who, const RoadVoteSweepParams& p);
+int launch_road_votes_sweep(const RoadVoteSweepParams& p, hipStream_t s);   // device pointers; clears the three tables and enqueues the kernel
+int host_road_votes_sweep(const RoadVoteSweepParams& p);                    // host pointers; the plain loops
+
 // The band histograms of the road labels of a batch of tiles (band_hist.h states the rule and the layout).  tiles as the engine holds
 // them, label_masks as CanvasRasterParams writes them, one canvas per label instance.
 struct BandHistParams {

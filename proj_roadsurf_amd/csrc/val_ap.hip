@@ -10,8 +10,10 @@
 //                             IoUs with the compiler's correctly rounded division, flags as bit words.  No atomics.
 //   road_vote_kernel          the road cover vote (road_vote.h) on the same pair counts, one road label per "ground truth": one work
 //                             item per (label, class) cell, float64 in numpy's order.  No atomics.
-// host_coco_match and host_road_votes are the same rules as plain host loops (rs_host_coco_match, rs_host_road_votes); they live
-// here for the compile flags.
+//   road_vote_sweep_kernel    the same walk for a list of score thresholds, the threshold's index in blockIdx.z: slice j of its tables has
+//                             the bits of road_vote_kernel's at thresholds[j].
+// host_coco_match, host_road_votes and host_road_votes_sweep are the same rules as plain host loops (rs_host_coco_match,
+// rs_host_road_votes, rs_host_road_votes_sweep); they live here for the compile flags.
 #include <string.h>
 
 #include "val_ap.h"
@@ -279,6 +281,31 @@ __global__ __launch_bounds__(256) void road_vote_kernel(const RoadVoteParams p) 
   p.pairs[o] = a.pairs;
 }
 
+// The sweep (road_vote.h): road_vote_kernel's walk once per threshold.  blockIdx.z is the threshold's index, so thresholds[j] is read
+// from the by-value parameters as one value for the whole workgroup and the compare of rv_pair is against a wave-uniform double; no
+// array is indexed per lane, nothing lives in scratch.  The division of rv_frac is repeated per threshold: every slice walks the same
+// slots with the same arithmetic as the single-threshold kernel, which is what makes slice j its tables bit for bit.
+__global__ __launch_bounds__(256) void road_vote_sweep_kernel(const RoadVoteSweepParams p) {
+  const int t = blockIdx.y, j = blockIdx.z, cell = blockIdx.x * 256 + threadIdx.x;
+  if (j >= p.T || cell >= p.g_cap * p.K) return;
+  const int c = cell / p.g_cap, g = cell - c * p.g_cap;
+  if (g >= rv_tile_labels(p.tile_first, t, p.g_cap)) return;
+  const int area = p.gt_area[(long long)t * p.g_cap + g];
+  if (area <= 0) return;
+  const double threshold = p.thresholds[j];
+  const int n = rv_tile_dets(p.det_count, t, p.D);
+  const int* col = p.inter + (long long)t * p.D * p.g_cap + g;
+  const int* cls = p.det_classes + (long long)t * p.D;
+  const float* sc = p.det_scores + (long long)t * p.D;
+  RvCell a;
+  rv_clear(&a);
+  for (int d = 0; d < n; ++d) rv_pair(&a, col[(long long)d * p.g_cap], area, cls[d], sc[d], c, threshold);
+  const long long o = (((long long)t * p.T + j) * p.g_cap + g) * p.K + c;
+  p.wscore[o] = a.ws;
+  p.wfrac[o] = a.wa;
+  p.pairs[o] = a.pairs;
+}
+
 }  // namespace
 
 int road_vote_check(const char* who, const RoadVoteParams& p) {
@@ -325,6 +352,60 @@ int host_road_votes(const RoadVoteParams& p) {
         p.wscore[o] = a.ws;
         p.wfrac[o] = a.wa;
         p.pairs[o] = a.pairs;
+      }
+    }
+  }
+  return RS_OK;
+}
+
+int road_vote_sweep_check(const char* who, const RoadVoteSweepParams& p) {
+  RoadVoteParams q;
+  memset(&q, 0, sizeof q);
+  q.det_scores = p.det_scores; q.det_classes = p.det_classes; q.det_count = p.det_count; q.tile_first = p.tile_first; q.inter = p.inter;
+  q.gt_area = p.gt_area; q.wscore = p.wscore; q.wfrac = p.wfrac; q.pairs = p.pairs; q.threshold = 0.0;
+  q.n = p.n; q.K = p.K; q.D = p.D; q.g_cap = p.g_cap;
+  { int rc = road_vote_check(who, q); if (rc) return rc; }
+  RS_CHECK(p.T >= 1 && p.T <= RV_SWEEP_MAX, RS_ERR_ARG, "%s: %d thresholds outside [1, %d]", who, p.T, RV_SWEEP_MAX);
+  for (int j = 0; j < p.T; ++j)
+    RS_CHECK(p.thresholds[j] - p.thresholds[j] == 0.0, RS_ERR_ARG, "%s: threshold %d is not finite", who, j);
+  return RS_OK;
+}
+
+int launch_road_votes_sweep(const RoadVoteSweepParams& p, hipStream_t s) {
+  { int rc = road_vote_sweep_check("road vote sweep", p); if (rc) return rc; }
+  const size_t cells = (size_t)p.n * p.T * p.g_cap * p.K;
+  RS_HIP(hipMemsetAsync(p.wscore, 0, cells * 8, s));
+  RS_HIP(hipMemsetAsync(p.wfrac, 0, cells * 8, s));
+  RS_HIP(hipMemsetAsync(p.pairs, 0, cells * 4, s));
+  hipLaunchKernelGGL(road_vote_sweep_kernel, dim3((unsigned)cdiv(p.g_cap * p.K, 256), (unsigned)p.n, (unsigned)p.T), dim3(256), 0, s, p);
+  RS_HIP(hipGetLastError());
+  return RS_OK;
+}
+
+// The host restatement of the sweep: host_road_votes' loops once per threshold, slice by slice.
+int host_road_votes_sweep(const RoadVoteSweepParams& p) {
+  { int rc = road_vote_sweep_check("rs_host_road_votes_sweep", p); if (rc) return rc; }
+  const size_t cells = (size_t)p.n * p.T * p.g_cap * p.K;
+  memset(p.wscore, 0, cells * 8);
+  memset(p.wfrac, 0, cells * 8);
+  memset(p.pairs, 0, cells * 4);
+  for (int t = 0; t < p.n; ++t) {
+    const int G = rv_tile_labels(p.tile_first, t, p.g_cap), n = rv_tile_dets(p.det_count, t, p.D);
+    for (int j = 0; j < p.T; ++j) {
+      const double threshold = p.thresholds[j];
+      for (int g = 0; g < G; ++g) {
+        const int area = p.gt_area[(size_t)t * p.g_cap + g];
+        if (area <= 0) continue;
+        for (int c = 0; c < p.K; ++c) {
+          RvCell a;
+          rv_clear(&a);
+          for (int d = 0; d < n; ++d)
+            rv_pair(&a, p.inter[((size_t)t * p.D + d) * p.g_cap + g], area, p.det_classes[(size_t)t * p.D + d], p.det_scores[(size_t)t * p.D + d], c, threshold);
+          const size_t o = (((size_t)t * p.T + j) * p.g_cap + g) * p.K + c;
+          p.wscore[o] = a.ws;
+          p.wfrac[o] = a.wa;
+          p.pairs[o] = a.pairs;
+        }
       }
     }
   }

@@ -109,6 +109,12 @@ class RsRoadVotes(C.Structure):
                 ("label_area", C.POINTER(C.c_int32))]
 
 
+class RsRoadVoteSweep(C.Structure):
+    """include/rs_engine.h ``rs_road_vote_sweep``: the tables of ``RsRoadVotes`` with a threshold axis behind the tile's."""
+    _fields_ = [("wscore", C.POINTER(C.c_double)), ("wfrac", C.POINTER(C.c_double)), ("pairs", C.POINTER(C.c_int32)),
+                ("label_area", C.POINTER(C.c_int32))]
+
+
 class RsBandHist(C.Structure):
     _fields_ = [("hist", C.POINTER(C.c_uint32))]
 
@@ -315,7 +321,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.rs_host_road_votes.argtypes = [vp] * 6 + [i32] * 4 + [C.c_double] + [vp] * 3
         lib.rs_engine_fetch_votes_async.argtypes = [vp, i32] + [vp] * 5 + [C.c_double, C.POINTER(RsRoadVotes)]
         lib.rs_engine_fetch_votes_wait.argtypes = [vp]
-    if hasattr(lib, "rs_op_band_hist"):               # RS_ENGINE_LIB may name an older build
+    if hasattr(lib, "rs_op_road_votes_sweep"):        # RS_ENGINE_LIB may name an older build
+        lib.rs_op_road_votes_sweep.argtypes = [vp] * 6 + [i32] * 4 + [vp, i32] + [vp] * 4
+        lib.rs_host_road_votes_sweep.argtypes = [vp] * 6 + [i32] * 4 + [vp, i32] + [vp] * 3
+        lib.rs_engine_fetch_vote_sweep_async.argtypes = [vp, i32] + [vp] * 5 + [vp, i32, C.POINTER(RsRoadVoteSweep)]
+        lib.rs_engine_fetch_vote_sweep_wait.argtypes = [vp]
+    if hasattr(lib, "rs_op_band_hist"):              # RS_ENGINE_LIB may name an older build
         lib.rs_op_band_hist.argtypes = [vp] * 3 + [i32] * 4 + [vp, vp]
         lib.rs_host_band_hist.argtypes = [vp] * 3 + [i32] * 4 + [vp]
         lib.rs_engine_fetch_band_hist_async.argtypes = [vp, i32] + [vp] * 5 + [C.POINTER(RsBandHist)]
@@ -582,6 +593,9 @@ class Engine:
         # road votes (rs_engine_fetch_votes_*): pinned tables, allocated on the first road_votes; batches that did not fit
         self._vote_struct: Optional[RsRoadVotes] = None
         self._vote_labels: List[int] = []
+        # the vote sweep (rs_engine_fetch_vote_sweep_*): pinned tables for 32 thresholds, allocated on the first road_votes_sweep
+        self._sweep_struct: Optional[RsRoadVoteSweep] = None
+        self._sweep_labels: Tuple[List[int], int] = ([], 0)
         self.vote_fallbacks = 0
         # band histograms (rs_engine_fetch_band_hist_*): one pinned table, allocated on the first band_hist; batches that did not fit
         self._band_struct: Optional[RsBandHist] = None
@@ -945,6 +959,69 @@ class Engine:
             out.append(row)
         return out
 
+    def road_votes_sweep(self, tiles_or_n, labels: Sequence[Sequence[Sequence[np.ndarray]]], thresholds, wait: bool = True):
+        """``road_votes`` for a list of 1 to 32 finite score thresholds at once (csrc/road_vote.h, THE SWEEP): labels are uploaded,
+        rasterised and counted once, ``road_vote_sweep_kernel`` forms the tables of every threshold, and only they travel.  Returns
+        per tile ``(Instances without masks, wscore (T, L_t, K), wfrac (T, L_t, K), pairs (T, L_t, K), label_area (L_t,))``; slice j
+        has the bits of ``road_votes`` at ``thresholds[j]`` (``raster_vote.sweep_slice`` gives it to ``reduce_votes``).  ``None``
+        when the batch does not fit the device pool, under the conditions of ``road_votes`` and counted in ``vote_fallbacks`` like
+        there: sweep that batch with ``raster_vote.vote_tables_host(..., thresholds=)``.  ``wait=False`` returns True once
+        everything is enqueued; ``road_votes_sweep_wait(n)`` then gives the result."""
+        from .raster_vote import sweep_thresholds
+        n = int(tiles_or_n) if np.isscalar(tiles_or_n) else int(tiles_or_n.shape[0])
+        thr = sweep_thresholds(thresholds)            # before the forward: a refused call enqueues nothing
+        packed = self._vote_label_tables(n, labels)
+        if packed is None:
+            return None
+        if not np.isscalar(tiles_or_n):
+            self.infer_device(self.upload_async(np.ascontiguousarray(tiles_or_n)), n)
+        self._sweep_labels = self._sweep_enqueue(n, packed, thr)
+        return self.road_votes_sweep_wait(n) if wait else True
+
+    def _sweep_enqueue(self, n: int, packed, thresholds) -> Tuple[List[int], int]:
+        """Enqueue the sweep of ``_vote_label_tables``' tables behind the last forward (and behind its fetch, when one is in flight);
+        returns (the labels per tile, the number of thresholds)."""
+        from .raster_vote import sweep_thresholds
+        thr = sweep_thresholds(thresholds)
+        flat, off, lens, inst_first, tile_first = packed
+        if self._fetch_pending is None:               # no fetch of this forward in flight: bring the detections (no masks) along
+            d = self._dets_struct(False)
+            d.masks = None
+            _check(self.lib, self.lib.rs_engine_fetch_async(self._h, n, C.byref(d)), "rs_engine_fetch_async")
+        K = self.spec.num_classes
+        if self._sweep_struct is None:
+            cells = self.max_batch * VOTE_SWEEP_MAX * EVAL_GT_CAP * K      # flat: the layout [n][T][cap][K] depends on the call's n and T
+            self._sweep_tables = {"wscore": self._pinned((cells,), np.float64), "wfrac": self._pinned((cells,), np.float64),
+                                  "pairs": self._pinned((cells,), np.int32),
+                                  "label_area": self._pinned((self.max_batch, EVAL_GT_CAP), np.int32)}
+            v = RsRoadVoteSweep()
+            for k, a in self._sweep_tables.items():
+                setattr(v, k, a.ctypes.data_as(C.POINTER(C.c_double if a.dtype == np.float64 else C.c_int32)))
+            self._sweep_struct = v
+        rc = self.lib.rs_engine_fetch_vote_sweep_async(self._h, n, flat.ctypes.data, off.ctypes.data, lens.ctypes.data, inst_first.ctypes.data,
+                                                       tile_first.ctypes.data, thr.ctypes.data, int(thr.size), C.byref(self._sweep_struct))
+        _check(self.lib, rc, "rs_engine_fetch_vote_sweep_async")   # the fit was checked above: any other code here is an error
+        return np.diff(tile_first).tolist(), int(thr.size)
+
+    def road_votes_sweep_wait(self, n: int, with_instances: bool = True, label_counts=None):
+        """The second half of ``road_votes_sweep(..., wait=False)``, as ``road_votes_wait`` is of ``road_votes``.  ``label_counts``:
+        what ``_sweep_enqueue`` returned for the batch the tables belong to, for a caller that has enqueued another since."""
+        _check(self.lib, self.lib.rs_engine_fetch_vote_sweep_wait(self._h), "rs_engine_fetch_vote_sweep_wait")
+        counts, T = self._sweep_labels if label_counts is None else label_counts
+        K = self.spec.num_classes
+        t = {k: a[:n * T * EVAL_GT_CAP * K].reshape(n, T, EVAL_GT_CAP, K) for k, a in self._sweep_tables.items() if k != "label_area"}
+        out = []
+        for i in range(n):
+            g = int(counts[i])
+            row = (t["wscore"][i, :, :g].copy(), t["wfrac"][i, :, :g].copy(), t["pairs"][i, :, :g].copy(),
+                   self._sweep_tables["label_area"][i, :g].copy())
+            if with_instances:
+                c = int(self._count[i])
+                row = (Instances((self.tile_h, self.tile_w), self._boxes[i, :c].copy(), self._scores[i, :c].copy(),
+                                 self._classes[i, :c].astype(np.int64), None, None),) + row
+            out.append(row)
+        return out
+
     def band_hist(self, tiles_or_n, labels: Sequence[Sequence[Sequence[np.ndarray]]], wait: bool = True):
         """The band histograms under the road labels of a batch, counted on the device (csrc/band_hist.h): ``tiles_or_n`` and ``labels``
         as for ``road_votes``.  The labels are rasterised on the GPU exactly as ``raster_vote.label_rasters`` does on the host and
@@ -1225,7 +1302,8 @@ class LanePipeline:
         """Enqueue the outstanding mask-head phase; after this every submitted batch is fully enqueued."""
         self._finish_pending()
 
-    def run(self, batches, labels=None, vote_threshold: float = 0.0, band_stats: bool = False, road_votes: bool = True) -> "Iterator[List[Instances]]":
+    def run(self, batches, labels=None, vote_threshold: float = 0.0, band_stats: bool = False, road_votes: bool = True,
+            vote_sweep=None) -> "Iterator[List[Instances]]":
         """Stream host batches ((n,h,w,c) uint8 arrays) through the lanes and yield their detections in order.  Uploads go
         through pinned staging on the lane's stream, every batch's results come back on its lane's copy stream behind an event,
         and the generator runs ``lanes`` batches ahead of what it yields, so host-side collection overlaps the GPU.  Independent lanes:
@@ -1239,17 +1317,36 @@ class LanePipeline:
         ``band_stats=True`` (needs ``labels``): every yielded ``Instances`` also carries ``band_hist``, the (L_t, C, 256) histograms of
         its tile's labels (``Engine.band_hist``), enqueued behind the batch's other fetches on its lane; a batch that does not fit gets
         them from ``band_stats.band_hist_host`` on its own host tiles, which the pipeline keeps until the batch is yielded, counted in
-        ``band_fallbacks``.  ``road_votes=False`` leaves the vote out: labels then serve the histograms alone."""
+        ``band_fallbacks``.  ``road_votes=False`` leaves the vote out: labels then serve the histograms alone.
+        ``vote_sweep=thresholds`` (needs ``labels``; 1 to 32 finite values): every yielded ``Instances`` also carries
+        ``road_vote_sweep`` = (wscore (T, L, K), wfrac, pairs, label_area) of its tile (``Engine.road_votes_sweep``), swept on the host
+        (``vote_tables_host(..., thresholds=)``) for a batch that does not fit, counted in ``vote_fallbacks``.  With ``road_votes``
+        as well the pipeline runs the sweep alone, ``vote_threshold`` appended as its last entry (so at most 31 thresholds then), and
+        sets ``road_votes`` from that slice -- slice j of a sweep has the bits of the vote at ``thresholds[j]`` (csrc/road_vote.h) --
+        so the rasteriser and the pair counts run once per batch, not twice."""
         if band_stats and labels is None:
             raise ValueError("band_stats needs the road labels of every batch")
+        if vote_sweep is not None and labels is None:
+            raise ValueError("vote_sweep needs the road labels of every batch")
         want_votes = labels is not None and bool(road_votes)
+        sweep_all, sweep_T = None, 0                # the list the sweep runs on (vote_threshold behind the caller's), the caller's length
+        if vote_sweep is not None:
+            from .raster_vote import sweep_thresholds
+            sweep_all = sweep_thresholds(vote_sweep)
+            sweep_T = int(sweep_all.size)
+            if want_votes:
+                if not np.isfinite(vote_threshold):
+                    raise ValueError(f"vote threshold {vote_threshold!r} is not finite")
+                if sweep_T >= VOTE_SWEEP_MAX:
+                    raise ValueError(f"vote_sweep with road_votes takes at most {VOTE_SWEEP_MAX - 1} thresholds: the vote's own is appended")
+                sweep_all = np.append(sweep_all, float(vote_threshold))
         L = len(self.engines)
         lab_it = iter(labels) if labels is not None else None
         lab_of: Dict[int, Any] = {}                 # lane -> the labels of the batch it was given last
         vote_of: Dict[int, Any] = {}                # lane -> ("device", labels per tile) / ("host", labels) of the fetch in flight
         tiles_of: Dict[int, Any] = {}               # lane -> the host tiles of the batch it was given last (band_stats: the host route reads them)
         band_of: Dict[int, Any] = {}                # lane -> ("device", labels per tile) / ("host", labels, tiles) of the histograms in flight
-        if want_votes:
+        if want_votes or sweep_all is not None:
             self.vote_fallbacks = 0
         if band_stats:
             self.band_fallbacks = 0
@@ -1265,7 +1362,7 @@ class LanePipeline:
 
         def fetch(lane: int, n: int) -> None:
             eng = self.engines[lane]
-            if not want_votes:
+            if not want_votes and sweep_all is None:
                 self._fetch_async(eng, n)
                 if band_stats:
                     fetch_band(lane, n)
@@ -1275,6 +1372,9 @@ class LanePipeline:
                 self.vote_fallbacks += 1
                 self._fetch_async(eng, n, masks=True)
                 vote_of[lane] = ("host", lab_of[lane])
+            elif sweep_all is not None:
+                self._fetch_async(eng, n)
+                vote_of[lane] = ("device", eng._sweep_enqueue(n, packed, sweep_all))
             else:
                 self._fetch_async(eng, n)
                 vote_of[lane] = ("device", eng._vote_enqueue(n, packed, vote_threshold))
@@ -1295,10 +1395,20 @@ class LanePipeline:
             return res
 
         def voted(lane: int, res: List[Instances]) -> List[Instances]:
-            if not want_votes:
+            if not want_votes and sweep_all is None:
                 return with_band(lane, res)
             from . import raster_vote
             kind, what = vote_of.pop(lane)
+            if sweep_all is not None:
+                if kind == "device":
+                    rows = self.engines[lane].road_votes_sweep_wait(len(res), False, what)
+                else:
+                    rows = raster_vote.vote_tables_host(res, what, self.engines[lane].spec.num_classes, thresholds=sweep_all)
+                for inst, row in zip(res, rows):
+                    if want_votes:                  # the appended slice is the vote at vote_threshold, bit for bit
+                        inst.road_votes = raster_vote.sweep_slice(row, sweep_T)
+                    inst.road_vote_sweep = (row[0][:sweep_T], row[1][:sweep_T], row[2][:sweep_T], row[3])
+                return with_band(lane, res)
             if kind == "device":
                 rows = self.engines[lane].road_votes_wait(len(res), False, what)
             else:
@@ -1480,7 +1590,7 @@ class Predictor:
         return out
 
     def predict_stream(self, batches, labels=None, vote_threshold: float = 0.0, band_stats: bool = False,
-                       road_votes: bool = True) -> "Iterator[List[Dict[str, Instances]]]":
+                       road_votes: bool = True, vote_sweep=None) -> "Iterator[List[Dict[str, Instances]]]":
         """Streaming form for a whole tileset: ``batches`` is an iterator of image lists (each at most ``max_batch`` images);
         yields one result list per batch, in order.  Consecutive batches of one tile shape flow through ONE
         ``LanePipeline.run`` generator, so the upload, forward and result copy of batch k+1 overlap batch k (calling
@@ -1489,9 +1599,12 @@ class Predictor:
         (``LanePipeline.run``); every yielded ``Instances`` then carries ``road_votes``, and ``vote_fallbacks`` counts the batches
         of the stream that were voted on the host.  Labels need batches of one tile shape.  ``band_stats=True``: every yielded
         ``Instances`` also carries ``band_hist`` (``LanePipeline.run``), ``band_fallbacks`` counts the batches whose histograms the
-        host formed; ``road_votes=False`` leaves the vote out and the labels serve the histograms alone."""
+        host formed; ``road_votes=False`` leaves the vote out and the labels serve the histograms alone.  ``vote_sweep=thresholds``:
+        every yielded ``Instances`` also carries ``road_vote_sweep``, the vote tables of every threshold (``LanePipeline.run``)."""
         if band_stats and labels is None:
             raise ValueError("band_stats needs the road labels of every batch")
+        if vote_sweep is not None and labels is None:
+            raise ValueError("vote_sweep needs the road labels of every batch")
         it = iter(batches)
         lab_src = iter(labels) if labels is not None else None
         lab_q: List[Any] = []            # labels of the batches handed to the running pipeline and not yet taken by it
@@ -1535,7 +1648,7 @@ class Predictor:
             before = pipe.vote_fallbacks if lab_src is None else 0
             band_before = 0
             for res in pipe.run(run_of_shape(), labels=taken_labels() if lab_src is not None else None, vote_threshold=vote_threshold,
-                                band_stats=band_stats, road_votes=road_votes):
+                                band_stats=band_stats, road_votes=road_votes, vote_sweep=vote_sweep):
                 self.vote_fallbacks += pipe.vote_fallbacks - before
                 before = pipe.vote_fallbacks
                 self.band_fallbacks += pipe.band_fallbacks - band_before
@@ -1556,6 +1669,7 @@ DGRAD_MODES = ("f32", "split")   # rs_trainer_set_dgrad_mode 0 / 1
 FWD_MODES = ("f32", "split")     # rs_trainer_set_fwd_mode 0 / 1
 RS_EVAL_DOES_NOT_FIT = 2       # include/rs_engine.h: rs_engine_fetch_eval_async, the batch's ground truth exceeds the device pool
 EVAL_GT_CAP = 128              # RS_EVAL_GT_CAP: ground truths per tile, and the row length of the count tables
+VOTE_SWEEP_MAX = 32            # RS_VOTE_SWEEP_MAX: thresholds per vote sweep
 RS_POLYGONS_DO_NOT_FIT = 1     # include/rs_engine.h: rs_trainer_set_polygons, the batch's polygons exceed the device pool
 FREEZE_AT_VALUES = (0, 1, 2)   # MODEL.BACKBONE.FREEZE_AT a trainer implements (rs_train_options.freeze_at)
 

@@ -174,6 +174,15 @@ def build_parser() -> argparse.ArgumentParser:
                          "category): the road labels of --road-votes (which it does not need), their pixels counted into histograms on the GPU "
                          "behind every batch's forward (csrc/band_hist.h); a batch beyond the device pool is counted on the host.  Needs "
                          "datasets of one tile shape.  Every other output is unchanged")
+    ap.add_argument("--road-metrics", action="store_true",
+                    help="after the last dataset also write road_metrics.json, the reference's final metrics (road_metrics.py: the balanced F1 of "
+                         "the per-road cover classes at the best score threshold, per dataset and zone, accuracy, the sweep on the difference of "
+                         "indices, the baseline): the road labels of --road-votes (which it does not need) and their categories, the vote of "
+                         "every threshold formed in one pass on the GPU behind every batch's forward (csrc/road_vote.h, the sweep).  Needs "
+                         "categories in the COCO files and datasets of one tile shape.  Every other output is unchanged")
+    ap.add_argument("--metric-thresholds", default=None,
+                    help="comma-separated score thresholds of --road-metrics, at most 32 (31 together with --road-votes); default: "
+                         "np.arange(0, 1., 0.05), the reference's 20")
     ap.add_argument("--vote-threshold", type=float, default=None,
                     help="score a detection needs to vote (default: 'threshold' of the YAML's 'determine_class.py' section where it exists, else 0)")
     return ap
@@ -192,6 +201,20 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     vote_thr = float(args.vote_threshold if args.vote_threshold is not None else (whole_cfg.get("determine_class.py") or {}).get("threshold", 0))
     votes: Dict[str, Any] = {"labels": None, "by_file": {}}      # --road-votes / --road-stats: the running dataset's labels per batch, its vote tables per tile
     band_by_file: Dict[str, Any] = {}                            # --road-stats: the running dataset's histograms per tile
+    sweep_by_file: Dict[str, Any] = {}                           # --road-metrics: the running dataset's sweep tables per tile
+    metric_sets: Dict[str, Any] = {}                             # --road-metrics, rank 0: dataset -> (road ids per tile, sweep tables per tile)
+    metric_batches = {"host": 0, "of": 0}
+    metric_thr = None
+    if args.road_metrics:
+        from .road_metrics import REFERENCE_THRESHOLDS
+        try:
+            metric_thr = (np.asarray([float(v) for v in args.metric_thresholds.split(",")], np.float64) if args.metric_thresholds
+                          else REFERENCE_THRESHOLDS)
+        except ValueError:
+            raise SystemExit(f"--metric-thresholds: {args.metric_thresholds!r} is not a comma-separated list of numbers")
+        most = 31 if args.road_votes else 32
+        if not 1 <= metric_thr.size <= most or not np.isfinite(metric_thr).all():
+            raise SystemExit(f"--road-metrics takes 1 to {most} finite thresholds{' with --road-votes' if args.road_votes else ''}, got {metric_thr.size}")
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -214,6 +237,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         with open(path) as f:
             coco[name] = json.load(f)
     cats = sorted({c["id"] for d in coco.values() for c in d.get("categories", [])})
+    if args.road_metrics and not all(any(c.get("name") for c in d.get("categories", [])) for d in coco.values()):
+        raise SystemExit("--road-metrics needs the categories of the road labels: a COCO file names none")
     thr = float(cfg.get("score_lower_threshold", 0.05))
     rdp_cfg = cfg.get("rdp_simplification", {}) or {}
 
@@ -279,7 +304,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             it = predictor.predict_stream(batches)
         else:
             it = predictor.predict_stream(batches, labels=iter(votes["labels"]), vote_threshold=vote_thr, band_stats=args.road_stats,
-                                          road_votes=args.road_votes)
+                                          road_votes=args.road_votes, vote_sweep=metric_thr)
         while True:
             t = time.perf_counter()
             out = next(it, None)
@@ -302,6 +327,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 votes["by_file"][e["file_name"]] = o["instances"].road_votes
             if votes["labels"] is not None and args.road_stats:
                 band_by_file[e["file_name"]] = o["instances"].band_hist
+            if votes["labels"] is not None and args.road_metrics:
+                sweep_by_file[e["file_name"]] = o["instances"].road_vote_sweep
             carried = getattr(o["instances"], "_polygons", None)
             if carried is not None:
                 fell_back["instances"] += int(len(carried.flagged))
@@ -358,11 +385,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                         return
                     yield b
             source = pool_source if pool is not None else None
-        if args.road_votes or args.road_stats:
+        if args.road_votes or args.road_stats or args.road_metrics:
             lo, hi = shard_range(len(images), rank, world)
             by_image = road_labels(d, dataset)
             votes["by_file"] = {}
             band_by_file.clear()
+            sweep_by_file.clear()
             votes["labels"] = [[by_image.get(e["id"], ([], []))[1] for e in images[i:min(i + args.batch, hi)]] for i in range(lo, hi, args.batch)]
         try:
             try:
@@ -441,6 +469,20 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 log.info("%s: band statistics of %d roads%s in %s_road_stats.json; %d of %d batches were counted on the host", dataset, len(by_road),
                          f" and {len(doc['covers'])} cover types" if covers else "", dataset, sum(fb for _, fb in parts_h),
                          sum(len(range(*shard_range(len(images), r, world), args.batch)) for r in range(world)))
+        if args.road_metrics:
+            # as --road-votes: every rank's per-(tile, label) tables of every threshold travel to rank 0 in tile order, which keeps them
+            # until the last dataset: the file does not depend on the world size
+            mine_s = [(by_image.get(e["id"], ([], []))[0], sweep_by_file[e["file_name"]][:3]) for e in images[lo:hi]]
+            parts_s: List[Any] = [(mine_s, predictor.vote_fallbacks)]
+            if world > 1:
+                import torch.distributed as dist
+                parts_s = [None] * world if rank == 0 else None
+                dist.gather_object((mine_s, predictor.vote_fallbacks), parts_s, dst=0)
+            if rank == 0:
+                rows_s = [t for part, _ in parts_s for t in part]
+                metric_sets[dataset] = ([ids for ids, _ in rows_s], [t for _, t in rows_s], road_covers(d))
+                metric_batches["host"] += sum(fb for _, fb in parts_s)
+                metric_batches["of"] += sum(len(range(*shard_range(len(images), r, world), args.batch)) for r in range(world))
         votes["labels"] = None
         # Every rank writes the rows of ITS block of tiles into its own GeoPackage shard (rank 0: the output file itself); rank 0 then appends the
         # other ranks' shards in rank order = tile order with SQLite ATTACH -- no row travels between processes ("each rank ...
@@ -508,6 +550,27 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 png = os.path.join(sub, f"{dataset}_det_{os.path.splitext(os.path.basename(e['file_name']))[0]}.png")
                 draw_instances(rgb, inst.pred_boxes, inst.pred_classes, inst.scores, inst.pred_masks, names or None).save(png)
             log.info("%s: %d tagged sample images -> %s/", dataset, min(len(images), args.tagged_samples), sub)
+    if args.road_metrics and rank == 0:
+        from . import road_metrics
+        from .raster_vote import CLASS_NAMES
+        K = spec.num_classes
+        by_id = {c["id"]: c.get("name") for d in coco.values() for c in d.get("categories", [])}
+        names = {i: by_id.get(cid) for i, cid in enumerate(cats)}
+        if len(names) != K or not all(names.values()):
+            names = dict(CLASS_NAMES) if K == len(CLASS_NAMES) else {i: str(i) for i in range(K)}
+        classes = [names[i] for i in range(K)]
+        categories: Dict[Any, str] = {}
+        for _, _, covers in metric_sets.values():            # a road's category: its first label's, in dataset order
+            for rid, c in covers.items():
+                categories.setdefault(rid, c)
+        asked = str((whole_cfg.get("final_metrics.py") or {}).get("baseline", ""))
+        base_cls = next((c for c in classes if c in asked), "artificial")
+        doc = road_metrics.report({k: v[:2] for k, v in metric_sets.items()}, categories, classes, metric_thr, names, base_cls)
+        with open("road_metrics.json", "w") as f:
+            f.write(json.dumps(doc))
+        log.info("road metrics: %d thresholds on %d roads of %d datasets -> best threshold %g (balanced f1 %.4f on %s) in road_metrics.json; "
+                 "%d of %d batches were voted on the host", len(doc["thresholds"]), len(categories), len(metric_sets), doc["best_threshold"],
+                 doc["sweep"][doc["best_index"]]["global"]["f1b"], doc["sweep_on"], metric_batches["host"], metric_batches["of"])
     _close_pools(pools)
     if world > 1:
         import torch.distributed as dist

@@ -15,7 +15,10 @@ oracle of its test) is ``oracle/host_tail_oracle.py::overlap_counts``.
 The streamed form (second half of this module) runs the whole vote behind the engine's forward: road labels as polygons in
 tile pixels, rasterised and counted on the device, the per-(tile, label, class) sums formed by ``road_vote_kernel`` (csrc/road_vote.h), and
 only those tables travel (``Engine.road_votes``, ``LanePipeline.run(..., labels=...)``).  ``vote_tables_host`` is the numpy route to the
-same tables from fetched masks, ``reduce_votes`` the vectorised step from the tables of all tiles to the road table."""
+same tables from fetched masks, ``reduce_votes`` the vectorised step from the tables of all tiles to the road table.  The sweep
+(``Engine.road_votes_sweep``, ``road_votes_sweep_host / _device``, ``thresholds=`` of the numpy route) forms the tables of up to 32 score
+thresholds in one pass, slice j with the bits of the tables at ``thresholds[j]``; ``road_metrics.py`` turns them into the reference's
+final metrics."""
 from __future__ import annotations
 
 import ctypes as C
@@ -134,11 +137,23 @@ _POP8 = np.array([bin(i).count("1") for i in range(256)], np.int32)
 TABLE_KEYS = ("det_scores", "det_classes", "det_count", "tile_first", "inter", "gt_area")
 
 
+def sweep_thresholds(thresholds) -> np.ndarray:
+    """A threshold list as the sweep takes it (csrc/road_vote.h, THE SWEEP): 1 to 32 finite float64 values, in any order."""
+    thr = np.ascontiguousarray(thresholds, np.float64).reshape(-1)
+    if not 1 <= thr.size <= 32 or not np.isfinite(thr).all():
+        raise ValueError(f"a vote sweep takes 1 to 32 finite thresholds, got {thr.tolist()!r}")
+    return thr
+
+
 def votes_from_counts(inter: np.ndarray, label_area: np.ndarray, scores: np.ndarray, classes: np.ndarray, num_classes: int,
-                      threshold: float = 0.0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                      threshold: float = 0.0, thresholds=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """The rule of csrc/road_vote.h on one tile's counts in numpy: inter (D, L) and label_area (L,) pixel counts, scores / classes
     (D,) -> wscore, wfrac (L, K) float64 and pairs (L, K) int32.  The detections are walked in ascending order, so every cell is the
-    sequential float64 sum the kernel forms."""
+    sequential float64 sum the kernel forms.  ``thresholds=`` (a list, ``threshold`` is then not read): the sweep, tables of shape
+    (T, L, K) whose slice j is this function at ``thresholds[j]``."""
+    if thresholds is not None:
+        per = [votes_from_counts(inter, label_area, scores, classes, num_classes, float(t)) for t in sweep_thresholds(thresholds)]
+        return tuple(np.stack([p[i] for p in per]) for i in range(3))
     L, K = int(label_area.shape[0]), int(num_classes)
     ws, wa, pairs = np.zeros((L, K)), np.zeros((L, K)), np.zeros((L, K), np.int32)
     area = np.asarray(label_area, np.int64)
@@ -158,11 +173,12 @@ def votes_from_counts(inter: np.ndarray, label_area: np.ndarray, scores: np.ndar
 
 
 def vote_tables_host(instances: Sequence, labels: Sequence[Sequence[Sequence[np.ndarray]]], num_classes: int,
-                     threshold: float = 0.0) -> List[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
+                     threshold: float = 0.0, thresholds=None) -> List[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
     """The numpy route to the tables ``Engine.road_votes`` gives, from fetched masks: per tile, ``label_rasters`` of labels[tile] (lists
     of rings in tile pixels), popcounts of the packed label AND the packed detection masks of instances[tile] (``Instances`` with
     masks), then ``votes_from_counts``.  Returns per tile ``(wscore (L, K), wfrac (L, K), pairs (L, K), label_area (L,))``.  The
-    fallback of a batch that does not fit the device pool."""
+    fallback of a batch that does not fit the device pool.  ``thresholds=``: the sweep (``Engine.road_votes_sweep``), the three
+    tables then have the shape (T, L, K); rasters and counts are formed once."""
     if len(instances) != len(labels):
         raise ValueError(f"{len(labels)} label lists for {len(instances)} tiles")
     out = []
@@ -176,7 +192,7 @@ def vote_tables_host(instances: Sequence, labels: Sequence[Sequence[Sequence[np.
         for g in range(len(labs)):
             inter[:, g] = _POP8[det & lab[g][None]].sum(axis=(1, 2), dtype=np.int64)
         area = _POP8[lab].sum(axis=(1, 2), dtype=np.int64).astype(np.int32) if len(labs) else np.zeros(0, np.int32)
-        out.append(votes_from_counts(inter, area, inst.scores, inst.pred_classes, num_classes, threshold) + (area,))
+        out.append(votes_from_counts(inter, area, inst.scores, inst.pred_classes, num_classes, threshold, thresholds) + (area,))
     return out
 
 
@@ -213,6 +229,49 @@ def road_votes_host(b: Dict[str, np.ndarray], num_classes: int, threshold: float
 def road_votes_device(b: Dict[str, np.ndarray], num_classes: int, threshold: float = 0.0, prefill: float = 0.0):
     """``rs_op_road_votes`` on the same dict, uploaded through torch: the kernel's tables."""
     return _vote_call("rs_op_road_votes", b, num_classes, threshold, prefill, True)
+
+
+def _vote_sweep_call(entry: str, b: Dict[str, np.ndarray], num_classes: int, thresholds, prefill: float, device: bool):
+    from .engine import _check, load_library
+    lib = load_library()
+    n, slots = b["det_scores"].shape
+    cap = int(b["gt_area"].shape[1])
+    thr = np.ascontiguousarray(thresholds, np.float64).reshape(-1)      # unchecked: the entry refuses a bad list itself
+    T = int(thr.size)
+    tabs = [np.ascontiguousarray(b["det_scores"], np.float32), np.ascontiguousarray(b["det_classes"], np.int32),
+            np.ascontiguousarray(b["det_count"], np.int32), np.ascontiguousarray(b["tile_first"], np.int32),
+            np.ascontiguousarray(b["inter"], np.int32), np.ascontiguousarray(b["gt_area"], np.int32)]
+    shape = (n, max(T, 1), cap, num_classes)
+    outs = [np.full(shape, prefill, np.float64), np.full(shape, prefill, np.float64), np.full(shape, int(prefill), np.int32)]
+    if not device:
+        _check(lib, lib.rs_host_road_votes_sweep(*[a.ctypes.data for a in tabs], n, num_classes, slots, cap, thr.ctypes.data, T,
+                                                 *[a.ctypes.data for a in outs]), entry)
+        return tuple(outs)
+    import torch
+    dev = [torch.from_numpy(a).cuda() for a in tabs + outs]
+    torch.cuda.synchronize()
+    _check(lib, lib.rs_op_road_votes_sweep(*[a.data_ptr() for a in dev[:6]], n, num_classes, slots, cap, thr.ctypes.data, T,
+                                           *[a.data_ptr() for a in dev[6:]], None), entry)
+    torch.cuda.synchronize()
+    return tuple(a.cpu().numpy() for a in dev[6:])
+
+
+def road_votes_sweep_host(b: Dict[str, np.ndarray], num_classes: int, thresholds, prefill: float = 0.0):
+    """``rs_host_road_votes_sweep`` on the dict of ``road_votes_host`` and a threshold list (1 to 32 finite values) -> wscore, wfrac
+    (n, T, gt_cap, K) float64, pairs (n, T, gt_cap, K) int32; slice ``[:, j]`` has the bits of ``road_votes_host`` at
+    ``thresholds[j]``.  ``prefill`` as there.  Needs no device."""
+    return _vote_sweep_call("rs_host_road_votes_sweep", b, num_classes, thresholds, prefill, False)
+
+
+def road_votes_sweep_device(b: Dict[str, np.ndarray], num_classes: int, thresholds, prefill: float = 0.0):
+    """``rs_op_road_votes_sweep`` on the same dict, uploaded through torch: ``road_vote_sweep_kernel``'s tables."""
+    return _vote_sweep_call("rs_op_road_votes_sweep", b, num_classes, thresholds, prefill, True)
+
+
+def sweep_slice(row: Sequence[np.ndarray], j: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """Slice j of one tile's sweep tables ``(wscore (T, L, K), wfrac, pairs, label_area)``: the tile's single-threshold tables at
+    ``thresholds[j]``, as ``reduce_votes`` takes them."""
+    return row[0][j], row[1][j], row[2][j], row[3]
 
 
 def reduce_votes(tables: Sequence[Sequence[np.ndarray]], road_ids: Sequence[Sequence], class_names: Dict[int, str] = CLASS_NAMES,
