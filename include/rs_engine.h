@@ -1065,6 +1065,67 @@ int rs_engine_fetch_vote_sweep_async(rs_engine* e, int n, const double* polys, c
                                      rs_road_vote_sweep* sweep_host);
 int rs_engine_fetch_vote_sweep_wait(rs_engine* e);
 
+/* ------------------------------------------------------------------ the vote on polygon areas (csrc/poly_overlap.h)
+ * An opt-in geometry of the same vote: the reference overlays the vector road labels with the POLYGONS that make_detections wrote
+ * (after Ramer-Douglas-Peucker) and weights a pair by round(area(label ∩ detection) / area(label), 2), both areas on polygons.  The
+ * entries below compute that weight from the device polygoniser's vertex tables and the labels' float64 rings, exactly as far as
+ * float64 allows: csrc/poly_overlap.h states the closed-form sum over pairs of edges, its summation order (which the host restatement
+ * repeats bit for bit), the translation, and the error bound po_bound on the computed area.  A detection's first ring per polygon is
+ * its exterior, the rest are holes, an instance of several polygons is their sum.  EVERY LABEL RING IS AN EXTERIOR and a label's
+ * rings are taken as simple and pairwise interior-disjoint (area(label) = the sum of |shoelace| / 2 over its rings); the pixel
+ * geometry above takes the union of a label's rings instead.  This is not checked; overlapping label rings and labels with holes are
+ * not covered.  Area ratios do not change under the tile's affine map, so georeferencing does not enter.
+ *
+ * Tables of rs_op_polygon_overlaps (device pointers, clears its outputs, enqueues on `stream`, does not wait) and
+ * rs_host_polygon_overlaps (host pointers, no device): header [n_tiles * slots][RS_POLY_HDR], poly_ring_count, ring_len, xy as
+ * rs_op_polygonize_crops writes them (instance = tile * slots + slot); det_count [n_tiles]; the labels as the packed pool holds
+ * them: tile_first [n_tiles + 1] (first label of every tile, at most gt_cap are read), inst_first [labels + 1] (first ring of every
+ * label), poly_off [rings] int32 (doubles into polys), poly_len [rings] (doubles), polys float64 tile pixels.  Out: frac
+ * [n_tiles][slots][gt_cap] double (the rounded weight; 0 for pairs whose boxes do not overlap, for slots at or past det_count, for
+ * labels past the tile's own or of area 0), label_area [n_tiles][gt_cap] double, flagged [n_tiles] int32 = instances among the
+ * tile's slots in use that the polygoniser flagged: they have no rows, their pairs are 0, and the caller redoes such a tile on the
+ * host after vectorising them there.  raw_areas != 0 leaves the last step out: `frac` then holds the computed areas A themselves,
+ * which is how the tests hold them to po_bound.  Both refuse, before anything is touched, a null table, n_tiles < 1, slots or gt_cap < 1
+ * (RS_ERR_ARG); slots > 1024 or gt_cap > RS_EVAL_GT_CAP (RS_ERR_UNSUPPORTED).
+ *
+ * rs_op_road_votes_area_sweep / rs_host_road_votes_area_sweep: rs_op_road_votes_sweep with `frac` in place of inter / gt_area -- the
+ * same walk over the slots (csrc/road_vote.h, rv_pair_area: class test, frac > 0.05, score >= threshold, the three accumulators, slots
+ * ascending), the same tables [n_tiles][n_thresholds][gt_cap][num_classes], the same refusals and codes.  The single vote is
+ * n_thresholds = 1. */
+int rs_op_polygon_overlaps(const int32_t* header, const int32_t* poly_ring_count, const int32_t* ring_len, const int16_t* xy,
+                           const int32_t* det_count, const int32_t* tile_first, const int32_t* inst_first, const int32_t* poly_off,
+                           const int32_t* poly_len, const double* polys, int n_tiles, int slots, int gt_cap, int raw_areas, double* frac,
+                           double* label_area, int32_t* flagged, void* stream);
+int rs_host_polygon_overlaps(const int32_t* header, const int32_t* poly_ring_count, const int32_t* ring_len, const int16_t* xy,
+                             const int32_t* det_count, const int32_t* tile_first, const int32_t* inst_first, const int32_t* poly_off,
+                             const int32_t* poly_len, const double* polys, int n_tiles, int slots, int gt_cap, int raw_areas, double* frac,
+                             double* label_area, int32_t* flagged);
+int rs_op_road_votes_area_sweep(const float* det_scores, const int32_t* det_classes, const int32_t* det_count, const int32_t* tile_first,
+                                const double* frac, int n_tiles, int num_classes, int slots, int gt_cap, const double* thresholds,
+                                int n_thresholds, double* wscore, double* wfrac, int32_t* pairs, void* stream);
+int rs_host_road_votes_area_sweep(const float* det_scores, const int32_t* det_classes, const int32_t* det_count, const int32_t* tile_first,
+                                  const double* frac, int n_tiles, int num_classes, int slots, int gt_cap, const double* thresholds,
+                                  int n_thresholds, double* wscore, double* wfrac, int32_t* pairs);
+
+/* The same behind the engine's last forward: an add-on like rs_engine_fetch_vote_sweep_async, which must FOLLOW an
+ * rs_engine_fetch_polygons_async of the same forward and batch, because it reads the vertex tables that fetch left on the device
+ * (otherwise RS_ERR_ARG, nothing enqueued).  On the copy stream it enqueues the label upload, the overlap kernel, the area sweep and
+ * the copies of the three vote tables, label_area (double) and flagged.  Neither the rasteriser nor the pair counts run.  The same
+ * label pool and the same RS_EVAL_DOES_NOT_FIT conditions as the other add-ons; its device tables are allocated on the first call
+ * (the sweep's tables are shared with rs_engine_fetch_vote_sweep_async), an engine that never calls it allocates nothing and its
+ * stages and tensors are unchanged.  A tile with flagged[t] > 0 has zero weights for the flagged instances: redo it on the host. */
+typedef struct rs_road_votes_poly {
+  double* wscore;       /* [n][T][RS_EVAL_GT_CAP][K] */
+  double* wfrac;        /* [n][T][RS_EVAL_GT_CAP][K] */
+  int32_t* pairs;       /* [n][T][RS_EVAL_GT_CAP][K] */
+  double* label_area;   /* [n][RS_EVAL_GT_CAP] */
+  int32_t* flagged;     /* [n] */
+} rs_road_votes_poly;
+int rs_engine_fetch_votes_poly_async(rs_engine* e, int n, const double* polys, const int64_t* poly_off, const int32_t* poly_len,
+                                     const int32_t* inst_first, const int32_t* tile_first, const double* thresholds, int n_thresholds,
+                                     rs_road_votes_poly* votes_host);
+int rs_engine_fetch_votes_poly_wait(rs_engine* e);
+
 /* ------------------------------------------------------------------ band histograms under the road labels (csrc/band_hist.h)
  * The reference's second answer for a road's cover is statistical: scripts/statistical_analysis collects, per road, the pixels of
  * every band under the road's polygon over all tiles the road touches, drops the nodata pixels (without a nodata value in the TIFF:

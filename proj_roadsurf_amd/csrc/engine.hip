@@ -11,6 +11,7 @@
 #include "polygon_pool.h"
 #include "train.h"
 #include "val_ap.h"
+#include "poly_vote.h"
 
 // ------------------------------------------------------------------------------------- errors
 static thread_local char g_err[1024] = "";
@@ -1238,6 +1239,14 @@ int rs_engine::ensure_vote_sweep_buffers() {
   return alloc((void**)&sweep_pairs, sweep_cells * 4); // last: its presence says that all of the above exists
 }
 
+int rs_engine::ensure_poly_vote_buffers() {
+  if (pvote_flagged) return RS_OK;
+  int rc;
+  if ((rc = alloc((void**)&pvote_frac, (size_t)max_batch * D * RS_EVAL_GT_CAP * 8))) return rc;
+  if ((rc = alloc((void**)&pvote_area, (size_t)max_batch * RS_EVAL_GT_CAP * 8))) return rc;
+  return alloc((void**)&pvote_flagged, (size_t)max_batch * 4);   // last: its presence says that all of the above exists
+}
+
 int rs_engine::ensure_band_buffers() {
   if (band_hist_dev) return RS_OK;
   RS_HIP(hipEventCreateWithFlags(&ev_band_tiles, hipEventDisableTiming));
@@ -1574,6 +1583,7 @@ int rs_engine_fetch_polygons_async(rs_engine* e, int n, rs_dets* o, rs_polygons*
   if ((rc = e->begin_fetch(&s))) return rc;
   if ((rc = e->launch_crops(n, s))) return rc;
   if ((rc = e->launch_polygons(n, rdp_epsilon, s))) return rc;
+  e->poly_forward = e->forward_index; e->poly_tiles = n;      // what rs_engine_fetch_votes_poly_async may read
   if ((rc = e->enqueue_dets(o, n, s, false))) return rc;
   if ((rc = e->enqueue_crop_table(c, n, s))) return rc;
   RS_HIP(hipMemcpyAsync(g->header, e->poly.header, (size_t)n * e->D * PG_HDR * 4, hipMemcpyDeviceToHost, s));
@@ -1781,6 +1791,63 @@ int rs_engine_fetch_vote_sweep_async(rs_engine* e, int n, const double* polys, c
 
 int rs_engine_fetch_vote_sweep_wait(rs_engine* e) { return rs_engine_fetch_wait(e); }
 
+// The vote on polygon areas (poly_overlap.h): the labels' rings against the vertex tables that rs_engine_fetch_polygons_async of THIS
+// forward left on the device.  An add-on like the sweep, but neither the rasteriser nor the pair counts run: label upload, overlap
+// kernel, the area sweep and five small copies.  The sweep's device tables are shared with rs_engine_fetch_vote_sweep_async (both
+// copy them out behind their own kernel on the one copy stream).
+int rs_engine_fetch_votes_poly_async(rs_engine* e, int n, const double* polys, const int64_t* poly_off, const int32_t* poly_len,
+                                     const int32_t* inst_first, const int32_t* tile_first, const double* thresholds, int n_thresholds,
+                                     rs_road_votes_poly* v) {
+  RS_CHECK(e && v && v->wscore && v->wfrac && v->pairs && v->label_area && v->flagged && n >= 1 && n <= e->max_batch, RS_ERR_ARG,
+           "rs_engine_fetch_votes_poly_async: bad argument");
+  RS_CHECK(thresholds && n_thresholds >= 1 && n_thresholds <= RS_VOTE_SWEEP_MAX, RS_ERR_ARG,
+           "rs_engine_fetch_votes_poly_async: %d thresholds outside [1, %d], or a null list", n_thresholds, RS_VOTE_SWEEP_MAX);
+  for (int j = 0; j < n_thresholds; ++j)
+    RS_CHECK(thresholds[j] - thresholds[j] == 0.0, RS_ERR_ARG, "rs_engine_fetch_votes_poly_async: threshold %d is not finite", j);
+  RS_CHECK(e->poly_ready && e->poly_forward == e->forward_index && e->poly_tiles == n, RS_ERR_ARG,
+           "rs_engine_fetch_votes_poly_async must follow rs_engine_fetch_polygons_async of the same forward and batch");
+  { int rc = rs_engine_eval_fits(e, n, poly_off, poly_len, inst_first, tile_first); if (rc) return rc; }
+  if (e->D > RV_MAX_SLOTS) return RS_EVAL_DOES_NOT_FIT;
+  const int K = e->spec.num_classes, T = n_thresholds;
+  MtLayout L;
+  { int rc = mt_measure(polys, poly_off, poly_len, inst_first, tile_first[n], n, &L); if (rc) return rc; }
+  hipStream_t s = nullptr;
+  int rc;
+  if ((rc = e->ensure_eval_buffers())) return rc;
+  if ((rc = e->ensure_vote_sweep_buffers())) return rc;
+  if ((rc = e->ensure_poly_vote_buffers())) return rc;
+  RS_CHECK(L.bytes <= e->eval_pool_bytes, RS_ERR_ARG, "road labels: %zu bytes packed, the pool holds %zu", L.bytes, e->eval_pool_bytes);
+  if (e->eval_upload_pending) { RS_HIP(hipEventSynchronize(e->ev_eval_upload)); e->eval_upload_pending = false; }
+  mt_pack(e->eval_pinned, L, polys, poly_off, poly_len, inst_first, tile_first);
+  if ((rc = e->begin_fetch(&s))) return rc;
+  RS_HIP(hipMemcpyAsync(e->eval_pool, e->eval_pinned, L.bytes, hipMemcpyHostToDevice, s));
+  RS_HIP(hipEventRecord(e->ev_eval_upload, s));
+  e->eval_upload_pending = true;
+  PolyOverlapParams o;
+  memset(&o, 0, sizeof o);
+  o.header = e->poly.header; o.poly_ring_count = e->poly.poly_ring_count; o.ring_len = e->poly.ring_len; o.xy = (const int16_t*)e->poly.xy;
+  o.det_count = e->det_count; o.tile_first = (const int*)e->eval_pool; o.inst_first = (const int*)(e->eval_pool + L.o_inst);
+  o.poly_off = (const int*)(e->eval_pool + L.o_off); o.poly_len = (const int*)(e->eval_pool + L.o_len); o.polys = (const double*)(e->eval_pool + L.o_xy);
+  o.frac = e->pvote_frac; o.label_area = e->pvote_area; o.flagged = e->pvote_flagged; o.n = n; o.D = e->D; o.g_cap = RS_EVAL_GT_CAP;
+  if ((rc = launch_poly_overlaps(o, s))) return rc;
+  RoadVoteAreaSweepParams q;
+  memset(&q, 0, sizeof q);
+  q.det_scores = e->det_scores; q.det_classes = e->det_classes; q.det_count = e->det_count; q.tile_first = (const int*)e->eval_pool;
+  q.frac = e->pvote_frac; q.wscore = e->sweep_wscore; q.wfrac = e->sweep_wscore + e->sweep_cells; q.pairs = e->sweep_pairs;
+  q.T = T; q.n = n; q.K = K; q.D = e->D; q.g_cap = RS_EVAL_GT_CAP;
+  for (int j = 0; j < T; ++j) q.thresholds[j] = thresholds[j];
+  if ((rc = launch_road_votes_area_sweep(q, s))) return rc;
+  const size_t cells = (size_t)n * T * RS_EVAL_GT_CAP * K;           // <= sweep_cells: n <= max_batch, T <= RS_VOTE_SWEEP_MAX
+  RS_HIP(hipMemcpyAsync(v->wscore, q.wscore, cells * 8, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(v->wfrac, q.wfrac, cells * 8, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(v->pairs, q.pairs, cells * 4, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(v->label_area, e->pvote_area, (size_t)n * RS_EVAL_GT_CAP * 8, hipMemcpyDeviceToHost, s));
+  RS_HIP(hipMemcpyAsync(v->flagged, e->pvote_flagged, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  return e->end_fetch(s, nullptr);            // the tables live in their own buffers: detections and vertex tables are free for the next forward
+}
+
+int rs_engine_fetch_votes_poly_wait(rs_engine* e) { return rs_engine_fetch_wait(e); }
+
 // The band histograms of the road labels under the last forward's tiles (band_hist.h): upload, rasteriser, histogram kernel, one copy.
 // An add-on like the vote: no detections, no pair counts.  The kernel is the one reader of tiles_dev on the copy stream: the event
 // behind it holds back the next write into the buffer (wait_band_tiles).
@@ -1840,6 +1907,7 @@ int rs_engine_set_profiling(rs_engine* e, int enabled) {
   RS_CHECK(enabled >= 0 && enabled <= 3, RS_ERR_ARG, "profiling mode %d", enabled);
   if (e->ev_used) { int rc = e->resolve_profile(); if (rc) return rc; }
   e->forward_index = 0;
+  e->poly_forward = -1;
   e->ev_used = 0;
   e->profiling = enabled;
   for (Stage& s : e->stages) { s.ms_total = 0; s.calls = 0; }

@@ -137,6 +137,13 @@ struct rs_engine {
   int* sweep_pairs = nullptr;
   size_t sweep_cells = 0;
   int ensure_vote_sweep_buffers();
+  // the polygon geometry of the vote (rs_engine_fetch_votes_poly_*, poly_overlap.h): allocated on the first call
+  double* pvote_frac = nullptr;                 // device: [max_batch][D][RS_EVAL_GT_CAP]
+  double* pvote_area = nullptr;                 // device: [max_batch][RS_EVAL_GT_CAP]
+  int* pvote_flagged = nullptr;                 // device: [max_batch]
+  long long poly_forward = -1;                  // forward_index at the last rs_engine_fetch_polygons_async, and its batch
+  int poly_tiles = 0;
+  int ensure_poly_vote_buffers();
   // band histograms (rs_engine_fetch_band_hist_*, band_hist.h): allocated on the first call
   uint32_t* band_hist_dev = nullptr;            // device: [max_batch * RS_EVAL_GT_CAP][tile_c][256]
   hipEvent_t ev_band_tiles = nullptr;           // recorded on the copy stream behind the histogram kernel, the one reader of tiles_dev there

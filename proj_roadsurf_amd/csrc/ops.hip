@@ -10,6 +10,7 @@
 #include "train.h"
 #include "train_stats.h"
 #include "val_ap.h"
+#include "poly_vote.h"
 
 namespace {
 
@@ -386,6 +387,72 @@ int rs_host_road_votes_sweep(const float* det_scores, const int32_t* det_classes
                                     num_classes, slots, gt_cap, thresholds, n_thresholds, wscore, wfrac, pairs);
     if (rc) return rc; }
   return host_road_votes_sweep(q);    // val_ap.hip: the float64 arithmetic is compiled there, without mul+add contraction
+}
+
+// The polygon geometry of the vote (poly_overlap.h; see include/rs_engine.h): overlaps of the polygoniser's tables with the labels' rings,
+// then the sweep on those weights.  Device pointers enqueued on `stream`, or host pointers.
+static_assert(PO_HDR == RS_POLY_HDR, "poly_overlap.h restates the polygon header's width");
+static int poly_overlap_params(const char* who, PolyOverlapParams* q, const int32_t* header, const int32_t* poly_ring_count, const int32_t* ring_len,
+                               const int16_t* xy, const int32_t* det_count, const int32_t* tile_first, const int32_t* inst_first,
+                               const int32_t* poly_off, const int32_t* poly_len, const double* polys, int n_tiles, int slots, int gt_cap,
+                               int raw_areas, double* frac, double* label_area, int32_t* flagged) {
+  memset(q, 0, sizeof *q);
+  q->header = header; q->poly_ring_count = poly_ring_count; q->ring_len = ring_len; q->xy = xy; q->det_count = det_count;
+  q->tile_first = tile_first; q->inst_first = inst_first; q->poly_off = poly_off; q->poly_len = poly_len; q->polys = polys;
+  q->frac = frac; q->label_area = label_area; q->flagged = flagged;
+  q->n = n_tiles; q->D = slots; q->g_cap = gt_cap; q->raw_areas = raw_areas;
+  return poly_overlap_check(who, *q);
+}
+int rs_op_polygon_overlaps(const int32_t* header, const int32_t* poly_ring_count, const int32_t* ring_len, const int16_t* xy,
+                           const int32_t* det_count, const int32_t* tile_first, const int32_t* inst_first, const int32_t* poly_off,
+                           const int32_t* poly_len, const double* polys, int n_tiles, int slots, int gt_cap, int raw_areas, double* frac,
+                           double* label_area, int32_t* flagged, void* stream) {
+  PolyOverlapParams q;
+  { int rc = poly_overlap_params("rs_op_polygon_overlaps", &q, header, poly_ring_count, ring_len, xy, det_count, tile_first, inst_first, poly_off, poly_len,
+                                 polys, n_tiles, slots, gt_cap, raw_areas, frac, label_area, flagged);
+    if (rc) return rc; }
+  return launch_poly_overlaps(q, (hipStream_t)stream);
+}
+int rs_host_polygon_overlaps(const int32_t* header, const int32_t* poly_ring_count, const int32_t* ring_len, const int16_t* xy,
+                             const int32_t* det_count, const int32_t* tile_first, const int32_t* inst_first, const int32_t* poly_off,
+                             const int32_t* poly_len, const double* polys, int n_tiles, int slots, int gt_cap, int raw_areas, double* frac,
+                             double* label_area, int32_t* flagged) {
+  PolyOverlapParams q;
+  { int rc = poly_overlap_params("rs_host_polygon_overlaps", &q, header, poly_ring_count, ring_len, xy, det_count, tile_first, inst_first, poly_off,
+                                 poly_len, polys, n_tiles, slots, gt_cap, raw_areas, frac, label_area, flagged);
+    if (rc) return rc; }
+  return host_poly_overlaps(q);       // poly_vote.hip: the float64 arithmetic is compiled there, without mul+add contraction
+}
+
+static int road_vote_area_sweep_params(const char* who, RoadVoteAreaSweepParams* q, const float* det_scores, const int32_t* det_classes,
+                                       const int32_t* det_count, const int32_t* tile_first, const double* frac, int n_tiles, int num_classes,
+                                       int slots, int gt_cap, const double* thresholds, int n_thresholds, double* wscore, double* wfrac,
+                                       int32_t* pairs) {
+  memset(q, 0, sizeof *q);
+  q->det_scores = det_scores; q->det_classes = det_classes; q->det_count = det_count; q->tile_first = tile_first; q->frac = frac;
+  q->wscore = wscore; q->wfrac = wfrac; q->pairs = pairs;
+  q->n = n_tiles; q->K = num_classes; q->D = slots; q->g_cap = gt_cap; q->T = n_thresholds;
+  RS_CHECK(thresholds, RS_ERR_ARG, "%s: null threshold list", who);
+  for (int j = 0; j < n_thresholds && j < RV_SWEEP_MAX; ++j) q->thresholds[j] = thresholds[j];
+  return road_vote_area_sweep_check(who, *q);
+}
+int rs_op_road_votes_area_sweep(const float* det_scores, const int32_t* det_classes, const int32_t* det_count, const int32_t* tile_first,
+                                const double* frac, int n_tiles, int num_classes, int slots, int gt_cap, const double* thresholds,
+                                int n_thresholds, double* wscore, double* wfrac, int32_t* pairs, void* stream) {
+  RoadVoteAreaSweepParams q;
+  { int rc = road_vote_area_sweep_params("rs_op_road_votes_area_sweep", &q, det_scores, det_classes, det_count, tile_first, frac, n_tiles, num_classes,
+                                         slots, gt_cap, thresholds, n_thresholds, wscore, wfrac, pairs);
+    if (rc) return rc; }
+  return launch_road_votes_area_sweep(q, (hipStream_t)stream);
+}
+int rs_host_road_votes_area_sweep(const float* det_scores, const int32_t* det_classes, const int32_t* det_count, const int32_t* tile_first,
+                                  const double* frac, int n_tiles, int num_classes, int slots, int gt_cap, const double* thresholds,
+                                  int n_thresholds, double* wscore, double* wfrac, int32_t* pairs) {
+  RoadVoteAreaSweepParams q;
+  { int rc = road_vote_area_sweep_params("rs_host_road_votes_area_sweep", &q, det_scores, det_classes, det_count, tile_first, frac, n_tiles,
+                                         num_classes, slots, gt_cap, thresholds, n_thresholds, wscore, wfrac, pairs);
+    if (rc) return rc; }
+  return host_road_votes_area_sweep(q);
 }
 
 // The band histograms under label canvases on caller-owned tables (see include/rs_engine.h): device pointers enqueued on `stream`, or

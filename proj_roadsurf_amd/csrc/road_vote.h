@@ -60,6 +60,17 @@ RV_HD void rv_pair(RvCell* a, int inter, int area, int cls, float score, int c, 
   a->pairs += 1;
 }
 
+// The same slot of the walk on POLYGON areas (poly_overlap.h): frac arrives rounded (po_frac: np.round(area(label ∩ detection) /
+// area(label), 2), 0 for a pair without overlap), so the count test and the division of rv_pair fall away and the rest is its text.
+RV_HD void rv_pair_area(RvCell* a, double frac, int cls, float score, int c, double threshold) {
+  if (cls != c) return;
+  const double s = (double)score;
+  if (!(frac > 0.05) || !(s >= threshold)) return;
+  a->ws += frac * s;
+  a->wa += frac;
+  a->pairs += 1;
+}
+
 // the labels of tile t that the stage reads, and its detections: clamped to the tables' capacities
 RV_HD int rv_tile_labels(const int* tile_first, int t, int gt_cap) {
   const int G = tile_first[t + 1] - tile_first[t];

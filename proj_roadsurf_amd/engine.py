@@ -109,6 +109,12 @@ class RsRoadVotes(C.Structure):
                 ("label_area", C.POINTER(C.c_int32))]
 
 
+class RsRoadVotesPoly(C.Structure):
+    """include/rs_engine.h ``rs_road_votes_poly``: the sweep's tables on polygon areas, float64 label areas and the flagged counts."""
+    _fields_ = [("wscore", C.POINTER(C.c_double)), ("wfrac", C.POINTER(C.c_double)), ("pairs", C.POINTER(C.c_int32)),
+                ("label_area", C.POINTER(C.c_double)), ("flagged", C.POINTER(C.c_int32))]
+
+
 class RsRoadVoteSweep(C.Structure):
     """include/rs_engine.h ``rs_road_vote_sweep``: the tables of ``RsRoadVotes`` with a threshold axis behind the tile's."""
     _fields_ = [("wscore", C.POINTER(C.c_double)), ("wfrac", C.POINTER(C.c_double)), ("pairs", C.POINTER(C.c_int32)),
@@ -326,6 +332,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.rs_host_road_votes_sweep.argtypes = [vp] * 6 + [i32] * 4 + [vp, i32] + [vp] * 3
         lib.rs_engine_fetch_vote_sweep_async.argtypes = [vp, i32] + [vp] * 5 + [vp, i32, C.POINTER(RsRoadVoteSweep)]
         lib.rs_engine_fetch_vote_sweep_wait.argtypes = [vp]
+    if hasattr(lib, "rs_engine_fetch_votes_poly_async"):   # RS_ENGINE_LIB may name an older build
+        lib.rs_engine_fetch_votes_poly_async.argtypes = [vp, i32] + [vp] * 5 + [vp, i32, C.POINTER(RsRoadVotesPoly)]
+        lib.rs_engine_fetch_votes_poly_wait.argtypes = [vp]
     if hasattr(lib, "rs_op_band_hist"):              # RS_ENGINE_LIB may name an older build
         lib.rs_op_band_hist.argtypes = [vp] * 3 + [i32] * 4 + [vp, vp]
         lib.rs_host_band_hist.argtypes = [vp] * 3 + [i32] * 4 + [vp]
@@ -596,6 +605,10 @@ class Engine:
         # the vote sweep (rs_engine_fetch_vote_sweep_*): pinned tables for 32 thresholds, allocated on the first road_votes_sweep
         self._sweep_struct: Optional[RsRoadVoteSweep] = None
         self._sweep_labels: Tuple[List[int], int] = ([], 0)
+        # the polygon geometry of the vote (rs_engine_fetch_votes_poly_*): pinned tables, allocated on the first call that asks for it
+        self._pvote_struct: Optional[RsRoadVotesPoly] = None
+        self._pvote_labels: Tuple[List[int], int] = ([], 0)
+        self._pvote_batch = None                     # (labels, thresholds) of the batch in flight, for the host route of a flagged tile
         self.vote_fallbacks = 0
         # band histograms (rs_engine_fetch_band_hist_*): one pinned table, allocated on the first band_hist; batches that did not fit
         self._band_struct: Optional[RsBandHist] = None
@@ -881,7 +894,8 @@ class Engine:
         self.eval_unpack_s += time.perf_counter() - t0       # host time of this route's matching: unpacking the flag bits
         return out
 
-    def road_votes(self, tiles_or_n, labels: Sequence[Sequence[Sequence[np.ndarray]]], threshold: float = 0.0, wait: bool = True):
+    def road_votes(self, tiles_or_n, labels: Sequence[Sequence[Sequence[np.ndarray]]], threshold: float = 0.0, wait: bool = True,
+                   geometry: str = "pixels", rdp_epsilon: float = 0.75):
         """The road cover vote of a batch, counted and summed on the device (csrc/road_vote.h): ``tiles_or_n`` as for ``eval_counts``
         (tiles: a forward is run on them; n: the forward already enqueued, whether or not a ``fetch_async`` of it is in flight);
         labels[tile][label] = list of rings ([x0, y0, x1, y1, ...], tile pixels), the road labels clipped to the tile.  The labels are
@@ -892,10 +906,15 @@ class Engine:
         fit the device pool (the conditions of ``eval_counts``, shared with it; also more than 1024 slots): then nothing was enqueued,
         nothing is truncated, ``vote_fallbacks`` counts it and the caller votes on this batch with ``raster_vote.vote_tables_host``.
         Without a ``fetch_async`` in flight the detections (no masks) are fetched too; with one, its copies bring them.
-        ``wait=False`` returns True once everything is enqueued; ``road_votes_wait(n)`` then gives the result."""
+        ``wait=False`` returns True once everything is enqueued; ``road_votes_wait(n)`` then gives the result.
+        ``geometry="polygons"``: the weights are areas of polygon intersections (``road_votes_polygons``; T = 1, the threshold axis
+        dropped, ``label_area`` float64, the ``Instances`` carry the polygons); ``wait=False`` then pairs with ``road_votes_polygons_wait``."""
+        from .raster_vote import check_vote_geometry
         n = int(tiles_or_n) if np.isscalar(tiles_or_n) else int(tiles_or_n.shape[0])
         if not np.isfinite(threshold):                # before the forward: a refused call enqueues nothing
             raise ValueError(f"vote threshold {threshold!r} is not finite")
+        if check_vote_geometry(geometry) == "polygons":
+            return self.road_votes_polygons(tiles_or_n, labels, [threshold], wait=wait, rdp_epsilon=rdp_epsilon, squeeze=True)
         packed = self._vote_label_tables(n, labels)
         if packed is None:
             return None
@@ -959,7 +978,8 @@ class Engine:
             out.append(row)
         return out
 
-    def road_votes_sweep(self, tiles_or_n, labels: Sequence[Sequence[Sequence[np.ndarray]]], thresholds, wait: bool = True):
+    def road_votes_sweep(self, tiles_or_n, labels: Sequence[Sequence[Sequence[np.ndarray]]], thresholds, wait: bool = True,
+                         geometry: str = "pixels", rdp_epsilon: float = 0.75):
         """``road_votes`` for a list of 1 to 32 finite score thresholds at once (csrc/road_vote.h, THE SWEEP): labels are uploaded,
         rasterised and counted once, ``road_vote_sweep_kernel`` forms the tables of every threshold, and only they travel.  Returns
         per tile ``(Instances without masks, wscore (T, L_t, K), wfrac (T, L_t, K), pairs (T, L_t, K), label_area (L_t,))``; slice j
@@ -967,9 +987,11 @@ class Engine:
         when the batch does not fit the device pool, under the conditions of ``road_votes`` and counted in ``vote_fallbacks`` like
         there: sweep that batch with ``raster_vote.vote_tables_host(..., thresholds=)``.  ``wait=False`` returns True once
         everything is enqueued; ``road_votes_sweep_wait(n)`` then gives the result."""
-        from .raster_vote import sweep_thresholds
+        from .raster_vote import check_vote_geometry, sweep_thresholds
         n = int(tiles_or_n) if np.isscalar(tiles_or_n) else int(tiles_or_n.shape[0])
         thr = sweep_thresholds(thresholds)            # before the forward: a refused call enqueues nothing
+        if check_vote_geometry(geometry) == "polygons":
+            return self.road_votes_polygons(tiles_or_n, labels, thr, wait=wait, rdp_epsilon=rdp_epsilon)
         packed = self._vote_label_tables(n, labels)
         if packed is None:
             return None
@@ -977,6 +999,96 @@ class Engine:
             self.infer_device(self.upload_async(np.ascontiguousarray(tiles_or_n)), n)
         self._sweep_labels = self._sweep_enqueue(n, packed, thr)
         return self.road_votes_sweep_wait(n) if wait else True
+
+    # ------------------------------------------------------------------ the vote on polygon areas (csrc/poly_overlap.h)
+    def road_votes_polygons(self, tiles_or_n, labels: Sequence[Sequence[Sequence[np.ndarray]]], thresholds, wait: bool = True,
+                            rdp_epsilon: float = 0.75, squeeze: bool = False):
+        """The vote of ``road_votes_sweep`` with the reference's geometry: a (label, detection) pair weighs
+        ``round(area(label ∩ detection polygons) / area(label), 2)``, both areas on polygons -- the detection's as the device
+        polygoniser made them (simplified with ``rdp_epsilon``, the ones that go into the GeoPackage), the label's rings as given
+        (every ring an exterior; simple and pairwise interior-disjoint, which is not checked).  It rides behind a polygons fetch of
+        the same forward: with tiles, or with n and no fetch in flight, ``fetch_async(n, polygons=True, rdp_epsilon=...)`` is
+        enqueued here; a polygons fetch already in flight is used as it is (its epsilon counts); another kind of fetch in flight
+        is a ``ValueError``.  Neither the rasteriser nor the pair counts run.  Returns per tile ``(Instances with polygons, wscore
+        (T, L_t, K), wfrac, pairs, label_area (L_t,) float64)``, or ``None`` -- nothing enqueued, ``vote_fallbacks`` counted -- when
+        the batch does not fit the device pool: vote on it with ``raster_vote.vote_tables_polygons_host``.  A batch in which the
+        polygoniser flagged an instance comes back through that host route by itself (after the host vectoriser has made the
+        flagged instance's polygons), also counted in ``vote_fallbacks``.  ``squeeze``: T = 1 and the threshold axis dropped.
+        ``wait=False`` returns True once everything is enqueued; ``road_votes_polygons_wait(n)`` then gives the result and
+        completes the polygons fetch (use ``collect_results``, not ``wait_results``, after it)."""
+        from .raster_vote import sweep_thresholds
+        n = int(tiles_or_n) if np.isscalar(tiles_or_n) else int(tiles_or_n.shape[0])
+        thr = sweep_thresholds(thresholds)            # before the forward: a refused call enqueues nothing
+        if np.isscalar(tiles_or_n) and self._fetch_pending not in (None, "polygons"):
+            raise ValueError(f"the vote geometry 'polygons' rides behind a polygons fetch, a {self._fetch_pending} fetch is in flight")
+        packed = self._vote_label_tables(n, labels)
+        if packed is None:
+            return None
+        if not np.isscalar(tiles_or_n):
+            self.infer_device(self.upload_async(np.ascontiguousarray(tiles_or_n)), n)
+            self._fetch_pending = None
+        if self._fetch_pending is None:
+            self.fetch_async(n, polygons=True, rdp_epsilon=rdp_epsilon)
+        self._pvote_labels = self._pvote_enqueue(n, packed, thr)
+        self._pvote_batch = (labels, thr, bool(squeeze))
+        return self.road_votes_polygons_wait(n) if wait else True
+
+    def _pvote_enqueue(self, n: int, packed, thresholds) -> Tuple[List[int], int]:
+        """Enqueue the polygon vote of ``_vote_label_tables``' tables behind the polygons fetch of the last forward that is in flight;
+        returns (the labels per tile, the number of thresholds)."""
+        from .raster_vote import sweep_thresholds
+        thr = sweep_thresholds(thresholds)
+        flat, off, lens, inst_first, tile_first = packed
+        K = self.spec.num_classes
+        if self._pvote_struct is None:
+            cells = self.max_batch * VOTE_SWEEP_MAX * EVAL_GT_CAP * K      # flat: the layout [n][T][cap][K] depends on the call's n and T
+            self._pvote_tables = {"wscore": self._pinned((cells,), np.float64), "wfrac": self._pinned((cells,), np.float64),
+                                  "pairs": self._pinned((cells,), np.int32),
+                                  "label_area": self._pinned((self.max_batch, EVAL_GT_CAP), np.float64),
+                                  "flagged": self._pinned((self.max_batch,), np.int32)}
+            v = RsRoadVotesPoly()
+            for k, a in self._pvote_tables.items():
+                setattr(v, k, a.ctypes.data_as(C.POINTER(C.c_double if a.dtype == np.float64 else C.c_int32)))
+            self._pvote_struct = v
+        rc = self.lib.rs_engine_fetch_votes_poly_async(self._h, n, flat.ctypes.data, off.ctypes.data, lens.ctypes.data, inst_first.ctypes.data,
+                                                       tile_first.ctypes.data, thr.ctypes.data, int(thr.size), C.byref(self._pvote_struct))
+        _check(self.lib, rc, "rs_engine_fetch_votes_poly_async")   # the fit was checked above: any other code here is an error
+        return np.diff(tile_first).tolist(), int(thr.size)
+
+    def _pvote_wait(self, n: int, label_counts=None):
+        """Waits for the polygon vote's copies; the rows ``(wscore (T, L_t, K), wfrac, pairs, label_area)`` of tiles 0..n-1, or ``None``
+        when the polygoniser flagged an instance of the batch: its pairs were left at zero, the batch takes the host route."""
+        _check(self.lib, self.lib.rs_engine_fetch_votes_poly_wait(self._h), "rs_engine_fetch_votes_poly_wait")
+        if int(self._pvote_tables["flagged"][:n].sum()):
+            return None
+        counts, T = self._pvote_labels if label_counts is None else label_counts
+        K = self.spec.num_classes
+        t = {k: self._pvote_tables[k][:n * T * EVAL_GT_CAP * K].reshape(n, T, EVAL_GT_CAP, K) for k in ("wscore", "wfrac", "pairs")}
+        return [(t["wscore"][i, :, :int(counts[i])].copy(), t["wfrac"][i, :, :int(counts[i])].copy(), t["pairs"][i, :, :int(counts[i])].copy(),
+                 self._pvote_tables["label_area"][i, :int(counts[i])].copy()) for i in range(n)]
+
+    def polygon_vote_host_rows(self, inst: Sequence[Instances], labels, thresholds):
+        """The host route of the polygon vote on fetched ``Instances`` that carry polygons (and the crops of flagged instances, which
+        the host vectoriser turns into polygons first): ``raster_vote.vote_tables_polygons_host``'s rows."""
+        from .raster_vote import vote_tables_polygons_host
+        from .vectorize import vectorize_masks_native
+        lists = [vectorize_masks_native(None, self.tile_h, self.tile_w, i._polygons.rdp_epsilon, polygons=i._polygons, crops=i._crops) for i in inst]
+        return vote_tables_polygons_host(lists, labels, [i.scores for i in inst], [i.pred_classes for i in inst], thresholds, self.spec.num_classes)
+
+    def road_votes_polygons_wait(self, n: int):
+        """The second half of ``road_votes_polygons(..., wait=False)``: waits for the vote's copies and for the polygons fetch it
+        rides behind, and returns the rows of tiles 0..n-1.  A batch with a flagged instance is voted again on the host."""
+        rows = self._pvote_wait(n)
+        if self._fetch_pending == "polygons":
+            self.wait_results()
+        inst = self.collect_results(n)
+        labels, thr, squeeze = self._pvote_batch
+        if rows is None:
+            self.vote_fallbacks += 1
+            rows = self.polygon_vote_host_rows(inst, labels, thr)
+        if squeeze:
+            rows = [(r[0][0], r[1][0], r[2][0], r[3]) for r in rows]
+        return [(i,) + tuple(r) for i, r in zip(inst, rows)]
 
     def _sweep_enqueue(self, n: int, packed, thresholds) -> Tuple[List[int], int]:
         """Enqueue the sweep of ``_vote_label_tables``' tables behind the last forward (and behind its fetch, when one is in flight);
@@ -1303,7 +1415,7 @@ class LanePipeline:
         self._finish_pending()
 
     def run(self, batches, labels=None, vote_threshold: float = 0.0, band_stats: bool = False, road_votes: bool = True,
-            vote_sweep=None) -> "Iterator[List[Instances]]":
+            vote_sweep=None, vote_geometry: str = "pixels") -> "Iterator[List[Instances]]":
         """Stream host batches ((n,h,w,c) uint8 arrays) through the lanes and yield their detections in order.  Uploads go
         through pinned staging on the lane's stream, every batch's results come back on its lane's copy stream behind an event,
         and the generator runs ``lanes`` batches ahead of what it yields, so host-side collection overlaps the GPU.  Independent lanes:
@@ -1323,7 +1435,15 @@ class LanePipeline:
         (``vote_tables_host(..., thresholds=)``) for a batch that does not fit, counted in ``vote_fallbacks``.  With ``road_votes``
         as well the pipeline runs the sweep alone, ``vote_threshold`` appended as its last entry (so at most 31 thresholds then), and
         sets ``road_votes`` from that slice -- slice j of a sweep has the bits of the vote at ``thresholds[j]`` (csrc/road_vote.h) --
-        so the rasteriser and the pair counts run once per batch, not twice."""
+        so the rasteriser and the pair counts run once per batch, not twice.
+        ``vote_geometry="polygons"`` (needs ``vectorize="device"``, refused before any forward otherwise): the weights of both are areas
+        of polygon intersections (csrc/poly_overlap.h, ``Engine.road_votes_polygons``) on the polygons of the batch's own fetch; neither
+        the rasteriser nor the pair counts run, ``label_area`` is float64.  A batch with a flagged instance, and one that does not fit
+        the pool, is voted on the host (``raster_vote.vote_tables_polygons_host``), counted in ``vote_fallbacks``."""
+        from .raster_vote import check_vote_geometry
+        poly_geo = check_vote_geometry(vote_geometry, self.vectorize) == "polygons"
+        if poly_geo and not self.engines[0].spec.mask_on:
+            raise ValueError("the vote geometry 'polygons' needs MASK_ON")
         if band_stats and labels is None:
             raise ValueError("band_stats needs the road labels of every batch")
         if vote_sweep is not None and labels is None:
@@ -1372,6 +1492,9 @@ class LanePipeline:
                 self.vote_fallbacks += 1
                 self._fetch_async(eng, n, masks=True)
                 vote_of[lane] = ("host", lab_of[lane])
+            elif poly_geo:
+                self._fetch_async(eng, n)
+                vote_of[lane] = ("device", (eng._pvote_enqueue(n, packed, sweep_all if sweep_all is not None else [vote_threshold]), lab_of[lane]))
             elif sweep_all is not None:
                 self._fetch_async(eng, n)
                 vote_of[lane] = ("device", eng._sweep_enqueue(n, packed, sweep_all))
@@ -1399,6 +1522,21 @@ class LanePipeline:
                 return with_band(lane, res)
             from . import raster_vote
             kind, what = vote_of.pop(lane)
+            if poly_geo:
+                thr = sweep_all if sweep_all is not None else [vote_threshold]
+                labs = what[1] if kind == "device" else what
+                rows = self.engines[lane]._pvote_wait(len(res), what[0]) if kind == "device" else None
+                if rows is None:                    # a flagged instance, or a batch that did not fit (already counted): the host route
+                    self.vote_fallbacks += kind == "device"
+                    rows = self.engines[lane].polygon_vote_host_rows(res, labs, thr)
+                for inst, row in zip(res, rows):
+                    if sweep_all is None:
+                        inst.road_votes = raster_vote.sweep_slice(row, 0)
+                        continue
+                    if want_votes:
+                        inst.road_votes = raster_vote.sweep_slice(row, sweep_T)
+                    inst.road_vote_sweep = (row[0][:sweep_T], row[1][:sweep_T], row[2][:sweep_T], row[3])
+                return with_band(lane, res)
             if sweep_all is not None:
                 if kind == "device":
                     rows = self.engines[lane].road_votes_sweep_wait(len(res), False, what)
@@ -1590,7 +1728,7 @@ class Predictor:
         return out
 
     def predict_stream(self, batches, labels=None, vote_threshold: float = 0.0, band_stats: bool = False,
-                       road_votes: bool = True, vote_sweep=None) -> "Iterator[List[Dict[str, Instances]]]":
+                       road_votes: bool = True, vote_sweep=None, vote_geometry: str = "pixels") -> "Iterator[List[Dict[str, Instances]]]":
         """Streaming form for a whole tileset: ``batches`` is an iterator of image lists (each at most ``max_batch`` images);
         yields one result list per batch, in order.  Consecutive batches of one tile shape flow through ONE
         ``LanePipeline.run`` generator, so the upload, forward and result copy of batch k+1 overlap batch k (calling
@@ -1600,7 +1738,11 @@ class Predictor:
         of the stream that were voted on the host.  Labels need batches of one tile shape.  ``band_stats=True``: every yielded
         ``Instances`` also carries ``band_hist`` (``LanePipeline.run``), ``band_fallbacks`` counts the batches whose histograms the
         host formed; ``road_votes=False`` leaves the vote out and the labels serve the histograms alone.  ``vote_sweep=thresholds``:
-        every yielded ``Instances`` also carries ``road_vote_sweep``, the vote tables of every threshold (``LanePipeline.run``)."""
+        every yielded ``Instances`` also carries ``road_vote_sweep``, the vote tables of every threshold (``LanePipeline.run``).
+        ``vote_geometry="polygons"``: both on polygon areas (``LanePipeline.run``); needs ``vectorize="device"``, otherwise a
+        ``ValueError`` before any forward."""
+        from .raster_vote import check_vote_geometry
+        check_vote_geometry(vote_geometry, self.vectorize)
         if band_stats and labels is None:
             raise ValueError("band_stats needs the road labels of every batch")
         if vote_sweep is not None and labels is None:
@@ -1648,7 +1790,7 @@ class Predictor:
             before = pipe.vote_fallbacks if lab_src is None else 0
             band_before = 0
             for res in pipe.run(run_of_shape(), labels=taken_labels() if lab_src is not None else None, vote_threshold=vote_threshold,
-                                band_stats=band_stats, road_votes=road_votes, vote_sweep=vote_sweep):
+                                band_stats=band_stats, road_votes=road_votes, vote_sweep=vote_sweep, vote_geometry=vote_geometry):
                 self.vote_fallbacks += pipe.vote_fallbacks - before
                 before = pipe.vote_fallbacks
                 self.band_fallbacks += pipe.band_fallbacks - band_before

@@ -183,6 +183,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--metric-thresholds", default=None,
                     help="comma-separated score thresholds of --road-metrics, at most 32 (31 together with --road-votes); default: "
                          "np.arange(0, 1., 0.05), the reference's 20")
+    ap.add_argument("--vote-geometry", choices=("pixels", "polygons"), default="pixels",
+                    help="what the weight of a (road, detection) pair of --road-votes / --road-metrics is measured on: 'pixels' = counts on the tile "
+                         "grid against the masks; 'polygons' = the area of the polygon intersection of the label's rings with the detection polygons "
+                         "that go into the GeoPackage (after RDP), as the reference's overlay (csrc/poly_overlap.h).  Needs --vectorize device; a "
+                         "label's rings are taken as disjoint exteriors.  The JSON files then carry \"geometry\": \"polygons\"")
     ap.add_argument("--vote-threshold", type=float, default=None,
                     help="score a detection needs to vote (default: 'threshold' of the YAML's 'determine_class.py' section where it exists, else 0)")
     return ap
@@ -195,6 +200,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     logging.getLogger("make_detections").info("host pools of this rank: %d decode processes, %d host threads, %d vectoriser threads (%d cores for the rank)",
                                               args.decode_procs, args.host_workers, args.vector_threads, share)
 
+    if args.vote_geometry == "polygons":             # refused up front, before a file is read or a device touched
+        if args.vectorize != "device":
+            raise SystemExit("--vote-geometry polygons reads the device polygoniser's vertex tables: it needs --vectorize device")
+        if not (args.road_votes or args.road_metrics):
+            raise SystemExit("--vote-geometry polygons serves --road-votes / --road-metrics: name one of them")
     with open(args.config_file) as f:
         whole_cfg = yaml.safe_load(f)
     cfg = whole_cfg[SECTION]
@@ -304,7 +314,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             it = predictor.predict_stream(batches)
         else:
             it = predictor.predict_stream(batches, labels=iter(votes["labels"]), vote_threshold=vote_thr, band_stats=args.road_stats,
-                                          road_votes=args.road_votes, vote_sweep=metric_thr)
+                                          road_votes=args.road_votes, vote_sweep=metric_thr, vote_geometry=args.vote_geometry)
         while True:
             t = time.perf_counter()
             out = next(it, None)
@@ -439,7 +449,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                     names = dict(CLASS_NAMES) if K == len(CLASS_NAMES) else {i: str(i) for i in range(K)}
                 table = reduce_votes([t for _, t in rows], [ids for ids, _ in rows], names)
                 with open(f"{dataset}_road_votes.json", "w") as f:
-                    f.write(json.dumps(table))
+                    f.write(json.dumps(table if args.vote_geometry == "pixels" else {"geometry": args.vote_geometry, "roads": table}))
                 log.info("%s: %d road labels on %d tiles -> %d roads in %s_road_votes.json (vote threshold %g); %d of %d batches were voted on the host",
                          dataset, sum(len(ids) for ids, _ in rows), len(rows), len(table), dataset, vote_thr, sum(fb for _, fb in parts),
                          sum(len(range(*shard_range(len(images), r, world), args.batch)) for r in range(world)))
@@ -566,6 +576,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         asked = str((whole_cfg.get("final_metrics.py") or {}).get("baseline", ""))
         base_cls = next((c for c in classes if c in asked), "artificial")
         doc = road_metrics.report({k: v[:2] for k, v in metric_sets.items()}, categories, classes, metric_thr, names, base_cls)
+        if args.vote_geometry != "pixels":
+            doc["geometry"] = args.vote_geometry
         with open("road_metrics.json", "w") as f:
             f.write(json.dumps(doc))
         log.info("road metrics: %d thresholds on %d roads of %d datasets -> best threshold %g (balanced f1 %.4f on %s) in road_metrics.json; "

@@ -323,3 +323,197 @@ def reduce_votes(tables: Sequence[Sequence[np.ndarray]], road_ids: Sequence[Sequ
         out.append({"road_id": rid, "cover_type": names[order[0]] if unique else "undetermined",
                     **{f"{nm}_score": round(idx[c], ndigits) for c, nm in enumerate(names)}, "diff_score": best - second if unique else 0})
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- the polygon geometry
+# csrc/poly_overlap.h states the weight of a (label, detection) pair on POLYGONS, as the reference's overlay takes it: the area of
+# the intersection of the label's rings with the detection's (simplified) polygons over the label's area, rounded to two decimals.
+# ``rs_op_polygon_overlaps`` / ``rs_engine_fetch_votes_poly_async`` compute it on the device from the polygoniser's vertex tables,
+# ``rs_host_polygon_overlaps`` is the host restatement with the same bits; ``rs_*_road_votes_area_sweep`` is the vote's walk on those
+# weights.  A label's rings are all exteriors, taken as simple and pairwise interior-disjoint (the pixel geometry above takes their
+# union); overlapping label rings and labels with holes are not covered, and nothing checks for them.
+POLY_TABLE_KEYS = ("header", "poly_ring_count", "ring_len", "xy", "det_count", "tile_first", "inst_first", "poly_off", "poly_len", "polys")
+VOTE_GEOMETRIES = ("pixels", "polygons")
+
+
+def check_vote_geometry(geometry: str, vectorize: str = "device") -> str:
+    """``geometry`` as the vote entries take it; "polygons" reads the device polygoniser's tables, so it needs ``vectorize="device"``."""
+    if geometry not in VOTE_GEOMETRIES:
+        raise ValueError(f"vote geometry {geometry!r}: one of {VOTE_GEOMETRIES}")
+    if geometry == "polygons" and vectorize != "device":
+        raise ValueError("the vote geometry 'polygons' reads the device polygoniser's vertex tables: it needs vectorize='device'")
+    return geometry
+
+
+def pack_label_pool(labels: Sequence[Sequence[Sequence[np.ndarray]]]) -> Dict[str, np.ndarray]:
+    """labels[tile][label] = list of rings ([x0, y0, x1, y1, ...], tile pixels) -> the packed tables the polygon entries read:
+    tile_first (n + 1,), inst_first (labels + 1,), poly_off / poly_len (rings,) int32 in doubles, polys float64."""
+    arrs = [np.asarray(r, np.float64).reshape(-1) for tile in labels for lab in tile for r in lab]
+    lens = np.array([a.size for a in arrs] or [0], np.int32)
+    if any(int(k) < 2 or int(k) & 1 for k in lens[:len(arrs)]):
+        raise ValueError("a label ring is a flat list of x, y pairs")
+    off = np.zeros(max(len(arrs), 1), np.int32)
+    if len(arrs) > 1:
+        off[1:] = np.cumsum(lens[:-1])
+    inst_first = np.zeros(sum(len(t) for t in labels) + 1, np.int32)
+    inst_first[1:] = np.cumsum([len(lab) for t in labels for lab in t])
+    tile_first = np.zeros(len(labels) + 1, np.int32)
+    tile_first[1:] = np.cumsum([len(t) for t in labels])
+    return {"tile_first": tile_first, "inst_first": inst_first, "poly_off": off, "poly_len": lens,
+            "polys": np.ascontiguousarray(np.concatenate(arrs)) if arrs else np.zeros(1)}
+
+
+def stack_polygon_tables(tables: Sequence, slots: int = 0) -> Dict[str, np.ndarray]:
+    """``engine.PolygonTables`` of n tiles (offsets local to each) -> the batch form the polygoniser leaves on the device: header
+    (n, slots, 8) with offsets into the concatenated poly_ring_count / ring_len / xy, and det_count (n,).  ``slots`` 0: the largest
+    tile's count (at least 1)."""
+    n = len(tables)
+    D = max([int(slots), 1] + [int(t.header.shape[0]) for t in tables])
+    header = np.zeros((n, D, 8), np.int32)
+    base = np.zeros(3, np.int64)
+    for i, t in enumerate(tables):
+        c = int(t.header.shape[0])
+        header[i, :c] = t.header
+        header[i, :c, 4:7] += base.astype(np.int32)
+        base += (len(t.poly_ring_count), len(t.ring_len), len(t.xy))
+    return {"header": header, "poly_ring_count": np.ascontiguousarray(np.concatenate([t.poly_ring_count for t in tables] + [np.zeros(1, np.int32)])),
+            "ring_len": np.ascontiguousarray(np.concatenate([t.ring_len for t in tables] + [np.zeros(1, np.int32)])),
+            "xy": np.ascontiguousarray(np.concatenate([t.xy for t in tables] + [np.zeros((1, 2), np.int16)])),
+            "det_count": np.array([int(t.header.shape[0]) for t in tables], np.int32)}
+
+
+def polygon_tables_from_lists(polygons: Sequence[Sequence[Sequence[Sequence[Tuple[float, float]]]]], rdp_epsilon: float = 0.0):
+    """Nested polygon lists of one tile (per instance a list of polygons, each a list of closed rings of (x, y), the exterior first:
+    the form ``vectorize.vectorize_masks_native`` returns) -> ``engine.PolygonTables`` without a flagged instance.  The vertices are
+    pixel corners: integers, kept as int16."""
+    from .engine import POLY_HDR, PolygonTables
+    hdr = np.zeros((len(polygons), POLY_HDR), np.int32)
+    prc: List[int] = []
+    rlen: List[int] = []
+    xy: List[Tuple[int, int]] = []
+    for i, polys in enumerate(polygons):
+        hdr[i, 4:7] = (len(prc), len(rlen), len(xy))
+        for rings in polys:
+            prc.append(len(rings))
+            for ring in rings:
+                rlen.append(len(ring))
+                for x, y in ring:
+                    if x != int(x) or y != int(y) or not -32768 <= x <= 32767 or not -32768 <= y <= 32767:
+                        raise ValueError(f"detection vertex ({x!r}, {y!r}) is no int16 pixel corner")
+                    xy.append((int(x), int(y)))
+        hdr[i, 1:4] = (len(prc) - hdr[i, 4], len(rlen) - hdr[i, 5], len(xy) - hdr[i, 6])
+    return PolygonTables(hdr, np.array(prc, np.int32), np.array(rlen, np.int32), np.array(xy, np.int16).reshape(-1, 2), rdp_epsilon)
+
+
+def _overlap_call(entry: str, b: Dict[str, np.ndarray], gt_cap: int, prefill: float, device: bool, raw_areas: bool = False):
+    from .engine import _check, load_library
+    lib = load_library()
+    n, slots = b["header"].shape[:2]
+    dts = (np.int32, np.int32, np.int32, np.int16, np.int32, np.int32, np.int32, np.int32, np.int32, np.float64)
+    tabs = [np.ascontiguousarray(b[k], dt) for k, dt in zip(POLY_TABLE_KEYS, dts)]
+    outs = [np.full((n, slots, gt_cap), prefill, np.float64), np.full((n, gt_cap), prefill, np.float64), np.full((n,), int(prefill), np.int32)]
+    vp = C.c_void_p
+    if not device:
+        f = lib.rs_host_polygon_overlaps
+        f.argtypes = [vp] * 10 + [C.c_int] * 4 + [vp] * 3
+        _check(lib, f(*[a.ctypes.data for a in tabs], n, slots, gt_cap, int(raw_areas), *[a.ctypes.data for a in outs]), entry)
+        return tuple(outs)
+    import torch
+    dev = [torch.from_numpy(a).cuda() for a in tabs + outs]
+    torch.cuda.synchronize()
+    f = lib.rs_op_polygon_overlaps
+    f.argtypes = [vp] * 10 + [C.c_int] * 4 + [vp] * 4
+    _check(lib, f(*[a.data_ptr() for a in dev[:10]], n, slots, gt_cap, int(raw_areas), *[a.data_ptr() for a in dev[10:]], None), entry)
+    torch.cuda.synchronize()
+    return tuple(a.cpu().numpy() for a in dev[10:])
+
+
+def polygon_overlaps_host(b: Dict[str, np.ndarray], gt_cap: int = 128, prefill: float = 0.0, raw_areas: bool = False):
+    """``rs_host_polygon_overlaps`` on a dict of the tables ``POLY_TABLE_KEYS`` (``stack_polygon_tables`` and ``pack_label_pool``
+    give them) -> frac (n, slots, gt_cap) float64, label_area (n, gt_cap) float64, flagged (n,) int32.  ``prefill``: what the output
+    buffers hold before the call (the entry clears them itself); ``raw_areas``: ``frac`` holds the computed areas, not the rounded
+    weights.  Needs no device."""
+    return _overlap_call("rs_host_polygon_overlaps", b, gt_cap, prefill, False, raw_areas)
+
+
+def polygon_overlaps_device(b: Dict[str, np.ndarray], gt_cap: int = 128, prefill: float = 0.0, raw_areas: bool = False):
+    """``rs_op_polygon_overlaps`` on the same dict, uploaded through torch: ``poly_overlap_kernel``'s tables."""
+    return _overlap_call("rs_op_polygon_overlaps", b, gt_cap, prefill, True, raw_areas)
+
+
+def _area_sweep_call(entry: str, b: Dict[str, np.ndarray], num_classes: int, thresholds, prefill: float, device: bool):
+    from .engine import _check, load_library
+    lib = load_library()
+    n, slots = b["det_scores"].shape
+    cap = int(b["frac"].shape[2])
+    thr = np.ascontiguousarray(thresholds, np.float64).reshape(-1)      # unchecked: the entry refuses a bad list itself
+    T = int(thr.size)
+    tabs = [np.ascontiguousarray(b["det_scores"], np.float32), np.ascontiguousarray(b["det_classes"], np.int32),
+            np.ascontiguousarray(b["det_count"], np.int32), np.ascontiguousarray(b["tile_first"], np.int32),
+            np.ascontiguousarray(b["frac"], np.float64)]
+    shape = (n, max(T, 1), cap, num_classes)
+    outs = [np.full(shape, prefill, np.float64), np.full(shape, prefill, np.float64), np.full(shape, int(prefill), np.int32)]
+    vp = C.c_void_p
+    if not device:
+        f = lib.rs_host_road_votes_area_sweep
+        f.argtypes = [vp] * 5 + [C.c_int] * 4 + [vp, C.c_int] + [vp] * 3
+        _check(lib, f(*[a.ctypes.data for a in tabs], n, num_classes, slots, cap, thr.ctypes.data, T, *[a.ctypes.data for a in outs]), entry)
+        return tuple(outs)
+    import torch
+    dev = [torch.from_numpy(a).cuda() for a in tabs + outs]
+    torch.cuda.synchronize()
+    f = lib.rs_op_road_votes_area_sweep
+    f.argtypes = [vp] * 5 + [C.c_int] * 4 + [vp, C.c_int] + [vp] * 4
+    _check(lib, f(*[a.data_ptr() for a in dev[:5]], n, num_classes, slots, cap, thr.ctypes.data, T, *[a.data_ptr() for a in dev[5:]], None), entry)
+    torch.cuda.synchronize()
+    return tuple(a.cpu().numpy() for a in dev[5:])
+
+
+def road_votes_area_sweep_host(b: Dict[str, np.ndarray], num_classes: int, thresholds, prefill: float = 0.0):
+    """``rs_host_road_votes_area_sweep`` on a dict with det_scores / det_classes (n, slots), det_count (n,), tile_first (n + 1,) and frac
+    (n, slots, gt_cap) float64 -> wscore, wfrac (n, T, gt_cap, K) float64, pairs (n, T, gt_cap, K) int32.  Needs no device."""
+    return _area_sweep_call("rs_host_road_votes_area_sweep", b, num_classes, thresholds, prefill, False)
+
+
+def road_votes_area_sweep_device(b: Dict[str, np.ndarray], num_classes: int, thresholds, prefill: float = 0.0):
+    """``rs_op_road_votes_area_sweep`` on the same dict, uploaded through torch: ``road_vote_area_sweep_kernel``'s tables."""
+    return _area_sweep_call("rs_op_road_votes_area_sweep", b, num_classes, thresholds, prefill, True)
+
+
+def vote_tables_polygons_host(polygons: Sequence, labels: Sequence[Sequence[Sequence[np.ndarray]]], scores: Sequence[np.ndarray],
+                              classes: Sequence[np.ndarray], thresholds, num_classes: int = len(CLASS_NAMES)):
+    """The host route to the tables ``Engine.road_votes_sweep(..., geometry="polygons")`` gives, through the host restatements (the
+    device route's bits): polygons[tile] = ``engine.PolygonTables`` WITHOUT a flagged instance, or the nested polygon lists of
+    ``vectorize.vectorize_masks_native`` (which fills in what the device flagged); labels[tile][label] = list of rings; scores[tile],
+    classes[tile] (D_t,).  Returns per tile ``(wscore (T, L_t, K), wfrac (T, L_t, K), pairs (T, L_t, K), label_area (L_t,) float64)``.
+    The fallback of a batch with a flagged instance and of one that does not fit the device pool: a tile's labels are taken 128 at a
+    time, so nothing is truncated."""
+    from .engine import PolygonTables
+    thr = sweep_thresholds(thresholds)
+    if not (len(polygons) == len(labels) == len(scores) == len(classes)):
+        raise ValueError(f"{len(polygons)} polygon tables, {len(labels)} label lists, {len(scores)} score and {len(classes)} class arrays")
+    out = []
+    for tabs, labs, sc, cl in zip(polygons, labels, scores, classes):
+        if not isinstance(tabs, PolygonTables):
+            tabs = polygon_tables_from_lists(tabs)
+        if len(tabs.flagged):
+            raise ValueError("the host vote needs every instance's polygons: vectorise the flagged ones first (vectorize.vectorize_masks_native)")
+        D = int(tabs.header.shape[0])
+        if len(sc) != D or len(cl) != D:
+            raise ValueError(f"{D} instances, {len(sc)} scores, {len(cl)} classes")
+        det = stack_polygon_tables([tabs])
+        slots = det["header"].shape[1]
+        s_pad, c_pad = np.zeros((1, slots), np.float32), np.zeros((1, slots), np.int32)
+        s_pad[0, :D], c_pad[0, :D] = np.asarray(sc, np.float32), np.asarray(cl, np.int32)
+        parts = []
+        for lo in range(0, max(len(labs), 1), 128):
+            part = list(labs[lo:lo + 128])
+            cap = max(len(part), 1)
+            pool = pack_label_pool([part])
+            frac, area, _ = polygon_overlaps_host({**det, **pool}, gt_cap=cap)
+            ws, wa, pr = road_votes_area_sweep_host({"det_scores": s_pad, "det_classes": c_pad, "det_count": det["det_count"],
+                                                     "tile_first": pool["tile_first"], "frac": frac}, num_classes, thr)
+            parts.append((ws[0, :, :len(part)], wa[0, :, :len(part)], pr[0, :, :len(part)], area[0, :len(part)]))
+        out.append((np.concatenate([p[0] for p in parts], axis=1), np.concatenate([p[1] for p in parts], axis=1),
+                    np.concatenate([p[2] for p in parts], axis=1), np.concatenate([p[3] for p in parts])))
+    return out
